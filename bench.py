@@ -6,12 +6,17 @@ Workload (BASELINE.json configs[2]/[3]): CIFAR-10-shaped synthetic batches 3x32x
 lr 3e-4, fp32.  One "step" = the reference's per-batch body (ddpm_utils.py:499-507): timestep draw,
 noise_images, UNet forward, MSE, backward, [gradient all-reduce], AdamW.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
   N>1: python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
-Rank 0 prints ONE JSON line.  Extra objects: `roofline` (dominant kernel, timed live with HIP events
-on the launch stream), `kernels` (every kernel family timed the same way), `cpu_baseline`
-(the CPU oracle's train step on the host cores, bounded sample), `sample` (Diffusion.sample).
+Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times K train steps in the two-lane replay launch mode
+(TrainStep(graph="lanes"), the fastest of the three in every probe so far) and reports them.  --dump-outputs DIR writes what
+the last timed step computed (its loss and the updated parameters) as DIR/<name>.npy; the inputs are seeded, so two builds
+can be compared output for output.
+--full adds what takes runs of its own: the launch-mode probe (eager / hipGraph / lanes after warm-up, the fastest one is
+timed), `sample` (Diffusion.sample), `roofline` (dominant kernel, timed live with HIP events on the launch stream),
+`kernels` (every kernel family timed the same way) and `cpu_baseline` (the CPU oracle's train step on the host cores,
+bounded sample).
 """
 import argparse
 import gc
@@ -24,6 +29,7 @@ import time
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
+import numpy as np
 import torch
 import torch.distributed as dist
 
@@ -483,6 +489,28 @@ def cpu_baseline(variant=3, batch=256):
             "legs": legs}
 
 
+DUMP_LIMIT = 64 << 20          # bytes, all files of one --dump-outputs together
+
+
+def step_outputs(loss, model):
+    """What a caller of the timed path receives from its last step: the loss it returns and the parameters it updated in
+    place (the model's state_dict, flattened in its order: 5,897,155 fp32 values for Config D)."""
+    params = torch.cat([v.detach().reshape(-1).float() for v in model.state_dict().values() if v.is_floating_point()])
+    return {"loss": np.asarray([loss.item()], dtype=np.float32), "params": params.cpu().numpy()}
+
+
+def dump_outputs(out_dir, arrays, limit=DUMP_LIMIT):
+    """DIR/<name>.npy for every array (float32 / float64 kept, anything else as float32); refuses more than `limit` bytes."""
+    arrays = {k: (a if a.dtype in (np.float32, np.float64) else a.astype(np.float32)) for k, a in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    if total > limit:
+        raise ValueError(f"--dump-outputs: {total} bytes exceed the {limit}-byte limit")
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, f"{k}.npy"), a)
+    return total
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -491,13 +519,19 @@ def main():
     ap.add_argument("--batch", type=int, default=256, help="images per GPU")
     ap.add_argument("--variant", type=int, default=3)
     ap.add_argument("--no-graph", action="store_true", help="eager launches only")
-    ap.add_argument("--graph", action="store_true", help="hipGraph replay only (default: probe both after warm-up, keep the faster)")
-    ap.add_argument("--no-sample", action="store_true")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-kernels", action="store_true")
+    ap.add_argument("--graph", action="store_true",
+                    help="hipGraph replay only (default: the two-lane replay; with --full: probe all three after warm-up, keep the fastest)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the last timed step's loss and updated parameters as DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also the launch-mode probe, sampling, the per-kernel tables and the CPU baseline (runs of their own)")
+    ap.add_argument("--no-sample", action="store_true", help="(--full) skip sampling")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(--full) skip the CPU baseline")
+    ap.add_argument("--no-kernels", action="store_true", help="(--full) skip the per-kernel tables")
     ap.add_argument("--sample-n", type=int, default=256)
     ap.add_argument("--sample-steps", type=int, default=1000, help="noise_steps T of the sampling run (999 forwards at 1000)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -559,11 +593,16 @@ def main():
     # launch mode: the same step launched eagerly (with the weight-gradient kernels overlapped on a second stream), replayed from a
     # captured hipGraph, or re-issued from the captured graph on two real streams by a C++ loop ("lanes": csrc/replay.hip -- the
     # eager step's stream semantics without the interpreter).  Which is fastest depends on how quickly the host issues ~330
-    # launches per step (5.6 ms of interpreter time against 6.7-7.0 ms of device time), so by default all three are probed
-    # after warm-up (untimed) and the fastest one is measured.
+    # launches per step (5.6 ms of interpreter time against 6.7-7.0 ms of device time); lanes, whose host time is ~0.7 ms, has
+    # been the fastest in every probe, so a plain run times it alone.  With --full all three are probed after warm-up (untimed)
+    # and the fastest one is measured.
     if args.no_graph or args.graph:
         step, graph_ok = make_step(args.graph)
         mode = "hipGraph" if graph_ok else "eager"
+        log(f"rank {rank}/{world}: model ready ({mode})")
+    elif not args.full:
+        step, graph_ok = make_step("lanes")
+        mode = "lanes" if graph_ok else "eager"
         log(f"rank {rank}/{world}: model ready ({mode})")
     else:
         probes = {}
@@ -609,7 +648,11 @@ def main():
     }
 
     log(f"train: {ms:.2f} ms/step, {value:.0f} img/s, loss {final_loss:.4f}")
-    if not args.no_sample:
+    if args.dump_outputs and rank == 0:                # (every rank holds the same parameters after the exchange)
+        outs = step_outputs(loss, model)
+        nb = dump_outputs(args.dump_outputs, outs)
+        log(f"outputs of the last timed step: {', '.join(outs)} ({nb / 2**20:.1f} MiB) -> {args.dump_outputs}")
+    if args.full and not args.no_sample:
         log("sampling")
         n = args.sample_n
         ds = afdm.Diffusion(noise_steps=args.sample_steps, img_size=32, device=dev)
@@ -639,7 +682,7 @@ def main():
         result["sample"]["trajectories_in_flight"] = {"value": round(NS * n * world / cdt, 3), "unit": "images/s",
                                                       "n_per_gpu": NS * n, "streams": NS, "seconds": round(cdt, 3)}
 
-    if rank == 0 and world == 1:
+    if args.full and rank == 0 and world == 1:
         if not args.no_kernels and args.variant == 3:       # (the family tables are written over Config D's layer shapes)
             log("per-kernel timing: train step")
             table, rows = kernel_table(dev, args.batch, "train")

@@ -255,10 +255,17 @@ def noise_schedule(T=1000, beta_start=1e-4, beta_end=0.02):
     return beta, alpha, torch.cumprod(alpha, dim=0)
 
 
+def _sqrt_f32(v):
+    """fp32 square root rounded as IEEE 754 prescribes, on any host: taken in fp64 and rounded once to fp32 (exact for the
+    square root, 53 >= 2 * 24 + 2).  torch's vectorised fp32 sqrt is not correctly rounded on every CPU (1-ulp differences on
+    some AVX-512 hosts); on one where it is, this gives the same bits."""
+    return torch.sqrt(v.double()).float()
+
+
 def noise_images(alpha_hat, x, t, eps):
     """Diffusion.noise_images (ddpm_models.py:317-321) with the noise injected."""
-    a = torch.sqrt(alpha_hat[t])[:, None, None, None]
-    b = torch.sqrt(1 - alpha_hat[t])[:, None, None, None]
+    a = _sqrt_f32(alpha_hat[t])[:, None, None, None]
+    b = _sqrt_f32(1 - alpha_hat[t])[:, None, None, None]
     return a * x + b * eps
 
 

@@ -704,6 +704,36 @@ def test_bench_entry_point_two_ranks_dry_run(A, tmp_path):
     assert d["metric"] == "train_step_images_per_sec" and d["unit"] == "images/s" and d["vs_baseline"] is None
 
 
+def test_bench_plain_run_is_lean_and_dumps_identical_outputs(A, tmp_path):
+    """`bench.py --gpus 1 --steps K --warmup W --dump-outputs DIR` twice: a plain run prints the headline only (none of the
+    --full objects), times K steps in the two-lane replay, and writes the last step's loss and parameters (float32); the
+    inputs are seeded, so the two runs' outputs are bit-identical."""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    runs = []
+    for k in range(2):
+        out = tmp_path / f"out{k}"
+        cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "2", "--batch", "16",
+               "--dump-outputs", str(out)]
+        r = subprocess.run(cmd, timeout=600, capture_output=True, text=True)
+        assert r.returncode == 0, r.stderr[-3000:]
+        lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+        assert len(lines) == 1, r.stdout
+        d = json.loads(lines[0])
+        assert d["steps"] == 3 and d["warmup"] == 2 and d["config"]["launch_mode"] == "lanes"
+        assert d["metric"] == "train_step_images_per_sec" and d["unit"] == "images/s" and d["higher_is_better"] is True
+        assert d["dtype"] == "f32" and d["ms_per_step"] > 0 and abs(d["value"] - 16 / (d["ms_per_step"] * 1e-3)) < 0.01 * d["value"]
+        assert not {"sample", "roofline", "kernels", "cpu_baseline"} & set(d)
+        got = {n: np.load(out / f"{n}.npy") for n in ("loss", "params")}
+        assert got["params"].dtype == np.float32 and got["params"].size == 5897155 and np.isfinite(got["params"]).all()
+        assert abs(float(got["loss"][0]) - d["final_loss"]) < 1e-5
+        runs.append(got)
+    for n in ("loss", "params"):
+        assert np.array_equal(runs[0][n], runs[1][n]), n
+
+
 def test_conditional_train_step_updates_label_embedding(A):
     """TrainStep(conditional=True): labels go to UNet.forward(x, t, y) (ddpm_models.py:276-277) and label_emb is inside the
     optimised / exchanged range; with the default (the reference's loop passes no labels, ddpm_utils.py:502) it stays outside

@@ -250,3 +250,24 @@ def test_unet_gradient_buckets_follow_the_layer_order():
     ddp = afdm.GradAllReduce(fp, n_buckets=4, model=net)
     assert ddp.slices == [(0, 554144), (554144, 2163232), (2163232, 3786784), (3786784, 5897155)]
     assert sum(ddp._count) == len(fp.params) and ddp.world == 1 and ddp.finish() == 1.0
+
+
+def test_bench_dump_outputs_writes_the_step_outputs_within_the_limit(tmp_path):
+    """bench.py --dump-outputs: the loss and every parameter of the model, flattened in state_dict order, as float32 .npy
+    files (Config D: 23.6 MB, under the 64 MB limit); integer arrays are stored as float32; an oversized dump is refused
+    before anything is written."""
+    import afdm
+    import bench
+    afdm.set_seed(0)
+    net = afdm.UNet(c_in=3, c_out=3, image_size=32, f_settings=dict(F_SET), device="cpu", variant=3)
+    outs = bench.step_outputs(torch.tensor(0.25), net)
+    assert sorted(outs) == ["loss", "params"] and outs["loss"].tolist() == [0.25]
+    assert outs["params"].dtype == np.float32 and outs["params"].size == bench.N_PARAMS
+    nb = bench.dump_outputs(str(tmp_path / "out"), dict(outs, steps=np.arange(3)))
+    assert nb == 4 * (1 + bench.N_PARAMS + 3) <= bench.DUMP_LIMIT
+    got = {k: np.load(tmp_path / "out" / f"{k}.npy") for k in ("loss", "params", "steps")}
+    assert np.array_equal(got["params"], outs["params"]) and got["loss"].dtype == np.float32
+    assert got["steps"].dtype == np.float32 and got["steps"].tolist() == [0.0, 1.0, 2.0]
+    with pytest.raises(ValueError, match="limit"):
+        bench.dump_outputs(str(tmp_path / "big"), {"x": np.zeros(bench.DUMP_LIMIT // 8 + 1)})
+    assert not (tmp_path / "big").exists()

@@ -9,7 +9,7 @@ O=$R/gpurun_out/final_r02
 mkdir -p $O
 cd $R
 python -m pytest tests -m gpu -x -q > $O/pytest.log 2>&1; echo "pytest exit $?" >> $O/pytest.log; tail -2 $O/pytest.log
-python bench.py > $O/bench.json 2> $O/bench.err
+python bench.py --full > $O/bench.json 2> $O/bench.err
 cd /tmp && export TMPDIR=/tmp
 A="--steps 10 --warmup 3 --no-graph --no-sample --no-cpu-baseline --no-kernels"
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof -o step -- python3 $R/bench.py $A > $O/prof.log 2>&1 || exit 1

@@ -12,7 +12,7 @@ cd $R
 if [ $STAGE = all ] || [ $STAGE = a ]; then
   python -m pytest tests -m gpu -x -q > $O/pytest.log 2>&1; rc=$?; echo "pytest exit $rc" >> $O/pytest.log; tail -3 $O/pytest.log
   [ $rc -eq 0 ] || exit 1
-  python bench.py > $O/bench.json 2> $O/bench.err || { tail -20 $O/bench.err; exit 1; }
+  python bench.py --full > $O/bench.json 2> $O/bench.err || { tail -20 $O/bench.err; exit 1; }
   cd /tmp && export TMPDIR=/tmp
   A="--steps 10 --warmup 3 --no-graph --no-sample --no-cpu-baseline --no-kernels"
   rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof -o step -- python3 $R/bench.py $A > $O/prof.log 2>&1 || exit 1
