@@ -50,6 +50,91 @@ __global__ void denoise_step_k(const float* __restrict__ x, const float* __restr
   }
 }
 
+// ---- classifier-free guidance: the guided noise and the update above in one pass ------------------------------------
+// eps2 holds the 2n-row forward: element j of the conditional half at j, of the unconditional half at n + j.
+// e = torch.lerp(e_u, e_c, s) with ATen's scalar formula (aten/src/ATen/native/Lerp.h), one rounding per operation:
+//   |s| < 0.5:  u + s * (c - u)        otherwise:  c - (c - u) * (1 - s)
+// then exactly denoise_step_k's expression.  x_out may alias x (elementwise); x_out2 (optional) receives the same values:
+// the sampler writes both halves of its 2n input buffer, so the next forward needs no concatenation.
+struct CfgCoef {
+  float c1, c2, sb, s, one_minus_s;
+  bool small;
+};
+__device__ __forceinline__ CfgCoef cfg_coef(const float* alpha, const float* alpha_hat, const float* beta, int step, float s) {
+  const float a = alpha[step], ah = alpha_hat[step], bt = beta[step];
+  CfgCoef k;
+  k.c1 = 1.0f / sqrtf(a);
+  k.c2 = (1.0f - a) / sqrtf(1.0f - ah);
+  k.sb = sqrtf(bt);
+  k.s = s;
+  k.one_minus_s = 1.0f - s;
+  k.small = fabsf(s) < 0.5f;
+  return k;
+}
+__device__ __forceinline__ float cfg_update(const CfgCoef& k, float x, float ec, float eu, float nz_in, bool has_noise) {
+  const float d = ec - eu;
+  const float e = k.small ? eu + k.s * d : ec - d * k.one_minus_s;
+  const float pe = k.c2 * e;
+  const float inner = x - pe;
+  const float lhs = k.c1 * inner;
+  const float nz = has_noise ? k.sb * nz_in : 0.0f;
+  return lhs + nz;
+}
+
+// 16-byte accesses (n % 4 == 0, every pointer 16-byte aligned); n4 = n / 4
+__global__ __launch_bounds__(256) void denoise_step_cfg_x4_k(const float* x, const float* __restrict__ eps2, const float* __restrict__ noise,
+                                                             const float* __restrict__ alpha, const float* __restrict__ alpha_hat,
+                                                             const float* __restrict__ beta, int step_arg, const int64_t* __restrict__ step_dev,
+                                                             float s, float* x_out, float* x_out2, long n4) {
+  const int step = step_dev ? (int)step_dev[0] : step_arg;
+  const CfgCoef k = cfg_coef(alpha, alpha_hat, beta, step, s);
+  const float4* x4 = reinterpret_cast<const float4*>(x);
+  const float4* ec4 = reinterpret_cast<const float4*>(eps2);
+  const float4* eu4 = ec4 + n4;
+  const float4* nz4 = reinterpret_cast<const float4*>(noise);
+  const bool has_noise = noise != nullptr;
+  AFD_GRID_STRIDE(i, n4) {
+    const float4 xv = x4[i], c = ec4[i], u = eu4[i];
+    const float4 z = has_noise ? nz4[i] : make_float4(0.f, 0.f, 0.f, 0.f);
+    float4 r;
+    r.x = cfg_update(k, xv.x, c.x, u.x, z.x, has_noise);
+    r.y = cfg_update(k, xv.y, c.y, u.y, z.y, has_noise);
+    r.z = cfg_update(k, xv.z, c.z, u.z, z.z, has_noise);
+    r.w = cfg_update(k, xv.w, c.w, u.w, z.w, has_noise);
+    reinterpret_cast<float4*>(x_out)[i] = r;
+    if (x_out2) reinterpret_cast<float4*>(x_out2)[i] = r;
+  }
+}
+__global__ __launch_bounds__(256) void denoise_step_cfg_k(const float* x, const float* __restrict__ eps2, const float* __restrict__ noise,
+                                                          const float* __restrict__ alpha, const float* __restrict__ alpha_hat,
+                                                          const float* __restrict__ beta, int step_arg, const int64_t* __restrict__ step_dev,
+                                                          float s, float* x_out, float* x_out2, long n) {
+  const int step = step_dev ? (int)step_dev[0] : step_arg;
+  const CfgCoef k = cfg_coef(alpha, alpha_hat, beta, step, s);
+  const bool has_noise = noise != nullptr;
+  AFD_GRID_STRIDE(i, n) {
+    const float r = cfg_update(k, x[i], eps2[i], eps2[n + i], has_noise ? noise[i] : 0.0f, has_noise);
+    x_out[i] = r;
+    if (x_out2) x_out2[i] = r;
+  }
+}
+
+static int launch_denoise_step_cfg(const float* x, const float* eps2, const float* noise, const float* alpha, const float* alpha_hat,
+                                   const float* beta, int i, const int64_t* t_dev, float s, float* x_out, float* x_out2, long n,
+                                   hipStream_t st) {
+  auto a16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
+  const bool vec = n % 4 == 0 && a16(x) && a16(eps2) && a16(x_out) && (!noise || a16(noise)) && (!x_out2 || a16(x_out2));
+  const long work = vec ? n / 4 : n;
+  const int grid = (int)std::min<long>(2048, std::max<long>(1, (work + 255) / 256));      // memory-bound: grid-stride the rest
+  if (vec)
+    hipLaunchKernelGGL(denoise_step_cfg_x4_k, dim3(grid), dim3(256), 0, st, x, eps2, noise, alpha, alpha_hat, beta, i, t_dev, s, x_out,
+                       x_out2, work);
+  else
+    hipLaunchKernelGGL(denoise_step_cfg_k, dim3(grid), dim3(256), 0, st, x, eps2, noise, alpha, alpha_hat, beta, i, t_dev, s, x_out,
+                       x_out2, n);
+  return AFD_OK;
+}
+
 // ((clamp(x,-1,1) + 1) / 2 * 255).type(uint8): truncation toward zero
 __global__ void quantize_u8_k(const float* __restrict__ x, uint8_t* __restrict__ out, long n) {
   AFD_GRID_STRIDE(i, n) {
@@ -128,6 +213,19 @@ int afd_denoise_step_dev(const float* x, const float* eps_pred, const float* noi
   AFD_REQUIRE(x && eps_pred && alpha && alpha_hat && beta && t_dev && x_out && n > 0, "afd_denoise_step_dev: bad argument");
   hipLaunchKernelGGL(denoise_step_k, dim3(gs_grid(n)), dim3(256), 0, as_stream(st), x, eps_pred, noise, alpha, alpha_hat, beta, 0, t_dev, x_out, n);
   return check_launch("afd_denoise_step_dev");
+}
+int afd_denoise_step_cfg(const float* x, const float* eps2, const float* noise, const float* alpha, const float* alpha_hat,
+                         const float* beta, int i, float cfg_scale, float* x_out, float* x_out2, long n, afd_stream_t st) {
+  AFD_REQUIRE(x && eps2 && alpha && alpha_hat && beta && x_out && n > 0 && i >= 0, "afd_denoise_step_cfg: bad argument");
+  launch_denoise_step_cfg(x, eps2, noise, alpha, alpha_hat, beta, i, nullptr, cfg_scale, x_out, x_out2, n, as_stream(st));
+  return check_launch("afd_denoise_step_cfg");
+}
+int afd_denoise_step_cfg_dev(const float* x, const float* eps2, const float* noise, const float* alpha, const float* alpha_hat,
+                             const float* beta, const int64_t* t_dev, float cfg_scale, float* x_out, float* x_out2, long n,
+                             afd_stream_t st) {
+  AFD_REQUIRE(x && eps2 && alpha && alpha_hat && beta && t_dev && x_out && n > 0, "afd_denoise_step_cfg_dev: bad argument");
+  launch_denoise_step_cfg(x, eps2, noise, alpha, alpha_hat, beta, 0, t_dev, cfg_scale, x_out, x_out2, n, as_stream(st));
+  return check_launch("afd_denoise_step_cfg_dev");
 }
 int afd_quantize_u8(const float* x, uint8_t* out, long n, afd_stream_t st) {
   AFD_REQUIRE(x && out && n > 0, "afd_quantize_u8: bad argument");

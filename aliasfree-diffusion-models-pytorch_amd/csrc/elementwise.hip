@@ -408,6 +408,21 @@ __global__ __launch_bounds__(256) void embed_add_fwd_k(const float* __restrict__
   k = k < 0 ? 0 : (k >= K ? K - 1 : k);          // an out-of-range label cannot fault the launch (torch would raise)
   out[i] = temb[i] + table[k * D + d];
 }
+// the same with the NULL label: a row whose y[b] < 0 carries no label and keeps temb bit for bit (classifier-free guidance's
+// unconditional rows); every other row is exactly embed_add_fwd_k's (over-range labels clamp to K - 1).  out may alias temb.
+__global__ __launch_bounds__(256) void label_embed_add_fwd_k(const float* temb, const float* __restrict__ table,
+                                                             const int64_t* __restrict__ y, float* out, int B, int D, int K) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= B * D) return;
+  const int b = i / D, d = i - b * D;
+  long k = y[b];
+  if (k < 0) {
+    out[i] = temb[i];
+    return;
+  }
+  k = k >= K ? K - 1 : k;
+  out[i] = temb[i] + table[k * D + d];
+}
 // one thread per (class, column); the batch is walked in order, so the row sums are deterministic
 __global__ __launch_bounds__(256) void embed_add_bwd_k(const float* __restrict__ dout, const int64_t* __restrict__ y,
                                                        float* __restrict__ dtable, int B, int D, int K, int accumulate) {
@@ -425,6 +440,13 @@ int afd_embed_add_fwd(const float* temb, const float* table, const int64_t* y, f
   AFD_REQUIRE(temb && table && y && out && B > 0 && D > 0 && num_classes > 0, "afd_embed_add_fwd: bad argument");
   hipLaunchKernelGGL(embed_add_fwd_k, dim3((B * D + 255) / 256), dim3(256), 0, as_stream(st), temb, table, y, out, B, D, num_classes);
   return check_launch("afd_embed_add_fwd");
+}
+int afd_label_embed_add_fwd(const float* temb, const float* table, const int64_t* y, float* out, int B, int D, int num_classes,
+                            afd_stream_t st) {
+  AFD_REQUIRE(temb && table && y && out && B > 0 && D > 0 && num_classes > 0, "afd_label_embed_add_fwd: bad argument");
+  hipLaunchKernelGGL(label_embed_add_fwd_k, dim3((B * D + 255) / 256), dim3(256), 0, as_stream(st), temb, table, y, out, B, D,
+                     num_classes);
+  return check_launch("afd_label_embed_add_fwd");
 }
 int afd_embed_add_bwd(const float* dout, const int64_t* y, float* dtable, int B, int D, int num_classes, int accumulate,
                       afd_stream_t st) {

@@ -96,14 +96,18 @@ class Diffusion:
             z = torch.randn(shape, device=x.device)
         return z if shard is None else z[shard[0]:shard[1]].contiguous()
 
-    def _loop(self, model, n, image_channels, theta=None, noise_source="reference", graph=None, shard=None):
+    def _loop(self, model, n, image_channels, theta=None, noise_source="reference", graph=None, shard=None, labels=None,
+              cfg_scale=0.0):
         """Shared body of sample / revert.  noise_source: 'reference' (x_T from the CPU generator,
         per-step noise from the device generator -- what the reference does on a GPU), 'cpu'
         (everything from the CPU generator: reproduces the reference's CPU run), 'device'.
         graph: capture ONE denoise step (UNet forward + device noise + update) into a hipGraph and replay
         it for i = T-1 .. 2 (the step index lives in device memory).  Off by default: measured on MI355X the
         loop is bound by the ~330 dependent kernel boundaries per step on the device (2.18 ms/step at n=6
-        with or without replay), not by host launches."""
+        with or without replay), not by host launches.
+        labels: (n,) int64 device tensor (checked by `sample`) or None.  With labels and cfg_scale > 0 (classifier-free
+        guidance) every step runs ONE forward over 2n rows [x ; x] with labels [labels ; NULL_LABEL] and the fused guided
+        update writes both halves of the next 2n input; the noise drawn is that of n images, as without labels."""
         theta_step = None if theta is None else theta / self.noise_steps
         if graph is None:
             graph = False
@@ -113,11 +117,16 @@ class Diffusion:
         with torch.no_grad():
             x = self._initial_noise(n, image_channels, noise_source, shard)
             n_all, n = n, x.shape[0]
+            guided = labels is not None and cfg_scale > 0
+            y = labels
+            if guided:                                   # built once per trajectory
+                y = torch.cat([labels, torch.full_like(labels, ops.NULL_LABEL)])
             if graph and theta is None and noise_source != "cpu" and shard is None:
-                x = self._graph_steps(model, x, snaps)
+                x = self._graph_steps(model, x, snaps, y, cfg_scale if guided else 0.0)
                 first_eager = 1
             else:
                 first_eager = self.noise_steps - 1
+            xs2 = torch.cat([x, x]) if guided else None
             for i in reversed(range(1, first_eager + 1)):
                 if n == 0:                               # an empty shard still consumes the shared noise stream
                     if i > 1:
@@ -125,8 +134,17 @@ class Diffusion:
                     if i % 100 == 0:
                         snaps.append(x)
                     continue
+                if guided:
+                    eps2 = model(xs2, self._t_full(2 * n, i, x.device), y)
+                    noise = self._step_noise(x, noise_source, shard, n_all) if i > 1 else None
+                    nxt = torch.empty_like(xs2)
+                    ops.denoise_step_cfg(x, eps2, noise, self.alpha, self.alpha_hat, self.beta, i, cfg_scale, nxt[:n], nxt[n:])
+                    xs2, x = nxt, nxt[:n]
+                    if i % 100 == 0:
+                        snaps.append(x)
+                    continue
                 t = self._t_full(n, i, x.device)
-                eps = model(x, t)
+                eps = model(x, t) if y is None else model(x, t, y)
                 noise = self._step_noise(x, noise_source, shard, n_all) if i > 1 else None
                 x = ops.denoise_step(x, eps, noise, self.alpha, self.alpha_hat, self.beta, i)
                 if theta_step is not None:
@@ -151,14 +169,23 @@ class Diffusion:
         if hasattr(model, "_t_range"):
             model._t_range = None
 
-    def _graph_steps(self, model, x, snaps):
-        """Steps i = T-1 .. 2 by replaying one captured step; returns x after step 2."""
+    def _graph_steps(self, model, x, snaps, y=None, cfg_scale=0.0):
+        """Steps i = T-1 .. 2 by replaying one captured step; returns x after step 2.  y: class labels of the forward's rows
+        (2n of them when cfg_scale > 0: the captured step is then the 2n-row forward and the fused guided update, which writes
+        both halves of the static 2n input)."""
         n = x.shape[0]
-        t_dev = torch.full((n,), self.noise_steps - 1, device=x.device, dtype=torch.long)
-        xs = x.clone()
+        guided = cfg_scale > 0
+        t_dev = torch.full((2 * n if guided else n,), self.noise_steps - 1, device=x.device, dtype=torch.long)
+        xs = torch.cat([x, x]) if guided else x.clone()
+        xh = xs[:n]
 
         def one_step():
-            eps = model(xs, t_dev)
+            if guided:
+                eps2 = model(xs, t_dev, y)
+                noise = torch.randn_like(xh)
+                ops.denoise_step_cfg_dev(xh, eps2, noise, self.alpha, self.alpha_hat, self.beta, t_dev, cfg_scale, xh, xs[n:])
+                return
+            eps = model(xs, t_dev) if y is None else model(xs, t_dev, y)
             noise = torch.randn_like(xs)
             ops.denoise_step_dev(xs, eps, noise, self.alpha, self.alpha_hat, self.beta, t_dev, xs)   # in place (elementwise)
 
@@ -178,14 +205,35 @@ class Diffusion:
             t_dev.fill_(i)
             g.replay()
             if i % 100 == 0:
-                snaps.append(xs.clone())
-        return xs.clone()
+                snaps.append(xh.clone())
+        return xh.clone()
 
-    def sample(self, model, n, image_channels, theta=None, noise_source="reference", return_float=False, graph=None):
+    def _check_labels(self, model, n, theta, labels):
+        if theta is not None:
+            raise NotImplementedError("Diffusion.sample: class labels together with a rotation (theta) are not supported")
+        if getattr(model, "label_emb", None) is None:
+            raise ValueError("Diffusion.sample: labels were passed but the model has no label embedding (build UNet(num_classes=K))")
+        y = torch.as_tensor(labels)
+        if y.dtype.is_floating_point or y.dtype.is_complex or y.dtype == torch.bool:
+            raise ValueError(f"Diffusion.sample: labels must be integers (got {y.dtype})")
+        if tuple(y.shape) != (n,):
+            raise ValueError(f"Diffusion.sample: expected {n} labels, one per image (got shape {tuple(y.shape)})")
+        return y.to(device=self.device, dtype=torch.long).contiguous()
+
+    def sample(self, model, n, image_channels, theta=None, noise_source="reference", return_float=False, graph=None,
+               labels=None, cfg_scale=0.0):
+        """labels: (n,) integer class labels (NULL_LABEL for an unconditional image) for a UNet(num_classes=K); None = the
+        unconditional sampler.  cfg_scale > 0: classifier-free guidance, eps = torch.lerp(eps_uncond, eps_cond, cfg_scale),
+        both predictions from ONE forward over 2n rows per step; cfg_scale <= 0: the conditional prediction alone.  The noise
+        drawn (x_T and every step's) is that of the unconditional sampler for the same seed and noise_source."""
         logging.info(f"Sampling {n} new images....")
         if theta is not None:
             logging.info(f"Theta {theta} provided. Rotation will be applied.")
-        x, snaps = self._loop(model, n, image_channels, theta, noise_source, graph)
+        if labels is not None:
+            labels = self._check_labels(model, n, theta, labels)
+        elif cfg_scale:
+            raise ValueError("Diffusion.sample: cfg_scale needs class labels")
+        x, snaps = self._loop(model, n, image_channels, theta, noise_source, graph, labels=labels, cfg_scale=float(cfg_scale))
         self.last_float_snapshots = snaps          # pre-quantisation x at i % 100 == 0 and the final x (parity tests)
         xq = ops.quantize_u8(x)
         rq = ops.quantize_u8(torch.cat(snaps))

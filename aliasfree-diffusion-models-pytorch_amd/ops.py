@@ -14,6 +14,7 @@ from ._lib import AfdError, lib
 
 GN_EPS = 1e-5
 LN_EPS = 1e-5
+NULL_LABEL = -1      # class label of a row that carries none (classifier-free guidance): UNet.forward adds no label embedding to it
 
 
 _raw_stream = getattr(torch._C, "_cuda_getCurrentRawStream", None)
@@ -954,7 +955,8 @@ def pos_encoding(t, inv_freq):
 
 class EmbedAdd(_Fn):
     """t_emb + label_emb(y)  (ddpm_models.py:276-277): nn.Embedding lookup and the add in one launch; backward is the
-    deterministic row scatter into the table's gradient (the positional encoding itself carries no gradient)."""
+    deterministic row scatter into the table's gradient (the positional encoding itself carries no gradient).
+    A negative label (NULL_LABEL) marks a row without a label: it keeps t_emb as it is and sends no gradient to the table."""
 
     @staticmethod
     def forward(ctx, temb, table, y):
@@ -966,7 +968,7 @@ class EmbedAdd(_Fn):
         if table.shape[1] != D or y.shape[0] != B:
             raise AfdError(f"afdm: label embedding shape mismatch (temb {tuple(temb.shape)}, table {tuple(table.shape)}, y {tuple(y.shape)})")
         out = torch.empty_like(temb)
-        lib().afd_embed_add_fwd(_p(temb), _p(table), _p(y), _p(out), B, D, table.shape[0], _stream())
+        lib().afd_label_embed_add_fwd(_p(temb), _p(table), _p(y), _p(out), B, D, table.shape[0], _stream())
         ctx.save_for_backward(y)
         ctx.table = table if isinstance(table, torch.nn.Parameter) else None
         ctx.K = table.shape[0]
@@ -1121,6 +1123,38 @@ def denoise_step_dev(x, eps_pred, noise, alpha, alpha_hat, beta, t_dev, out):
     _chk(x, eps_pred, noise)
     lib().afd_denoise_step_dev(_p(x), _p(eps_pred), _p(noise), _p(alpha), _p(alpha_hat), _p(beta), _p(t_dev), _p(out),
                                x.numel(), _stream())
+    return out
+
+
+def _cfg_args(x, eps2, noise, out, out2):
+    _chk(x, eps2, noise, out, out2)
+    n = x.numel()
+    if eps2.numel() != 2 * n or (noise is not None and noise.numel() != n):
+        raise AfdError(f"afdm: guided denoise step needs eps2 of 2 x {n} elements (got {eps2.numel()}) and noise of {n}")
+    for o in (x, eps2, noise, out, out2):
+        if o is not None and not o.is_contiguous():
+            raise AfdError("afdm: guided denoise step: every tensor must be contiguous")
+        if o is not None and o is not eps2 and o.numel() != n:
+            raise AfdError(f"afdm: guided denoise step: x / noise / outputs must hold {n} elements")
+    return n
+
+
+def denoise_step_cfg(x, eps2, noise, alpha, alpha_hat, beta, i, cfg_scale, out=None, out2=None):
+    """Classifier-free guided update: eps2 = the forward over [conditional rows ; unconditional rows] (2n images),
+    e = torch.lerp(eps2[n:], eps2[:n], cfg_scale) and then exactly `denoise_step(x, e, ...)`, in one launch.  `out` may be
+    x (in place); `out2` (optional) receives the same values."""
+    out = torch.empty_like(x) if out is None else out
+    n = _cfg_args(x, eps2, noise, out, out2)
+    lib().afd_denoise_step_cfg(_p(x), _p(eps2), _p(noise), _p(alpha), _p(alpha_hat), _p(beta), int(i), float(cfg_scale), _p(out),
+                               _p(out2), n, _stream())
+    return out
+
+
+def denoise_step_cfg_dev(x, eps2, noise, alpha, alpha_hat, beta, t_dev, cfg_scale, out, out2=None):
+    """denoise_step_cfg with the step index t_dev[0] read on the device (graph-replayable)."""
+    n = _cfg_args(x, eps2, noise, out, out2)
+    lib().afd_denoise_step_cfg_dev(_p(x), _p(eps2), _p(noise), _p(alpha), _p(alpha_hat), _p(beta), _p(t_dev), float(cfg_scale),
+                                   _p(out), _p(out2), n, _stream())
     return out
 
 

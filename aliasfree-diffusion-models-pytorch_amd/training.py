@@ -260,6 +260,12 @@ class GradAllReduce:
         return self.finish()
 
 
+def label_dropout_mask(n, p_uncond):
+    """(n,) bool mask of the samples whose class label a classifier-free-guidance step drops (replaces by NULL_LABEL): each
+    with probability p_uncond, drawn from torch's CPU global generator like Diffusion.sample_timesteps."""
+    return torch.rand(n) < p_uncond
+
+
 class TrainStep:
     """The reference's per-batch body (ddpm_utils.py:499-507) as one callable:
          t -> noise_images -> UNet -> MSE -> zero_grad -> backward -> [all-reduce] -> AdamW.
@@ -273,12 +279,22 @@ class TrainStep:
     hipGraph launch's cross-branch cost: 6.79 / 6.84 / 7.00 ms (lanes / eager / hipGraph) at B = 256, 3.7 / 5.2 / 4.0 at
     B = 16, bit-identical to the eager step.  The noise is drawn outside the replayed list (no generator state in it)."""
 
-    def __init__(self, model, diffusion, lr, graph=False, distributed=None, n_buckets=4, overlap_wgrad=None, conditional=False):
+    def __init__(self, model, diffusion, lr, graph=False, distributed=None, n_buckets=4, overlap_wgrad=None, conditional=False,
+                 p_uncond=0.0):
         """conditional=True: the step takes class labels (`step(images, y=labels)`, UNet.forward(x, t, y): ddpm_models.py:276-277)
         and `label_emb` is optimised and exchanged like every other parameter.  With the default (the reference's loop,
-        ddpm_utils.py:502, never passes labels) `label_emb` stays untouched, as under the reference's AdamW, and passing y raises."""
+        ddpm_utils.py:502, never passes labels) `label_emb` stays untouched, as under the reference's AdamW, and passing y raises.
+        p_uncond > 0 (needs conditional=True): label dropout for classifier-free guidance -- each sample's label is replaced by
+        NULL_LABEL with probability p_uncond, the mask drawn from the CPU generator right after the timesteps
+        (label_dropout_mask), outside any captured work.  p_uncond = 0 draws nothing."""
+        if not 0.0 <= p_uncond <= 1.0:
+            raise ValueError(f"TrainStep: p_uncond must lie in [0, 1] (got {p_uncond})")
+        if p_uncond > 0 and not conditional:
+            raise ValueError("TrainStep: p_uncond > 0 drops class labels, which needs a conditional step (conditional=True)")
         self.model, self.diffusion = model, diffusion
         self.conditional = conditional
+        self.p_uncond = float(p_uncond)
+        self.last_labels = None          # the labels the last call trained on, after dropout
         # weight-gradient kernels on a second stream (ops._GradMode.side): off the critical path of backward, they fill
         # the CUs the dependent chain of small kernels leaves idle.  Measured on MI355X (B=256): eager 12.0 -> 11.1
         # ms/step, captured graph 11.45 -> 11.3 (forks batched 16 layers at a time: every fork is a cross-stream edge
@@ -372,16 +388,23 @@ class TrainStep:
 
     def __call__(self, images, t=None, eps=None, y=None):
         """images (B,C,S,S) on the device; t (B,) int64 [default: diffusion.sample_timesteps];
-        eps: injected noise or None (device RNG); y (B,) int64 class labels (only with conditional=True, eager launches).
+        eps: injected noise or None (device RNG); y (B,) int64 class labels (only with conditional=True; NULL_LABEL = no label
+        for that sample).  Under graph=True / "lanes" the labels are a static captured input like images, t and eps: a step
+        captured with labels must get them on every call, one captured without must never get them.
         Returns the loss as a 0-d device tensor."""
         if y is not None and not self.conditional:
             raise ValueError("TrainStep: class labels were passed but the step was built with conditional=False: label_emb sits "
                              "outside the optimised range (FlatParams) and would never be updated; build TrainStep(..., conditional=True)")
-        if y is not None and self.use_graph:
-            raise ValueError("TrainStep(graph=True) does not take class labels; use eager launches for conditional training")
         if t is None:
             t = self.diffusion.sample_timesteps(images.shape[0])
         t = t.to(images.device, non_blocking=True)
+        if y is not None:
+            y = torch.as_tensor(y)
+            if self.p_uncond > 0:
+                drop = label_dropout_mask(images.shape[0], self.p_uncond)
+                y = y.masked_fill(drop.to(y.device), ops.NULL_LABEL)
+            y = y.to(images.device, non_blocking=True)
+            self.last_labels = y
         if self.lanes and eps is None:
             eps = torch.randn_like(images)          # drawn outside: the replayed list holds no generator state
         if not self.use_graph:
@@ -395,7 +418,8 @@ class TrainStep:
             return self._body(images, t, eps, y)
         whole = self.ddp is None                    # single GPU: AdamW is captured too
         if self._graph is None:
-            self._static = {"images": images.clone(), "t": t.clone(), "eps": None if eps is None else eps.clone()}
+            self._static = {"images": images.clone(), "t": t.clone(), "eps": None if eps is None else eps.clone(),
+                            "y": None if y is None else y.clone()}
             st = self._static
             # warm-up outside capture (allocator, lazy init, the Winograd plan's recording step).  These are real steps on
             # the first batch, so everything they change is put back afterwards -- parameters, AdamW moments and step
@@ -408,7 +432,7 @@ class TrainStep:
             s.wait_stream(torch.cuda.current_stream())
             with torch.cuda.stream(s):
                 for _ in range(2):
-                    (self._body if whole else self._fwd_bwd)(st["images"], st["t"], st["eps"])
+                    (self._body if whole else self._fwd_bwd)(st["images"], st["t"], st["eps"], st["y"])
             torch.cuda.current_stream().wait_stream(s)
             for b, k in zip((fp.flat, opt.m, opt.v, opt.state), keep):
                 b.copy_(k)
@@ -416,7 +440,7 @@ class TrainStep:
             ops.bump_param_epoch()
             self._graph = torch.cuda.CUDAGraph(keep_graph=True) if self.lanes else torch.cuda.CUDAGraph()
             with torch.cuda.graph(self._graph):
-                st["loss"] = (self._body if whole else self._fwd_bwd)(st["images"], st["t"], st["eps"])
+                st["loss"] = (self._body if whole else self._fwd_bwd)(st["images"], st["t"], st["eps"], st["y"])
             if self.lanes:
                 import ctypes
                 h, counts = ctypes.c_void_p(), (ctypes.c_int * 4)()
@@ -426,8 +450,13 @@ class TrainStep:
         if (eps is None) != (st["eps"] is None):
             raise ValueError("TrainStep(graph=True): the step was captured " + ("without" if st["eps"] is None else "with") +
                              " injected noise; `eps` must be passed (or omitted) on every call alike")
+        if (y is None) != (st["y"] is None):
+            raise ValueError("TrainStep(graph=True): the step was captured " + ("without" if st["y"] is None else "with") +
+                             " class labels; `y` must be passed (or omitted) on every call alike")
         st["images"].copy_(images)
         st["t"].copy_(t)
+        if y is not None:
+            st["y"].copy_(y)
         if eps is not None:
             st["eps"].copy_(eps)
         if self.lanes:

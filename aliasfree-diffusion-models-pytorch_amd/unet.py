@@ -131,7 +131,7 @@ class UNet(nn.Module):
         else:
             t = self.pos_encoding(t_idx, self.time_dim)
             if y is not None:
-                t = ops.EmbedAdd.apply(t, self.label_emb.weight, y.to(x.device))        # t += label_emb(y)   (:276-277)
+                t = ops.EmbedAdd.apply(t, self.label_emb.weight, y.to(x.device))        # t += label_emb(y)   (:276-277); y < 0: no label
             if not t.requires_grad:                       # the six stages' emb_layer(t) in one launch (t is ready now)
                 for s, e in zip(stages, ops.silu_linear_batched(t, layers)):
                     s._emb_pre = (t, e)

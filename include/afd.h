@@ -342,6 +342,13 @@ int afd_gather_rows_batched(const int64_t* idx, const afd_silu_desc* descs, int 
  * rows of classes absent from y are zeroed (accumulate = 0) or left alone (accumulate = 1). */
 int afd_embed_add_fwd(const float* temb, const float* table, const int64_t* y, float* out, int B, int D, int num_classes,
                       afd_stream_t stream);
+/* the same with the NULL label (classifier-free guidance): a row with y[b] < 0 carries no label and out[b, :] is a bit copy of
+ * temb[b, :]; every row with y[b] >= 0 is bit-identical to afd_embed_add_fwd (labels >= num_classes clamp the same way).
+ * afd_embed_add_fwd itself clamps a negative label to class 0.  out may alias temb.
+ * afd_embed_add_bwd below needs no null-label form: y[b] == k never holds for k >= 0 when y[b] < 0, so a null row adds
+ * nothing to any row of dtable (and a class that only appears as a null label gets a zero row). */
+int afd_label_embed_add_fwd(const float* temb, const float* table, const int64_t* y, float* out, int B, int D, int num_classes,
+                            afd_stream_t stream);
 int afd_embed_add_bwd(const float* dout, const int64_t* y, float* dtable, int B, int D, int num_classes, int accumulate,
                       afd_stream_t stream);
 
@@ -357,6 +364,18 @@ int afd_denoise_step(const float* x, const float* eps_pred, const float* noise /
 int afd_denoise_step_dev(const float* x, const float* eps_pred, const float* noise,
                          const float* alpha, const float* alpha_hat, const float* beta, const int64_t* t_dev,
                          float* x_out, long n, afd_stream_t stream);
+/* classifier-free guidance: the guided noise and the denoise update in one pass.  eps2: the (2n)-element output of ONE forward
+ * over [conditional rows ; unconditional rows] (element j at j and n + j).  e = torch.lerp(e_u, e_c, cfg_scale) with ATen's
+ * scalar formula, one rounding per operation (|s| < 0.5: u + s (c - u); otherwise c - (c - u)(1 - s)), then exactly the
+ * afd_denoise_step expression.  x_out may alias x; x_out2 is NULL or a second destination of the same n values (the other
+ * half of the sampler's 2n input buffer).  n: elements of x (n images times the per-image size). */
+int afd_denoise_step_cfg(const float* x, const float* eps2, const float* noise /* NULL => zeros (i == 1) */,
+                         const float* alpha, const float* alpha_hat, const float* beta, int i, float cfg_scale,
+                         float* x_out, float* x_out2, long n, afd_stream_t stream);
+/* same with the step index read from t_dev[0] (graph-replayable) */
+int afd_denoise_step_cfg_dev(const float* x, const float* eps2, const float* noise,
+                             const float* alpha, const float* alpha_hat, const float* beta, const int64_t* t_dev, float cfg_scale,
+                             float* x_out, float* x_out2, long n, afd_stream_t stream);
 int afd_quantize_u8(const float* x, uint8_t* out, long n, afd_stream_t stream);
 
 /* ---- F17 (Config E): scipy.ndimage.rotate(order=3, mode='grid-wrap', prefilter=True) per (H,W) plane ----
