@@ -71,9 +71,12 @@ __device__ __forceinline__ CfgCoef cfg_coef(const float* alpha, const float* alp
   k.small = fabsf(s) < 0.5f;
   return k;
 }
-__device__ __forceinline__ float cfg_update(const CfgCoef& k, float x, float ec, float eu, float nz_in, bool has_noise) {
+__device__ __forceinline__ float cfg_lerp(float s, float one_minus_s, bool small, float ec, float eu) {
   const float d = ec - eu;
-  const float e = k.small ? eu + k.s * d : ec - d * k.one_minus_s;
+  return small ? eu + s * d : ec - d * one_minus_s;
+}
+__device__ __forceinline__ float cfg_update(const CfgCoef& k, float x, float ec, float eu, float nz_in, bool has_noise) {
+  const float e = cfg_lerp(k.s, k.one_minus_s, k.small, ec, eu);
   const float pe = k.c2 * e;
   const float inner = x - pe;
   const float lhs = k.c1 * inner;
@@ -133,6 +136,106 @@ static int launch_denoise_step_cfg(const float* x, const float* eps2, const floa
     hipLaunchKernelGGL(denoise_step_cfg_k, dim3(grid), dim3(256), 0, st, x, eps2, noise, alpha, alpha_hat, beta, i, t_dev, s, x_out,
                        x_out2, n);
   return AFD_OK;
+}
+
+// ---- DDIM (Song et al. 2021): one step t -> t_prev of a strided chain ------------------------------------------------
+// a_t = alpha_hat[t], a_p = alpha_hat[t_prev]; fp32, one rounding per operation, in this order:
+//   x0  = (x - sqrt(1 - a_t) * e) / sqrt(a_t)
+//   r   = (1 - a_p) / (1 - a_t)        q = 1 - a_t / a_p
+//   var = (eta * eta) * (r * q)        sigma = sqrt(var)        dir = sqrt(max((1 - a_p) - var, 0))
+//   out = ((sqrt(a_p) * x0) + (dir * e)) + (noise ? sigma * noise : +0)
+// The division by sqrt(a_t) stays a division (a reciprocal would round differently).  With CFG, e is cfg_lerp of the
+// conditional (j) and unconditional (n + j) halves of eps2 first.  x_out may alias x; x_out2 is optional (nullptr).
+struct DdimCoef {
+  float sq1m_at, sq_at, sq_ap, sigma, dir, s, one_minus_s;
+  bool small;
+};
+__device__ __forceinline__ DdimCoef ddim_coef(const float* alpha_hat, int t, int tp, float eta, float s) {
+  const float a_t = alpha_hat[t], a_p = alpha_hat[tp];
+  DdimCoef k;
+  k.sq1m_at = sqrtf(1.0f - a_t);
+  k.sq_at = sqrtf(a_t);
+  k.sq_ap = sqrtf(a_p);
+  const float r = (1.0f - a_p) / (1.0f - a_t);
+  const float q = 1.0f - a_t / a_p;
+  const float var = (eta * eta) * (r * q);
+  k.sigma = sqrtf(var);
+  k.dir = sqrtf(fmaxf((1.0f - a_p) - var, 0.0f));
+  k.s = s;
+  k.one_minus_s = 1.0f - s;
+  k.small = fabsf(s) < 0.5f;
+  return k;
+}
+__device__ __forceinline__ float ddim_update(const DdimCoef& k, float x, float e, float z, bool has_noise) {
+  const float pe = k.sq1m_at * e;
+  const float x0 = (x - pe) / k.sq_at;
+  const float mean = (k.sq_ap * x0) + (k.dir * e);
+  const float nz = has_noise ? k.sigma * z : 0.0f;
+  return mean + nz;
+}
+template <bool kCfg>
+__device__ __forceinline__ float ddim_eps(const DdimCoef& k, float ec, float eu) {
+  return kCfg ? cfg_lerp(k.s, k.one_minus_s, k.small, ec, eu) : ec;
+}
+
+// 16-byte accesses (n % 4 == 0, every pointer 16-byte aligned); n4 = n / 4.  kCfg: eps holds 2n elements.
+template <bool kCfg>
+__global__ __launch_bounds__(256) void ddim_step_x4_k(const float* x, const float* __restrict__ eps, const float* __restrict__ noise,
+                                                      const float* __restrict__ alpha_hat, int t_arg, int tp_arg,
+                                                      const int64_t* __restrict__ t_dev, const int64_t* __restrict__ tp_dev, float eta,
+                                                      float s, float* x_out, float* x_out2, long n4) {
+  const int t = t_dev ? (int)t_dev[0] : t_arg;                 // device-resident indices: a captured graph replays every step
+  const int tp = tp_dev ? (int)tp_dev[0] : tp_arg;
+  const DdimCoef k = ddim_coef(alpha_hat, t, tp, eta, s);
+  const float4* x4 = reinterpret_cast<const float4*>(x);
+  const float4* ec4 = reinterpret_cast<const float4*>(eps);
+  const float4* eu4 = ec4 + n4;                                // read only when kCfg
+  const float4* nz4 = reinterpret_cast<const float4*>(noise);
+  const bool has_noise = noise != nullptr;
+  AFD_GRID_STRIDE(i, n4) {
+    const float4 xv = x4[i], c = ec4[i];
+    const float4 u = kCfg ? eu4[i] : c;
+    const float4 z = has_noise ? nz4[i] : make_float4(0.f, 0.f, 0.f, 0.f);
+    float4 r;
+    r.x = ddim_update(k, xv.x, ddim_eps<kCfg>(k, c.x, u.x), z.x, has_noise);
+    r.y = ddim_update(k, xv.y, ddim_eps<kCfg>(k, c.y, u.y), z.y, has_noise);
+    r.z = ddim_update(k, xv.z, ddim_eps<kCfg>(k, c.z, u.z), z.z, has_noise);
+    r.w = ddim_update(k, xv.w, ddim_eps<kCfg>(k, c.w, u.w), z.w, has_noise);
+    reinterpret_cast<float4*>(x_out)[i] = r;
+    if (x_out2) reinterpret_cast<float4*>(x_out2)[i] = r;
+  }
+}
+template <bool kCfg>
+__global__ __launch_bounds__(256) void ddim_step_k(const float* x, const float* __restrict__ eps, const float* __restrict__ noise,
+                                                   const float* __restrict__ alpha_hat, int t_arg, int tp_arg,
+                                                   const int64_t* __restrict__ t_dev, const int64_t* __restrict__ tp_dev, float eta,
+                                                   float s, float* x_out, float* x_out2, long n) {
+  const int t = t_dev ? (int)t_dev[0] : t_arg;
+  const int tp = tp_dev ? (int)tp_dev[0] : tp_arg;
+  const DdimCoef k = ddim_coef(alpha_hat, t, tp, eta, s);
+  const bool has_noise = noise != nullptr;
+  AFD_GRID_STRIDE(i, n) {
+    const float e = ddim_eps<kCfg>(k, eps[i], kCfg ? eps[n + i] : 0.0f);
+    const float r = ddim_update(k, x[i], e, has_noise ? noise[i] : 0.0f, has_noise);
+    x_out[i] = r;
+    if (x_out2) x_out2[i] = r;
+  }
+}
+
+template <bool kCfg>
+static void launch_ddim_step(const float* x, const float* eps, const float* noise, const float* alpha_hat, int t, int tp,
+                             const int64_t* t_dev, const int64_t* tp_dev, float eta, float s, float* x_out, float* x_out2, long n,
+                             hipStream_t st) {
+  auto a16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
+  const bool vec = n % 4 == 0 && a16(x) && a16(eps) && a16(x_out) && (!noise || a16(noise)) && (!x_out2 || a16(x_out2));
+  const long work = vec ? n / 4 : n;
+  const int grid = (int)std::min<long>(2048, std::max<long>(1, (work + 255) / 256));      // memory-bound: grid-stride the rest
+  if (vec)
+    hipLaunchKernelGGL(ddim_step_x4_k<kCfg>, dim3(grid), dim3(256), 0, st, x, eps, noise, alpha_hat, t, tp, t_dev, tp_dev, eta, s,
+                       x_out, x_out2, work);
+  else
+    hipLaunchKernelGGL(ddim_step_k<kCfg>, dim3(grid), dim3(256), 0, st, x, eps, noise, alpha_hat, t, tp, t_dev, tp_dev, eta, s,
+                       x_out, x_out2, n);
 }
 
 // ((clamp(x,-1,1) + 1) / 2 * 255).type(uint8): truncation toward zero
@@ -226,6 +329,42 @@ int afd_denoise_step_cfg_dev(const float* x, const float* eps2, const float* noi
   AFD_REQUIRE(x && eps2 && alpha && alpha_hat && beta && t_dev && x_out && n > 0, "afd_denoise_step_cfg_dev: bad argument");
   launch_denoise_step_cfg(x, eps2, noise, alpha, alpha_hat, beta, 0, t_dev, cfg_scale, x_out, x_out2, n, as_stream(st));
   return check_launch("afd_denoise_step_cfg_dev");
+}
+int afd_ddim_step(const float* x, const float* eps, const float* noise, const float* alpha_hat, int t, int t_prev, float eta,
+                  float* x_out, long n, afd_stream_t st) {
+  AFD_REQUIRE(x && eps && alpha_hat && x_out, "afd_ddim_step: x, eps, alpha_hat and x_out must not be NULL");
+  AFD_REQUIRE(n > 0, "afd_ddim_step: n must be positive (got %ld)", n);
+  AFD_REQUIRE(t_prev >= 0 && t_prev < t, "afd_ddim_step: need 0 <= t_prev < t (got t = %d, t_prev = %d)", t, t_prev);
+  AFD_REQUIRE(eta >= 0.0f, "afd_ddim_step: eta must be >= 0");
+  launch_ddim_step<false>(x, eps, noise, alpha_hat, t, t_prev, nullptr, nullptr, eta, 0.0f, x_out, nullptr, n, as_stream(st));
+  return check_launch("afd_ddim_step");
+}
+int afd_ddim_step_dev(const float* x, const float* eps, const float* noise, const float* alpha_hat, const int64_t* t_dev,
+                      const int64_t* t_prev_dev, float eta, float* x_out, long n, afd_stream_t st) {
+  AFD_REQUIRE(x && eps && alpha_hat && t_dev && t_prev_dev && x_out,
+              "afd_ddim_step_dev: x, eps, alpha_hat, t_dev, t_prev_dev and x_out must not be NULL");
+  AFD_REQUIRE(n > 0, "afd_ddim_step_dev: n must be positive (got %ld)", n);
+  AFD_REQUIRE(eta >= 0.0f, "afd_ddim_step_dev: eta must be >= 0");
+  launch_ddim_step<false>(x, eps, noise, alpha_hat, 0, 0, t_dev, t_prev_dev, eta, 0.0f, x_out, nullptr, n, as_stream(st));
+  return check_launch("afd_ddim_step_dev");
+}
+int afd_ddim_step_cfg(const float* x, const float* eps2, const float* noise, const float* alpha_hat, int t, int t_prev, float eta,
+                      float cfg_scale, float* x_out, float* x_out2, long n, afd_stream_t st) {
+  AFD_REQUIRE(x && eps2 && alpha_hat && x_out, "afd_ddim_step_cfg: x, eps2, alpha_hat and x_out must not be NULL");
+  AFD_REQUIRE(n > 0, "afd_ddim_step_cfg: n must be positive (got %ld)", n);
+  AFD_REQUIRE(t_prev >= 0 && t_prev < t, "afd_ddim_step_cfg: need 0 <= t_prev < t (got t = %d, t_prev = %d)", t, t_prev);
+  AFD_REQUIRE(eta >= 0.0f, "afd_ddim_step_cfg: eta must be >= 0");
+  launch_ddim_step<true>(x, eps2, noise, alpha_hat, t, t_prev, nullptr, nullptr, eta, cfg_scale, x_out, x_out2, n, as_stream(st));
+  return check_launch("afd_ddim_step_cfg");
+}
+int afd_ddim_step_cfg_dev(const float* x, const float* eps2, const float* noise, const float* alpha_hat, const int64_t* t_dev,
+                          const int64_t* t_prev_dev, float eta, float cfg_scale, float* x_out, float* x_out2, long n, afd_stream_t st) {
+  AFD_REQUIRE(x && eps2 && alpha_hat && t_dev && t_prev_dev && x_out,
+              "afd_ddim_step_cfg_dev: x, eps2, alpha_hat, t_dev, t_prev_dev and x_out must not be NULL");
+  AFD_REQUIRE(n > 0, "afd_ddim_step_cfg_dev: n must be positive (got %ld)", n);
+  AFD_REQUIRE(eta >= 0.0f, "afd_ddim_step_cfg_dev: eta must be >= 0");
+  launch_ddim_step<true>(x, eps2, noise, alpha_hat, 0, 0, t_dev, t_prev_dev, eta, cfg_scale, x_out, x_out2, n, as_stream(st));
+  return check_launch("afd_ddim_step_cfg_dev");
 }
 int afd_quantize_u8(const float* x, uint8_t* out, long n, afd_stream_t st) {
   AFD_REQUIRE(x && out && n > 0, "afd_quantize_u8: bad argument");

@@ -156,6 +156,130 @@ class Diffusion:
         snaps.append(x)
         return x, snaps
 
+    # DDIM (Song et al. 2021) over a strided subsequence of the timesteps -------------------------------------------------
+    def ddim_timesteps(self, steps):
+        """The S = `steps` timesteps of a DDIM chain, strictly decreasing: tau_k = 1 + (k (T - 2)) // (S - 1) for k = 0 .. S-1,
+        in descending order (S = 1: [T - 1]).  S = T - 1 gives T-1 .. 1, the DDPM chain's own indices; the last tau is 1."""
+        T = self.noise_steps
+        if isinstance(steps, bool) or not isinstance(steps, (int, np.integer)):
+            raise ValueError(f"Diffusion.ddim_timesteps: steps must be an int (got {type(steps).__name__})")
+        S = int(steps)
+        if not 1 <= S <= T - 1:
+            raise ValueError(f"Diffusion.ddim_timesteps: steps must lie in [1, {T - 1}] (got {S})")
+        if S == 1:
+            return [T - 1]
+        return [1 + (k * (T - 2)) // (S - 1) for k in reversed(range(S))]
+
+    def _ddim_pairs(self, steps, eta):
+        """steps (an int S or an explicit strictly decreasing sequence of ints in [1, T-1]) -> [(t, t_prev)], the last
+        t_prev 0.  Raises ValueError for anything else, and for eta < 0."""
+        eta = float(eta)
+        if not eta >= 0:
+            raise ValueError(f"Diffusion: DDIM needs eta >= 0 (got {eta})")
+        if isinstance(steps, (int, np.integer)) and not isinstance(steps, bool):
+            taus = self.ddim_timesteps(steps)
+        else:
+            try:
+                taus = list(steps)
+            except TypeError:
+                raise ValueError(f"Diffusion: steps must be an int or a sequence of ints (got {type(steps).__name__})") from None
+            T = self.noise_steps
+            if not taus or any(isinstance(v, bool) or not isinstance(v, (int, np.integer)) for v in taus):
+                raise ValueError("Diffusion: an explicit steps sequence must be a non-empty sequence of ints")
+            taus = [int(v) for v in taus]
+            if any(not 1 <= v <= T - 1 for v in taus):
+                raise ValueError(f"Diffusion: every step of an explicit steps sequence must lie in [1, {T - 1}] (got {taus})")
+            if any(a <= b for a, b in zip(taus, taus[1:])):
+                raise ValueError(f"Diffusion: an explicit steps sequence must be strictly decreasing (got {taus})")
+        return list(zip(taus, taus[1:] + [0]))
+
+    @staticmethod
+    def ddim_snapshot(t, t_prev):
+        """Whether x is kept as a snapshot after the step t -> t_prev: when the step crosses a multiple of 100.  On the
+        full chain (t_prev = t - 1) this is the DDPM sampler's i % 100 == 0."""
+        return t_prev // 100 < t // 100
+
+    def _ddim_loop(self, model, n, image_channels, pairs, eta, noise_source="reference", graph=None, labels=None, cfg_scale=0.0):
+        """`_loop` over the DDIM steps `pairs` (see `sample`).  x_T is drawn as in `_loop`; with eta > 0 every step but the
+        last draws the noise of n images (`_step_noise`), with eta == 0 none is drawn.  graph: capture one step (forward,
+        noise, ddim_step_dev) and replay it for every step but the last, which runs eagerly."""
+        self._hint(model)
+        try:
+            model.eval()
+            snaps = []
+            with torch.no_grad():
+                x = self._initial_noise(n, image_channels, noise_source)
+                guided = labels is not None and cfg_scale > 0
+                y = labels
+                if guided:
+                    y = torch.cat([labels, torch.full_like(labels, ops.NULL_LABEL)])
+                first = 0
+                if graph and noise_source != "cpu" and len(pairs) > 1:
+                    x = self._ddim_graph_steps(model, x, snaps, pairs[:-1], eta, y, cfg_scale if guided else 0.0)
+                    first = len(pairs) - 1
+                xs2 = torch.cat([x, x]) if guided else None
+                for t, tp in pairs[first:]:
+                    draw = eta > 0 and tp > 0
+                    if guided:
+                        eps2 = model(xs2, self._t_full(2 * n, t, x.device), y)
+                        noise = self._step_noise(x, noise_source) if draw else None
+                        nxt = torch.empty_like(xs2)
+                        ops.ddim_step_cfg(x, eps2, noise, self.alpha_hat, t, tp, eta, cfg_scale, nxt[:n], nxt[n:])
+                        xs2, x = nxt, nxt[:n]
+                    else:
+                        tt = self._t_full(n, t, x.device)
+                        eps = model(x, tt) if y is None else model(x, tt, y)
+                        noise = self._step_noise(x, noise_source) if draw else None
+                        x = ops.ddim_step(x, eps, noise, self.alpha_hat, t, tp, eta)
+                    if self.ddim_snapshot(t, tp):
+                        snaps.append(x)
+        finally:
+            model.train()
+            self._unhint(model)
+        snaps.append(x)
+        return x, snaps
+
+    def _ddim_graph_steps(self, model, x, snaps, pairs, eta, y=None, cfg_scale=0.0):
+        """The DDIM steps `pairs` (all but the chain's last) by replaying one captured step; t_dev (the forward's rows) and
+        t_prev_dev are filled on the host before each replay.  Returns x after the last of them."""
+        n = x.shape[0]
+        guided = cfg_scale > 0
+        noisy = eta > 0
+        t_dev = torch.full((2 * n if guided else n,), pairs[0][0], device=x.device, dtype=torch.long)
+        tp_dev = torch.full((1,), pairs[0][1], device=x.device, dtype=torch.long)
+        xs = torch.cat([x, x]) if guided else x.clone()
+        xh = xs[:n]
+
+        def one_step():
+            if guided:
+                eps2 = model(xs, t_dev, y)
+                noise = torch.randn_like(xh) if noisy else None
+                ops.ddim_step_cfg_dev(xh, eps2, noise, self.alpha_hat, t_dev, tp_dev, eta, cfg_scale, xh, xs[n:])
+                return
+            eps = model(xs, t_dev) if y is None else model(xs, t_dev, y)
+            noise = torch.randn_like(xs) if noisy else None
+            ops.ddim_step_dev(xs, eps, noise, self.alpha_hat, t_dev, tp_dev, eta, xs)            # in place (elementwise)
+
+        side = torch.cuda.Stream()
+        side.wait_stream(torch.cuda.current_stream())
+        keep = xs.clone()
+        rng = torch.cuda.get_rng_state(x.device)
+        with torch.cuda.stream(side):
+            one_step()                                   # warm-up; its effect (and its noise draw) is undone below
+        torch.cuda.current_stream().wait_stream(side)
+        xs.copy_(keep)
+        torch.cuda.set_rng_state(rng, x.device)
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g):
+            one_step()
+        for t, tp in pairs:
+            t_dev.fill_(t)
+            tp_dev.fill_(tp)
+            g.replay()
+            if self.ddim_snapshot(t, tp):
+                snaps.append(xh.clone())
+        return xh.clone()
+
     def _hint(self, model):
         """Tell the model the range of the timesteps this process will pass (all of them in [0, noise_steps)): lets the
         UNet tabulate its time embeddings once per trajectory (unet.UNet._timestep_tables); cleared again when the loop
@@ -220,20 +344,38 @@ class Diffusion:
             raise ValueError(f"Diffusion.sample: expected {n} labels, one per image (got shape {tuple(y.shape)})")
         return y.to(device=self.device, dtype=torch.long).contiguous()
 
+    def _check_ddim(self, where, steps, eta, theta=None):
+        """-> the DDIM (t, t_prev) pairs, or None for the DDPM chain (steps=None)."""
+        if steps is None:
+            if eta:
+                raise ValueError(f"Diffusion.{where}: eta applies to the DDIM sampler only (pass steps=)")
+            return None
+        if theta is not None:
+            raise NotImplementedError(f"Diffusion.{where}: steps (DDIM) together with a rotation (theta) is not supported")
+        return self._ddim_pairs(steps, eta)
+
     def sample(self, model, n, image_channels, theta=None, noise_source="reference", return_float=False, graph=None,
-               labels=None, cfg_scale=0.0):
+               labels=None, cfg_scale=0.0, steps=None, eta=0.0):
         """labels: (n,) integer class labels (NULL_LABEL for an unconditional image) for a UNet(num_classes=K); None = the
         unconditional sampler.  cfg_scale > 0: classifier-free guidance, eps = torch.lerp(eps_uncond, eps_cond, cfg_scale),
         both predictions from ONE forward over 2n rows per step; cfg_scale <= 0: the conditional prediction alone.  The noise
-        drawn (x_T and every step's) is that of the unconditional sampler for the same seed and noise_source."""
+        drawn (x_T and every step's) is that of the unconditional sampler for the same seed and noise_source.
+        steps: None = the full DDPM chain (T - 1 forwards).  An int S (1 <= S <= T - 1) or an explicit strictly decreasing
+        sequence of timesteps in [1, T - 1] selects DDIM over those timesteps (`ddim_timesteps`), S forwards, with
+        eta = 0 deterministic (no noise drawn after x_T) and eta = 1 ancestral.  Snapshots are taken after each step that
+        crosses a multiple of 100 (`ddim_snapshot`), plus the final x.  Not supported together with theta."""
         logging.info(f"Sampling {n} new images....")
         if theta is not None:
             logging.info(f"Theta {theta} provided. Rotation will be applied.")
+        pairs = self._check_ddim("sample", steps, eta, theta)
         if labels is not None:
             labels = self._check_labels(model, n, theta, labels)
         elif cfg_scale:
             raise ValueError("Diffusion.sample: cfg_scale needs class labels")
-        x, snaps = self._loop(model, n, image_channels, theta, noise_source, graph, labels=labels, cfg_scale=float(cfg_scale))
+        if pairs is None:
+            x, snaps = self._loop(model, n, image_channels, theta, noise_source, graph, labels=labels, cfg_scale=float(cfg_scale))
+        else:
+            x, snaps = self._ddim_loop(model, n, image_channels, pairs, float(eta), noise_source, graph, labels, float(cfg_scale))
         self.last_float_snapshots = snaps          # pre-quantisation x at i % 100 == 0 and the final x (parity tests)
         xq = ops.quantize_u8(x)
         rq = ops.quantize_u8(torch.cat(snaps))
@@ -241,13 +383,15 @@ class Diffusion:
             return xq, rq, x
         return xq, rq
 
-    def sample_sharded(self, model, n, image_channels, theta=None, noise_source="reference", group=None, dst=0):
+    def sample_sharded(self, model, n, image_channels, theta=None, noise_source="reference", group=None, dst=0, steps=None):
         """`sample` with the n images partitioned over the ranks of `group` (sampling is embarrassingly parallel per
         image: replicas only, no collective in the loop) and the uint8 results gathered on rank `dst`.
         Every rank must have been seeded alike (as the reference's scripts do with set_seed): each rank draws the noise
         of ALL n images from the same generator stream and keeps its rows, so the gathered (x, result) equal what one rank
         computes for the same seed -- whatever the world size.  Returns (x_u8, result_u8) on `dst`, (None, None) elsewhere;
-        without an initialised process group it is `sample`."""
+        without an initialised process group it is `sample`.  DDIM (steps=) is not supported here: use `sample`."""
+        if steps is not None:
+            raise NotImplementedError("Diffusion.sample_sharded: DDIM (steps=) is not supported; use sample or sample_concurrent")
         if not dist.is_initialized() or dist.get_world_size(group) == 1:
             return self.sample(model, n, image_channels, theta=theta, noise_source=noise_source)
         world, rank = dist.get_world_size(group), dist.get_rank(group)
@@ -266,12 +410,15 @@ class Diffusion:
         per_rank = [rq[offs[r]:offs[r + 1]].reshape(S, counts[r], *rq.shape[1:]) for r in range(world)]
         return xq, torch.cat(per_rank, dim=1).reshape(S * n, *rq.shape[1:])
 
-    def sample_rotation_sweep_sharded(self, model, n, image_channels, thetas, group=None, dst=0):
+    def sample_rotation_sweep_sharded(self, model, n, image_channels, thetas, group=None, dst=0, steps=None):
         """Config E sweep (ddpm_tasks.py:346-369) with the ANGLES partitioned over the ranks (BASELINE config 5): each rank
         runs `sample_rotation_sweep` on its contiguous share of `thetas`; since that draws the n-image noise of every step
         once and shares it between its angles, all ranks (seeded alike, ddpm_tasks.py:365) consume the identical noise
         stream however many angles they hold -- "same seed per theta" holds across the shards.  Gathers on `dst`:
-        ([x_u8 per angle], [result_u8 per angle]) in the order of `thetas`; (None, None) elsewhere."""
+        ([x_u8 per angle], [result_u8 per angle]) in the order of `thetas`; (None, None) elsewhere.  A rotation by theta / T
+        per step has no meaning on a strided chain: DDIM (steps=) is not supported."""
+        if steps is not None:
+            raise NotImplementedError("Diffusion.sample_rotation_sweep_sharded: DDIM (steps=) is not supported with rotations")
         thetas = list(thetas)
         if not dist.is_initialized() or dist.get_world_size(group) == 1:
             return self.sample_rotation_sweep(model, n, image_channels, thetas)
@@ -289,14 +436,17 @@ class Diffusion:
             return None, None
         return list(xa.reshape(K, n, *shape)), list(ra.reshape(K, S * n, *shape))
 
-    def sample_rotation_sweep(self, model, n, image_channels, thetas):
+    def sample_rotation_sweep(self, model, n, image_channels, thetas, steps=None):
         """Config E sweep (ddpm_tasks.py:346-369) as ONE batched trajectory.  The reference re-seeds before every angle,
         so every angle consumes the identical noise stream and only the per-step rotation differs: here the
         len(thetas) * n images ride one batch, every noise draw (x_T from the CPU generator, the per-step noise from the
         device generator, n images each: the same draws in the same order as one `sample(n, theta)` call after the same
         seeding) is shared by all angles, and each angle's slice is rotated by its own theta / T after every step.
         One UNet forward per step instead of len(thetas): at n = 4 the sweep is launch-bound, so this is ~9x faster for
-        the reference's 9 angles.  Returns ([x_u8 per angle], [result_u8 per angle]) like `rotation_results`."""
+        the reference's 9 angles.  Returns ([x_u8 per angle], [result_u8 per angle]) like `rotation_results`.  A rotation by
+        theta / T per step has no meaning on a strided chain: DDIM (steps=) is not supported."""
+        if steps is not None:
+            raise NotImplementedError("Diffusion.sample_rotation_sweep: DDIM (steps=) is not supported with rotations")
         K = len(thetas)
         if K == 0:                                       # (a rank of the sharded sweep that holds no angle)
             return [], []
@@ -324,7 +474,7 @@ class Diffusion:
             results.append(ops.quantize_u8(torch.cat(snaps[k] + [xk])))
         return xs, results
 
-    def sample_concurrent(self, model, n, image_channels, batch=256, streams=4, noise_fn=None, graph=False):
+    def sample_concurrent(self, model, n, image_channels, batch=256, streams=4, noise_fn=None, graph=False, steps=None, eta=0.0):
         """Throughput form of `sample` for many images: the n images are cut into batches of `batch` and `streams`
         of those trajectories run CONCURRENTLY, each on its own HIP stream (the trajectories are independent: sampling
         is embarrassingly parallel per image).  One 256-image forward leaves CUs idle in its small layers; a second
@@ -333,11 +483,27 @@ class Diffusion:
         concatenated.  Noise comes from the device generator (or noise_fn(batch_index, i, x) for tests).
         graph=True: every trajectory's denoise step (UNet forward + update; the noise is drawn into a static buffer just
         before) is captured once into its own hipGraph and replayed on its stream, which takes the host's ~170 launches
-        per forward out of the loop."""
+        per forward out of the loop.
+        steps / eta: DDIM over a strided chain, as for `sample`; noise_fn is then called with i = the step's t (and not at
+        all after x_T when eta == 0)."""
+        pairs = self._check_ddim("sample_concurrent", steps, eta)
+        run = self._sample_concurrent_graphs if graph else self._sample_concurrent_eager
         self._hint(model)
         model.eval()
-        if graph:
-            return self._sample_concurrent_graphs(model, n, image_channels, batch, streams, noise_fn)
+        if pairs is None:                                    # the DDPM chain
+            out = run(model, n, image_channels, batch, streams, noise_fn, [(i, i - 1) for i in reversed(range(1, self.noise_steps))])
+            model.train()
+            self._unhint(model)
+            return out
+        try:
+            return run(model, n, image_channels, batch, streams, noise_fn, pairs, float(eta))
+        finally:
+            model.train()
+            self._unhint(model)
+
+    def _sample_concurrent_eager(self, model, n, image_channels, batch, streams, noise_fn, pairs, eta=None):
+        """pairs: the (t, t_prev) steps; eta None = DDPM updates (pairs are then (i, i - 1)), else DDIM with that eta."""
+        ddim = eta is not None
         sizes = [min(batch, n - o) for o in range(0, n, batch)]
         pool = [torch.cuda.Stream() for _ in range(max(1, min(streams, len(sizes))))]
         cur = torch.cuda.current_stream()
@@ -352,14 +518,18 @@ class Diffusion:
                     with torch.cuda.stream(st):
                         xs[k] = torch.randn(sizes[k], image_channels, self.img_size, self.img_size, device=self.device) \
                             if noise_fn is None else noise_fn(k, self.noise_steps, (sizes[k], image_channels, self.img_size, self.img_size))
-                for i in reversed(range(1, self.noise_steps)):
+                for i, tp in pairs:
+                    draw = tp > 0 and (not ddim or eta > 0)
                     for k in group:                                  # one denoise step of every trajectory of the group
                         with torch.cuda.stream(pool[k - g0]):
                             x = xs[k]
                             eps = model(x, self._t_full(x.shape[0], i, x.device))
-                            noise = None if i == 1 else (torch.randn_like(x) if noise_fn is None else noise_fn(k, i, x.shape))
-                            x = ops.denoise_step(x, eps, noise, self.alpha, self.alpha_hat, self.beta, i)
-                            if i % 100 == 0:
+                            noise = None if not draw else (torch.randn_like(x) if noise_fn is None else noise_fn(k, i, x.shape))
+                            if ddim:
+                                x = ops.ddim_step(x, eps, noise, self.alpha_hat, i, tp, eta)
+                            else:
+                                x = ops.denoise_step(x, eps, noise, self.alpha, self.alpha_hat, self.beta, i)
+                            if self.ddim_snapshot(i, tp):
                                 snaps[k].append(x)
                             xs[k] = x
                 for k in group:
@@ -368,19 +538,19 @@ class Diffusion:
                         xs_out[k] = ops.quantize_u8(xs[k])
                         snaps_out[k] = ops.quantize_u8(torch.cat(snaps[k]))
                     cur.wait_stream(pool[k - g0])
-        model.train()
-        self._unhint(model)
         for t in xs_out + snaps_out:
             t.record_stream(cur)
         return torch.cat(xs_out), torch.cat(snaps_out)
 
-    def _sample_concurrent_graphs(self, model, n, image_channels, batch, streams, noise_fn):
+    def _sample_concurrent_graphs(self, model, n, image_channels, batch, streams, noise_fn, pairs, eta=None):
+        ddim = eta is not None
+        noisy = not ddim or eta > 0
         sizes = [min(batch, n - o) for o in range(0, n, batch)]
         pool = [torch.cuda.Stream() for _ in range(max(1, min(streams, len(sizes))))]
         cur = torch.cuda.current_stream()
         xs_out, snaps_out = [None] * len(sizes), [None] * len(sizes)
         shape = (image_channels, self.img_size, self.img_size)
-        slots = {}                                           # (batch size, stream) -> (x, t, noise, graph), captured once
+        slots = {}                                           # (batch size, stream) -> (x, t, t_prev, noise, graph), captured once
         with torch.no_grad():
             for g0 in range(0, len(sizes), len(pool)):
                 group = list(range(g0, min(g0 + len(pool), len(sizes))))
@@ -393,36 +563,47 @@ class Diffusion:
                         if key not in slots:
                             xs = torch.zeros(sizes[k], *shape, device=self.device)
                             t_dev = torch.full((sizes[k],), self.noise_steps - 1, device=self.device, dtype=torch.long)
-                            nz = torch.zeros_like(xs)
+                            tp_dev = torch.full((1,), pairs[0][1], device=self.device, dtype=torch.long) if ddim else None
+                            nz = torch.zeros_like(xs) if noisy else None
 
-                            def one_step(xs=xs, t_dev=t_dev, nz=nz):
+                            def one_step(xs=xs, t_dev=t_dev, tp_dev=tp_dev, nz=nz):
                                 eps = model(xs, t_dev)
-                                ops.denoise_step_dev(xs, eps, nz, self.alpha, self.alpha_hat, self.beta, t_dev, xs)
+                                if ddim:
+                                    ops.ddim_step_dev(xs, eps, nz, self.alpha_hat, t_dev, tp_dev, eta, xs)
+                                else:
+                                    ops.denoise_step_dev(xs, eps, nz, self.alpha, self.alpha_hat, self.beta, t_dev, xs)
                             one_step()                       # warm-up outside capture (allocator, cached weight transforms)
                             st.synchronize()
                             g = torch.cuda.CUDAGraph()
                             with torch.cuda.graph(g, stream=st):
                                 one_step()
-                            slots[key] = (xs, t_dev, nz, g)
+                            slots[key] = (xs, t_dev, tp_dev, nz, g)
                         xs = slots[key][0]
                         xs.copy_(torch.randn(sizes[k], *shape, device=self.device) if noise_fn is None
                                  else noise_fn(k, self.noise_steps, (sizes[k], *shape)))
                     state[k] = slots[key]
-                for i in reversed(range(1, self.noise_steps)):
+                for i, tp in pairs:
                     for k in group:
-                        xs, t_dev, nz, g = state[k]
+                        xs, t_dev, tp_dev, nz, g = state[k]
                         with torch.cuda.stream(pool[k - g0]):
-                            if i > 1:
+                            if tp > 0:
                                 t_dev.fill_(i)
-                                if noise_fn is None:
+                                if tp_dev is not None:
+                                    tp_dev.fill_(tp)
+                                if nz is None:
+                                    pass
+                                elif noise_fn is None:
                                     nz.normal_()
                                 else:
                                     nz.copy_(noise_fn(k, i, xs.shape))
                                 g.replay()
                             else:                            # the last step adds no noise (ddpm_models.py:370-373)
-                                eps = model(xs, self._t_full(xs.shape[0], 1, xs.device))
-                                xs.copy_(ops.denoise_step(xs, eps, None, self.alpha, self.alpha_hat, self.beta, 1))
-                            if i % 100 == 0:
+                                eps = model(xs, self._t_full(xs.shape[0], i, xs.device))
+                                if ddim:
+                                    xs.copy_(ops.ddim_step(xs, eps, None, self.alpha_hat, i, 0, eta))
+                                else:
+                                    xs.copy_(ops.denoise_step(xs, eps, None, self.alpha, self.alpha_hat, self.beta, 1))
+                            if self.ddim_snapshot(i, tp):
                                 snaps[k].append(xs.clone())
                 for k in group:
                     with torch.cuda.stream(pool[k - g0]):
@@ -430,19 +611,25 @@ class Diffusion:
                         xs_out[k] = ops.quantize_u8(xs)
                         snaps_out[k] = ops.quantize_u8(torch.cat(snaps[k] + [xs]))
                     cur.wait_stream(pool[k - g0])
-        model.train()
-        self._unhint(model)
         for t in xs_out + snaps_out:
             t.record_stream(cur)
         return torch.cat(xs_out), torch.cat(snaps_out)
 
-    def revert(self, model, n, image_channels, noise_source="reference", graph=None):
+    def revert(self, model, n, image_channels, noise_source="reference", graph=None, steps=None, eta=0.0):
+        """steps / eta: DDIM over a strided chain, as for `sample`."""
         logging.info(f"Sampling {n} new images....")
-        _, snaps = self._loop(model, n, image_channels, None, noise_source, graph)
+        pairs = self._check_ddim("revert", steps, eta)
+        if pairs is None:
+            _, snaps = self._loop(model, n, image_channels, None, noise_source, graph)
+        else:
+            _, snaps = self._ddim_loop(model, n, image_channels, pairs, float(eta), noise_source, graph)
         return ops.quantize_u8(torch.cat(snaps))
 
     # under development in the reference (:388-419); kept as a host-driven loop over the HIP step
-    def sample_shift(self, model, n, image_channels, shift=None, noise_source="reference"):
+    def sample_shift(self, model, n, image_channels, shift=None, noise_source="reference", steps=None):
+        """The shift schedule is laid out over the full chain: DDIM (steps=) is not supported."""
+        if steps is not None:
+            raise NotImplementedError("Diffusion.sample_shift: DDIM (steps=) is not supported")
         logging.info(f"Sampling {n} new images....")
         if shift == 0:
             shift = None

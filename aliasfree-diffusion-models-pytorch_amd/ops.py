@@ -1158,6 +1158,73 @@ def denoise_step_cfg_dev(x, eps2, noise, alpha, alpha_hat, beta, t_dev, cfg_scal
     return out
 
 
+def _ddim_args(what, x, eps, noise, alpha_hat, out, out2=None, guided=False):
+    _chk(x, eps, noise, alpha_hat, out, out2)
+    n = x.numel()
+    ne = 2 * n if guided else n
+    if eps.numel() != ne:
+        raise AfdError(f"afdm: {what} needs eps{'2' if guided else ''} of {ne} elements (got {eps.numel()})")
+    for o in (x, eps, noise, alpha_hat, out, out2):
+        if o is not None and not o.is_contiguous():
+            raise AfdError(f"afdm: {what}: every tensor must be contiguous")
+        if o is not None and o is not eps and o is not alpha_hat and o.numel() != n:
+            raise AfdError(f"afdm: {what}: x / noise / outputs must hold {n} elements")
+    return n
+
+
+def _ddim_host_t(what, alpha_hat, t, t_prev, eta):
+    t, t_prev, eta = int(t), int(t_prev), float(eta)
+    if not 0 <= t_prev < t < alpha_hat.numel():
+        raise AfdError(f"afdm: {what} needs 0 <= t_prev < t < {alpha_hat.numel()} (got t = {t}, t_prev = {t_prev})")
+    if not eta >= 0:
+        raise AfdError(f"afdm: {what} needs eta >= 0 (got {eta})")
+    return t, t_prev, eta
+
+
+def _ddim_dev_t(what, t_dev, t_prev_dev):
+    for v in (t_dev, t_prev_dev):
+        if not v.is_cuda or v.dtype != torch.long or v.numel() < 1:
+            raise AfdError(f"afdm: {what}: t_dev / t_prev_dev must be int64 device tensors (element 0 is read)")
+
+
+def ddim_step(x, eps, noise, alpha_hat, t, t_prev, eta, out=None):
+    """DDIM update t -> t_prev (include/afd.h: afd_ddim_step gives the exact expression).  noise: None (the last step, or
+    eta = 0) or n standard-normal values scaled by sigma.  `out` may be x (in place)."""
+    out = torch.empty_like(x) if out is None else out
+    n = _ddim_args("DDIM step", x, eps, noise, alpha_hat, out)
+    t, t_prev, eta = _ddim_host_t("DDIM step", alpha_hat, t, t_prev, eta)
+    lib().afd_ddim_step(_p(x), _p(eps), _p(noise), _p(alpha_hat), t, t_prev, eta, _p(out), n, _stream())
+    return out
+
+
+def ddim_step_dev(x, eps, noise, alpha_hat, t_dev, t_prev_dev, eta, out):
+    """ddim_step with t = t_dev[0] and t_prev = t_prev_dev[0] read on the device (graph-replayable)."""
+    n = _ddim_args("DDIM step", x, eps, noise, alpha_hat, out)
+    _ddim_dev_t("DDIM step", t_dev, t_prev_dev)
+    lib().afd_ddim_step_dev(_p(x), _p(eps), _p(noise), _p(alpha_hat), _p(t_dev), _p(t_prev_dev), float(eta), _p(out), n, _stream())
+    return out
+
+
+def ddim_step_cfg(x, eps2, noise, alpha_hat, t, t_prev, eta, cfg_scale, out=None, out2=None):
+    """Classifier-free guided DDIM update: e = torch.lerp(eps2[n:], eps2[:n], cfg_scale), then exactly `ddim_step(x, e, ...)`,
+    in one launch.  `out` may be x (in place); `out2` (optional) receives the same values."""
+    out = torch.empty_like(x) if out is None else out
+    n = _ddim_args("guided DDIM step", x, eps2, noise, alpha_hat, out, out2, guided=True)
+    t, t_prev, eta = _ddim_host_t("guided DDIM step", alpha_hat, t, t_prev, eta)
+    lib().afd_ddim_step_cfg(_p(x), _p(eps2), _p(noise), _p(alpha_hat), t, t_prev, eta, float(cfg_scale), _p(out), _p(out2), n,
+                            _stream())
+    return out
+
+
+def ddim_step_cfg_dev(x, eps2, noise, alpha_hat, t_dev, t_prev_dev, eta, cfg_scale, out, out2=None):
+    """ddim_step_cfg with the step indices read on the device (graph-replayable)."""
+    n = _ddim_args("guided DDIM step", x, eps2, noise, alpha_hat, out, out2, guided=True)
+    _ddim_dev_t("guided DDIM step", t_dev, t_prev_dev)
+    lib().afd_ddim_step_cfg_dev(_p(x), _p(eps2), _p(noise), _p(alpha_hat), _p(t_dev), _p(t_prev_dev), float(eta), float(cfg_scale),
+                                _p(out), _p(out2), n, _stream())
+    return out
+
+
 def quantize_u8(x):
     _chk(x)
     x = _c(x)

@@ -102,9 +102,14 @@ def ddpm_run(params):
         save_dataset_MNIST(tr_dir, _loader(name, args)[1])
     else:
         print("skipped saving training dataset")
+    # optional DDIM for the FID/KID image set only: params["sample_steps"] (S, or an explicit list of timesteps) and
+    # params["sample_eta"] (default 0, deterministic); without them the full DDPM chain runs as before
+    gen_kw = {}
+    if params.get("sample_steps") is not None:
+        gen_kw = {"steps": params["sample_steps"], "eta": params.get("sample_eta", 0.0)}
     for start in np.arange(0, params["gen_total"], params["gen_per_batch"]):
         fileno = np.arange(start, start + params["gen_per_batch"], 1)
-        xg, _ = diffusion.sample(model, n=params["gen_per_batch"], image_channels=args.image_channels)
+        xg, _ = diffusion.sample(model, n=params["gen_per_batch"], image_channels=args.image_channels, **gen_kw)
         save_gen_images(gen_dir, xg, fileno)
     make_collage(gen_dir, gen_dir, params["collage_n_per_image"], params["collage_n"], args.image_size)
     torch.cuda.empty_cache()

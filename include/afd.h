@@ -376,6 +376,28 @@ int afd_denoise_step_cfg(const float* x, const float* eps2, const float* noise /
 int afd_denoise_step_cfg_dev(const float* x, const float* eps2, const float* noise,
                              const float* alpha, const float* alpha_hat, const float* beta, const int64_t* t_dev, float cfg_scale,
                              float* x_out, float* x_out2, long n, afd_stream_t stream);
+/* DDIM (Song et al. 2021): one step t -> t_prev of a strided chain, for a model trained on the eps-objective.
+ * a_t = alpha_hat[t], a_p = alpha_hat[t_prev].  fp32 with one IEEE rounding per operation (no FMA contraction, correctly
+ * rounded / and sqrt), evaluated in exactly this order:
+ *   x0  = (x - sqrt(1 - a_t) * eps) / sqrt(a_t)
+ *   r   = (1 - a_p) / (1 - a_t)          q = 1 - a_t / a_p
+ *   var = (eta * eta) * (r * q)          sigma = sqrt(var)          dir = sqrt(max((1 - a_p) - var, 0))
+ *   out = ((sqrt(a_p) * x0) + (dir * eps)) + (noise ? sigma * noise : +0)
+ * eta = 0: deterministic; eta = 1: ancestral.  noise is NULL for the last step of a chain (and for every step when eta = 0).
+ * Requires 0 <= t_prev < t (host form), eta >= 0, n > 0.  x_out may alias x.  n: elements of x. */
+int afd_ddim_step(const float* x, const float* eps, const float* noise /* NULL => none */, const float* alpha_hat, int t, int t_prev,
+                  float eta, float* x_out, long n, afd_stream_t stream);
+/* same with t = t_dev[0] and t_prev = t_prev_dev[0] read on the device (graph-replayable; the indices are not checked) */
+int afd_ddim_step_dev(const float* x, const float* eps, const float* noise, const float* alpha_hat, const int64_t* t_dev,
+                      const int64_t* t_prev_dev, float eta, float* x_out, long n, afd_stream_t stream);
+/* classifier-free guided DDIM step: eps2 as for afd_denoise_step_cfg (conditional element j at j, unconditional at n + j),
+ * eps = torch.lerp(e_u, e_c, cfg_scale) with the same scalar formula, then exactly the afd_ddim_step expression.  x_out may
+ * alias x; x_out2 is NULL or a second destination of the same n values. */
+int afd_ddim_step_cfg(const float* x, const float* eps2, const float* noise, const float* alpha_hat, int t, int t_prev, float eta,
+                      float cfg_scale, float* x_out, float* x_out2, long n, afd_stream_t stream);
+int afd_ddim_step_cfg_dev(const float* x, const float* eps2, const float* noise, const float* alpha_hat, const int64_t* t_dev,
+                          const int64_t* t_prev_dev, float eta, float cfg_scale, float* x_out, float* x_out2, long n,
+                          afd_stream_t stream);
 int afd_quantize_u8(const float* x, uint8_t* out, long n, afd_stream_t stream);
 
 /* ---- F17 (Config E): scipy.ndimage.rotate(order=3, mode='grid-wrap', prefilter=True) per (H,W) plane ----
