@@ -293,6 +293,104 @@ __global__ void adamw_step_k(float* __restrict__ p, const float* __restrict__ g,
   }
 }
 
+// ---- EMA of the weights (training.EMA, modules/ddpm_utils.py:26-51) -------------------------------------------------------
+// ema' = copy ? p : (ema * beta) + (p * omb), three roundings in that order (torch's `old * beta + (1 - beta) * new` on fp32
+// tensors; omb = float(1.0 - beta) formed in double on the host).  VEC: every pointer 16-byte aligned -> float4 accesses.
+__device__ __forceinline__ float ema_rule(float e, float p, int copy, float beta, float omb) {
+  if (copy) return p;
+  const float l = e * beta, r = p * omb;
+  return l + r;
+}
+template <bool VEC>
+__device__ __forceinline__ void ema_range(float* __restrict__ ema, const float* __restrict__ p, long lo, long hi, int copy,
+                                          float beta, float omb) {
+  const long tid = blockIdx.x * (long)blockDim.x + threadIdx.x, stride = (long)gridDim.x * blockDim.x;
+  long s = lo;
+  if (VEC && (lo & 3) == 0) {                   // lo % 4 == 0 keeps the 16-byte alignment of the base pointers
+    const long n4 = (hi - lo) >> 2;
+    float4* e4 = reinterpret_cast<float4*>(ema + lo);
+    const float4* p4 = reinterpret_cast<const float4*>(p + lo);
+    for (long k = tid; k < n4; k += stride) {
+      const float4 pv = p4[k];
+      float4 ev = e4[k];
+      ev.x = ema_rule(ev.x, pv.x, copy, beta, omb); ev.y = ema_rule(ev.y, pv.y, copy, beta, omb);
+      ev.z = ema_rule(ev.z, pv.z, copy, beta, omb); ev.w = ema_rule(ev.w, pv.w, copy, beta, omb);
+      e4[k] = ev;
+    }
+    s = lo + 4 * n4;
+  }
+  for (long i = s + tid; i < hi; i += stride) ema[i] = ema_rule(ema[i], p[i], copy, beta, omb);
+}
+template <bool VEC>
+__global__ void ema_step_k(float* __restrict__ ema, const float* __restrict__ p, long n, int copy, float beta, float omb) {
+  ema_range<VEC>(ema, p, 0, n, copy, beta, omb);
+}
+
+// adamw_tick_k's arithmetic, plus the EMA's call counter: ema_state = {calls, copy}; copy = calls < start, then ++calls
+// (the order of EMA.step_ema).  Device-resident so that a replayed step crosses `start` where the eager one would.
+__global__ void adamw_ema_tick_k(float* state, float b1, float b2, int* ema_state, int start) {
+  const double step = (double)state[0] + 1.0;
+  state[0] = (float)step;
+  state[1] = (float)(1.0 - pow((double)b1, step));
+  state[2] = (float)(1.0 - pow((double)b2, step));
+  const int calls = ema_state[0];
+  ema_state[1] = calls < start ? 1 : 0;
+  ema_state[0] = calls + 1;
+}
+
+// one AdamW element, the expressions and order of adamw_step_k
+__device__ __forceinline__ void adamw_elem(float& p, float g, float& m, float& v, float gscale, float decay, float b1, float b2,
+                                           float step_size, float inv_sqrt_bc2, float eps) {
+  const float gi = g * gscale;
+  const float pi = p * decay;
+  const float mi = m + (gi - m) * (1.0f - b1);
+  const float vi = v * b2 + gi * gi * (1.0f - b2);
+  const float denom = sqrtf(vi) * inv_sqrt_bc2 + eps;
+  p = pi - step_size * (mi / denom);
+  m = mi; v = vi;
+}
+
+// AdamW over [0, n_active) with the EMA rule applied to the NEW p, then the EMA rule alone over [n_active, n_ema) (FlatParams'
+// tail: parameters the optimiser never touches, which the reference's EMA still walks).  One pass: p, g, m, v, ema streamed once.
+template <bool VEC>
+__global__ void adamw_ema_step_k(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
+                                 long n_active, const float* __restrict__ state, float lr, float b1, float b2, float eps, float wd,
+                                 float gscale, float* __restrict__ ema, long n_ema, const int* __restrict__ ema_state, float beta,
+                                 float omb) {
+  const float bc1 = state[1], bc2 = state[2];
+  const float step_size = lr / bc1, inv_sqrt_bc2 = 1.0f / sqrtf(bc2), decay = 1.0f - lr * wd;
+  const int copy = ema_state[1];
+  const long tid = blockIdx.x * (long)blockDim.x + threadIdx.x, stride = (long)gridDim.x * blockDim.x;
+  long s = 0;
+  if (VEC) {
+    const long n4 = n_active >> 2;
+    for (long k = tid; k < n4; k += stride) {
+      float4 pv = reinterpret_cast<const float4*>(p)[k];
+      const float4 gv = reinterpret_cast<const float4*>(g)[k];
+      float4 mv = reinterpret_cast<const float4*>(m)[k], vv = reinterpret_cast<const float4*>(v)[k];
+      float4 ev = reinterpret_cast<const float4*>(ema)[k];
+      adamw_elem(pv.x, gv.x, mv.x, vv.x, gscale, decay, b1, b2, step_size, inv_sqrt_bc2, eps);
+      adamw_elem(pv.y, gv.y, mv.y, vv.y, gscale, decay, b1, b2, step_size, inv_sqrt_bc2, eps);
+      adamw_elem(pv.z, gv.z, mv.z, vv.z, gscale, decay, b1, b2, step_size, inv_sqrt_bc2, eps);
+      adamw_elem(pv.w, gv.w, mv.w, vv.w, gscale, decay, b1, b2, step_size, inv_sqrt_bc2, eps);
+      ev.x = ema_rule(ev.x, pv.x, copy, beta, omb); ev.y = ema_rule(ev.y, pv.y, copy, beta, omb);
+      ev.z = ema_rule(ev.z, pv.z, copy, beta, omb); ev.w = ema_rule(ev.w, pv.w, copy, beta, omb);
+      reinterpret_cast<float4*>(p)[k] = pv;
+      reinterpret_cast<float4*>(m)[k] = mv;
+      reinterpret_cast<float4*>(v)[k] = vv;
+      reinterpret_cast<float4*>(ema)[k] = ev;
+    }
+    s = 4 * n4;
+  }
+  for (long i = s + tid; i < n_active; i += stride) {
+    float pi = p[i], mi = m[i], vi = v[i];
+    adamw_elem(pi, g[i], mi, vi, gscale, decay, b1, b2, step_size, inv_sqrt_bc2, eps);
+    p[i] = pi; m[i] = mi; v[i] = vi;
+    ema[i] = ema_rule(ema[i], pi, copy, beta, omb);
+  }
+  ema_range<VEC>(ema, p, n_active, n_ema, copy, beta, omb);
+}
+
 }  // namespace afd
 using namespace afd;
 
@@ -393,6 +491,43 @@ int afd_adamw_step(float* p, const float* g, float* m, float* v, long n, const f
   AFD_REQUIRE(p && g && m && v && state && n > 0, "afd_adamw_step: bad argument");
   hipLaunchKernelGGL(adamw_step_k, dim3(gs_grid(n)), dim3(256), 0, as_stream(st), p, g, m, v, n, state, lr, b1, b2, eps, wd, gscale);
   return check_launch("afd_adamw_step");
+}
+
+static inline bool aligned16(const void* q) { return ((uintptr_t)q & 15) == 0; }
+static inline bool beta_ok(float beta, float omb) { return beta >= 0.0f && beta <= 1.0f && omb >= 0.0f && omb <= 1.0f; }
+int afd_ema_step(float* ema, const float* p, long n, int copy, float beta, float one_minus_beta, afd_stream_t st) {
+  AFD_REQUIRE(ema && p, "afd_ema_step: ema or p is NULL");
+  AFD_REQUIRE(n > 0, "afd_ema_step: n must be positive (got %ld)", n);
+  AFD_REQUIRE(beta_ok(beta, one_minus_beta), "afd_ema_step: beta and 1 - beta must lie in [0, 1] (got %g, %g)", (double)beta,
+              (double)one_minus_beta);
+  const int c = copy != 0;
+  if (aligned16(ema) && aligned16(p))
+    hipLaunchKernelGGL(ema_step_k<true>, dim3(gs_grid((n + 3) / 4)), dim3(256), 0, as_stream(st), ema, p, n, c, beta, one_minus_beta);
+  else
+    hipLaunchKernelGGL(ema_step_k<false>, dim3(gs_grid(n)), dim3(256), 0, as_stream(st), ema, p, n, c, beta, one_minus_beta);
+  return check_launch("afd_ema_step");
+}
+int afd_adamw_ema_tick(float* adam_state, float b1, float b2, int* ema_state, int start, afd_stream_t st) {
+  AFD_REQUIRE(adam_state && ema_state, "afd_adamw_ema_tick: adam_state or ema_state is NULL");
+  AFD_REQUIRE(start >= 0, "afd_adamw_ema_tick: start must be >= 0 (got %d)", start);
+  hipLaunchKernelGGL(adamw_ema_tick_k, dim3(1), dim3(1), 0, as_stream(st), adam_state, b1, b2, ema_state, start);
+  return check_launch("afd_adamw_ema_tick");
+}
+int afd_adamw_ema_step(float* p, const float* g, float* m, float* v, long n_active, const float* adam_state, float lr, float b1,
+                       float b2, float eps, float wd, float gscale, float* ema, long n_ema, const int* ema_state, float beta,
+                       float one_minus_beta, afd_stream_t st) {
+  AFD_REQUIRE(p && g && m && v && adam_state && ema && ema_state, "afd_adamw_ema_step: a pointer is NULL");
+  AFD_REQUIRE(n_active > 0 && n_ema > 0, "afd_adamw_ema_step: n_active and n_ema must be positive (got %ld, %ld)", n_active, n_ema);
+  AFD_REQUIRE(n_active <= n_ema, "afd_adamw_ema_step: n_active > n_ema (%ld > %ld)", n_active, n_ema);
+  AFD_REQUIRE(beta_ok(beta, one_minus_beta), "afd_adamw_ema_step: beta and 1 - beta must lie in [0, 1] (got %g, %g)",
+              (double)beta, (double)one_minus_beta);
+  if (aligned16(p) && aligned16(g) && aligned16(m) && aligned16(v) && aligned16(ema))
+    hipLaunchKernelGGL(adamw_ema_step_k<true>, dim3(gs_grid((n_ema + 3) / 4)), dim3(256), 0, as_stream(st), p, g, m, v, n_active,
+                       adam_state, lr, b1, b2, eps, wd, gscale, ema, n_ema, ema_state, beta, one_minus_beta);
+  else
+    hipLaunchKernelGGL(adamw_ema_step_k<false>, dim3(gs_grid(n_ema)), dim3(256), 0, as_stream(st), p, g, m, v, n_active,
+                       adam_state, lr, b1, b2, eps, wd, gscale, ema, n_ema, ema_state, beta, one_minus_beta);
+  return check_launch("afd_adamw_ema_step");
 }
 
 }  // extern "C"

@@ -12,7 +12,7 @@ import torch
 
 from .data import get_data, get_data_MNIST, make_collage, save_dataset_MNIST, save_gen_images
 from .diffusion import Diffusion
-from .training import argument, set_seed, train
+from .training import argument, ema_path, set_seed, train
 from .unet import UNet
 
 
@@ -35,6 +35,11 @@ def ddpm_run(params):
     args.image_channels, args.device, args.lr = params["image_channels"], params["device"], params["lr"]
     args.noise_steps, args.image_gen_n = params["noise_steps"], params["image_gen_per_epoch"]
     args.dataset_path = params["dataset_dir"]
+    # optional EMA of the weights (EMA(ema_beta), step_start_ema = ema_start): train() keeps it and saves it beside the
+    # checkpoint; the FID/KID image set is then drawn from it.  Without the keys nothing changes.
+    use_ema = params.get("ema_beta") is not None
+    if use_ema:
+        args.ema_beta, args.ema_start = params["ema_beta"], params.get("ema_start", 2000)
     cwd = os.getcwd()
     modelpath = os.path.join(cwd, f"models/DDPM_Uncondtional_{name}_{v}/ckpt_{name}_{v}.pt")
     f_settings = _f_settings(params)
@@ -107,14 +112,22 @@ def ddpm_run(params):
     gen_kw = {}
     if params.get("sample_steps") is not None:
         gen_kw = {"steps": params["sample_steps"], "eta": params.get("sample_eta", 0.0)}
+    gen_model = model
+    if use_ema:
+        gen_model = UNet(c_in=args.image_channels, c_out=args.image_channels, image_size=args.image_size, f_settings=f_settings,
+                         device=args.device, variant=v).to(args.device)
+        gen_model.load_state_dict(torch.load(ema_path(modelpath), weights_only=True))
     for start in np.arange(0, params["gen_total"], params["gen_per_batch"]):
         fileno = np.arange(start, start + params["gen_per_batch"], 1)
-        xg, _ = diffusion.sample(model, n=params["gen_per_batch"], image_channels=args.image_channels, **gen_kw)
+        xg, _ = diffusion.sample(gen_model, n=params["gen_per_batch"], image_channels=args.image_channels, **gen_kw)
         save_gen_images(gen_dir, xg, fileno)
     make_collage(gen_dir, gen_dir, params["collage_n_per_image"], params["collage_n"], args.image_size)
     torch.cuda.empty_cache()
     gc.collect()
-    return {"loss_all": loss_all, "sample": x, "revert": denoise_img, "modelpath": modelpath, "gen_dir": gen_dir}
+    out = {"loss_all": loss_all, "sample": x, "revert": denoise_img, "modelpath": modelpath, "gen_dir": gen_dir}
+    if use_ema:
+        out["ema_modelpath"] = ema_path(modelpath)
+    return out
 
 
 def _load(model_data):

@@ -4,6 +4,7 @@ hipGraph replay of the whole step.
 """
 import logging
 import os
+import weakref
 
 import torch
 import torch.distributed as dist
@@ -16,10 +17,13 @@ class argument:
     """Attribute bag of run settings (ddpm_utils.py:11-23)."""
 
     def __init__(self, run_name=None, epochs=None, batch_size=None, image_size=None, image_channels=3,
-                 dataset_path=None, device=None, lr=None, noise_steps=None, image_gen_n=4):
+                 dataset_path=None, device=None, lr=None, noise_steps=None, image_gen_n=4, ema_beta=None, ema_start=2000):
+        """ema_beta / ema_start (not in the reference's class): with ema_beta set, `train` keeps an EMA of the weights
+        (EMA(ema_beta), step_start_ema = ema_start)."""
         self.run_name, self.epochs, self.batch_size, self.image_size = run_name, epochs, batch_size, image_size
         self.image_channels, self.dataset_path, self.device, self.lr = image_channels, dataset_path, device, lr
         self.noise_steps, self.image_gen_n = noise_steps, image_gen_n
+        self.ema_beta, self.ema_start = ema_beta, ema_start
 
 
 def set_seed(seed):
@@ -42,6 +46,9 @@ def setup_logging(run_name):
     os.makedirs("results", exist_ok=True)
     os.makedirs(os.path.join("models", run_name), exist_ok=True)
     os.makedirs(os.path.join("results", run_name), exist_ok=True)
+
+
+_HOMES = weakref.WeakKeyDictionary()      # model -> the FlatParams its parameters live in (EMA's fast path looks it up)
 
 
 class FlatParams:
@@ -82,6 +89,7 @@ class FlatParams:
             p.grad = self.grad[o:o + n].view(p.shape)
             self.offsets.append(o)
             o += n
+        _HOMES[model] = self
 
     def zero_grad(self):
         self.grad.zero_()
@@ -107,13 +115,156 @@ class FusedAdamW:
     def zero_grad(self, set_to_none=False):
         self.fp.zero_grad()
 
-    def step(self, grad_scale=1.0):
+    def step(self, grad_scale=1.0, ema=None):
+        """ema: an _EMAHome (TrainStep(ema=...)): the same two launches, in their fused EMA form (afd.h)."""
         L, s = lib(), ops._stream()
+        if ema is not None:
+            L.afd_adamw_ema_tick(self.state.data_ptr(), self.betas[0], self.betas[1], ema.state.data_ptr(), ema.start, s)
+            L.afd_adamw_ema_step(self.fp.flat.data_ptr(), self.fp.grad.data_ptr(), self.m.data_ptr(), self.v.data_ptr(),
+                                 self.fp.n_active, self.state.data_ptr(), self.lr, self.betas[0], self.betas[1], self.eps,
+                                 self.weight_decay, grad_scale, ema.flat.data_ptr(), ema.flat.numel(), ema.state.data_ptr(),
+                                 ema.beta, ema.one_minus_beta, s)
+            ops.bump_param_epoch()                      # (both the model's and the EMA model's parameters moved)
+            return
         L.afd_adamw_tick(self.state.data_ptr(), self.betas[0], self.betas[1], s)
         L.afd_adamw_step(self.fp.flat.data_ptr(), self.fp.grad.data_ptr(), self.m.data_ptr(), self.v.data_ptr(),
                          self.fp.n_active, self.state.data_ptr(), self.lr, self.betas[0], self.betas[1], self.eps,
                          self.weight_decay, grad_scale, s)
         ops.bump_param_epoch()                          # the parameters moved under raw pointers: cached transforms are stale
+
+
+def _named_shapes(module):
+    return {k: tuple(v.shape) for k, v in module.state_dict().items()}
+
+
+def _check_pair(ema_model, model):
+    if ema_model is model:
+        raise ValueError("EMA: ema_model is model: the average needs a separate copy (copy.deepcopy(model))")
+    a, b = _named_shapes(model), _named_shapes(ema_model)
+    if a != b:
+        diff = sorted(set(a.items()) ^ set(b.items()))[:4]
+        raise ValueError(f"EMA: ema_model and model differ in architecture (state_dict names or shapes), e.g. {diff}")
+
+
+class _EMAHome:
+    """The fast path's device side: ema_model's parameters re-homed as views of ONE flat fp32 buffer, in the order of the
+    model's FlatParams (its unused tail included), so one kernel updates them all from the model's flat buffer.
+    `state` is the device int32 {calls, copy} of afd_adamw_ema_tick (TrainStep(ema=...))."""
+
+    def __init__(self, ema_model, model, fp):
+        self.ema_model, self.model, self.fp = ema_model, model, fp
+        name_of = {id(p): n for n, p in model.named_parameters()}
+        eparams = dict(ema_model.named_parameters())
+        self.flat = torch.empty(fp.numel, device=fp.flat.device, dtype=torch.float32)      # no grad buffer
+        with torch.no_grad():
+            for p, o in zip(fp.params, fp.offsets):
+                ep, n = eparams[name_of[id(p)]], p.numel()
+                self.flat[o:o + n].copy_(ep.data.reshape(-1))
+                ep.data = self.flat[o:o + n].view(ep.shape)
+                ep.grad = None
+        mbufs = dict(model.named_buffers())
+        self.buffers = [(b, mbufs[k]) for k, b in ema_model.named_buffers()]
+        self.state = torch.zeros(2, device=fp.flat.device, dtype=torch.int32)
+        self.start, self.beta, self.one_minus_beta = 0, 0.0, 1.0       # set by TrainStep when it drives the EMA
+
+
+class EMA:
+    """Exponential moving average of a model's weights: modules/ddpm_utils.py:26-51, same interface and call counting --
+    `step_ema` copies the weights (reset_parameters) while `step < step_start_ema` and blends them
+    (`old * beta + (1 - beta) * new`) after, incrementing `step` on every call.
+
+    Fast path: when `model` lives in a FlatParams (a TrainStep or FusedAdamW owns it), the first call re-homes `ema_model`'s
+    parameters as views of one flat buffer in the same order, and each call after that is ONE afd_ema_step launch (fp32, the same
+    three roundings as the torch expression).  Any other pair (CPU included) runs the torch expression per tensor.
+    TrainStep(ema=..., ema_model=...) goes further and fuses the update into its AdamW launch (afd_adamw_ema_step); the EMA is then
+    advanced by the step and calling `step_ema` by hand raises RuntimeError.
+
+    One deliberate difference from the reference: the update is IN PLACE (`copy_`, or the kernel writing the parameters'
+    storage), where the reference rebinds `ma_params.data` to a new tensor on every call -- so the EMA model's parameter storage,
+    and any pointer a captured graph or a cached weight image holds into it, stays valid.  Buffers (the UNet has none) are copied
+    on reset and left alone on blend, as load_state_dict does."""
+
+    def __init__(self, beta):
+        try:
+            ok = 0.0 <= float(beta) <= 1.0
+        except (TypeError, ValueError):
+            ok = False
+        if not ok:
+            raise ValueError(f"EMA: beta must lie in [0, 1] (got {beta!r})")
+        self.beta = beta
+        self.step = 0
+        self._home = None
+        self._driver = None          # the TrainStep whose AdamW launch advances this EMA
+
+    def _betas(self):
+        b = float(self.beta)
+        if not 0.0 <= b <= 1.0:
+            raise ValueError(f"EMA: beta must lie in [0, 1] (got {self.beta!r})")
+        return b, float(1.0 - b)     # 1 - beta in double, as Python evaluates `(1 - self.beta)`
+
+    def _fast(self, ema_model, model):
+        """The _EMAHome of this pair when `model` is homed in a FlatParams (built on first use), else None."""
+        h = self._home
+        if h is not None and h.ema_model is ema_model and h.model is model and _HOMES.get(model) is h.fp:
+            return h
+        fp = _HOMES.get(model)
+        if fp is None:
+            return None
+        _check_pair(ema_model, model)
+        if any(p.dtype != torch.float32 or p.device != fp.flat.device for p in ema_model.parameters()):
+            return None
+        self._home = _EMAHome(ema_model, model, fp)
+        return self._home
+
+    def _launch(self, h, copy):
+        b, omb = self._betas()
+        lib().afd_ema_step(h.flat.data_ptr(), h.fp.flat.data_ptr(), h.flat.numel(), int(copy), b, omb, ops._stream())
+        ops.bump_param_epoch()       # the EMA model's parameters moved under raw pointers: its cached weight images are stale
+
+    def update_model_average(self, ma_model, current_model):
+        h = self._fast(ma_model, current_model)
+        if h is not None:
+            self._launch(h, copy=False)
+            return
+        _check_pair(ma_model, current_model)
+        self._betas()
+        cur = dict(current_model.named_parameters())
+        with torch.no_grad():
+            for k, ma in ma_model.named_parameters():
+                ma.copy_(self.update_average(ma.data, cur[k].data))
+
+    def update_average(self, old, new):
+        if old is None:
+            return new
+        return old * self.beta + (1 - self.beta) * new
+
+    def step_ema(self, ema_model, model, step_start_ema=2000):
+        if self._driver is not None:
+            raise RuntimeError("EMA.step_ema: this EMA is advanced by a TrainStep(ema=...), inside its AdamW launch; "
+                               "calling step_ema as well would update it twice")
+        if self.step < step_start_ema:
+            self.reset_parameters(ema_model, model)
+            self.step += 1
+            return
+        self.update_model_average(ema_model, model)
+        self.step += 1
+
+    def reset_parameters(self, ema_model, model):
+        h = self._fast(ema_model, model)
+        if h is not None:
+            self._launch(h, copy=True)
+            with torch.no_grad():
+                for eb, mb in h.buffers:
+                    eb.copy_(mb)
+            return
+        _check_pair(ema_model, model)
+        cur = dict(model.named_parameters())
+        bufs = dict(model.named_buffers())
+        with torch.no_grad():
+            for k, ep in ema_model.named_parameters():
+                ep.copy_(cur[k])
+            for k, eb in ema_model.named_buffers():
+                eb.copy_(bufs[k])
 
 
 class GradAllReduce:
@@ -280,13 +431,24 @@ class TrainStep:
     B = 16, bit-identical to the eager step.  The noise is drawn outside the replayed list (no generator state in it)."""
 
     def __init__(self, model, diffusion, lr, graph=False, distributed=None, n_buckets=4, overlap_wgrad=None, conditional=False,
-                 p_uncond=0.0):
+                 p_uncond=0.0, ema=None, ema_model=None, ema_start=2000):
         """conditional=True: the step takes class labels (`step(images, y=labels)`, UNet.forward(x, t, y): ddpm_models.py:276-277)
         and `label_emb` is optimised and exchanged like every other parameter.  With the default (the reference's loop,
         ddpm_utils.py:502, never passes labels) `label_emb` stays untouched, as under the reference's AdamW, and passing y raises.
         p_uncond > 0 (needs conditional=True): label dropout for classifier-free guidance -- each sample's label is replaced by
         NULL_LABEL with probability p_uncond, the mask drawn from the CPU generator right after the timesteps
-        (label_dropout_mask), outside any captured work.  p_uncond = 0 draws nothing."""
+        (label_dropout_mask), outside any captured work.  p_uncond = 0 draws nothing.
+        ema (an EMA) with ema_model (a copy of model, e.g. copy.deepcopy(model)): keep an exponential moving average of the weights
+        in ema_model -- the reference's `ema.step_ema(ema_model, model, step_start_ema=ema_start)` after every optimizer step.  The
+        update is fused into the AdamW launch (afd_adamw_ema_tick + afd_adamw_ema_step instead of afd_adamw_tick + afd_adamw_step:
+        no extra launch), in every launch mode and under data parallelism; ema.beta is read here, once.  `ema.step` counts the
+        calls to this step (the host mirror of the device counter)."""
+        if (ema is None) != (ema_model is None):
+            raise ValueError("TrainStep: ema and ema_model go together (EMA(beta) and a copy of the model): got only one of them")
+        if ema is not None and (isinstance(ema_start, bool) or int(ema_start) != ema_start or ema_start < 0):
+            raise ValueError(f"TrainStep: ema_start must be an integer >= 0 (got {ema_start!r})")
+        if ema is not None and ema._driver is not None:
+            raise ValueError("TrainStep: this EMA is already driven by another TrainStep")
         if not 0.0 <= p_uncond <= 1.0:
             raise ValueError(f"TrainStep: p_uncond must lie in [0, 1] (got {p_uncond})")
         if p_uncond > 0 and not conditional:
@@ -316,6 +478,16 @@ class TrainStep:
         # 7.097 / 7.133 / 7.147 / 7.182; captured 8 / 16 / 24 / 32 / 40 / 48 / 64 / 128 -> 7.343 / 7.285 / 7.220 / 7.208 / 7.299 / 7.375 / 7.361 / 7.552
         self.wgrad_batch = 8 if (not graph or graph == "lanes") else 32      # ("lanes" has the eager step's stream semantics)
         self.opt = FusedAdamW(model, lr=lr, conditional=conditional)
+        self.ema, self._ema_home = ema, None
+        if ema is not None:
+            h = ema._fast(ema_model, model)          # (model now lives in self.opt's FlatParams)
+            if h is None:
+                raise ValueError("TrainStep: ema_model must hold float32 parameters on the model's device")
+            h.start = int(ema_start)
+            h.beta, h.one_minus_beta = ema._betas()
+            h.state.copy_(torch.tensor([ema.step, 0], dtype=torch.int32))      # the device counter continues the host's
+            ema._driver = self
+            self._ema_home = h
         want_ddp = distributed if distributed is not None else dist.is_initialized()
         self.ddp = GradAllReduce(self.opt.fp, n_buckets, model=model) if want_ddp else None
         if self.ddp is not None:
@@ -379,7 +551,7 @@ class TrainStep:
 
     def _update(self):
         scale = self.ddp.finish() if self.ddp is not None else 1.0
-        self.opt.step(grad_scale=scale)
+        self.opt.step(grad_scale=scale, ema=self._ema_home)
 
     def _body(self, images, t, eps, y=None):
         loss = self._fwd_bwd(images, t, eps, y)
@@ -387,6 +559,12 @@ class TrainStep:
         return loss
 
     def __call__(self, images, t=None, eps=None, y=None):
+        loss = self._step(images, t, eps, y)
+        if self.ema is not None:
+            self.ema.step += 1                          # one EMA call per step (the capture warm-up's are undone)
+        return loss
+
+    def _step(self, images, t=None, eps=None, y=None):
         """images (B,C,S,S) on the device; t (B,) int64 [default: diffusion.sample_timesteps];
         eps: injected noise or None (device RNG); y (B,) int64 class labels (only with conditional=True; NULL_LABEL = no label
         for that sample).  Under graph=True / "lanes" the labels are a static captured input like images, t and eps: a step
@@ -423,10 +601,11 @@ class TrainStep:
             st = self._static
             # warm-up outside capture (allocator, lazy init, the Winograd plan's recording step).  These are real steps on
             # the first batch, so everything they change is put back afterwards -- parameters, AdamW moments and step
-            # counter, the device generator -- and under data parallel they stop before the exchange: the first graph
-            # call is then exactly one step, like the eager one (and like the reference's).
-            fp, opt = self.opt.fp, self.opt
-            keep = [b.clone() for b in (fp.flat, opt.m, opt.v, opt.state)]
+            # counter, the EMA buffer and its counter, the device generator -- and under data parallel they stop before the
+            # exchange: the first graph call is then exactly one step, like the eager one (and like the reference's).
+            fp, opt, h = self.opt.fp, self.opt, self._ema_home
+            bufs = (fp.flat, opt.m, opt.v, opt.state) + ((h.flat, h.state) if h is not None else ())
+            keep = [b.clone() for b in bufs]
             rng = torch.cuda.get_rng_state(images.device)
             s = torch.cuda.Stream()
             s.wait_stream(torch.cuda.current_stream())
@@ -434,7 +613,7 @@ class TrainStep:
                 for _ in range(2):
                     (self._body if whole else self._fwd_bwd)(st["images"], st["t"], st["eps"], st["y"])
             torch.cuda.current_stream().wait_stream(s)
-            for b, k in zip((fp.flat, opt.m, opt.v, opt.state), keep):
+            for b, k in zip(bufs, keep):
                 b.copy_(k)
             torch.cuda.set_rng_state(rng, images.device)
             ops.bump_param_epoch()
@@ -476,7 +655,13 @@ def train(args, model_path=None, dataloader=None, model=None, diffusion=None):
     from tqdm import tqdm
     setup_logging(args.run_name)
     device = args.device
-    step = TrainStep(model, diffusion, lr=args.lr, graph=False)
+    ema_beta = getattr(args, "ema_beta", None)
+    ema = ema_model = None
+    if ema_beta is not None:              # (the reference's conditional recipe: EMA(0.995), ema_model = deepcopy(model))
+        import copy
+        ema, ema_model = EMA(ema_beta), copy.deepcopy(model)
+    step = TrainStep(model, diffusion, lr=args.lr, graph=False, ema=ema, ema_model=ema_model,
+                     ema_start=getattr(args, "ema_start", 2000))
     n_batches = len(dataloader)
     loss_all = []
     for epoch in range(args.epochs):
@@ -489,12 +674,22 @@ def train(args, model_path=None, dataloader=None, model=None, diffusion=None):
             if i % 50 == 0:
                 pbar.set_postfix(MSE=loss.item())
         loss_all.append(epoch_loss.item() / n_batches)
-        sampled, _ = diffusion.sample(model, n=args.image_gen_n, image_channels=args.image_channels)
-        try:
-            from .imageio_utils import save_images
-            save_images(sampled, os.path.join("results", args.run_name, f"{epoch}.jpg"))
-        except Exception as e:                                     # preview only; never fail a run on I/O
-            logging.warning(f"preview not saved: {e}")
+        previews = [(model, f"{epoch}.jpg")] + ([(ema_model, f"{epoch}_ema.jpg")] if ema is not None else [])
+        for net, fname in previews:
+            sampled, _ = diffusion.sample(net, n=args.image_gen_n, image_channels=args.image_channels)
+            try:
+                from .imageio_utils import save_images
+                save_images(sampled, os.path.join("results", args.run_name, fname))
+            except Exception as e:                                 # preview only; never fail a run on I/O
+                logging.warning(f"preview not saved: {e}")
         if model_path:
             torch.save(model.state_dict(), model_path)
+            if ema is not None:
+                torch.save(ema_model.state_dict(), ema_path(model_path))
     return loss_all
+
+
+def ema_path(model_path):
+    """Where `train` writes the EMA weights beside a checkpoint: ckpt_X.pt -> ckpt_X_ema.pt."""
+    root, ext = os.path.splitext(model_path)
+    return f"{root}_ema{ext}"

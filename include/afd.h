@@ -420,6 +420,25 @@ int afd_adamw_step(float* p, const float* g, float* m, float* v, long n, const f
                    float lr, float beta1, float beta2, float eps, float weight_decay, float grad_scale,
                    afd_stream_t stream);
 
+/* ---- EMA of the weights (modules/ddpm_utils.py:26-51) ------------------------------------------------- training.EMA / TrainStep(ema=)
+ * The rule, per fp32 element, with one rounding per operation in this order (torch's `old * beta + (1 - beta) * new`):
+ *     copy != 0:  ema = p                                        (bit for bit, as load_state_dict)
+ *     otherwise:  ema = (ema * beta) + (p * one_minus_beta)
+ * beta = float(beta) and one_minus_beta = float(1.0 - beta) with the subtraction done in double on the host (never 1 - beta in
+ * fp32 on the device).  Both must lie in [0, 1].
+ * afd_ema_step: the rule alone over n elements (ema and p must not overlap).
+ * afd_adamw_ema_tick: exactly afd_adamw_tick on adam_state, plus the EMA call counter ema_state = device int[2] {calls, copy}:
+ *   copy = (calls < start), then ++calls -- EMA.step_ema's order, kept on the device so a replayed step crosses `start` correctly.
+ * afd_adamw_ema_step: for i < n_active, p, m and v exactly as afd_adamw_step (same expressions, same order), then the rule on the
+ *   NEW p with copy = ema_state[1]; for n_active <= i < n_ema the rule alone on the unchanged p (parameters the optimiser never
+ *   touches, which the reference's EMA still walks).  Requires 0 < n_active <= n_ema.
+ * 16-byte accesses when every pointer is 16-byte aligned, element-wise otherwise; the results do not depend on which. */
+int afd_ema_step(float* ema, const float* p, long n, int copy, float beta, float one_minus_beta, afd_stream_t stream);
+int afd_adamw_ema_tick(float* adam_state, float beta1, float beta2, int* ema_state, int start, afd_stream_t stream);
+int afd_adamw_ema_step(float* p, const float* g, float* m, float* v, long n_active, const float* adam_state, float lr,
+                       float beta1, float beta2, float eps, float weight_decay, float grad_scale, float* ema, long n_ema,
+                       const int* ema_state, float beta, float one_minus_beta, afd_stream_t stream);
+
 /* ---- two-lane replay of a captured step (csrc/replay.hip) --------------------------------- training.TrainStep(graph="lanes")
  * A step captured by the host framework as a hipGraph (forward, backward with the weight gradients forked to a side stream,
  * AdamW) is re-issued from a C++ loop on TWO REAL STREAMS: afd_replay_build walks the graph once (kernel / memset / flat
