@@ -18,6 +18,9 @@ static inline int gs_grid(long total, int block = 256) {
 }
 #define AFD_GRID_STRIDE(i, total) \
   for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < (total); i += (long)gridDim.x * blockDim.x)
+// the same loop's start and stride, taken in a kernel and handed to a __device__ body (inside the body, blockDim.x would be
+// read without the kernel's uniform-work-group assumption: one extra load per thread)
+#define AFD_GRID_START blockIdx.x * (long)blockDim.x + threadIdx.x, (long)gridDim.x * blockDim.x
 
 // x_t = sqrt(ah[t]) * x + sqrt(1 - ah[t]) * eps
 __global__ void noise_images_k(const float* __restrict__ x, const float* __restrict__ eps, const int64_t* __restrict__ t,
@@ -75,51 +78,128 @@ __device__ __forceinline__ float cfg_lerp(float s, float one_minus_s, bool small
   const float d = ec - eu;
   return small ? eu + s * d : ec - d * one_minus_s;
 }
-__device__ __forceinline__ float cfg_update(const CfgCoef& k, float x, float ec, float eu, float nz_in, bool has_noise) {
-  const float e = cfg_lerp(k.s, k.one_minus_s, k.small, ec, eu);
+__device__ __forceinline__ float denoise_update(const CfgCoef& k, float x, float e, float nz_in, bool has_noise) {
   const float pe = k.c2 * e;
   const float inner = x - pe;
   const float lhs = k.c1 * inner;
   const float nz = has_noise ? k.sb * nz_in : 0.0f;
   return lhs + nz;
 }
+template <bool kCfg>
+__device__ __forceinline__ float denoise_eps(const CfgCoef& k, float ec, float eu) {
+  return kCfg ? cfg_lerp(k.s, k.one_minus_s, k.small, ec, eu) : ec;
+}
 
-// 16-byte accesses (n % 4 == 0, every pointer 16-byte aligned); n4 = n / 4
+// ---- masked step (inpainting, RePaint): the update above for the generated region, x0 noised to t_prev for the known one --
+// known = t_prev == 0 ? x0 : (sqrt(a_p) * x0) + (sqrt(1 - a_p) * z), a_p = alpha_hat[t_prev] (noise_images_k's expression)
+// out   = mask[j] ? known : gen.  One noise tensor z serves both regions (each element reads its z once).
+struct KnownCoef {
+  float sa, sb;
+  bool clean;
+};
+__device__ __forceinline__ KnownCoef known_coef(const float* alpha_hat, int tp) {
+  const float ah = alpha_hat[tp];
+  KnownCoef k;
+  k.sa = sqrtf(ah);
+  k.sb = sqrtf(1.0f - ah);
+  k.clean = tp == 0;
+  return k;
+}
+__device__ __forceinline__ float known_value(const KnownCoef& k, float x0, float z) {
+  if (k.clean) return x0;
+  const float l = k.sa * x0, r = k.sb * z;
+  return l + r;
+}
+__device__ __forceinline__ float4 masked4(const KnownCoef& k, uchar4 m, float4 x0, float4 z, float4 gen) {
+  float4 r;
+  r.x = m.x ? known_value(k, x0.x, z.x) : gen.x;
+  r.y = m.y ? known_value(k, x0.y, z.y) : gen.y;
+  r.z = m.z ? known_value(k, x0.z, z.z) : gen.z;
+  r.w = m.w ? known_value(k, x0.w, z.w) : gen.w;
+  return r;
+}
+
+// Bodies shared by the guided (kCfg) and masked (kMasked) kernels, so the generated region cannot drift from the unmasked
+// update.  kMasked: the step is step -> step - 1, and its generated region takes no noise at step 1 (the chain's last step).
+// 16-byte accesses (n % 4 == 0, every float pointer 16-byte aligned, mask 4-byte aligned); n4 = n / 4
+template <bool kCfg, bool kMasked>
+__device__ __forceinline__ void denoise_step_x4_body(long i0, long stride, const float* x, const float* __restrict__ eps, const float* __restrict__ noise,
+                                                     const float* __restrict__ alpha, const float* __restrict__ alpha_hat,
+                                                     const float* __restrict__ beta, int step_arg, const int64_t* __restrict__ step_dev,
+                                                     float s, const float* __restrict__ x0, const uint8_t* __restrict__ mask,
+                                                     float* x_out, float* x_out2, long n4) {
+  const int step = step_dev ? (int)step_dev[0] : step_arg;
+  const CfgCoef k = cfg_coef(alpha, alpha_hat, beta, step, s);
+  const float4* x4 = reinterpret_cast<const float4*>(x);
+  const float4* ec4 = reinterpret_cast<const float4*>(eps);
+  const float4* eu4 = ec4 + n4;                                // read only when kCfg
+  const float4* nz4 = reinterpret_cast<const float4*>(noise);
+  const bool has_noise = noise != nullptr;
+  const bool gen_noise = kMasked ? has_noise && step > 1 : has_noise;
+  const KnownCoef kn = kMasked ? known_coef(alpha_hat, step > 0 ? step - 1 : 0) : KnownCoef{};
+  for (long i = i0; i < n4; i += stride) {
+    const float4 xv = x4[i], c = ec4[i];
+    const float4 u = kCfg ? eu4[i] : c;
+    const float4 z = has_noise ? nz4[i] : make_float4(0.f, 0.f, 0.f, 0.f);
+    float4 r;
+    r.x = denoise_update(k, xv.x, denoise_eps<kCfg>(k, c.x, u.x), z.x, gen_noise);
+    r.y = denoise_update(k, xv.y, denoise_eps<kCfg>(k, c.y, u.y), z.y, gen_noise);
+    r.z = denoise_update(k, xv.z, denoise_eps<kCfg>(k, c.z, u.z), z.z, gen_noise);
+    r.w = denoise_update(k, xv.w, denoise_eps<kCfg>(k, c.w, u.w), z.w, gen_noise);
+    if (kMasked)
+      r = masked4(kn, reinterpret_cast<const uchar4*>(mask)[i], reinterpret_cast<const float4*>(x0)[i], z, r);
+    reinterpret_cast<float4*>(x_out)[i] = r;
+    if (x_out2) reinterpret_cast<float4*>(x_out2)[i] = r;
+  }
+}
+template <bool kCfg, bool kMasked>
+__device__ __forceinline__ void denoise_step_body(long i0, long stride, const float* x, const float* __restrict__ eps, const float* __restrict__ noise,
+                                                  const float* __restrict__ alpha, const float* __restrict__ alpha_hat,
+                                                  const float* __restrict__ beta, int step_arg, const int64_t* __restrict__ step_dev,
+                                                  float s, const float* __restrict__ x0, const uint8_t* __restrict__ mask,
+                                                  float* x_out, float* x_out2, long n) {
+  const int step = step_dev ? (int)step_dev[0] : step_arg;
+  const CfgCoef k = cfg_coef(alpha, alpha_hat, beta, step, s);
+  const bool has_noise = noise != nullptr;
+  const bool gen_noise = kMasked ? has_noise && step > 1 : has_noise;
+  const KnownCoef kn = kMasked ? known_coef(alpha_hat, step > 0 ? step - 1 : 0) : KnownCoef{};
+  for (long i = i0; i < n; i += stride) {
+    const float z = has_noise ? noise[i] : 0.0f;
+    float r = denoise_update(k, x[i], denoise_eps<kCfg>(k, eps[i], kCfg ? eps[n + i] : 0.0f), z, gen_noise);
+    if (kMasked && mask[i]) r = known_value(kn, x0[i], z);
+    x_out[i] = r;
+    if (x_out2) x_out2[i] = r;
+  }
+}
+
 __global__ __launch_bounds__(256) void denoise_step_cfg_x4_k(const float* x, const float* __restrict__ eps2, const float* __restrict__ noise,
                                                              const float* __restrict__ alpha, const float* __restrict__ alpha_hat,
                                                              const float* __restrict__ beta, int step_arg, const int64_t* __restrict__ step_dev,
                                                              float s, float* x_out, float* x_out2, long n4) {
-  const int step = step_dev ? (int)step_dev[0] : step_arg;
-  const CfgCoef k = cfg_coef(alpha, alpha_hat, beta, step, s);
-  const float4* x4 = reinterpret_cast<const float4*>(x);
-  const float4* ec4 = reinterpret_cast<const float4*>(eps2);
-  const float4* eu4 = ec4 + n4;
-  const float4* nz4 = reinterpret_cast<const float4*>(noise);
-  const bool has_noise = noise != nullptr;
-  AFD_GRID_STRIDE(i, n4) {
-    const float4 xv = x4[i], c = ec4[i], u = eu4[i];
-    const float4 z = has_noise ? nz4[i] : make_float4(0.f, 0.f, 0.f, 0.f);
-    float4 r;
-    r.x = cfg_update(k, xv.x, c.x, u.x, z.x, has_noise);
-    r.y = cfg_update(k, xv.y, c.y, u.y, z.y, has_noise);
-    r.z = cfg_update(k, xv.z, c.z, u.z, z.z, has_noise);
-    r.w = cfg_update(k, xv.w, c.w, u.w, z.w, has_noise);
-    reinterpret_cast<float4*>(x_out)[i] = r;
-    if (x_out2) reinterpret_cast<float4*>(x_out2)[i] = r;
-  }
+  denoise_step_x4_body<true, false>(AFD_GRID_START, x, eps2, noise, alpha, alpha_hat, beta, step_arg, step_dev, s, nullptr, nullptr, x_out, x_out2, n4);
 }
 __global__ __launch_bounds__(256) void denoise_step_cfg_k(const float* x, const float* __restrict__ eps2, const float* __restrict__ noise,
                                                           const float* __restrict__ alpha, const float* __restrict__ alpha_hat,
                                                           const float* __restrict__ beta, int step_arg, const int64_t* __restrict__ step_dev,
                                                           float s, float* x_out, float* x_out2, long n) {
-  const int step = step_dev ? (int)step_dev[0] : step_arg;
-  const CfgCoef k = cfg_coef(alpha, alpha_hat, beta, step, s);
-  const bool has_noise = noise != nullptr;
-  AFD_GRID_STRIDE(i, n) {
-    const float r = cfg_update(k, x[i], eps2[i], eps2[n + i], has_noise ? noise[i] : 0.0f, has_noise);
-    x_out[i] = r;
-    if (x_out2) x_out2[i] = r;
-  }
+  denoise_step_body<true, false>(AFD_GRID_START, x, eps2, noise, alpha, alpha_hat, beta, step_arg, step_dev, s, nullptr, nullptr, x_out, x_out2, n);
+}
+// masked DDPM step, plain (eps: n elements) or guided (kCfg, eps: 2n)
+template <bool kCfg>
+__global__ __launch_bounds__(256) void denoise_step_masked_x4_k(const float* x, const float* __restrict__ eps, const float* __restrict__ noise,
+                                                                const float* __restrict__ alpha, const float* __restrict__ alpha_hat,
+                                                                const float* __restrict__ beta, int step_arg,
+                                                                const int64_t* __restrict__ step_dev, float s, const float* __restrict__ x0,
+                                                                const uint8_t* __restrict__ mask, float* x_out, float* x_out2, long n4) {
+  denoise_step_x4_body<kCfg, true>(AFD_GRID_START, x, eps, noise, alpha, alpha_hat, beta, step_arg, step_dev, s, x0, mask, x_out, x_out2, n4);
+}
+template <bool kCfg>
+__global__ __launch_bounds__(256) void denoise_step_masked_k(const float* x, const float* __restrict__ eps, const float* __restrict__ noise,
+                                                             const float* __restrict__ alpha, const float* __restrict__ alpha_hat,
+                                                             const float* __restrict__ beta, int step_arg,
+                                                             const int64_t* __restrict__ step_dev, float s, const float* __restrict__ x0,
+                                                             const uint8_t* __restrict__ mask, float* x_out, float* x_out2, long n) {
+  denoise_step_body<kCfg, true>(AFD_GRID_START, x, eps, noise, alpha, alpha_hat, beta, step_arg, step_dev, s, x0, mask, x_out, x_out2, n);
 }
 
 static int launch_denoise_step_cfg(const float* x, const float* eps2, const float* noise, const float* alpha, const float* alpha_hat,
@@ -178,12 +258,16 @@ __device__ __forceinline__ float ddim_eps(const DdimCoef& k, float ec, float eu)
   return kCfg ? cfg_lerp(k.s, k.one_minus_s, k.small, ec, eu) : ec;
 }
 
-// 16-byte accesses (n % 4 == 0, every pointer 16-byte aligned); n4 = n / 4.  kCfg: eps holds 2n elements.
-template <bool kCfg>
-__global__ __launch_bounds__(256) void ddim_step_x4_k(const float* x, const float* __restrict__ eps, const float* __restrict__ noise,
-                                                      const float* __restrict__ alpha_hat, int t_arg, int tp_arg,
-                                                      const int64_t* __restrict__ t_dev, const int64_t* __restrict__ tp_dev, float eta,
-                                                      float s, float* x_out, float* x_out2, long n4) {
+// Bodies shared by the unmasked and masked (kMasked) kernels.  kMasked: the generated region takes no noise when eta == 0 or
+// t_prev == 0; the known region is x0 noised to t_prev (known_value).
+// 16-byte accesses (n % 4 == 0, every float pointer 16-byte aligned, mask 4-byte aligned); n4 = n / 4.  kCfg: eps holds 2n
+// elements.
+template <bool kCfg, bool kMasked>
+__device__ __forceinline__ void ddim_step_x4_body(long i0, long stride, const float* x, const float* __restrict__ eps, const float* __restrict__ noise,
+                                                  const float* __restrict__ alpha_hat, int t_arg, int tp_arg,
+                                                  const int64_t* __restrict__ t_dev, const int64_t* __restrict__ tp_dev, float eta,
+                                                  float s, const float* __restrict__ x0, const uint8_t* __restrict__ mask,
+                                                  float* x_out, float* x_out2, long n4) {
   const int t = t_dev ? (int)t_dev[0] : t_arg;                 // device-resident indices: a captured graph replays every step
   const int tp = tp_dev ? (int)tp_dev[0] : tp_arg;
   const DdimCoef k = ddim_coef(alpha_hat, t, tp, eta, s);
@@ -192,34 +276,74 @@ __global__ __launch_bounds__(256) void ddim_step_x4_k(const float* x, const floa
   const float4* eu4 = ec4 + n4;                                // read only when kCfg
   const float4* nz4 = reinterpret_cast<const float4*>(noise);
   const bool has_noise = noise != nullptr;
-  AFD_GRID_STRIDE(i, n4) {
+  const bool gen_noise = kMasked ? has_noise && eta != 0.0f && tp > 0 : has_noise;
+  const KnownCoef kn = kMasked ? known_coef(alpha_hat, tp) : KnownCoef{};
+  for (long i = i0; i < n4; i += stride) {
     const float4 xv = x4[i], c = ec4[i];
     const float4 u = kCfg ? eu4[i] : c;
     const float4 z = has_noise ? nz4[i] : make_float4(0.f, 0.f, 0.f, 0.f);
     float4 r;
-    r.x = ddim_update(k, xv.x, ddim_eps<kCfg>(k, c.x, u.x), z.x, has_noise);
-    r.y = ddim_update(k, xv.y, ddim_eps<kCfg>(k, c.y, u.y), z.y, has_noise);
-    r.z = ddim_update(k, xv.z, ddim_eps<kCfg>(k, c.z, u.z), z.z, has_noise);
-    r.w = ddim_update(k, xv.w, ddim_eps<kCfg>(k, c.w, u.w), z.w, has_noise);
+    r.x = ddim_update(k, xv.x, ddim_eps<kCfg>(k, c.x, u.x), z.x, gen_noise);
+    r.y = ddim_update(k, xv.y, ddim_eps<kCfg>(k, c.y, u.y), z.y, gen_noise);
+    r.z = ddim_update(k, xv.z, ddim_eps<kCfg>(k, c.z, u.z), z.z, gen_noise);
+    r.w = ddim_update(k, xv.w, ddim_eps<kCfg>(k, c.w, u.w), z.w, gen_noise);
+    if (kMasked)
+      r = masked4(kn, reinterpret_cast<const uchar4*>(mask)[i], reinterpret_cast<const float4*>(x0)[i], z, r);
     reinterpret_cast<float4*>(x_out)[i] = r;
     if (x_out2) reinterpret_cast<float4*>(x_out2)[i] = r;
   }
+}
+template <bool kCfg, bool kMasked>
+__device__ __forceinline__ void ddim_step_body(long i0, long stride, const float* x, const float* __restrict__ eps, const float* __restrict__ noise,
+                                               const float* __restrict__ alpha_hat, int t_arg, int tp_arg,
+                                               const int64_t* __restrict__ t_dev, const int64_t* __restrict__ tp_dev, float eta, float s,
+                                               const float* __restrict__ x0, const uint8_t* __restrict__ mask, float* x_out,
+                                               float* x_out2, long n) {
+  const int t = t_dev ? (int)t_dev[0] : t_arg;
+  const int tp = tp_dev ? (int)tp_dev[0] : tp_arg;
+  const DdimCoef k = ddim_coef(alpha_hat, t, tp, eta, s);
+  const bool has_noise = noise != nullptr;
+  const bool gen_noise = kMasked ? has_noise && eta != 0.0f && tp > 0 : has_noise;
+  const KnownCoef kn = kMasked ? known_coef(alpha_hat, tp) : KnownCoef{};
+  for (long i = i0; i < n; i += stride) {
+    const float e = ddim_eps<kCfg>(k, eps[i], kCfg ? eps[n + i] : 0.0f);
+    const float z = has_noise ? noise[i] : 0.0f;
+    float r = ddim_update(k, x[i], e, z, gen_noise);
+    if (kMasked && mask[i]) r = known_value(kn, x0[i], z);
+    x_out[i] = r;
+    if (x_out2) x_out2[i] = r;
+  }
+}
+
+template <bool kCfg>
+__global__ __launch_bounds__(256) void ddim_step_x4_k(const float* x, const float* __restrict__ eps, const float* __restrict__ noise,
+                                                      const float* __restrict__ alpha_hat, int t_arg, int tp_arg,
+                                                      const int64_t* __restrict__ t_dev, const int64_t* __restrict__ tp_dev, float eta,
+                                                      float s, float* x_out, float* x_out2, long n4) {
+  ddim_step_x4_body<kCfg, false>(AFD_GRID_START, x, eps, noise, alpha_hat, t_arg, tp_arg, t_dev, tp_dev, eta, s, nullptr, nullptr, x_out, x_out2, n4);
 }
 template <bool kCfg>
 __global__ __launch_bounds__(256) void ddim_step_k(const float* x, const float* __restrict__ eps, const float* __restrict__ noise,
                                                    const float* __restrict__ alpha_hat, int t_arg, int tp_arg,
                                                    const int64_t* __restrict__ t_dev, const int64_t* __restrict__ tp_dev, float eta,
                                                    float s, float* x_out, float* x_out2, long n) {
-  const int t = t_dev ? (int)t_dev[0] : t_arg;
-  const int tp = tp_dev ? (int)tp_dev[0] : tp_arg;
-  const DdimCoef k = ddim_coef(alpha_hat, t, tp, eta, s);
-  const bool has_noise = noise != nullptr;
-  AFD_GRID_STRIDE(i, n) {
-    const float e = ddim_eps<kCfg>(k, eps[i], kCfg ? eps[n + i] : 0.0f);
-    const float r = ddim_update(k, x[i], e, has_noise ? noise[i] : 0.0f, has_noise);
-    x_out[i] = r;
-    if (x_out2) x_out2[i] = r;
-  }
+  ddim_step_body<kCfg, false>(AFD_GRID_START, x, eps, noise, alpha_hat, t_arg, tp_arg, t_dev, tp_dev, eta, s, nullptr, nullptr, x_out, x_out2, n);
+}
+template <bool kCfg>
+__global__ __launch_bounds__(256) void ddim_step_masked_x4_k(const float* x, const float* __restrict__ eps, const float* __restrict__ noise,
+                                                             const float* __restrict__ alpha_hat, int t_arg, int tp_arg,
+                                                             const int64_t* __restrict__ t_dev, const int64_t* __restrict__ tp_dev,
+                                                             float eta, float s, const float* __restrict__ x0,
+                                                             const uint8_t* __restrict__ mask, float* x_out, float* x_out2, long n4) {
+  ddim_step_x4_body<kCfg, true>(AFD_GRID_START, x, eps, noise, alpha_hat, t_arg, tp_arg, t_dev, tp_dev, eta, s, x0, mask, x_out, x_out2, n4);
+}
+template <bool kCfg>
+__global__ __launch_bounds__(256) void ddim_step_masked_k(const float* x, const float* __restrict__ eps, const float* __restrict__ noise,
+                                                          const float* __restrict__ alpha_hat, int t_arg, int tp_arg,
+                                                          const int64_t* __restrict__ t_dev, const int64_t* __restrict__ tp_dev,
+                                                          float eta, float s, const float* __restrict__ x0,
+                                                          const uint8_t* __restrict__ mask, float* x_out, float* x_out2, long n) {
+  ddim_step_body<kCfg, true>(AFD_GRID_START, x, eps, noise, alpha_hat, t_arg, tp_arg, t_dev, tp_dev, eta, s, x0, mask, x_out, x_out2, n);
 }
 
 template <bool kCfg>
@@ -236,6 +360,60 @@ static void launch_ddim_step(const float* x, const float* eps, const float* nois
   else
     hipLaunchKernelGGL(ddim_step_k<kCfg>, dim3(grid), dim3(256), 0, st, x, eps, noise, alpha_hat, t, tp, t_dev, tp_dev, eta, s,
                        x_out, x_out2, n);
+}
+
+// one masked launch: the 16-byte kernel when n % 4 == 0 and the pointers allow it, else the scalar one
+static inline long step_grid(long work) { return std::min<long>(2048, std::max<long>(1, (work + 255) / 256)); }
+static inline bool masked_vec(long n, const float* x, const float* eps, const float* noise, const float* x0, const uint8_t* mask,
+                              const float* x_out, const float* x_out2) {
+  auto a16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
+  return n % 4 == 0 && a16(x) && a16(eps) && a16(x0) && a16(x_out) && (!noise || a16(noise)) && (!x_out2 || a16(x_out2)) &&
+         (reinterpret_cast<uintptr_t>(mask) & 3) == 0;
+}
+template <bool kCfg>
+static void launch_denoise_step_masked(const float* x, const float* eps, const float* noise, const float* x0, const uint8_t* mask,
+                                       const float* alpha, const float* alpha_hat, const float* beta, int i, const int64_t* t_dev,
+                                       float s, float* x_out, float* x_out2, long n, hipStream_t st) {
+  if (masked_vec(n, x, eps, noise, x0, mask, x_out, x_out2))
+    hipLaunchKernelGGL(denoise_step_masked_x4_k<kCfg>, dim3(step_grid(n / 4)), dim3(256), 0, st, x, eps, noise, alpha, alpha_hat,
+                       beta, i, t_dev, s, x0, mask, x_out, x_out2, n / 4);
+  else
+    hipLaunchKernelGGL(denoise_step_masked_k<kCfg>, dim3(step_grid(n)), dim3(256), 0, st, x, eps, noise, alpha, alpha_hat, beta, i,
+                       t_dev, s, x0, mask, x_out, x_out2, n);
+}
+template <bool kCfg>
+static void launch_ddim_step_masked(const float* x, const float* eps, const float* noise, const float* x0, const uint8_t* mask,
+                                    const float* alpha_hat, int t, int tp, const int64_t* t_dev, const int64_t* tp_dev, float eta,
+                                    float s, float* x_out, float* x_out2, long n, hipStream_t st) {
+  if (masked_vec(n, x, eps, noise, x0, mask, x_out, x_out2))
+    hipLaunchKernelGGL(ddim_step_masked_x4_k<kCfg>, dim3(step_grid(n / 4)), dim3(256), 0, st, x, eps, noise, alpha_hat, t, tp, t_dev,
+                       tp_dev, eta, s, x0, mask, x_out, x_out2, n / 4);
+  else
+    hipLaunchKernelGGL(ddim_step_masked_k<kCfg>, dim3(step_grid(n)), dim3(256), 0, st, x, eps, noise, alpha_hat, t, tp, t_dev, tp_dev,
+                       eta, s, x0, mask, x_out, x_out2, n);
+}
+
+// ---- renoise: q(x_{t_to} | x_{t_from}) of the forward process in one jump (RePaint's up-move) ---------------------------
+// a = alpha_hat[t_to] / alpha_hat[t_from]; out = (sqrt(a) * x) + (sqrt(1 - a) * noise), one rounding per operation.
+// x_out may alias x.  VEC: n % 4 == 0 and every pointer 16-byte aligned; then n counts float4s.
+template <bool VEC>
+__global__ __launch_bounds__(256) void renoise_k(const float* x, const float* __restrict__ noise, const float* __restrict__ alpha_hat,
+                                                 int t_from, int t_to, float* x_out, long n) {
+  const float a = alpha_hat[t_to] / alpha_hat[t_from];
+  const float sa = sqrtf(a), sb = sqrtf(1.0f - a);
+  AFD_GRID_STRIDE(i, n) {
+    if (VEC) {
+      const float4 xv = reinterpret_cast<const float4*>(x)[i], z = reinterpret_cast<const float4*>(noise)[i];
+      float4 r;
+      r.x = (sa * xv.x) + (sb * z.x);
+      r.y = (sa * xv.y) + (sb * z.y);
+      r.z = (sa * xv.z) + (sb * z.z);
+      r.w = (sa * xv.w) + (sb * z.w);
+      reinterpret_cast<float4*>(x_out)[i] = r;
+    } else {
+      x_out[i] = (sa * x[i]) + (sb * noise[i]);
+    }
+  }
 }
 
 // ((clamp(x,-1,1) + 1) / 2 * 255).type(uint8): truncation toward zero
@@ -464,6 +642,124 @@ int afd_ddim_step_cfg_dev(const float* x, const float* eps2, const float* noise,
   launch_ddim_step<true>(x, eps2, noise, alpha_hat, 0, 0, t_dev, t_prev_dev, eta, cfg_scale, x_out, x_out2, n, as_stream(st));
   return check_launch("afd_ddim_step_cfg_dev");
 }
+static inline bool aligned16(const void* q) { return ((uintptr_t)q & 15) == 0; }
+
+// ---- masked steps (inpainting) and renoise ---------------------------------------------------------------------------------
+static inline bool overlaps(const void* a, long abytes, const void* b, long bbytes) {
+  const uintptr_t pa = (uintptr_t)a, pb = (uintptr_t)b;
+  return b && pa < pb + (uintptr_t)bbytes && pb < pa + (uintptr_t)abytes;
+}
+// x0 and mask are read by every element while x_out / x_out2 are written: they must not share memory
+static inline bool masked_inputs_apart(const float* x0, const uint8_t* mask, const float* x_out, const float* x_out2, long n) {
+  const long fb = n * (long)sizeof(float);
+  return !overlaps(x0, fb, x_out, fb) && !overlaps(x0, fb, x_out2, fb) && !overlaps(mask, n, x_out, fb) && !overlaps(mask, n, x_out2, fb);
+}
+#define AFD_MASKED_CHECKS(name, x0, mask, x_out, x_out2, n)                                                                   \
+  AFD_REQUIRE(n > 0, name ": n must be positive (got %ld)", n);                                                           \
+  AFD_REQUIRE(masked_inputs_apart(x0, mask, x_out, x_out2, n), name ": x0 and mask must not overlap x_out or x_out2")
+
+int afd_denoise_step_masked(const float* x, const float* eps_pred, const float* noise, const float* x0, const uint8_t* mask,
+                            const float* alpha, const float* alpha_hat, const float* beta, int i, float* x_out, long n,
+                            afd_stream_t st) {
+  AFD_REQUIRE(x && eps_pred && x0 && mask && alpha && alpha_hat && beta && x_out,
+              "afd_denoise_step_masked: x, eps_pred, x0, mask, alpha, alpha_hat, beta and x_out must not be NULL");
+  AFD_MASKED_CHECKS("afd_denoise_step_masked", x0, mask, x_out, (const float*)nullptr, n);
+  AFD_REQUIRE(i >= 1, "afd_denoise_step_masked: need i >= 1 (the step i -> i - 1; got i = %d)", i);
+  AFD_REQUIRE(noise || i == 1, "afd_denoise_step_masked: noise must not be NULL when i > 1 (it noises the known region)");
+  launch_denoise_step_masked<false>(x, eps_pred, noise, x0, mask, alpha, alpha_hat, beta, i, nullptr, 0.0f, x_out, nullptr, n,
+                                    as_stream(st));
+  return check_launch("afd_denoise_step_masked");
+}
+int afd_denoise_step_masked_dev(const float* x, const float* eps_pred, const float* noise, const float* x0, const uint8_t* mask,
+                                const float* alpha, const float* alpha_hat, const float* beta, const int64_t* t_dev, float* x_out,
+                                long n, afd_stream_t st) {
+  AFD_REQUIRE(x && eps_pred && noise && x0 && mask && alpha && alpha_hat && beta && t_dev && x_out,
+              "afd_denoise_step_masked_dev: x, eps_pred, noise, x0, mask, alpha, alpha_hat, beta, t_dev and x_out must not be NULL");
+  AFD_MASKED_CHECKS("afd_denoise_step_masked_dev", x0, mask, x_out, (const float*)nullptr, n);
+  launch_denoise_step_masked<false>(x, eps_pred, noise, x0, mask, alpha, alpha_hat, beta, 0, t_dev, 0.0f, x_out, nullptr, n,
+                                    as_stream(st));
+  return check_launch("afd_denoise_step_masked_dev");
+}
+int afd_denoise_step_masked_cfg(const float* x, const float* eps2, const float* noise, const float* x0, const uint8_t* mask,
+                                const float* alpha, const float* alpha_hat, const float* beta, int i, float cfg_scale, float* x_out,
+                                float* x_out2, long n, afd_stream_t st) {
+  AFD_REQUIRE(x && eps2 && x0 && mask && alpha && alpha_hat && beta && x_out,
+              "afd_denoise_step_masked_cfg: x, eps2, x0, mask, alpha, alpha_hat, beta and x_out must not be NULL");
+  AFD_MASKED_CHECKS("afd_denoise_step_masked_cfg", x0, mask, x_out, x_out2, n);
+  AFD_REQUIRE(i >= 1, "afd_denoise_step_masked_cfg: need i >= 1 (the step i -> i - 1; got i = %d)", i);
+  AFD_REQUIRE(noise || i == 1, "afd_denoise_step_masked_cfg: noise must not be NULL when i > 1 (it noises the known region)");
+  launch_denoise_step_masked<true>(x, eps2, noise, x0, mask, alpha, alpha_hat, beta, i, nullptr, cfg_scale, x_out, x_out2, n,
+                                   as_stream(st));
+  return check_launch("afd_denoise_step_masked_cfg");
+}
+int afd_denoise_step_masked_cfg_dev(const float* x, const float* eps2, const float* noise, const float* x0, const uint8_t* mask,
+                                    const float* alpha, const float* alpha_hat, const float* beta, const int64_t* t_dev,
+                                    float cfg_scale, float* x_out, float* x_out2, long n, afd_stream_t st) {
+  AFD_REQUIRE(x && eps2 && noise && x0 && mask && alpha && alpha_hat && beta && t_dev && x_out,
+              "afd_denoise_step_masked_cfg_dev: x, eps2, noise, x0, mask, alpha, alpha_hat, beta, t_dev and x_out must not be NULL");
+  AFD_MASKED_CHECKS("afd_denoise_step_masked_cfg_dev", x0, mask, x_out, x_out2, n);
+  launch_denoise_step_masked<true>(x, eps2, noise, x0, mask, alpha, alpha_hat, beta, 0, t_dev, cfg_scale, x_out, x_out2, n,
+                                   as_stream(st));
+  return check_launch("afd_denoise_step_masked_cfg_dev");
+}
+int afd_ddim_step_masked(const float* x, const float* eps, const float* noise, const float* x0, const uint8_t* mask,
+                         const float* alpha_hat, int t, int t_prev, float eta, float* x_out, long n, afd_stream_t st) {
+  AFD_REQUIRE(x && eps && x0 && mask && alpha_hat && x_out, "afd_ddim_step_masked: x, eps, x0, mask, alpha_hat and x_out must not be NULL");
+  AFD_MASKED_CHECKS("afd_ddim_step_masked", x0, mask, x_out, (const float*)nullptr, n);
+  AFD_REQUIRE(t_prev >= 0 && t_prev < t, "afd_ddim_step_masked: need 0 <= t_prev < t (got t = %d, t_prev = %d)", t, t_prev);
+  AFD_REQUIRE(eta >= 0.0f, "afd_ddim_step_masked: eta must be >= 0");
+  AFD_REQUIRE(noise || t_prev == 0, "afd_ddim_step_masked: noise must not be NULL when t_prev > 0 (it noises the known region)");
+  launch_ddim_step_masked<false>(x, eps, noise, x0, mask, alpha_hat, t, t_prev, nullptr, nullptr, eta, 0.0f, x_out, nullptr, n,
+                                 as_stream(st));
+  return check_launch("afd_ddim_step_masked");
+}
+int afd_ddim_step_masked_dev(const float* x, const float* eps, const float* noise, const float* x0, const uint8_t* mask,
+                             const float* alpha_hat, const int64_t* t_dev, const int64_t* t_prev_dev, float eta, float* x_out, long n,
+                             afd_stream_t st) {
+  AFD_REQUIRE(x && eps && noise && x0 && mask && alpha_hat && t_dev && t_prev_dev && x_out,
+              "afd_ddim_step_masked_dev: x, eps, noise, x0, mask, alpha_hat, t_dev, t_prev_dev and x_out must not be NULL");
+  AFD_MASKED_CHECKS("afd_ddim_step_masked_dev", x0, mask, x_out, (const float*)nullptr, n);
+  AFD_REQUIRE(eta >= 0.0f, "afd_ddim_step_masked_dev: eta must be >= 0");
+  launch_ddim_step_masked<false>(x, eps, noise, x0, mask, alpha_hat, 0, 0, t_dev, t_prev_dev, eta, 0.0f, x_out, nullptr, n,
+                                 as_stream(st));
+  return check_launch("afd_ddim_step_masked_dev");
+}
+int afd_ddim_step_masked_cfg(const float* x, const float* eps2, const float* noise, const float* x0, const uint8_t* mask,
+                             const float* alpha_hat, int t, int t_prev, float eta, float cfg_scale, float* x_out, float* x_out2, long n,
+                             afd_stream_t st) {
+  AFD_REQUIRE(x && eps2 && x0 && mask && alpha_hat && x_out,
+              "afd_ddim_step_masked_cfg: x, eps2, x0, mask, alpha_hat and x_out must not be NULL");
+  AFD_MASKED_CHECKS("afd_ddim_step_masked_cfg", x0, mask, x_out, x_out2, n);
+  AFD_REQUIRE(t_prev >= 0 && t_prev < t, "afd_ddim_step_masked_cfg: need 0 <= t_prev < t (got t = %d, t_prev = %d)", t, t_prev);
+  AFD_REQUIRE(eta >= 0.0f, "afd_ddim_step_masked_cfg: eta must be >= 0");
+  AFD_REQUIRE(noise || t_prev == 0, "afd_ddim_step_masked_cfg: noise must not be NULL when t_prev > 0 (it noises the known region)");
+  launch_ddim_step_masked<true>(x, eps2, noise, x0, mask, alpha_hat, t, t_prev, nullptr, nullptr, eta, cfg_scale, x_out, x_out2, n,
+                                as_stream(st));
+  return check_launch("afd_ddim_step_masked_cfg");
+}
+int afd_ddim_step_masked_cfg_dev(const float* x, const float* eps2, const float* noise, const float* x0, const uint8_t* mask,
+                                 const float* alpha_hat, const int64_t* t_dev, const int64_t* t_prev_dev, float eta, float cfg_scale,
+                                 float* x_out, float* x_out2, long n, afd_stream_t st) {
+  AFD_REQUIRE(x && eps2 && noise && x0 && mask && alpha_hat && t_dev && t_prev_dev && x_out,
+              "afd_ddim_step_masked_cfg_dev: x, eps2, noise, x0, mask, alpha_hat, t_dev, t_prev_dev and x_out must not be NULL");
+  AFD_MASKED_CHECKS("afd_ddim_step_masked_cfg_dev", x0, mask, x_out, x_out2, n);
+  AFD_REQUIRE(eta >= 0.0f, "afd_ddim_step_masked_cfg_dev: eta must be >= 0");
+  launch_ddim_step_masked<true>(x, eps2, noise, x0, mask, alpha_hat, 0, 0, t_dev, t_prev_dev, eta, cfg_scale, x_out, x_out2, n,
+                                as_stream(st));
+  return check_launch("afd_ddim_step_masked_cfg_dev");
+}
+int afd_renoise(const float* x, const float* noise, const float* alpha_hat, int t_from, int t_to, float* x_out, long n,
+                afd_stream_t st) {
+  AFD_REQUIRE(x && noise && alpha_hat && x_out, "afd_renoise: x, noise, alpha_hat and x_out must not be NULL");
+  AFD_REQUIRE(n > 0, "afd_renoise: n must be positive (got %ld)", n);
+  AFD_REQUIRE(t_from >= 0 && t_from < t_to, "afd_renoise: need 0 <= t_from < t_to (got t_from = %d, t_to = %d)", t_from, t_to);
+  if (n % 4 == 0 && aligned16(x) && aligned16(noise) && aligned16(x_out))
+    hipLaunchKernelGGL(renoise_k<true>, dim3(step_grid(n / 4)), dim3(256), 0, as_stream(st), x, noise, alpha_hat, t_from, t_to, x_out,
+                       n / 4);
+  else
+    hipLaunchKernelGGL(renoise_k<false>, dim3(step_grid(n)), dim3(256), 0, as_stream(st), x, noise, alpha_hat, t_from, t_to, x_out, n);
+  return check_launch("afd_renoise");
+}
 int afd_quantize_u8(const float* x, uint8_t* out, long n, afd_stream_t st) {
   AFD_REQUIRE(x && out && n > 0, "afd_quantize_u8: bad argument");
   hipLaunchKernelGGL(quantize_u8_k, dim3(gs_grid(n)), dim3(256), 0, as_stream(st), x, out, n);
@@ -493,7 +789,6 @@ int afd_adamw_step(float* p, const float* g, float* m, float* v, long n, const f
   return check_launch("afd_adamw_step");
 }
 
-static inline bool aligned16(const void* q) { return ((uintptr_t)q & 15) == 0; }
 static inline bool beta_ok(float beta, float omb) { return beta >= 0.0f && beta <= 1.0f && omb >= 0.0f && omb <= 1.0f; }
 int afd_ema_step(float* ema, const float* p, long n, int copy, float beta, float one_minus_beta, afd_stream_t st) {
   AFD_REQUIRE(ema && p, "afd_ema_step: ema or p is NULL");

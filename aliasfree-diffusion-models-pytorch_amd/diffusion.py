@@ -383,6 +383,186 @@ class Diffusion:
             return xq, rq, x
         return xq, rq
 
+    # Inpainting (RePaint, Lugmayr et al. 2022) -----------------------------------------------------------------------------
+    @staticmethod
+    def repaint_moves(chain, jump_length, jump_n_sample):
+        """RePaint's resampling schedule (its get_schedule_jump, re-indexed onto chain positions) as a list of moves
+        (t_from, t_to).  chain: the strictly decreasing model timesteps (T-1 .. 1 for DDPM, the DDIM taus); levels = chain + [0].
+        A down-move (t > t_to) is one forward and a masked update; an up-move (t < t_to) renoises the whole image.  Every
+        position p (0 < p < S, (S - 1 - p) % j == 0, p >= j) is left jump_n_sample - 1 times by an up-move of jump_length
+        positions.  jump_n_sample = 1 gives the plain chain."""
+        for name, v in (("jump_length", jump_length), ("jump_n_sample", jump_n_sample)):
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v < 1:
+                raise ValueError(f"Diffusion.repaint_moves: {name} must be an int >= 1 (got {v!r})")
+        chain = [int(v) for v in chain]
+        if not chain or chain[-1] < 1 or any(a <= b for a, b in zip(chain, chain[1:])):
+            raise ValueError(f"Diffusion.repaint_moves: chain must be a non-empty, strictly decreasing list of timesteps >= 1")
+        j, r = int(jump_length), int(jump_n_sample)
+        levels, S = chain + [0], len(chain)
+        left = {p: r - 1 for p in range(j, S) if (S - 1 - p) % j == 0}
+        moves, p = [], 0
+        while p < S:
+            moves.append((levels[p], levels[p + 1]))
+            p += 1
+            if left.get(p, 0) > 0:
+                left[p] -= 1
+                moves.append((levels[p], levels[p - j]))
+                p -= j
+        return moves
+
+    def _inpaint_inputs(self, images, mask):
+        """-> (images, mask) on the device: fp32 (n, C, img_size, img_size) and a contiguous uint8 mask of the same shape."""
+        if not isinstance(images, torch.Tensor) or images.dtype != torch.float32:
+            raise ValueError("Diffusion.inpaint: images must be an fp32 tensor")
+        if images.dim() != 4 or images.shape[0] < 1 or tuple(images.shape[2:]) != (self.img_size, self.img_size):
+            raise ValueError(f"Diffusion.inpaint: images must have shape (n, C, {self.img_size}, {self.img_size}) "
+                             f"(got {tuple(images.shape)})")
+        m = torch.as_tensor(mask)
+        if m.dtype.is_complex:
+            raise ValueError("Diffusion.inpaint: mask must hold 0 or 1")
+        try:
+            shape = torch.broadcast_shapes(tuple(m.shape), tuple(images.shape))
+        except RuntimeError:
+            shape = None
+        if shape != tuple(images.shape):
+            raise ValueError(f"Diffusion.inpaint: mask of shape {tuple(m.shape)} does not broadcast to images {tuple(images.shape)}")
+        if not bool(((m == 0) | (m == 1)).all()):
+            raise ValueError("Diffusion.inpaint: every mask value must be 0 or 1 (1 = known: keep the pixel of images)")
+        x0 = images.to(self.device).contiguous()
+        m = m.to(self.device).to(torch.uint8).expand(x0.shape).contiguous()
+        return x0, m
+
+    def inpaint(self, model, images, mask, steps=None, eta=0.0, labels=None, cfg_scale=0.0, jump_length=10, jump_n_sample=1,
+                noise_source="reference", graph=None, return_float=False):
+        """Fill the region of `images` where `mask` is 0 and keep the rest (RePaint, Lugmayr et al. 2022): no retraining.
+        images: (n, C, img_size, img_size) fp32 in [-1, 1]; mask: broadcasts to images.shape, every value 0 or 1, 1 = known.
+        steps / eta / labels / cfg_scale / noise_source / graph: as for `sample`.  x_T is drawn as `sample` draws it.  Each
+        down-move t -> t_prev draws the noise of n images where `sample` draws it (after the forward), and whenever t_prev > 0
+        (also for DDIM with eta = 0): a generated pixel uses it as the sampler's step noise, a known pixel to noise images to
+        t_prev (at t_prev = 0 the known pixels are images itself).  With an all-zero mask the output is `sample`'s, bit for bit.
+        jump_n_sample (RePaint's r) and jump_length (j): resampling (`repaint_moves`); every up-move draws the noise of n
+        images and renoises the whole image.  graph=True captures one down-move and replays it; up-moves and the last step run
+        eagerly in between.  Snapshots: after every down-move that crosses a multiple of 100 (`ddim_snapshot`), so a
+        re-descended segment adds its snapshots again, plus the final x.  Returns what `sample` returns."""
+        logging.info(f"Inpainting {images.shape[0] if isinstance(images, torch.Tensor) else '?'} images....")
+        pairs = self._check_ddim("inpaint", steps, eta)
+        chain = list(range(self.noise_steps - 1, 0, -1)) if pairs is None else [t for t, _ in pairs]
+        moves = self.repaint_moves(chain, jump_length, jump_n_sample)
+        x0, m = self._inpaint_inputs(images, mask)
+        n = x0.shape[0]
+        if labels is not None:
+            labels = self._check_labels(model, n, None, labels)
+        elif cfg_scale:
+            raise ValueError("Diffusion.inpaint: cfg_scale needs class labels")
+        x, snaps = self._inpaint_loop(model, x0, m, moves, None if pairs is None else float(eta), noise_source, graph, labels,
+                                      float(cfg_scale))
+        self.last_float_snapshots = snaps
+        xq = ops.quantize_u8(x)
+        rq = ops.quantize_u8(torch.cat(snaps))
+        if return_float:
+            return xq, rq, x
+        return xq, rq
+
+    def _masked_update(self, xs, n, eps, z, x0, mask, t, tp, eta, cfg_scale, t_dev=None, tp_dev=None):
+        """One masked down-move, in place on xs[:n] (and on xs[n:] too when guided).  eta None: DDPM; t_dev: the _dev form."""
+        x = xs[:n]
+        out2 = xs[n:] if cfg_scale > 0 else None
+        if eta is None:
+            if cfg_scale > 0 and t_dev is not None:
+                ops.denoise_step_masked_cfg_dev(x, eps, z, x0, mask, self.alpha, self.alpha_hat, self.beta, t_dev, cfg_scale, x, out2)
+            elif cfg_scale > 0:
+                ops.denoise_step_masked_cfg(x, eps, z, x0, mask, self.alpha, self.alpha_hat, self.beta, t, cfg_scale, x, out2)
+            elif t_dev is not None:
+                ops.denoise_step_masked_dev(x, eps, z, x0, mask, self.alpha, self.alpha_hat, self.beta, t_dev, x)
+            else:
+                ops.denoise_step_masked(x, eps, z, x0, mask, self.alpha, self.alpha_hat, self.beta, t, x)
+        elif cfg_scale > 0 and t_dev is not None:
+            ops.ddim_step_masked_cfg_dev(x, eps, z, x0, mask, self.alpha_hat, t_dev, tp_dev, eta, cfg_scale, x, out2)
+        elif cfg_scale > 0:
+            ops.ddim_step_masked_cfg(x, eps, z, x0, mask, self.alpha_hat, t, tp, eta, cfg_scale, x, out2)
+        elif t_dev is not None:
+            ops.ddim_step_masked_dev(x, eps, z, x0, mask, self.alpha_hat, t_dev, tp_dev, eta, x)
+        else:
+            ops.ddim_step_masked(x, eps, z, x0, mask, self.alpha_hat, t, tp, eta, x)
+
+    def _inpaint_loop(self, model, x0, mask, moves, eta, noise_source, graph, labels, cfg_scale):
+        """`inpaint`'s trajectory over `moves`.  The state lives in xs: n rows, or the 2n rows [x ; x] of the guided forward,
+        which every update writes in place (both halves)."""
+        n, c = x0.shape[0], x0.shape[1]
+        guided = labels is not None and cfg_scale > 0
+        s = cfg_scale if guided else 0.0
+        self._hint(model)
+        try:
+            model.eval()
+            snaps = []
+            with torch.no_grad():
+                x = self._initial_noise(n, c, noise_source)
+                y = labels
+                if guided:
+                    y = torch.cat([labels, torch.full_like(labels, ops.NULL_LABEL)])
+                xs = torch.cat([x, x]) if guided else x
+                rows = xs.shape[0]
+
+                def forward(t_rows):
+                    return model(xs, t_rows) if y is None else model(xs, t_rows, y)
+
+                replay = None
+                first = next(((t, tp) for t, tp in moves if t > tp > 0), None)
+                if graph and noise_source != "cpu" and first is not None:
+                    t_dev = torch.full((rows,), first[0], device=x.device, dtype=torch.long)
+                    tp_dev = torch.full((1,), first[1], device=x.device, dtype=torch.long)
+
+                    def one_step():
+                        eps = forward(t_dev)
+                        z = torch.randn_like(xs[:n])
+                        self._masked_update(xs, n, eps, z, x0, mask, None, None, eta, s, t_dev, tp_dev)
+
+                    g = self._capture(one_step, xs)
+
+                    def replay(t, tp):
+                        t_dev.fill_(t)
+                        tp_dev.fill_(tp)
+                        g.replay()
+                for t, tp in moves:
+                    if tp > t:                                   # up-move: renoise the whole image from level t to tp
+                        z = self._step_noise(xs[:n], noise_source)
+                        ops.renoise(xs[:n], z, self.alpha_hat, t, tp, out=xs[:n])
+                        if guided:
+                            xs[n:].copy_(xs[:n])
+                        continue
+                    if replay is not None and tp > 0:
+                        replay(t, tp)
+                    else:
+                        eps = forward(self._t_full(rows, t, x.device))
+                        z = self._step_noise(xs[:n], noise_source) if tp > 0 else None
+                        self._masked_update(xs, n, eps, z, x0, mask, t, tp, eta, s)
+                    if self.ddim_snapshot(t, tp):
+                        snaps.append(xs[:n].clone())
+                x = xs[:n].clone()
+        finally:
+            model.train()
+            self._unhint(model)
+        snaps.append(x)
+        return x, snaps
+
+    @staticmethod
+    def _capture(one_step, xs):
+        """Capture one_step (which updates xs in place) into a hipGraph, after a warm-up on a side stream whose effect on xs
+        and on the device generator is undone: the replays consume the noise stream the eager loop would."""
+        side = torch.cuda.Stream()
+        side.wait_stream(torch.cuda.current_stream())
+        keep = xs.clone()
+        rng = torch.cuda.get_rng_state(xs.device)
+        with torch.cuda.stream(side):
+            one_step()
+        torch.cuda.current_stream().wait_stream(side)
+        xs.copy_(keep)
+        torch.cuda.set_rng_state(rng, xs.device)
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g):
+            one_step()
+        return g
+
     def sample_sharded(self, model, n, image_channels, theta=None, noise_source="reference", group=None, dst=0, steps=None):
         """`sample` with the n images partitioned over the ranks of `group` (sampling is embarrassingly parallel per
         image: replicas only, no collective in the loop) and the uint8 results gathered on rank `dst`.

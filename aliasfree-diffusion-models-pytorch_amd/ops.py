@@ -1225,6 +1225,98 @@ def ddim_step_cfg_dev(x, eps2, noise, alpha_hat, t_dev, t_prev_dev, eta, cfg_sca
     return out
 
 
+# ---- inpainting: masked steps and the renoise up-move (include/afd.h gives the exact expressions) --------------------------
+def _masked_args(what, x, eps, noise, x0, mask, out, out2=None, guided=False):
+    n = _ddim_args(what, x, eps, noise, None, out, out2, guided)
+    _chk(x0)
+    if x0.numel() != n or not x0.is_contiguous():
+        raise AfdError(f"afdm: {what}: x0 must be a contiguous tensor of {n} elements")
+    if not mask.is_cuda or mask.dtype != torch.uint8 or mask.numel() != n or not mask.is_contiguous():
+        raise AfdError(f"afdm: {what}: mask must be a contiguous uint8 device tensor of {n} elements")
+    return n
+
+
+def denoise_step_masked(x, eps, noise, x0, mask, alpha, alpha_hat, beta, i, out=None):
+    """Masked DDPM update i -> i - 1: where mask is 0, `denoise_step`; where it is 1, x0 noised to i - 1 with the same noise
+    (x0 itself at i == 1, where noise may be None).  `out` may be x (in place)."""
+    out = torch.empty_like(x) if out is None else out
+    n = _masked_args("masked denoise step", x, eps, noise, x0, mask, out)
+    lib().afd_denoise_step_masked(_p(x), _p(eps), _p(noise), _p(x0), _p(mask), _p(alpha), _p(alpha_hat), _p(beta), int(i), _p(out),
+                                  n, _stream())
+    return out
+
+
+def denoise_step_masked_dev(x, eps, noise, x0, mask, alpha, alpha_hat, beta, t_dev, out):
+    """denoise_step_masked with the step index t_dev[0] read on the device (graph-replayable); noise is required."""
+    n = _masked_args("masked denoise step", x, eps, noise, x0, mask, out)
+    lib().afd_denoise_step_masked_dev(_p(x), _p(eps), _p(noise), _p(x0), _p(mask), _p(alpha), _p(alpha_hat), _p(beta), _p(t_dev),
+                                      _p(out), n, _stream())
+    return out
+
+
+def denoise_step_masked_cfg(x, eps2, noise, x0, mask, alpha, alpha_hat, beta, i, cfg_scale, out=None, out2=None):
+    """The guided form of denoise_step_masked (eps2 as for denoise_step_cfg); `out2` (optional) receives the same values."""
+    out = torch.empty_like(x) if out is None else out
+    n = _masked_args("guided masked denoise step", x, eps2, noise, x0, mask, out, out2, guided=True)
+    lib().afd_denoise_step_masked_cfg(_p(x), _p(eps2), _p(noise), _p(x0), _p(mask), _p(alpha), _p(alpha_hat), _p(beta), int(i),
+                                      float(cfg_scale), _p(out), _p(out2), n, _stream())
+    return out
+
+
+def denoise_step_masked_cfg_dev(x, eps2, noise, x0, mask, alpha, alpha_hat, beta, t_dev, cfg_scale, out, out2=None):
+    n = _masked_args("guided masked denoise step", x, eps2, noise, x0, mask, out, out2, guided=True)
+    lib().afd_denoise_step_masked_cfg_dev(_p(x), _p(eps2), _p(noise), _p(x0), _p(mask), _p(alpha), _p(alpha_hat), _p(beta),
+                                          _p(t_dev), float(cfg_scale), _p(out), _p(out2), n, _stream())
+    return out
+
+
+def ddim_step_masked(x, eps, noise, x0, mask, alpha_hat, t, t_prev, eta, out=None):
+    """Masked DDIM update t -> t_prev: where mask is 0, `ddim_step` (no noise term when eta == 0); where it is 1, x0 noised to
+    t_prev with the same noise (x0 itself at t_prev == 0, where noise may be None).  `out` may be x (in place)."""
+    out = torch.empty_like(x) if out is None else out
+    n = _masked_args("masked DDIM step", x, eps, noise, x0, mask, out)
+    t, t_prev, eta = _ddim_host_t("masked DDIM step", alpha_hat, t, t_prev, eta)
+    lib().afd_ddim_step_masked(_p(x), _p(eps), _p(noise), _p(x0), _p(mask), _p(alpha_hat), t, t_prev, eta, _p(out), n, _stream())
+    return out
+
+
+def ddim_step_masked_dev(x, eps, noise, x0, mask, alpha_hat, t_dev, t_prev_dev, eta, out):
+    n = _masked_args("masked DDIM step", x, eps, noise, x0, mask, out)
+    _ddim_dev_t("masked DDIM step", t_dev, t_prev_dev)
+    lib().afd_ddim_step_masked_dev(_p(x), _p(eps), _p(noise), _p(x0), _p(mask), _p(alpha_hat), _p(t_dev), _p(t_prev_dev), float(eta),
+                                   _p(out), n, _stream())
+    return out
+
+
+def ddim_step_masked_cfg(x, eps2, noise, x0, mask, alpha_hat, t, t_prev, eta, cfg_scale, out=None, out2=None):
+    out = torch.empty_like(x) if out is None else out
+    n = _masked_args("guided masked DDIM step", x, eps2, noise, x0, mask, out, out2, guided=True)
+    t, t_prev, eta = _ddim_host_t("guided masked DDIM step", alpha_hat, t, t_prev, eta)
+    lib().afd_ddim_step_masked_cfg(_p(x), _p(eps2), _p(noise), _p(x0), _p(mask), _p(alpha_hat), t, t_prev, eta, float(cfg_scale),
+                                   _p(out), _p(out2), n, _stream())
+    return out
+
+
+def ddim_step_masked_cfg_dev(x, eps2, noise, x0, mask, alpha_hat, t_dev, t_prev_dev, eta, cfg_scale, out, out2=None):
+    n = _masked_args("guided masked DDIM step", x, eps2, noise, x0, mask, out, out2, guided=True)
+    _ddim_dev_t("guided masked DDIM step", t_dev, t_prev_dev)
+    lib().afd_ddim_step_masked_cfg_dev(_p(x), _p(eps2), _p(noise), _p(x0), _p(mask), _p(alpha_hat), _p(t_dev), _p(t_prev_dev),
+                                       float(eta), float(cfg_scale), _p(out), _p(out2), n, _stream())
+    return out
+
+
+def renoise(x, noise, alpha_hat, t_from, t_to, out=None):
+    """q(x_{t_to} | x_{t_from}) in one jump: sqrt(a) * x + sqrt(1 - a) * noise, a = alpha_hat[t_to] / alpha_hat[t_from].
+    `out` may be x (in place)."""
+    out = torch.empty_like(x) if out is None else out
+    n = _ddim_args("renoise", x, noise, None, alpha_hat, out)
+    t_from, t_to = int(t_from), int(t_to)
+    if not 0 <= t_from < t_to < alpha_hat.numel():
+        raise AfdError(f"afdm: renoise needs 0 <= t_from < t_to < {alpha_hat.numel()} (got {t_from}, {t_to})")
+    lib().afd_renoise(_p(x), _p(noise), _p(alpha_hat), t_from, t_to, _p(out), n, _stream())
+    return out
+
+
 def quantize_u8(x):
     _chk(x)
     x = _c(x)

@@ -149,6 +149,14 @@ def rotation_results(model_data, thatas):
     return diffusion.sample_rotation_sweep_sharded(model, 4, args.image_channels, list(thatas))
 
 
+def inpaint_results(model_data, images, mask, **kw):
+    """Load the checkpoint as rotation_results does, seed, and fill the region of `images` where `mask` is 0
+    (Diffusion.inpaint; **kw: steps, eta, labels, cfg_scale, jump_length, jump_n_sample, noise_source, graph, return_float)."""
+    model, diffusion, _ = _load(model_data)
+    set_seed(model_data["seed"])
+    return diffusion.inpaint(model, images, mask, **kw)
+
+
 def shift_results(model_data, shift):
     model, diffusion, args = _load(model_data)
     x_all = []

@@ -398,6 +398,45 @@ int afd_ddim_step_cfg(const float* x, const float* eps2, const float* noise, con
 int afd_ddim_step_cfg_dev(const float* x, const float* eps2, const float* noise, const float* alpha_hat, const int64_t* t_dev,
                           const int64_t* t_prev_dev, float eta, float cfg_scale, float* x_out, float* x_out2, long n,
                           afd_stream_t stream);
+/* ---- inpainting (RePaint, Lugmayr et al. 2022): masked steps and the renoise up-move ----
+ * Each masked entry point is its unmasked counterpart above with two more operands after noise: x0 (n fp32 values, the known
+ * image) and mask (n bytes; nonzero = known).  Per element j, with t_prev = i - 1 for the DDPM forms:
+ *   gen   = the unmasked update, bit for bit (for the guided forms the lerp first, as above), except that its noise term is
+ *           +0 when t_prev == 0 (DDPM: i == 1) and, for DDIM, when eta == 0
+ *   known = x0                                               if t_prev == 0
+ *           (sqrt(a_p) * x0) + (sqrt(1 - a_p) * noise)       otherwise, a_p = alpha_hat[t_prev] (afd_noise_images' order)
+ *   out   = mask[j] ? known : gen                            (x_out2, when given, receives the same values)
+ * noise is read once per element and serves whichever region the element is in; it may be NULL only when t_prev == 0 on the
+ * host forms and never on the _dev forms.  x_out may alias x; x0 and mask must not overlap x_out or x_out2.  The host forms
+ * need i >= 1 (DDPM) or 0 <= t_prev < t (DDIM); every form needs eta >= 0 and n > 0. */
+int afd_denoise_step_masked(const float* x, const float* eps_pred, const float* noise, const float* x0, const uint8_t* mask,
+                            const float* alpha, const float* alpha_hat, const float* beta, int i, float* x_out, long n,
+                            afd_stream_t stream);
+int afd_denoise_step_masked_dev(const float* x, const float* eps_pred, const float* noise, const float* x0, const uint8_t* mask,
+                                const float* alpha, const float* alpha_hat, const float* beta, const int64_t* t_dev, float* x_out,
+                                long n, afd_stream_t stream);
+int afd_denoise_step_masked_cfg(const float* x, const float* eps2, const float* noise, const float* x0, const uint8_t* mask,
+                                const float* alpha, const float* alpha_hat, const float* beta, int i, float cfg_scale, float* x_out,
+                                float* x_out2, long n, afd_stream_t stream);
+int afd_denoise_step_masked_cfg_dev(const float* x, const float* eps2, const float* noise, const float* x0, const uint8_t* mask,
+                                    const float* alpha, const float* alpha_hat, const float* beta, const int64_t* t_dev,
+                                    float cfg_scale, float* x_out, float* x_out2, long n, afd_stream_t stream);
+int afd_ddim_step_masked(const float* x, const float* eps, const float* noise, const float* x0, const uint8_t* mask,
+                         const float* alpha_hat, int t, int t_prev, float eta, float* x_out, long n, afd_stream_t stream);
+int afd_ddim_step_masked_dev(const float* x, const float* eps, const float* noise, const float* x0, const uint8_t* mask,
+                             const float* alpha_hat, const int64_t* t_dev, const int64_t* t_prev_dev, float eta, float* x_out, long n,
+                             afd_stream_t stream);
+int afd_ddim_step_masked_cfg(const float* x, const float* eps2, const float* noise, const float* x0, const uint8_t* mask,
+                             const float* alpha_hat, int t, int t_prev, float eta, float cfg_scale, float* x_out, float* x_out2, long n,
+                             afd_stream_t stream);
+int afd_ddim_step_masked_cfg_dev(const float* x, const float* eps2, const float* noise, const float* x0, const uint8_t* mask,
+                                 const float* alpha_hat, const int64_t* t_dev, const int64_t* t_prev_dev, float eta, float cfg_scale,
+                                 float* x_out, float* x_out2, long n, afd_stream_t stream);
+/* q(x_{t_to} | x_{t_from}) of the forward process in one jump, fp32 with one rounding per operation:
+ *   a = alpha_hat[t_to] / alpha_hat[t_from];   out = (sqrt(a) * x) + (sqrt(1 - a) * noise)
+ * Requires 0 <= t_from < t_to (t_to is not checked against the table's length) and n > 0.  x_out may alias x. */
+int afd_renoise(const float* x, const float* noise, const float* alpha_hat, int t_from, int t_to, float* x_out, long n,
+                afd_stream_t stream);
 int afd_quantize_u8(const float* x, uint8_t* out, long n, afd_stream_t stream);
 
 /* ---- F17 (Config E): scipy.ndimage.rotate(order=3, mode='grid-wrap', prefilter=True) per (H,W) plane ----
