@@ -416,6 +416,81 @@ __global__ __launch_bounds__(256) void renoise_k(const float* x, const float* __
   }
 }
 
+// ---- DPM-Solver++(2M) (Lu et al. 2022): one multistep update t -> t_prev -------------------------------------------------
+// coef (device, 5 floats, built on the host per step: Diffusion.dpmpp_coefficients) = [alpha_t, sigma_t, A, B0, B1];
+// fp32, one rounding per operation, in this order:
+//   x0  = (x - (sigma_t * e)) / alpha_t
+//   out = ((A * x) + (B0 * x0)) + (x0_prev ? B1 * x0_prev : +0)        x0_out = x0
+// With CFG, e is cfg_lerp of the two halves of eps2 first.  The coefficients are read on the device, so one launch serves the
+// eager loop and graph replay.  x_out may alias x; x0_out may be x0_prev itself (each element reads its x0_prev before it
+// writes x0_out) but overlaps nothing else; x_out2 is optional.  VEC: n % 4 == 0, every pointer 16-byte aligned; n counts float4s.
+struct DpmCoef {
+  float alpha, sigma, A, B0, B1, s, one_minus_s;
+  bool small;
+};
+__device__ __forceinline__ float dpmpp_update(const DpmCoef& k, float x, float e, float xp, bool has_prev, float& x0) {
+  const float pe = k.sigma * e;
+  x0 = (x - pe) / k.alpha;
+  const float l = k.A * x, r = k.B0 * x0;
+  const float m = l + r;
+  const float p = has_prev ? k.B1 * xp : 0.0f;
+  return m + p;
+}
+template <bool kCfg>
+__device__ __forceinline__ float dpmpp_eps(const DpmCoef& k, float ec, float eu) {
+  return kCfg ? cfg_lerp(k.s, k.one_minus_s, k.small, ec, eu) : ec;
+}
+template <bool kCfg, bool VEC>
+__global__ __launch_bounds__(256) void dpmpp_step_k(const float* x, const float* __restrict__ eps, const float* x0_prev,
+                                                    const float* __restrict__ coef, float s, float* x_out, float* x_out2,
+                                                    float* x0_out, long n) {
+  DpmCoef k;
+  k.alpha = coef[0];
+  k.sigma = coef[1];
+  k.A = coef[2];
+  k.B0 = coef[3];
+  k.B1 = coef[4];
+  k.s = s;
+  k.one_minus_s = 1.0f - s;
+  k.small = fabsf(s) < 0.5f;
+  const bool has_prev = x0_prev != nullptr;
+  AFD_GRID_STRIDE(i, n) {
+    if (VEC) {
+      const float4 xv = reinterpret_cast<const float4*>(x)[i], c = reinterpret_cast<const float4*>(eps)[i];
+      const float4 u = kCfg ? reinterpret_cast<const float4*>(eps)[n + i] : c;
+      const float4 p = has_prev ? reinterpret_cast<const float4*>(x0_prev)[i] : make_float4(0.f, 0.f, 0.f, 0.f);
+      float4 r, x0;
+      r.x = dpmpp_update(k, xv.x, dpmpp_eps<kCfg>(k, c.x, u.x), p.x, has_prev, x0.x);
+      r.y = dpmpp_update(k, xv.y, dpmpp_eps<kCfg>(k, c.y, u.y), p.y, has_prev, x0.y);
+      r.z = dpmpp_update(k, xv.z, dpmpp_eps<kCfg>(k, c.z, u.z), p.z, has_prev, x0.z);
+      r.w = dpmpp_update(k, xv.w, dpmpp_eps<kCfg>(k, c.w, u.w), p.w, has_prev, x0.w);
+      reinterpret_cast<float4*>(x_out)[i] = r;
+      if (x_out2) reinterpret_cast<float4*>(x_out2)[i] = r;
+      reinterpret_cast<float4*>(x0_out)[i] = x0;
+    } else {
+      float x0;
+      const float e = dpmpp_eps<kCfg>(k, eps[i], kCfg ? eps[n + i] : 0.0f);
+      const float r = dpmpp_update(k, x[i], e, has_prev ? x0_prev[i] : 0.0f, has_prev, x0);
+      x_out[i] = r;
+      if (x_out2) x_out2[i] = r;
+      x0_out[i] = x0;
+    }
+  }
+}
+template <bool kCfg>
+static void launch_dpmpp_step(const float* x, const float* eps, const float* x0_prev, const float* coef, float s, float* x_out,
+                              float* x_out2, float* x0_out, long n, hipStream_t st) {
+  auto a16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
+  const bool vec = n % 4 == 0 && a16(x) && a16(eps) && a16(x_out) && a16(x0_out) && (!x0_prev || a16(x0_prev)) &&
+                   (!x_out2 || a16(x_out2));
+  const long work = vec ? n / 4 : n;
+  const int grid = (int)std::min<long>(2048, std::max<long>(1, (work + 255) / 256));      // memory-bound: grid-stride the rest
+  if (vec)
+    hipLaunchKernelGGL((dpmpp_step_k<kCfg, true>), dim3(grid), dim3(256), 0, st, x, eps, x0_prev, coef, s, x_out, x_out2, x0_out, work);
+  else
+    hipLaunchKernelGGL((dpmpp_step_k<kCfg, false>), dim3(grid), dim3(256), 0, st, x, eps, x0_prev, coef, s, x_out, x_out2, x0_out, n);
+}
+
 // ((clamp(x,-1,1) + 1) / 2 * 255).type(uint8): truncation toward zero
 __global__ void quantize_u8_k(const float* __restrict__ x, uint8_t* __restrict__ out, long n) {
   AFD_GRID_STRIDE(i, n) {
@@ -759,6 +834,34 @@ int afd_renoise(const float* x, const float* noise, const float* alpha_hat, int 
   else
     hipLaunchKernelGGL(renoise_k<false>, dim3(step_grid(n)), dim3(256), 0, as_stream(st), x, noise, alpha_hat, t_from, t_to, x_out, n);
   return check_launch("afd_renoise");
+}
+
+// ---- DPM-Solver++(2M) ------------------------------------------------------------------------------------------------------
+// x0_out is written while x, eps, x_out and x_out2 are read or written by other elements: it must share no memory with them.
+// x0_prev may be x0_out itself (the sampler's in-place state) but may not overlap it partly.
+static inline bool dpmpp_apart(const float* x, const float* eps, long eps_n, const float* x0_prev, float* x_out, float* x_out2,
+                               float* x0_out, long n) {
+  const long fb = n * (long)sizeof(float);
+  return !overlaps(x0_out, fb, x, fb) && !overlaps(x0_out, fb, eps, eps_n * (long)sizeof(float)) && !overlaps(x0_out, fb, x_out, fb) &&
+         !overlaps(x0_out, fb, x_out2, fb) && (x0_prev == x0_out || !overlaps(x0_out, fb, x0_prev, fb));
+}
+int afd_dpmpp_step(const float* x, const float* eps, const float* x0_prev, const float* coef, float* x_out, float* x0_out, long n,
+                   afd_stream_t st) {
+  AFD_REQUIRE(x && eps && coef && x_out && x0_out, "afd_dpmpp_step: x, eps, coef, x_out and x0_out must not be NULL");
+  AFD_REQUIRE(n > 0, "afd_dpmpp_step: n must be positive (got %ld)", n);
+  AFD_REQUIRE(dpmpp_apart(x, eps, n, x0_prev, x_out, nullptr, x0_out, n),
+              "afd_dpmpp_step: x0_out must not overlap x, eps or x_out, and must be x0_prev itself or apart from it");
+  launch_dpmpp_step<false>(x, eps, x0_prev, coef, 0.0f, x_out, nullptr, x0_out, n, as_stream(st));
+  return check_launch("afd_dpmpp_step");
+}
+int afd_dpmpp_step_cfg(const float* x, const float* eps2, const float* x0_prev, const float* coef, float cfg_scale, float* x_out,
+                       float* x_out2, float* x0_out, long n, afd_stream_t st) {
+  AFD_REQUIRE(x && eps2 && coef && x_out && x0_out, "afd_dpmpp_step_cfg: x, eps2, coef, x_out and x0_out must not be NULL");
+  AFD_REQUIRE(n > 0, "afd_dpmpp_step_cfg: n must be positive (got %ld)", n);
+  AFD_REQUIRE(dpmpp_apart(x, eps2, 2 * n, x0_prev, x_out, x_out2, x0_out, n),
+              "afd_dpmpp_step_cfg: x0_out must not overlap x, eps2, x_out or x_out2, and must be x0_prev itself or apart from it");
+  launch_dpmpp_step<true>(x, eps2, x0_prev, coef, cfg_scale, x_out, x_out2, x0_out, n, as_stream(st));
+  return check_launch("afd_dpmpp_step_cfg");
 }
 int afd_quantize_u8(const float* x, uint8_t* out, long n, afd_stream_t st) {
   AFD_REQUIRE(x && out && n > 0, "afd_quantize_u8: bad argument");

@@ -7,6 +7,7 @@ restatements (csrc/ddpm.hip).  The sampling loop stays on the device: no per-ste
 (the reference does one per step, :362) and no per-step host sync.
 """
 import logging
+import math
 
 import numpy as np
 import torch
@@ -170,14 +171,15 @@ class Diffusion:
             return [T - 1]
         return [1 + (k * (T - 2)) // (S - 1) for k in reversed(range(S))]
 
-    def _ddim_pairs(self, steps, eta):
+    def _ddim_pairs(self, steps, eta, timesteps=None):
         """steps (an int S or an explicit strictly decreasing sequence of ints in [1, T-1]) -> [(t, t_prev)], the last
-        t_prev 0.  Raises ValueError for anything else, and for eta < 0."""
+        t_prev 0.  Raises ValueError for anything else, and for eta < 0.  timesteps: the rule for an int S (default
+        `ddim_timesteps`)."""
         eta = float(eta)
         if not eta >= 0:
             raise ValueError(f"Diffusion: DDIM needs eta >= 0 (got {eta})")
         if isinstance(steps, (int, np.integer)) and not isinstance(steps, bool):
-            taus = self.ddim_timesteps(steps)
+            taus = (timesteps or self.ddim_timesteps)(steps)
         else:
             try:
                 taus = list(steps)
@@ -280,6 +282,145 @@ class Diffusion:
                 snaps.append(xh.clone())
         return xh.clone()
 
+    # DPM-Solver++(2M) (Lu et al. 2022): a second-order multistep solver of the probability-flow ODE ------------------------
+    def _logsnr(self):
+        """lam(t) = log(sqrt(a_t)) - log(sqrt(1 - a_t)) in fp64 for every t, a_t the fp32 alpha_hat[t] (decreasing in t)."""
+        a = self.alpha_hat.detach().cpu().double().numpy()
+        return np.log(np.sqrt(a)) - np.log(np.sqrt(1.0 - a))
+
+    def logsnr_timesteps(self, steps):
+        """The S = `steps` timesteps of a DPM-Solver++ chain, uniform in log-SNR and strictly decreasing from T - 1 to 1.
+        r_0 = T - 1, r_{S-1} = 1; for 0 < k < S - 1, r_k is the t in [1, T - 1] whose lam(t) is nearest to
+        lam(T-1) + (k / (S-1)) (lam(1) - lam(T-1)), ties to the smaller t.  Then r_k = max(r_k, r_{k+1} + 1) for k = S-2 .. 0,
+        and r_k = min(r_k, T - 1 - k).  S = 1: [T - 1]; S = T - 1: T-1 .. 1.  Argument errors as `ddim_timesteps`."""
+        T = self.noise_steps
+        if isinstance(steps, bool) or not isinstance(steps, (int, np.integer)):
+            raise ValueError(f"Diffusion.logsnr_timesteps: steps must be an int (got {type(steps).__name__})")
+        S = int(steps)
+        if not 1 <= S <= T - 1:
+            raise ValueError(f"Diffusion.logsnr_timesteps: steps must lie in [1, {T - 1}] (got {S})")
+        if S == 1:
+            return [T - 1]
+        lam = self._logsnr()
+        k = np.arange(1, S - 1)
+        target = lam[T - 1] + (k / (S - 1)) * (lam[1] - lam[T - 1])
+        up = -lam[1:T]                                   # increasing; position j is t = j + 1
+        hi = np.clip(np.searchsorted(up, -target), 0, T - 2)
+        lo = np.clip(hi - 1, 0, T - 2)
+        pick = np.where(np.abs(up[hi] + target) < np.abs(up[lo] + target), hi, lo)     # ties: lo, the smaller t
+        r = np.concatenate([[T - 1], pick + 1, [1]]).astype(np.int64)
+        for i in range(S - 2, -1, -1):
+            r[i] = max(r[i], r[i + 1] + 1)
+        r = np.minimum(r, T - 1 - np.arange(S))
+        return [int(v) for v in r]
+
+    def dpmpp_pairs(self, steps):
+        """steps (an int S, spaced by `logsnr_timesteps`, or an explicit strictly decreasing sequence validated as for DDIM)
+        -> [(t, t_prev)], the last t_prev 0."""
+        return self._ddim_pairs(steps, 0.0, self.logsnr_timesteps)
+
+    @staticmethod
+    def dpmpp_order(k, S):
+        """The order of step k of an S-step DPM-Solver++(2M) chain: 1 at k = 0 (no previous x0) and, when S < 15, at the last
+        step (diffusers' lower_order_final); 2 otherwise."""
+        return 1 if k == 0 or (k == S - 1 and S < 15) else 2
+
+    def dpmpp_coefficients(self, pairs):
+        """(S, 5) fp32 host table of the DPM-Solver++(2M) chain `pairs`: row k = [alpha(t), sigma(t), A, B0, B1] of the step
+        t -> tp, computed in fp64 and rounded once.  alpha(t) = sqrt(a_t), sigma(t) = sqrt(1 - a_t), h_k = lam(tp) - lam(t),
+        A = sigma(tp) / sigma(t), B = -alpha(tp) expm1(-h_k).  First order (B0 = B, B1 = 0) at k = 0 and, when S < 15, at
+        k = S - 1; otherwise second order with r = h_{k-1} / h_k: B0 = B (1 + 1 / (2 r)), B1 = -B / (2 r)."""
+        ah = self.alpha_hat.detach().cpu().tolist()                      # one copy; Python floats hold the fp32 values exactly
+        alpha = lambda t: math.sqrt(ah[t])
+        sigma = lambda t: math.sqrt(1.0 - ah[t])
+        lam = lambda t: math.log(alpha(t)) - math.log(sigma(t))
+        S = len(pairs)
+        rows, h_prev = [], None
+        for k, (t, tp) in enumerate(pairs):
+            h = lam(tp) - lam(t)
+            A = sigma(tp) / sigma(t)
+            B = -alpha(tp) * math.expm1(-h)
+            if self.dpmpp_order(k, S) == 1:
+                B0, B1 = B, 0.0
+            else:
+                r = h_prev / h
+                B0, B1 = B * (1.0 + 1.0 / (2.0 * r)), -B / (2.0 * r)
+            rows.append([alpha(t), sigma(t), A, B0, B1])
+            h_prev = h
+        return torch.tensor(np.array(rows, dtype=np.float64).astype(np.float32))
+
+    def _dpmpp_loop(self, model, n, image_channels, pairs, noise_source="reference", graph=None, labels=None, cfg_scale=0.0):
+        """`_loop` over the DPM-Solver++(2M) steps `pairs`: x_T drawn as in `_loop`, no noise after it, one forward per step
+        (2n rows when guided).  The x0 of the previous step is the solver's state, updated in place by the kernel.  graph:
+        capture one step (forward and update, reading the step's coefficients from a static device buffer) and replay it for
+        every step but the last, which runs eagerly."""
+        self._hint(model)
+        try:
+            model.eval()
+            snaps = []
+            with torch.no_grad():
+                x = self._initial_noise(n, image_channels, noise_source)
+                table = self.dpmpp_coefficients(pairs).to(x.device)          # once per trajectory
+                guided = labels is not None and cfg_scale > 0
+                s = cfg_scale if guided else 0.0
+                y = labels
+                if guided:
+                    y = torch.cat([labels, torch.full_like(labels, ops.NULL_LABEL)])
+                xs = torch.cat([x, x]) if guided else x
+                x0 = torch.zeros_like(x)                                      # the solver state: the previous step's x0
+                first = 0
+                if graph and len(pairs) > 1:
+                    xs = self._dpmpp_graph_steps(model, xs, n, x0, snaps, pairs[:-1], table, y, s)
+                    first = len(pairs) - 1
+                for k in range(first, len(pairs)):
+                    t, tp = pairs[k]
+                    prev = x0 if self.dpmpp_order(k, len(pairs)) == 2 else None
+                    if guided:
+                        eps2 = model(xs, self._t_full(2 * n, t, x.device), y)
+                        nxt = torch.empty_like(xs)
+                        ops.dpmpp_step_cfg(xs[:n], eps2, prev, table[k], s, nxt[:n], nxt[n:], x0)
+                        xs = nxt
+                    else:
+                        tt = self._t_full(n, t, x.device)
+                        eps = model(xs, tt) if y is None else model(xs, tt, y)
+                        xs = ops.dpmpp_step(xs, eps, prev, table[k], x0_out=x0)[0]
+                    if self.ddim_snapshot(t, tp):
+                        snaps.append(xs[:n])
+                x = xs[:n]
+        finally:
+            model.train()
+            self._unhint(model)
+        snaps.append(x)
+        return x, snaps
+
+    def _dpmpp_graph_steps(self, model, xs, n, x0, snaps, pairs, table, y=None, cfg_scale=0.0):
+        """The DPM++ steps `pairs` (all but the chain's last) by replaying one captured step.  Before each replay t_dev (the
+        forward's rows) and the static coefficient buffer are filled from the host's step index; the state x0 starts at zero,
+        so the first-order first step (B1 = 0) adds B1 * 0 = +0.  Returns a fresh xs after the last of them; x0 holds that step's x0."""
+        guided = cfg_scale > 0
+        xs = xs.clone()
+        t_dev = torch.full((xs.shape[0],), pairs[0][0], device=xs.device, dtype=torch.long)
+        coef = table[0].clone()
+        xh = xs[:n]
+
+        def one_step():
+            if guided:
+                eps2 = model(xs, t_dev, y)
+                ops.dpmpp_step_cfg(xh, eps2, x0, coef, cfg_scale, xh, xs[n:], x0)
+                return
+            eps = model(xs, t_dev) if y is None else model(xs, t_dev, y)
+            ops.dpmpp_step(xs, eps, x0, coef, xs, x0)                         # in place (elementwise)
+
+        g = self._capture(one_step, xs)
+        x0.zero_()                                                            # undo the warm-up's state as well
+        for k, (t, tp) in enumerate(pairs):
+            t_dev.fill_(t)
+            coef.copy_(table[k])
+            g.replay()
+            if self.ddim_snapshot(t, tp):
+                snaps.append(xh.clone())
+        return xs.clone()
+
     def _hint(self, model):
         """Tell the model the range of the timesteps this process will pass (all of them in [0, noise_steps)): lets the
         UNet tabulate its time embeddings once per trajectory (unet.UNet._timestep_tables); cleared again when the loop
@@ -354,8 +495,23 @@ class Diffusion:
             raise NotImplementedError(f"Diffusion.{where}: steps (DDIM) together with a rotation (theta) is not supported")
         return self._ddim_pairs(steps, eta)
 
+    def _check_sampler(self, where, sampler, steps, eta, theta=None):
+        """-> (solver, pairs): ("ddim", the `_check_ddim` pairs or None) for sampler None / "ddim", ("dpmpp_2m", the DPM++
+        pairs) for "dpmpp_2m"."""
+        if sampler is None or (isinstance(sampler, str) and sampler == "ddim"):
+            return "ddim", self._check_ddim(where, steps, eta, theta)
+        if not (isinstance(sampler, str) and sampler == "dpmpp_2m"):
+            raise ValueError(f"Diffusion.{where}: unknown sampler {sampler!r} (None, 'ddim' or 'dpmpp_2m')")
+        if theta is not None:
+            raise NotImplementedError(f"Diffusion.{where}: sampler='dpmpp_2m' together with a rotation (theta) is not supported")
+        if steps is None:
+            raise ValueError(f"Diffusion.{where}: sampler='dpmpp_2m' needs steps (an int or an explicit sequence of timesteps)")
+        if eta != 0:
+            raise ValueError(f"Diffusion.{where}: sampler='dpmpp_2m' is deterministic: eta must be 0 (got {eta})")
+        return "dpmpp_2m", self.dpmpp_pairs(steps)
+
     def sample(self, model, n, image_channels, theta=None, noise_source="reference", return_float=False, graph=None,
-               labels=None, cfg_scale=0.0, steps=None, eta=0.0):
+               labels=None, cfg_scale=0.0, steps=None, eta=0.0, sampler=None):
         """labels: (n,) integer class labels (NULL_LABEL for an unconditional image) for a UNet(num_classes=K); None = the
         unconditional sampler.  cfg_scale > 0: classifier-free guidance, eps = torch.lerp(eps_uncond, eps_cond, cfg_scale),
         both predictions from ONE forward over 2n rows per step; cfg_scale <= 0: the conditional prediction alone.  The noise
@@ -363,16 +519,21 @@ class Diffusion:
         steps: None = the full DDPM chain (T - 1 forwards).  An int S (1 <= S <= T - 1) or an explicit strictly decreasing
         sequence of timesteps in [1, T - 1] selects DDIM over those timesteps (`ddim_timesteps`), S forwards, with
         eta = 0 deterministic (no noise drawn after x_T) and eta = 1 ancestral.  Snapshots are taken after each step that
-        crosses a multiple of 100 (`ddim_snapshot`), plus the final x.  Not supported together with theta."""
+        crosses a multiple of 100 (`ddim_snapshot`), plus the final x.  Not supported together with theta.
+        sampler: None or "ddim" (the samplers above); "dpmpp_2m" runs DPM-Solver++(2M) over `steps` (an int S, spaced
+        uniformly in log-SNR by `logsnr_timesteps`, or an explicit sequence), S forwards, deterministic (eta must be 0; no
+        noise is drawn after x_T).  Guidance, graph= and the snapshots work as for DDIM."""
         logging.info(f"Sampling {n} new images....")
         if theta is not None:
             logging.info(f"Theta {theta} provided. Rotation will be applied.")
-        pairs = self._check_ddim("sample", steps, eta, theta)
+        solver, pairs = self._check_sampler("sample", sampler, steps, eta, theta)
         if labels is not None:
             labels = self._check_labels(model, n, theta, labels)
         elif cfg_scale:
             raise ValueError("Diffusion.sample: cfg_scale needs class labels")
-        if pairs is None:
+        if solver == "dpmpp_2m":
+            x, snaps = self._dpmpp_loop(model, n, image_channels, pairs, noise_source, graph, labels, float(cfg_scale))
+        elif pairs is None:
             x, snaps = self._loop(model, n, image_channels, theta, noise_source, graph, labels=labels, cfg_scale=float(cfg_scale))
         else:
             x, snaps = self._ddim_loop(model, n, image_channels, pairs, float(eta), noise_source, graph, labels, float(cfg_scale))
@@ -795,11 +956,13 @@ class Diffusion:
             t.record_stream(cur)
         return torch.cat(xs_out), torch.cat(snaps_out)
 
-    def revert(self, model, n, image_channels, noise_source="reference", graph=None, steps=None, eta=0.0):
-        """steps / eta: DDIM over a strided chain, as for `sample`."""
+    def revert(self, model, n, image_channels, noise_source="reference", graph=None, steps=None, eta=0.0, sampler=None):
+        """steps / eta / sampler: as for `sample`."""
         logging.info(f"Sampling {n} new images....")
-        pairs = self._check_ddim("revert", steps, eta)
-        if pairs is None:
+        solver, pairs = self._check_sampler("revert", sampler, steps, eta)
+        if solver == "dpmpp_2m":
+            _, snaps = self._dpmpp_loop(model, n, image_channels, pairs, noise_source, graph)
+        elif pairs is None:
             _, snaps = self._loop(model, n, image_channels, None, noise_source, graph)
         else:
             _, snaps = self._ddim_loop(model, n, image_channels, pairs, float(eta), noise_source, graph)

@@ -1225,6 +1225,37 @@ def ddim_step_cfg_dev(x, eps2, noise, alpha_hat, t_dev, t_prev_dev, eta, cfg_sca
     return out
 
 
+def _dpmpp_args(what, x, eps, x0_prev, coef, out, x0_out, out2=None, guided=False):
+    n = _ddim_args(what, x, eps, x0_prev, coef, out, out2, guided)
+    _chk(x0_out)
+    if coef.numel() != 5:
+        raise AfdError(f"afdm: {what} needs coef of 5 values [alpha_t, sigma_t, A, B0, B1] (got {coef.numel()})")
+    if not x0_out.is_contiguous() or x0_out.numel() != n:
+        raise AfdError(f"afdm: {what}: x0_out must be contiguous and hold {n} elements")
+    return n
+
+
+def dpmpp_step(x, eps, x0_prev, coef, out=None, x0_out=None):
+    """DPM-Solver++(2M) update t -> t_prev (include/afd.h: afd_dpmpp_step gives the exact expression).  coef: the step's row of
+    `Diffusion.dpmpp_coefficients`, 5 fp32 values on the device (read there: graph-replayable).  x0_prev: None on a first-order
+    step, else the previous step's x0.  `out` may be x; `x0_out` may be x0_prev (in place).  Returns (out, x0_out)."""
+    out = torch.empty_like(x) if out is None else out
+    x0_out = torch.empty_like(x) if x0_out is None else x0_out
+    n = _dpmpp_args("DPM++ step", x, eps, x0_prev, coef, out, x0_out)
+    lib().afd_dpmpp_step(_p(x), _p(eps), _p(x0_prev), _p(coef), _p(out), _p(x0_out), n, _stream())
+    return out, x0_out
+
+
+def dpmpp_step_cfg(x, eps2, x0_prev, coef, cfg_scale, out=None, out2=None, x0_out=None):
+    """Classifier-free guided DPM++ update: e = torch.lerp(eps2[n:], eps2[:n], cfg_scale), then exactly `dpmpp_step(x, e, ...)`,
+    in one launch.  `out2` (optional) receives the same values as `out`.  Returns (out, x0_out)."""
+    out = torch.empty_like(x) if out is None else out
+    x0_out = torch.empty_like(x) if x0_out is None else x0_out
+    n = _dpmpp_args("guided DPM++ step", x, eps2, x0_prev, coef, out, x0_out, out2, guided=True)
+    lib().afd_dpmpp_step_cfg(_p(x), _p(eps2), _p(x0_prev), _p(coef), float(cfg_scale), _p(out), _p(out2), _p(x0_out), n, _stream())
+    return out, x0_out
+
+
 # ---- inpainting: masked steps and the renoise up-move (include/afd.h gives the exact expressions) --------------------------
 def _masked_args(what, x, eps, noise, x0, mask, out, out2=None, guided=False):
     n = _ddim_args(what, x, eps, noise, None, out, out2, guided)

@@ -108,10 +108,13 @@ def ddpm_run(params):
     else:
         print("skipped saving training dataset")
     # optional DDIM for the FID/KID image set only: params["sample_steps"] (S, or an explicit list of timesteps) and
-    # params["sample_eta"] (default 0, deterministic); without them the full DDPM chain runs as before
+    # params["sample_eta"] (default 0, deterministic); params["sample_solver"]: None / "ddim" or "dpmpp_2m" (DPM-Solver++(2M)
+    # over the same steps, eta 0); without them the full DDPM chain runs as before
     gen_kw = {}
     if params.get("sample_steps") is not None:
         gen_kw = {"steps": params["sample_steps"], "eta": params.get("sample_eta", 0.0)}
+    if params.get("sample_solver") is not None:
+        gen_kw["sampler"] = params["sample_solver"]
     gen_model = model
     if use_ema:
         gen_model = UNet(c_in=args.image_channels, c_out=args.image_channels, image_size=args.image_size, f_settings=f_settings,

@@ -398,6 +398,23 @@ int afd_ddim_step_cfg(const float* x, const float* eps2, const float* noise, con
 int afd_ddim_step_cfg_dev(const float* x, const float* eps2, const float* noise, const float* alpha_hat, const int64_t* t_dev,
                           const int64_t* t_prev_dev, float eta, float cfg_scale, float* x_out, float* x_out2, long n,
                           afd_stream_t stream);
+/* DPM-Solver++(2M) (Lu et al. 2022): one multistep update t -> t_prev of the probability-flow ODE, for a model trained on the
+ * eps-objective.  coef: 5 fp32 values in device memory, [alpha_t, sigma_t, A, B0, B1] of this step (Diffusion.dpmpp_coefficients
+ * builds the table on the host).  fp32 with one IEEE rounding per operation (no FMA contraction, correctly rounded /), in
+ * exactly this order:
+ *   x0     = (x - (sigma_t * eps)) / alpha_t
+ *   out    = ((A * x) + (B0 * x0)) + (x0_prev ? B1 * x0_prev : +0)
+ *   x0_out = x0                     (the next step's x0_prev)
+ * x0_prev is NULL on a first-order step.  Because coef is read on the device, the same call serves graph replay.  x_out may
+ * alias x; x0_out may be x0_prev itself (in-place state) and must not overlap x, eps, x_out or any other part of x0_prev.
+ * Requires n > 0.  n: elements of x. */
+int afd_dpmpp_step(const float* x, const float* eps, const float* x0_prev /* NULL => +0 */, const float* coef, float* x_out,
+                   float* x0_out, long n, afd_stream_t stream);
+/* classifier-free guided form: eps2 as for afd_denoise_step_cfg, eps = torch.lerp(e_u, e_c, cfg_scale) with the same scalar
+ * formula, then exactly the afd_dpmpp_step expression.  x_out2 is NULL or a second destination of out; x0_out must not overlap
+ * it either (nor any of eps2's 2n values). */
+int afd_dpmpp_step_cfg(const float* x, const float* eps2, const float* x0_prev, const float* coef, float cfg_scale, float* x_out,
+                       float* x_out2, float* x0_out, long n, afd_stream_t stream);
 /* ---- inpainting (RePaint, Lugmayr et al. 2022): masked steps and the renoise up-move ----
  * Each masked entry point is its unmasked counterpart above with two more operands after noise: x0 (n fp32 values, the known
  * image) and mask (n bytes; nonzero = known).  Per element j, with t_prev = i - 1 for the DDPM forms:
