@@ -491,6 +491,163 @@ static void launch_dpmpp_step(const float* x, const float* eps, const float* x0_
     hipLaunchKernelGGL((dpmpp_step_k<kCfg, false>), dim3(grid), dim3(256), 0, st, x, eps, x0_prev, coef, s, x_out, x_out2, x0_out, n);
 }
 
+// ---- likelihood (bits/dim, Ho et al. 2020 section 3.3): gathered noising, the bound's per-row terms, the prior ------------
+// A row r pairs image img[r] of x0 with timestep t[r].  Every kernel below walks rows with whole workgroups (a row's
+// coefficients are wave-uniform) and the row's `per` values with the threads; VEC: per % 4 == 0 and the float pointers
+// 16-byte aligned, so every row starts on a 16-byte boundary; `per` then counts float4s.
+
+// x_t[r] = sqrt(ah[t[r]]) * x0[img[r]] + sqrt(1 - ah[t[r]]) * eps[r]: noise_images_k's expression, operation for operation
+template <bool VEC>
+__global__ __launch_bounds__(256) void noise_images_gather_k(const float* __restrict__ x0, const int64_t* __restrict__ img,
+                                                             const float* __restrict__ eps, const int64_t* __restrict__ t,
+                                                             const float* __restrict__ alpha_hat, float* __restrict__ xt, long rows,
+                                                             long per) {
+  for (long r = blockIdx.x; r < rows; r += gridDim.x) {
+    const float ah = alpha_hat[t[r]];
+    const float sa = sqrtf(ah);
+    const float sb = sqrtf(1.0f - ah);
+    const long src = img[r] * per, dst = r * per;
+    for (long j = threadIdx.x; j < per; j += blockDim.x) {
+      if (VEC) {
+        const float4 x = reinterpret_cast<const float4*>(x0)[src + j], e = reinterpret_cast<const float4*>(eps)[dst + j];
+        float4 o;
+        { const float l = sa * x.x, q = sb * e.x; o.x = l + q; }
+        { const float l = sa * x.y, q = sb * e.y; o.y = l + q; }
+        { const float l = sa * x.z, q = sb * e.z; o.z = l + q; }
+        { const float l = sa * x.w, q = sb * e.w; o.w = l + q; }
+        reinterpret_cast<float4*>(xt)[dst + j] = o;
+      } else {
+        const float l = sa * x0[src + j], q = sb * eps[dst + j];
+        xt[dst + j] = l + q;
+      }
+    }
+  }
+}
+
+// Sum of two fp64 values over a 256-thread workgroup in a fixed order: a shuffle tree inside each wave, then the four waves'
+// partial sums in wave order.  The result is valid in thread 0.  red: 8 doubles of LDS.
+__device__ __forceinline__ void block_sum2_f64(double& a, double& b, double* red) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    a += __shfl_down(a, o, kWave);
+    b += __shfl_down(b, o, kWave);
+  }
+  const int w = threadIdx.x >> 6;
+  if ((threadIdx.x & 63) == 0) {
+    red[2 * w] = a;
+    red[2 * w + 1] = b;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    a = red[0];
+    b = red[1];
+    for (int i = 1; i < (int)(blockDim.x >> 6); ++i) {
+      a += red[2 * i];
+      b += red[2 * i + 1];
+    }
+  }
+}
+
+// Ho et al.'s discretised Gaussian, log p of the 8-bit level x0 under N(mean, exp(2 log_scale)), in fp64: bins of half-width
+// 1/255, the edge bins open below -0.999 and above 0.999, Phi by the tanh approximation, probabilities clamped at 1e-12.
+__device__ __forceinline__ double approx_std_normal_cdf(double x) {
+  return 0.5 * (1.0 + tanh(0.7978845608028654 * (x + 0.044715 * (x * x * x))));     // sqrt(2 / pi)
+}
+__device__ __forceinline__ double decoder_log_prob(double x, double mean, double inv_stdv) {
+  const double c = x - mean;
+  const double cdf_plus = approx_std_normal_cdf(inv_stdv * (c + 1.0 / 255.0));
+  const double cdf_min = approx_std_normal_cdf(inv_stdv * (c - 1.0 / 255.0));
+  if (x < -0.999) return log(fmax(cdf_plus, 1e-12));
+  if (x > 0.999) return log(fmax(1.0 - cdf_min, 1e-12));
+  return log(fmax(cdf_plus - cdf_min, 1e-12));
+}
+
+// One workgroup per row.  coef: the (T, 4) fp64 table of Diffusion.vlb_coefficients, row t = [w_t, c_t, log_scale_t, prior].
+//   sq[r]   = sum_j (double(eps_hat_j) - double(eps_j))^2
+//   term[r] = w_t * sq[r] + per * c_t                                                       t != 1: KL(q || p_theta)
+//           = -sum_j decoder_log_prob(x0_j, mean_j, exp(-log_scale_1)),                    t == 1: the decoder
+// with mean_j = denoise_step_k's fp32 expression at step 1 without noise, c1 * (x_t - c2 * eps_hat) (what the sampler returns).
+// Only decoder rows read x0 and x_t.  Each thread sums its elements in index order (x, y, z, w within a float4).
+template <bool VEC>
+__global__ __launch_bounds__(256) void vlb_terms_k(const float* __restrict__ x0, const int64_t* __restrict__ img,
+                                                   const float* __restrict__ xt, const float* __restrict__ eps,
+                                                   const float* __restrict__ eps_hat, const int64_t* __restrict__ t,
+                                                   const double* __restrict__ coef, const float* __restrict__ alpha,
+                                                   const float* __restrict__ alpha_hat, const float* __restrict__ beta,
+                                                   double* __restrict__ term, double* __restrict__ sq, long per, long n_elem) {
+  __shared__ double red[8];
+  const long r = blockIdx.x;
+  const int tr = (int)t[r];
+  const long row = r * per;
+  double s_sq = 0.0, s_ll = 0.0;
+  if (tr == 1) {                                    // uniform per workgroup
+    const CfgCoef k = cfg_coef(alpha, alpha_hat, beta, 1, 0.0f);
+    const double inv_stdv = exp(-coef[4 * 1 + 2]);              // row t = 1, log_scale
+    const long src = img[r] * per;
+    for (long j = threadIdx.x; j < per; j += blockDim.x) {
+      if (VEC) {
+        const float4 e = reinterpret_cast<const float4*>(eps)[row + j], h = reinterpret_cast<const float4*>(eps_hat)[row + j];
+        const float4 x = reinterpret_cast<const float4*>(xt)[row + j], v = reinterpret_cast<const float4*>(x0)[src + j];
+        const float ev[4] = {e.x, e.y, e.z, e.w}, hv[4] = {h.x, h.y, h.z, h.w}, xv[4] = {x.x, x.y, x.z, x.w};
+        const float vv[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+          const double d = (double)hv[q] - (double)ev[q];
+          s_sq += d * d;
+          s_ll += decoder_log_prob(vv[q], denoise_update(k, xv[q], hv[q], 0.0f, false), inv_stdv);
+        }
+      } else {
+        const double d = (double)eps_hat[row + j] - (double)eps[row + j];
+        s_sq += d * d;
+        s_ll += decoder_log_prob(x0[src + j], denoise_update(k, xt[row + j], eps_hat[row + j], 0.0f, false), inv_stdv);
+      }
+    }
+  } else {
+    for (long j = threadIdx.x; j < per; j += blockDim.x) {
+      if (VEC) {
+        const float4 e = reinterpret_cast<const float4*>(eps)[row + j], h = reinterpret_cast<const float4*>(eps_hat)[row + j];
+        const double dx = (double)h.x - (double)e.x, dy = (double)h.y - (double)e.y;
+        const double dz = (double)h.z - (double)e.z, dw = (double)h.w - (double)e.w;
+        s_sq += dx * dx;
+        s_sq += dy * dy;
+        s_sq += dz * dz;
+        s_sq += dw * dw;
+      } else {
+        const double d = (double)eps_hat[row + j] - (double)eps[row + j];
+        s_sq += d * d;
+      }
+    }
+  }
+  block_sum2_f64(s_sq, s_ll, red);
+  if (threadIdx.x == 0) {
+    const double* c = coef + 4 * (long)tr;
+    term[r] = tr == 1 ? -s_ll : c[0] * s_sq + (double)n_elem * c[1];
+    sq[r] = s_sq;
+  }
+}
+
+// out[i] = half_ah * sum_j x0[i, j]^2 in fp64 (the data-dependent part of KL(q(x_{T-1} | x0) || N(0, I))); one workgroup per image
+template <bool VEC>
+__global__ __launch_bounds__(256) void vlb_prior_k(const float* __restrict__ x0, double half_ah, double* __restrict__ out, long per) {
+  __shared__ double red[8];
+  const long row = blockIdx.x * per;
+  double s = 0.0, unused = 0.0;
+  for (long j = threadIdx.x; j < per; j += blockDim.x) {
+    if (VEC) {
+      const float4 v = reinterpret_cast<const float4*>(x0)[row + j];
+      s += (double)v.x * (double)v.x;
+      s += (double)v.y * (double)v.y;
+      s += (double)v.z * (double)v.z;
+      s += (double)v.w * (double)v.w;
+    } else {
+      const double v = x0[row + j];
+      s += v * v;
+    }
+  }
+  block_sum2_f64(s, unused, red);
+  if (threadIdx.x == 0) out[blockIdx.x] = half_ah * s;
+}
+
 // ((clamp(x,-1,1) + 1) / 2 * 255).type(uint8): truncation toward zero
 __global__ void quantize_u8_k(const float* __restrict__ x, uint8_t* __restrict__ out, long n) {
   AFD_GRID_STRIDE(i, n) {
@@ -862,6 +1019,61 @@ int afd_dpmpp_step_cfg(const float* x, const float* eps2, const float* x0_prev, 
               "afd_dpmpp_step_cfg: x0_out must not overlap x, eps2, x_out or x_out2, and must be x0_prev itself or apart from it");
   launch_dpmpp_step<true>(x, eps2, x0_prev, coef, cfg_scale, x_out, x_out2, x0_out, n, as_stream(st));
   return check_launch("afd_dpmpp_step_cfg");
+}
+// ---- likelihood (bits/dim) ------------------------------------------------------------------------------------------------
+// img and t are read on the device and not range-checked here (the Python layer checks them); every output must share no
+// memory with any input.
+static inline int row_grid(long rows) { return (int)std::min<long>(rows, 4096); }
+int afd_noise_images_gather(const float* x0, long n_img, const int64_t* img, const float* eps, const int64_t* t, const float* alpha_hat,
+                            float* x_t, long rows, long per, afd_stream_t st) {
+  AFD_REQUIRE(x0 && img && eps && t && alpha_hat && x_t, "afd_noise_images_gather: x0, img, eps, t, alpha_hat and x_t must not be NULL");
+  AFD_REQUIRE(n_img > 0 && rows > 0 && per > 0, "afd_noise_images_gather: n_img, rows and per must be positive (got %ld, %ld, %ld)",
+              n_img, rows, per);
+  const long fb = rows * per * (long)sizeof(float), ib = rows * (long)sizeof(int64_t);
+  AFD_REQUIRE(!overlaps(x_t, fb, x0, n_img * per * (long)sizeof(float)) && !overlaps(x_t, fb, eps, fb) && !overlaps(x_t, fb, img, ib) &&
+                  !overlaps(x_t, fb, t, ib),
+              "afd_noise_images_gather: x_t must not overlap x0, eps, img or t");
+  if (per % 4 == 0 && aligned16(x0) && aligned16(eps) && aligned16(x_t))
+    hipLaunchKernelGGL(noise_images_gather_k<true>, dim3(row_grid(rows)), dim3(256), 0, as_stream(st), x0, img, eps, t, alpha_hat, x_t,
+                       rows, per / 4);
+  else
+    hipLaunchKernelGGL(noise_images_gather_k<false>, dim3(row_grid(rows)), dim3(256), 0, as_stream(st), x0, img, eps, t, alpha_hat, x_t,
+                       rows, per);
+  return check_launch("afd_noise_images_gather");
+}
+int afd_vlb_terms(const float* x0, long n_img, const int64_t* img, const float* x_t, const float* eps, const float* eps_hat,
+                  const int64_t* t, const double* coef, long T, const float* alpha, const float* alpha_hat, const float* beta,
+                  double* term, double* sq, long rows, long per, afd_stream_t st) {
+  AFD_REQUIRE(x0 && img && x_t && eps && eps_hat && t && coef && alpha && alpha_hat && beta && term && sq,
+              "afd_vlb_terms: no pointer may be NULL");
+  AFD_REQUIRE(n_img > 0 && rows > 0 && per > 0 && T >= 2, "afd_vlb_terms: n_img, rows and per must be positive and T >= 2 (got %ld, %ld, %ld, %ld)",
+              n_img, rows, per, T);
+  AFD_REQUIRE(rows <= 0x7fffffffL, "afd_vlb_terms: at most 2^31 - 1 rows per call (got %ld)", rows);
+  const long db = rows * (long)sizeof(double), fb = rows * per * (long)sizeof(float), ib = rows * (long)sizeof(int64_t);
+  const long tb = T * (long)sizeof(float);
+  const void* in[] = {x0, img, x_t, eps, eps_hat, t, coef, alpha, alpha_hat, beta};
+  const long in_b[] = {n_img * per * (long)sizeof(float), ib, fb, fb, fb, ib, 4 * T * (long)sizeof(double), tb, tb, tb};
+  bool apart = !overlaps(term, db, sq, db);
+  for (int i = 0; i < 10; ++i) apart = apart && !overlaps(term, db, in[i], in_b[i]) && !overlaps(sq, db, in[i], in_b[i]);
+  AFD_REQUIRE(apart, "afd_vlb_terms: term and sq must not overlap each other or any input");
+  if (per % 4 == 0 && aligned16(x0) && aligned16(x_t) && aligned16(eps) && aligned16(eps_hat))
+    hipLaunchKernelGGL(vlb_terms_k<true>, dim3((unsigned)rows), dim3(256), 0, as_stream(st), x0, img, x_t, eps, eps_hat, t, coef, alpha,
+                       alpha_hat, beta, term, sq, per / 4, per);
+  else
+    hipLaunchKernelGGL(vlb_terms_k<false>, dim3((unsigned)rows), dim3(256), 0, as_stream(st), x0, img, x_t, eps, eps_hat, t, coef, alpha,
+                       alpha_hat, beta, term, sq, per, per);
+  return check_launch("afd_vlb_terms");
+}
+int afd_vlb_prior(const float* x0, double half_ah, double* out, long n_img, long per, afd_stream_t st) {
+  AFD_REQUIRE(x0 && out, "afd_vlb_prior: x0 and out must not be NULL");
+  AFD_REQUIRE(n_img > 0 && per > 0, "afd_vlb_prior: n_img and per must be positive (got %ld, %ld)", n_img, per);
+  AFD_REQUIRE(n_img <= 0x7fffffffL, "afd_vlb_prior: at most 2^31 - 1 images per call (got %ld)", n_img);
+  AFD_REQUIRE(!overlaps(out, n_img * (long)sizeof(double), x0, n_img * per * (long)sizeof(float)), "afd_vlb_prior: out must not overlap x0");
+  if (per % 4 == 0 && aligned16(x0))
+    hipLaunchKernelGGL(vlb_prior_k<true>, dim3((unsigned)n_img), dim3(256), 0, as_stream(st), x0, half_ah, out, per / 4);
+  else
+    hipLaunchKernelGGL(vlb_prior_k<false>, dim3((unsigned)n_img), dim3(256), 0, as_stream(st), x0, half_ah, out, per);
+  return check_launch("afd_vlb_prior");
 }
 int afd_quantize_u8(const float* x, uint8_t* out, long n, afd_stream_t st) {
   AFD_REQUIRE(x && out && n > 0, "afd_quantize_u8: bad argument");

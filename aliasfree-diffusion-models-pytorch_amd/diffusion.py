@@ -473,16 +473,16 @@ class Diffusion:
                 snaps.append(xh.clone())
         return xh.clone()
 
-    def _check_labels(self, model, n, theta, labels):
+    def _check_labels(self, model, n, theta, labels, where="sample"):
         if theta is not None:
-            raise NotImplementedError("Diffusion.sample: class labels together with a rotation (theta) are not supported")
+            raise NotImplementedError(f"Diffusion.{where}: class labels together with a rotation (theta) are not supported")
         if getattr(model, "label_emb", None) is None:
-            raise ValueError("Diffusion.sample: labels were passed but the model has no label embedding (build UNet(num_classes=K))")
+            raise ValueError(f"Diffusion.{where}: labels were passed but the model has no label embedding (build UNet(num_classes=K))")
         y = torch.as_tensor(labels)
         if y.dtype.is_floating_point or y.dtype.is_complex or y.dtype == torch.bool:
-            raise ValueError(f"Diffusion.sample: labels must be integers (got {y.dtype})")
+            raise ValueError(f"Diffusion.{where}: labels must be integers (got {y.dtype})")
         if tuple(y.shape) != (n,):
-            raise ValueError(f"Diffusion.sample: expected {n} labels, one per image (got shape {tuple(y.shape)})")
+            raise ValueError(f"Diffusion.{where}: expected {n} labels, one per image (got shape {tuple(y.shape)})")
         return y.to(device=self.device, dtype=torch.long).contiguous()
 
     def _check_ddim(self, where, steps, eta, theta=None):
@@ -723,6 +723,187 @@ class Diffusion:
         with torch.cuda.graph(g):
             one_step()
         return g
+
+    # Likelihood: the variational bound in bits per dimension (Ho et al. 2020, section 3.3) -----------------------------------
+    VLB_SIGMAS = ("beta", "posterior")
+
+    def vlb_coefficients(self, sigma="beta"):
+        """(T, 4) fp64 host table of the bound's coefficients, from the fp32 schedule tables widened to fp64.  Row t (1 <= t < T)
+        = [w_t, c_t, log_scale_t, prior], row 0 is zeros except the prior column:
+          beta~_t = (1 - ah[t-1]) / (1 - ah[t]) * beta[t];  s2 = beta[t] (sigma="beta") or beta~_t (sigma="posterior")
+          w_t = beta[t]^2 / (2 s2 alpha[t] (1 - ah[t]))       (the KL term per unit of sum (eps_hat - eps)^2)
+          c_t = (-1 + log(s2 / beta~_t) + beta~_t / s2) / 2   (per element; exactly 0 for "posterior", computed without
+                                                                cancellation for "beta": (u - log1p(u)) / 2, u = beta~_t / s2 - 1)
+          log_scale_t = log(s2) / 2                            (the decoder's at t = 1)
+          prior = (-1 - log(1 - ah[T-1]) + (1 - ah[T-1])) / 2  (per element, the same in every row)."""
+        if not isinstance(sigma, str) or sigma not in self.VLB_SIGMAS:
+            raise ValueError(f"Diffusion.vlb_coefficients: unknown sigma {sigma!r} ('beta' or 'posterior')")
+        T = self.noise_steps
+        if T < 2:
+            raise ValueError(f"Diffusion.vlb_coefficients: needs noise_steps >= 2 (got {T})")
+        b = self.beta.detach().cpu().double().numpy()
+        a = self.alpha.detach().cpu().double().numpy()
+        ah = self.alpha_hat.detach().cpu().double().numpy()
+        om = 1.0 - ah                                            # exact: 1 - an fp32 value in [0, 1] fits an fp64
+        tab = np.zeros((T, 4), dtype=np.float64)
+        for t in range(1, T):
+            bt = om[t - 1] / om[t] * b[t]
+            s2 = b[t] if sigma == "beta" else bt
+            tab[t, 0] = b[t] * b[t] / (2.0 * s2 * a[t] * om[t])
+            if sigma == "beta":                                 # beta~ / beta - 1 = (ah[t] - ah[t-1]) / (1 - ah[t])
+                u = (ah[t] - ah[t - 1]) / om[t]
+                if abs(u) < 0.1:
+                    tab[t, 1] = 0.5 * sum((-u) ** k / k for k in range(2, 40))     # u - log1p(u), summed from its series
+                else:
+                    tab[t, 1] = 0.5 * (u - math.log1p(u))
+            tab[t, 2] = 0.5 * math.log(s2)
+        tab[:, 3] = 0.5 * (-1.0 - math.log(om[T - 1]) + om[T - 1])
+        return torch.from_numpy(tab)
+
+    @staticmethod
+    def snap_8bit(images):
+        """The 8-bit image the bound is evaluated on, as fp32 on the host: uint8 k -> k / 127.5 - 1; float x ->
+        k = round((x + 1) * 127.5) (half to even) clamped to 0 .. 255, then k / 127.5 - 1 (fp32 arithmetic throughout)."""
+        x = images.detach().cpu()
+        if x.dtype == torch.uint8:
+            k = x.float()
+        else:
+            k = torch.round((x.float() + 1.0) * 127.5).clamp_(0.0, 255.0)
+        return k / 127.5 - 1.0
+
+    def bpd_timesteps(self, n, t_samples=None, noise_source="device"):
+        """The timesteps of each of n images, each list descending: T-1 .. 1 for the full bound (t_samples None or T - 1);
+        otherwise K = t_samples distinct values drawn per image, uniformly without replacement from [1, T-1], by one
+        torch.randperm(T - 1) per image from the device generator (noise_source "device") or the CPU generator ("cpu")."""
+        T = self.noise_steps
+        K = T - 1 if t_samples is None else t_samples
+        if K == T - 1:
+            return [list(range(T - 1, 0, -1)) for _ in range(n)]
+        out = []
+        for _ in range(n):
+            p = torch.randperm(T - 1, device=self.device) if noise_source == "device" else torch.randperm(T - 1)
+            out.append(sorted((int(v) + 1 for v in p[:K].cpu()), reverse=True))
+        return out
+
+    @staticmethod
+    def bpd_rows(timesteps):
+        """The rows of the bound loop, image-major in the order of each image's timesteps -> (img, t), two int64 arrays."""
+        img = np.concatenate([np.full(len(ts), i, dtype=np.int64) for i, ts in enumerate(timesteps)])
+        t = np.concatenate([np.asarray(ts, dtype=np.int64) for ts in timesteps])
+        return img, t
+
+    @staticmethod
+    def bpd_chunks(rows, batch):
+        """The [lo, hi) row ranges of the forwards: consecutive chunks of `batch` rows, the last one shorter."""
+        return [(lo, min(rows, lo + batch)) for lo in range(0, rows, batch)]
+
+    def bpd_combine(self, n, per, img, t, term, sq, prior, K, return_terms=False):
+        """Per-image parts from the rows' terms (fp64 host arrays, nats) -> the dict `calc_bpd` returns.  prior: (n,) nats.
+        The terms of the K evaluated timesteps of an image are scaled by (T - 1) / K (1 for the full bound)."""
+        T = self.noise_steps
+        scale = (T - 1) / K
+        norm = per * math.log(2.0)
+        dec = t == 1
+        vb = np.bincount(img[~dec], weights=term[~dec], minlength=n) * scale
+        dd = np.bincount(img[dec], weights=term[dec], minlength=n) * scale
+        prior = np.asarray(prior, dtype=np.float64)
+        out = {"bpd": (prior + vb + dd) / norm, "prior_bpd": prior / norm, "vb_bpd": vb / norm, "decoder_bpd": dd / norm}
+        if return_terms:
+            terms = np.zeros((n, T))
+            mse = np.zeros((n, T))
+            terms[img, t] = term
+            mse[img, t] = sq / per
+            out["terms"], out["mse"] = terms, mse
+        return {k: torch.from_numpy(np.ascontiguousarray(v, dtype=np.float64)) for k, v in out.items()}
+
+    def _bpd_images(self, model, images):
+        """Validated, snapped images -> fp32 (n, C, img_size, img_size) host tensor."""
+        if not isinstance(images, torch.Tensor) or images.dim() != 4 or images.shape[0] < 1:
+            raise ValueError("Diffusion.calc_bpd: images must be an (n, C, H, W) tensor with n >= 1")
+        C = next((p.shape[1] for p in model.inc.parameters() if p.dim() == 4), None) if hasattr(model, "inc") else None
+        size = getattr(model, "image_size", self.img_size)
+        if tuple(images.shape[2:]) != (self.img_size, self.img_size) or size != self.img_size or (C is not None and images.shape[1] != C):
+            raise ValueError(f"Diffusion.calc_bpd: images of shape {tuple(images.shape)} do not match the model "
+                             f"({C if C is not None else 'C'} channels, {size} x {size}) and img_size {self.img_size}")
+        if images.dtype != torch.uint8:
+            if not images.dtype.is_floating_point:
+                raise ValueError(f"Diffusion.calc_bpd: images must be float in [-1, 1] or uint8 (got {images.dtype})")
+            x = images.detach()
+            if not bool(((x >= -1.0 - 1e-5) & (x <= 1.0 + 1e-5)).all()):
+                raise ValueError("Diffusion.calc_bpd: float images must lie in [-1, 1]")
+        return self.snap_8bit(images)
+
+    def calc_bpd(self, model, images, labels=None, sigma="beta", t_samples=None, batch=256, noise_source="device", noise_fn=None,
+                 return_terms=False):
+        """Negative log-likelihood bound of `images` under `model`, in bits per dimension (Ho et al. 2020, section 3.3;
+        Nichol & Dhariwal's calc_bpd_loop): prior + sum_{t=2}^{T-1} L_t + L_1, over D ln 2 with D = C * H * W.
+        images: (n, C, img_size, img_size), float in [-1, 1] or uint8.  Float values are snapped once to the nearest of the
+        256 levels (`snap_8bit`): the result is the likelihood of that 8-bit image, not of the float one.
+        prior = KL(q(x_{T-1} | x0) || N(0, I)); L_t = KL(q(x_{t-1} | x_t, x0) || p(x_{t-1} | x_t)) with variance s2 from
+        sigma ("beta": beta_t, what the sampler draws; "posterior": beta~_t); L_1 = -log p(x0 | x_1), the discretised
+        Gaussian around the image the sampler returns.  Coefficients: `vlb_coefficients`.
+        Rows (image, t) are image-major, t descending within an image (`bpd_rows`), and go to the model in chunks of `batch`
+        (`bpd_chunks`), one forward per chunk with per-row t.  Each chunk draws its noise, (rows, C, H, W), from the device
+        generator (noise_source "device"), the CPU generator ("cpu", then copied), or noise_fn(shape) when given.
+        t_samples = K < T - 1: K timesteps per image (`bpd_timesteps`, drawn before any noise) and the unbiased estimate
+        prior + (T - 1) / K * sum_k L_{t_k}; None (or T - 1): the full bound, T - 1 rows per image.
+        labels: (n,) int64 class labels for a UNet(num_classes=K): the bound of log p(x | y); NULL_LABEL rows give the
+        unconditional bound.  Returns a dict of CPU fp64 (n,) tensors bpd, prior_bpd, vb_bpd (the KL terms), decoder_bpd
+        (bpd is their sum); with return_terms also terms (n, T), nats per t (0 where not evaluated; unscaled), and mse (n, T),
+        the per-element mean of (eps_hat - eps)^2."""
+        T = self.noise_steps
+        if T < 3:
+            raise ValueError(f"Diffusion.calc_bpd: needs noise_steps >= 3 (got {T})")
+        coef = self.vlb_coefficients(sigma)
+        if t_samples is not None and (isinstance(t_samples, bool) or not isinstance(t_samples, (int, np.integer))
+                                      or not 1 <= t_samples <= T - 1):
+            raise ValueError(f"Diffusion.calc_bpd: t_samples must be an int in [1, {T - 1}] or None (got {t_samples!r})")
+        if isinstance(batch, bool) or not isinstance(batch, (int, np.integer)) or batch < 1:
+            raise ValueError(f"Diffusion.calc_bpd: batch must be a positive int (got {batch!r})")
+        if noise_source not in ("device", "cpu"):
+            raise ValueError(f"Diffusion.calc_bpd: noise_source must be 'device' or 'cpu' (got {noise_source!r})")
+        x0 = self._bpd_images(model, images)
+        n, shape = x0.shape[0], tuple(x0.shape[1:])
+        per = int(np.prod(shape))
+        y = None if labels is None else self._check_labels(model, n, None, labels, "calc_bpd")
+        K = T - 1 if t_samples is None else int(t_samples)
+
+        timesteps = self.bpd_timesteps(n, K, noise_source)
+        img, t = self.bpd_rows(timesteps)
+        assert img.min() >= 0 and img.max() < n and t.min() >= 1 and t.max() < T     # the kernels read them unchecked
+        dev = self.device
+        x0 = x0.to(dev).contiguous()
+        img_d, t_d = torch.from_numpy(img).to(dev), torch.from_numpy(t).to(dev)
+        y_rows = None if y is None else y[img_d]
+        coef_d = coef.to(dev)
+        term = torch.empty(len(t), device=dev, dtype=torch.float64)
+        sq = torch.empty_like(term)
+        prior = ops.vlb_prior(x0, 0.5 * float(self.alpha_hat[T - 1]))
+        was_training, hint = model.training, getattr(model, "_t_range", None)
+        self._hint(model)
+        try:
+            model.eval()
+            with torch.no_grad():
+                for lo, hi in self.bpd_chunks(len(t), batch):
+                    cs = (hi - lo,) + shape
+                    if noise_fn is not None:
+                        eps = noise_fn(cs)
+                    elif noise_source == "device":
+                        eps = torch.randn(cs, device=dev)
+                    else:
+                        eps = torch.randn(cs).to(dev)
+                    eps = eps.to(device=dev, dtype=torch.float32).contiguous()
+                    rows_i, rows_t = img_d[lo:hi], t_d[lo:hi]
+                    xt = ops.noise_images_gather(x0, rows_i, eps, rows_t, self.alpha_hat, check_range=False)
+                    eh = model(xt, rows_t) if y_rows is None else model(xt, rows_t, y_rows[lo:hi])
+                    ops.vlb_terms(x0, rows_i, xt, eps, eh.contiguous(), rows_t, coef_d, self.alpha, self.alpha_hat, self.beta,
+                                  term[lo:hi], sq[lo:hi], check_range=False)
+        finally:
+            model.train(was_training)
+            if hasattr(model, "_t_range"):
+                model._t_range = hint
+        prior_nats = prior.cpu().numpy() + per * float(coef[0, 3])
+        return self.bpd_combine(n, per, img, t, term.cpu().numpy(), sq.cpu().numpy(), prior_nats, K, return_terms)
 
     def sample_sharded(self, model, n, image_channels, theta=None, noise_source="reference", group=None, dst=0, steps=None):
         """`sample` with the n images partitioned over the ranks of `group` (sampling is embarrassingly parallel per

@@ -1256,6 +1256,76 @@ def dpmpp_step_cfg(x, eps2, x0_prev, coef, cfg_scale, out=None, out2=None, x0_ou
     return out, x0_out
 
 
+# ---- likelihood: gathered noising, the bound's per-row terms, the prior (include/afd.h gives the exact expressions) ---------
+def _rows_args(what, x0, img, t, rows_like, check_range, T=None):
+    """Common checks of the row-wise entry points -> (n_img, rows, per).  img / t: int64 device vectors of one value per row;
+    check_range: verify on the host (one device sync) that img lies in [0, n_img) and t in [1, T); callers that built them on
+    the host and checked them there pass False."""
+    _chk(x0, rows_like)
+    if x0.dim() < 2 or not x0.is_contiguous() or not rows_like.is_contiguous():
+        raise AfdError(f"afdm: {what}: x0 (n_img, ...) and the row tensors must be contiguous")
+    n_img, per = x0.shape[0], x0.numel() // max(x0.shape[0], 1)
+    rows = rows_like.shape[0]
+    if rows_like.numel() != rows * per:
+        raise AfdError(f"afdm: {what}: the row tensors must hold {per} values per row like x0 (got shape {tuple(rows_like.shape)})")
+    for name, v in (("img", img), ("t", t)):
+        if not v.is_cuda or v.dtype != torch.long or v.dim() != 1 or v.numel() != rows or not v.is_contiguous():
+            raise AfdError(f"afdm: {what}: {name} must be a contiguous int64 device vector of {rows} values")
+    if check_range and rows > 0:
+        lo_i, hi_i, lo_t, hi_t = (int(v) for v in torch.stack([img.min(), img.max(), t.min(), t.max()]).cpu())
+        if lo_i < 0 or hi_i >= n_img:
+            raise AfdError(f"afdm: {what}: img must lie in [0, {n_img}) (got {lo_i} .. {hi_i})")
+        if lo_t < 1 or hi_t >= (T if T is not None else 1 << 62):
+            raise AfdError(f"afdm: {what}: t must lie in [1, {T}) (got {lo_t} .. {hi_t})")
+    return n_img, rows, per
+
+
+def noise_images_gather(x0, img, eps, t, alpha_hat, out=None, check_range=True):
+    """x_t of the rows (img[r], t[r]): `noise_images(x0[img], eps, t, alpha_hat)` bit for bit, without the gather.
+    x0: (n_img, C, H, W); img, t: (rows,) int64 device; eps: (rows, C, H, W)."""
+    out = torch.empty_like(eps) if out is None else out
+    n_img, rows, per = _rows_args("gathered noising", x0, img, t, eps, check_range, alpha_hat.numel())
+    _chk(alpha_hat, out)
+    if out.shape != eps.shape or not out.is_contiguous():
+        raise AfdError("afdm: gathered noising: out must be contiguous and shaped like eps")
+    lib().afd_noise_images_gather(_p(x0), n_img, _p(img), _p(eps), _p(t), _p(alpha_hat), _p(out), rows, per, _stream())
+    return out
+
+
+def vlb_terms(x0, img, x_t, eps, eps_hat, t, coef, alpha, alpha_hat, beta, term=None, sq=None, check_range=True):
+    """The bound's term of each row, in nats, and sum_j (eps_hat - eps)^2, both fp64 (rows,) device tensors (include/afd.h:
+    afd_vlb_terms).  coef: the (T, 4) fp64 table of `Diffusion.vlb_coefficients` on the device.  Returns (term, sq)."""
+    n_img, rows, per = _rows_args("bound terms", x0, img, t, eps, check_range, alpha_hat.numel())
+    _chk(x_t, eps_hat, alpha, alpha_hat, beta)
+    for v in (x_t, eps_hat):
+        if v.shape != eps.shape or not v.is_contiguous():
+            raise AfdError("afdm: bound terms: x_t and eps_hat must be contiguous and shaped like eps")
+    T = alpha_hat.numel()
+    if not coef.is_cuda or coef.dtype != torch.float64 or tuple(coef.shape) != (T, 4) or not coef.is_contiguous():
+        raise AfdError(f"afdm: bound terms: coef must be the contiguous ({T}, 4) fp64 device table (Diffusion.vlb_coefficients)")
+    term = torch.empty(rows, device=eps.device, dtype=torch.float64) if term is None else term
+    sq = torch.empty(rows, device=eps.device, dtype=torch.float64) if sq is None else sq
+    for v in (term, sq):
+        if not v.is_cuda or v.dtype != torch.float64 or v.numel() != rows or not v.is_contiguous():
+            raise AfdError(f"afdm: bound terms: term and sq must be contiguous fp64 device tensors of {rows} values")
+    lib().afd_vlb_terms(_p(x0), n_img, _p(img), _p(x_t), _p(eps), _p(eps_hat), _p(t), _p(coef), T, _p(alpha), _p(alpha_hat),
+                        _p(beta), _p(term), _p(sq), rows, per, _stream())
+    return term, sq
+
+
+def vlb_prior(x0, half_ah, out=None):
+    """half_ah * sum_j x0[i, j]^2 per image in fp64 (the prior's data-dependent part), an (n_img,) fp64 device tensor."""
+    _chk(x0)
+    if x0.dim() < 2 or not x0.is_contiguous():
+        raise AfdError("afdm: prior: x0 must be a contiguous (n_img, ...) tensor")
+    n_img, per = x0.shape[0], x0.numel() // max(x0.shape[0], 1)
+    out = torch.empty(n_img, device=x0.device, dtype=torch.float64) if out is None else out
+    if not out.is_cuda or out.dtype != torch.float64 or out.numel() != n_img or not out.is_contiguous():
+        raise AfdError(f"afdm: prior: out must be a contiguous fp64 device tensor of {n_img} values")
+    lib().afd_vlb_prior(_p(x0), float(half_ah), _p(out), n_img, per, _stream())
+    return out
+
+
 # ---- inpainting: masked steps and the renoise up-move (include/afd.h gives the exact expressions) --------------------------
 def _masked_args(what, x, eps, noise, x0, mask, out, out2=None, guided=False):
     n = _ddim_args(what, x, eps, noise, None, out, out2, guided)

@@ -130,7 +130,30 @@ def ddpm_run(params):
     out = {"loss_all": loss_all, "sample": x, "revert": denoise_img, "modelpath": modelpath, "gen_dir": gen_dir}
     if use_ema:
         out["ema_modelpath"] = ema_path(modelpath)
+    # optional likelihood: params["eval_bpd"] = N scores the first N training images, in dataset order, on the model the
+    # FID/KID image set came from (Diffusion.calc_bpd; "eval_bpd_t_samples": K timesteps per image, "eval_bpd_sigma")
+    if params.get("eval_bpd"):
+        out["bpd"] = _eval_bpd(params, args, diffusion, gen_model, run_dir, name, v, seed)
     return out
+
+
+def _eval_bpd(params, args, diffusion, model, run_dir, name, v, seed):
+    N, K, sigma = int(params["eval_bpd"]), params.get("eval_bpd_t_samples"), params.get("eval_bpd_sigma", "beta")
+    dataset = _loader(name, args)[1]
+    if not 1 <= N <= len(dataset):
+        raise ValueError(f"ddpm_run: eval_bpd must lie in [1, {len(dataset)}] (the training set's size; got {N})")
+    images = torch.stack([dataset[i][0] for i in range(N)])
+    set_seed(seed)
+    r = diffusion.calc_bpd(model, images, sigma=sigma, t_samples=K)
+    bpd = r["bpd"].numpy()
+    se = float(bpd.std(ddof=1) / np.sqrt(N)) if N > 1 else float("nan")
+    lines = [f"bpd: {bpd.mean():.6f}", f"bpd_stderr: {se:.6f}"]
+    lines += [f"{k}: {float(r[k].mean()):.6f}" for k in ("prior_bpd", "vb_bpd", "decoder_bpd")]
+    lines += [f"N: {N}", f"t_samples: {diffusion.noise_steps - 1 if K is None else int(K)}", f"sigma: {sigma}"]
+    with open(os.path.join(run_dir, f"bpd_{name}_{v}.txt"), "w") as fh:
+        fh.write("\n".join(lines) + "\n")
+    print("\n".join(lines))
+    return float(bpd.mean())
 
 
 def _load(model_data):
@@ -158,6 +181,14 @@ def inpaint_results(model_data, images, mask, **kw):
     model, diffusion, _ = _load(model_data)
     set_seed(model_data["seed"])
     return diffusion.inpaint(model, images, mask, **kw)
+
+
+def bpd_results(model_data, images, **kw):
+    """Load the checkpoint as rotation_results does, seed, and score `images` in bits/dim (Diffusion.calc_bpd; **kw: labels,
+    sigma, t_samples, batch, noise_source, noise_fn, return_terms).  Returns calc_bpd's dict."""
+    model, diffusion, _ = _load(model_data)
+    set_seed(model_data["seed"])
+    return diffusion.calc_bpd(model, images, **kw)
 
 
 def shift_results(model_data, shift):

@@ -415,6 +415,27 @@ int afd_dpmpp_step(const float* x, const float* eps, const float* x0_prev /* NUL
  * it either (nor any of eps2's 2n values). */
 int afd_dpmpp_step_cfg(const float* x, const float* eps2, const float* x0_prev, const float* coef, float cfg_scale, float* x_out,
                        float* x_out2, float* x0_out, long n, afd_stream_t stream);
+/* ---- likelihood: the variational bound in bits/dim (Ho et al. 2020, section 3.3; Diffusion.calc_bpd) ----
+ * A row r pairs image img[r] of x0 (n_img images of `per` fp32 values each) with timestep t[r].  img and t are int64 device
+ * arrays of `rows` values, read on the device: the caller keeps them in [0, n_img) and [1, T) (nothing checks them here).
+ * Outputs may overlap no input.  Every entry point needs its counts > 0.
+ * Gathered noising: x_t[r] = afd_noise_images' expression on x0[img[r]], eps[r] and t[r], bit for bit. */
+int afd_noise_images_gather(const float* x0, long n_img, const int64_t* img, const float* eps, const int64_t* t, const float* alpha_hat,
+                            float* x_t, long rows, long per, afd_stream_t stream);
+/* The bound's term of each row, one workgroup per row, in fp64.  coef: the (T, 4) fp64 device table of
+ * Diffusion.vlb_coefficients, row t = [w_t, c_t, log_scale_t, prior constant].  With d_j = double(eps_hat_j) - double(eps_j):
+ *   sq[r]   = sum_j d_j^2
+ *   term[r] = w_t * sq[r] + per * c_t                                                         t != 1 (KL, nats)
+ *           = -sum_j log P(x0_j | mean_j, log_scale_1)                                       t == 1 (decoder, nats)
+ * mean_j = c1 * (x_t_j - c2 * eps_hat_j) in fp32, afd_denoise_step's expression at i = 1 without noise, and P the discretised
+ * Gaussian of Ho et al. in fp64 (bins of half-width 1/255, open edge bins below -0.999 and above 0.999, Phi by the tanh
+ * approximation, probabilities clamped at 1e-12).  Only decoder rows read x0 and x_t.  Deterministic: fixed per-thread order,
+ * fixed wave tree, waves summed in order, no atomics.  alpha, alpha_hat, beta: the (T,) fp32 schedule tables. */
+int afd_vlb_terms(const float* x0, long n_img, const int64_t* img, const float* x_t, const float* eps, const float* eps_hat,
+                  const int64_t* t, const double* coef, long T, const float* alpha, const float* alpha_hat, const float* beta,
+                  double* term, double* sq, long rows, long per, afd_stream_t stream);
+/* The prior's data-dependent part: out[i] = half_ah * sum_j double(x0[i, j])^2, half_ah = alpha_hat[T-1] / 2 from the host */
+int afd_vlb_prior(const float* x0, double half_ah, double* out, long n_img, long per, afd_stream_t stream);
 /* ---- inpainting (RePaint, Lugmayr et al. 2022): masked steps and the renoise up-move ----
  * Each masked entry point is its unmasked counterpart above with two more operands after noise: x0 (n fp32 values, the known
  * image) and mask (n bytes; nonzero = known).  Per element j, with t_prev = i - 1 for the DDPM forms:
