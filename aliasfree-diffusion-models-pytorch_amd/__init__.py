@@ -15,7 +15,7 @@ from .diffusion import Diffusion  # noqa: F401
 from .training import (argument, set_seed, setup_logging, train, TrainStep, FusedAdamW, FlatParams,  # noqa: F401
                        GradAllReduce, EMA)
 
-from .tasks import bpd_results, ddpm_run, inpaint_results, rotation_results, shift_results  # noqa: F401
+from .tasks import bpd_results, ddpm_run, equivariance_results, inpaint_results, rotation_results, shift_results  # noqa: F401
 from .data import get_data, get_data_MNIST, save_gen_images, make_collage  # noqa: F401
 
 __version__ = "0.1.0"

@@ -905,6 +905,173 @@ class Diffusion:
         prior_nats = prior.cpu().numpy() + per * float(coef[0, 3])
         return self.bpd_combine(n, per, img, t, term.cpu().numpy(), sq.cpu().numpy(), prior_nats, K, return_terms)
 
+    # Equivariance scores: EQ-T / EQ-R of Karras et al. 2021 (StyleGAN3, section 2 and appendix E) for eps_theta -------------
+    EQ_KINDS = ("translate", "rotate")
+
+    def equivariance_transforms(self, specs):
+        """(K, 6) fp64 host table of affine maps in scipy's convention, out[o] = spline3(in)(M o + off) per (img_size, img_size)
+        plane with periodic wrap, row k = [m00, m01, m10, m11, off0, off1] in (row, col) order, from a list of specs:
+          ("translate", dy, dx): M = I, off = (-dy, -dx): the content moves down by dy and right by dx, as ndimage.shift does
+                                 (whole or fractional pixels);
+          ("rotate", degrees):   the M and off `ops.rotate_spline3_wrap` builds (ndimage.rotate, reshape=False)."""
+        if isinstance(specs, (str, bytes)) or not hasattr(specs, "__len__") or len(specs) == 0:
+            raise ValueError("Diffusion.equivariance_transforms: needs a non-empty list of ('translate', dy, dx) / ('rotate', degrees)")
+        S = self.img_size
+        tab = np.zeros((len(specs), 6), dtype=np.float64)
+        for i, sp in enumerate(specs):
+            if isinstance(sp, (str, bytes)) or not hasattr(sp, "__len__") or len(sp) == 0 or not isinstance(sp[0], str) \
+                    or sp[0] not in self.EQ_KINDS:
+                raise ValueError(f"Diffusion.equivariance_transforms: unknown transform {sp!r} ('translate' or 'rotate')")
+            want = 2 if sp[0] == "translate" else 1
+            try:
+                v = [float(a) for a in sp[1:]]
+            except (TypeError, ValueError):
+                v = None
+            if v is None or len(v) != want or any(isinstance(a, bool) for a in sp[1:]) or not all(math.isfinite(a) for a in v):
+                raise ValueError(f"Diffusion.equivariance_transforms: {sp!r} needs {want} finite number(s) after the kind")
+            if sp[0] == "translate":
+                tab[i] = [1.0, 0.0, 0.0, 1.0, -v[0], -v[1]]
+            else:
+                m, off = ops.rotate_affine(v[0], S, S)
+                tab[i] = [m[0, 0], m[0, 1], m[1, 0], m[1, 1], off[0], off[1]]
+        return torch.from_numpy(tab)
+
+    @staticmethod
+    def equivariance_mask(affine_row, H, W, margin):
+        """The validity mask of one transform, a bool (H, W) numpy array: output pixel o = (oy, ox) counts iff o and its source
+        c = M o + off, taken before any wrapping, both lie in [margin, H-1-margin] x [margin, W-1-margin].  It drops what the
+        wrap would bring in from the other side and a border band (the UNet's zero-padded convolutions are not equivariant
+        there).  c is evaluated in fp64 as (m_0 oy + m_1 ox) + off, every operation rounded, as `afd_eq_terms` does."""
+        a = np.asarray(affine_row, dtype=np.float64).reshape(6)
+        m = float(margin)
+        oy, ox = np.meshgrid(np.arange(H, dtype=np.float64), np.arange(W, dtype=np.float64), indexing="ij")
+        cy = (a[0] * oy + a[1] * ox) + a[4]
+        cx = (a[2] * oy + a[3] * ox) + a[5]
+        hy, hx = float(H - 1) - m, float(W - 1) - m
+        return (oy >= m) & (oy <= hy) & (ox >= m) & (ox <= hx) & (cy >= m) & (cy <= hy) & (cx >= m) & (cx <= hx)
+
+    @staticmethod
+    def equivariance_rows(n, J, K):
+        """The rows of the transformed pass, image-major, then timestep, then transform -> (img, j, k), three int64 arrays of
+        n * J * K values.  Row r compares source field img[r] * J + j[r] (one per image and timestep) under transform k[r]."""
+        r = np.arange(n * J * K, dtype=np.int64)
+        return r // (J * K), (r // K) % J, r % K
+
+    @staticmethod
+    def equivariance_combine(n, J, K, C, sums, peak=2.0):
+        """The rows' sums [sum d^2, sum ref^2, masked pixels * C] ((n * J * K, 3) fp64, `equivariance_rows` order) -> the dict
+        `equivariance` returns: mse, power (n, J, K): the sums over C * count; count (K,): masked pixels per transform;
+        eq_db (J, K) = 10 log10(peak^2 / mean_i mse); snr_db (J, K) = 10 log10(mean_i power / mean_i mse); +inf where the mean
+        mse is 0."""
+        s = np.asarray(sums, dtype=np.float64).reshape(n, J, K, 3)
+        elems = s[..., 2]
+        if not (elems > 0).all() or not (elems == elems[:1, :1]).all():
+            raise ValueError("Diffusion.equivariance_combine: every row of a transform must count the same, non-zero number of elements")
+        mse, power = s[..., 0] / elems, s[..., 1] / elems
+        m, pw = mse.mean(axis=0), power.mean(axis=0)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            eq = np.where(m == 0, np.inf, 10.0 * np.log10(float(peak) ** 2 / m))
+            snr = np.where(m == 0, np.inf, 10.0 * np.log10(pw / m))
+        out = {"mse": mse, "power": power, "eq_db": eq, "snr_db": snr, "count": elems[0, 0] / C}
+        return {k: torch.from_numpy(np.ascontiguousarray(v, dtype=np.float64)) for k, v in out.items()}
+
+    def _equivariance_images(self, model, images):
+        if not isinstance(images, torch.Tensor) or images.dtype != torch.float32:
+            raise ValueError("Diffusion.equivariance: images must be an fp32 tensor")
+        if images.dim() != 4 or images.shape[0] < 1 or tuple(images.shape[2:]) != (self.img_size, self.img_size):
+            raise ValueError(f"Diffusion.equivariance: images must have shape (n, C, {self.img_size}, {self.img_size}) "
+                             f"(got {tuple(images.shape)})")
+        C = next((p.shape[1] for p in model.inc.parameters() if p.dim() == 4), None) if hasattr(model, "inc") else None
+        size = getattr(model, "image_size", self.img_size)
+        if size != self.img_size or (C is not None and images.shape[1] != C):
+            raise ValueError(f"Diffusion.equivariance: images of shape {tuple(images.shape)} do not match the model "
+                             f"({C if C is not None else 'C'} channels, {size} x {size})")
+        return images.detach()
+
+    def equivariance(self, model, images, t, transforms, margin=4.0, peak=2.0, labels=None, batch=256, noise_source="device",
+                     noise_fn=None):
+        """How equivariant eps_theta is, in dB (EQ-T / EQ-R of Karras et al. 2021): the PSNR between "transform the input, then
+        run the model" and "run the model, then transform the output".  images: (n, C, img_size, img_size) fp32; t: an int or a
+        sequence of J ints in [1, T-1]; transforms: a list of K specs (`equivariance_transforms`).  For image i, timestep t_j and
+        transform S_k, with one noise eps_ij shared by every k:
+          x = noise_images(x0_i, t_j, eps_ij);  g = model(S_k x, t_j), S_k x rounded once to fp32;  r = S_k model(x, t_j) in fp64
+          mse[i, j, k] = sum_mask (g - r)^2 / (C count_k),  power[i, j, k] = sum_mask r^2 / (C count_k)
+        over the transform's validity mask for `margin` pixels (`equivariance_mask`; an empty mask is a ValueError).
+        First pass: the n * J base rows (image-major), in chunks of `batch` (`bpd_chunks`), one forward per chunk with per-row
+        t; each chunk draws its noise, (rows, C, H, W), from the device generator (noise_source "device"), the CPU generator
+        ("cpu") or noise_fn(shape); x and the model's output are prefiltered once into fp64 spline coefficients.  Second pass:
+        the n * J * K rows (`equivariance_rows`) in chunks of `batch`: one row-wise resampling of x, one forward, one fused
+        comparison (`ops.eq_terms`).  labels: (n,) int64 for a UNet(num_classes=).  Returns a dict of CPU fp64 tensors: mse,
+        power (n, J, K), eq_db = 10 log10(peak^2 / mean_i mse) and snr_db = 10 log10(mean_i power / mean_i mse) (J, K), and
+        count (K,).  peak = 2 is StyleGAN3's I_max, the range of x0 in [-1, 1]; snr_db assumes no range.  Fractional shifts and
+        rotations resample with a cubic spline, a mild low-pass: compare scores under the same transforms only."""
+        T = self.noise_steps
+        ts = [t] if isinstance(t, (int, np.integer)) and not isinstance(t, bool) else t
+        if isinstance(ts, (str, bytes, bool)) or not hasattr(ts, "__len__") or len(ts) == 0 or \
+                any(isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not 1 <= v <= T - 1 for v in ts):
+            raise ValueError(f"Diffusion.equivariance: t must be an int or a non-empty sequence of ints in [1, {T - 1}] (got {t!r})")
+        ts = [int(v) for v in ts]
+        aff = self.equivariance_transforms(transforms)
+        for name, v, ok in (("margin", margin, lambda a: a >= 0), ("peak", peak, lambda a: a > 0)):
+            if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not math.isfinite(v) or not ok(v):
+                raise ValueError(f"Diffusion.equivariance: {name} must be a finite number {'>= 0' if name == 'margin' else '> 0'} (got {v!r})")
+        if isinstance(batch, bool) or not isinstance(batch, (int, np.integer)) or batch < 1:
+            raise ValueError(f"Diffusion.equivariance: batch must be a positive int (got {batch!r})")
+        if noise_source not in ("device", "cpu"):
+            raise ValueError(f"Diffusion.equivariance: noise_source must be 'device' or 'cpu' (got {noise_source!r})")
+        x0 = self._equivariance_images(model, images)
+        n, shape = x0.shape[0], tuple(x0.shape[1:])
+        C, S = shape[0], self.img_size
+        for k_, row in enumerate(aff.numpy()):
+            if not self.equivariance_mask(row, S, S, margin).any():
+                raise ValueError(f"Diffusion.equivariance: transform {k_} ({transforms[k_]!r}) leaves no pixel inside the margin "
+                                 f"of {margin} on {S} x {S}")
+        y = None if labels is None else self._check_labels(model, n, None, labels, "equivariance")
+        J, K = len(ts), aff.shape[0]
+
+        img, j, k = self.equivariance_rows(n, J, K)
+        src = img * J + j                                                  # the source field of each transformed row
+        src0 = np.arange(n * J, dtype=np.int64)                            # base rows: (image, t_j), image-major
+        assert src.min() >= 0 and src.max() < n * J and k.min() >= 0 and k.max() < K       # the kernels read them unchecked
+        dev = self.device
+        x0 = x0.to(dev).contiguous()
+        t_host = np.asarray(ts, dtype=np.int64)
+        img0_d, t0_d = torch.from_numpy(src0 // J).to(dev), torch.from_numpy(t_host[src0 % J]).to(dev)
+        src_d, k_d, t_d = torch.from_numpy(src).to(dev), torch.from_numpy(k).to(dev), torch.from_numpy(t_host[j]).to(dev)
+        aff_d = aff.to(dev)
+        coef_x = torch.empty((n * J,) + shape, device=dev, dtype=torch.float64)
+        coef_f = torch.empty_like(coef_x)
+        sums = torch.empty((len(k), 3), device=dev, dtype=torch.float64)
+        was_training, hint = model.training, getattr(model, "_t_range", None)
+        self._hint(model)
+        try:
+            model.eval()
+            with torch.no_grad():
+                for lo, hi in self.bpd_chunks(n * J, batch):
+                    cs = (hi - lo,) + shape
+                    if noise_fn is not None:
+                        eps = noise_fn(cs)
+                    elif noise_source == "device":
+                        eps = torch.randn(cs, device=dev)
+                    else:
+                        eps = torch.randn(cs).to(dev)
+                    eps = eps.to(device=dev, dtype=torch.float32).contiguous()
+                    rows_t = t0_d[lo:hi]
+                    xt = ops.noise_images_gather(x0, img0_d[lo:hi], eps, rows_t, self.alpha_hat, check_range=False)
+                    f = model(xt, rows_t) if y is None else model(xt, rows_t, y[img0_d[lo:hi]])
+                    ops.spline3_prefilter_wrap(xt, coef_x[lo:hi])
+                    ops.spline3_prefilter_wrap(f.contiguous(), coef_f[lo:hi])
+                for lo, hi in self.bpd_chunks(len(k), batch):
+                    rows_s, rows_k, rows_t = src_d[lo:hi], k_d[lo:hi], t_d[lo:hi]
+                    sx = ops.affine_spline3_wrap_rows(coef_x, rows_s, aff_d, rows_k, check_range=False)
+                    g = model(sx, rows_t) if y is None else model(sx, rows_t, y[rows_s // J])
+                    ops.eq_terms(coef_f, rows_s, aff_d, rows_k, g.contiguous(), margin, sums[lo:hi], check_range=False)
+        finally:
+            model.train(was_training)
+            if hasattr(model, "_t_range"):
+                model._t_range = hint
+        return self.equivariance_combine(n, J, K, C, sums.cpu().numpy(), peak)
+
     def sample_sharded(self, model, n, image_channels, theta=None, noise_source="reference", group=None, dst=0, steps=None):
         """`sample` with the n images partitioned over the ranks of `group` (sampling is embarrassingly parallel per
         image: replicas only, no collective in the loop) and the uint8 results gathered on rank `dst`.
@@ -1188,9 +1355,13 @@ class Diffusion:
     @staticmethod
     def shift_2d_matrix(matrix, hshift, vshift, device):
         """ndimage.shift(x, (0,0,v,h), mode='grid-wrap') (ddpm_models.py:431-436).  The reference only ever
-        shifts by whole pixels (:415), where the periodic spline shift is exactly a roll: done on the device."""
+        shifts by whole pixels (:415), where the periodic spline shift is exactly a roll: done on the device.  A fractional
+        shift of a device tensor is the affine spline kernel with the identity matrix and offset (-v, -h), which is what
+        ndimage.shift computes; host tensors go through scipy."""
         if matrix.is_cuda and float(hshift).is_integer() and float(vshift).is_integer():
             return torch.roll(matrix, shifts=(int(vshift), int(hshift)), dims=(2, 3)).to(device)
+        if matrix.is_cuda and matrix.dtype == torch.float32 and matrix.dim() == 4:
+            return ops.affine_spline3_wrap(matrix, np.eye(2), (-float(vshift), -float(hshift))).to(device)
         from scipy import ndimage
         r = ndimage.shift(input=matrix.cpu().numpy(), shift=(0, 0, vshift, hshift), mode="grid-wrap")
         return torch.from_numpy(r).to(device)

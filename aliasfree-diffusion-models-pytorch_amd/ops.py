@@ -1426,23 +1426,108 @@ def quantize_u8(x):
     return out
 
 
-def rotate_spline3_wrap(x, degrees):
-    """scipy.ndimage.rotate(x, degrees, axes=(2,3), reshape=False, order=3, mode='grid-wrap') on the device."""
+def rotate_affine(degrees, H, W):
+    """The (matrix, offset) scipy.ndimage.rotate builds for an (H, W) plane: in = matrix @ out + offset, fp64 host arrays."""
     import math
-    _chk(x)
-    x = _c(x)
-    n, c, H, W = x.shape
     a = np.deg2rad(degrees)
     cs, sn = math.cos(a), math.sin(a)
     m = np.array([[cs, sn], [-sn, cs]], dtype=np.float64)                  # scipy.ndimage.rotate's rot_matrix
     plane = np.array([H, W], dtype=np.float64)
     off = (plane - 1) / 2 - m @ ((plane - 1) / 2)                           # in_center - rot @ out_center
-    m = np.ascontiguousarray(m)
-    off = np.ascontiguousarray(off)
+    return np.ascontiguousarray(m), np.ascontiguousarray(off)
+
+
+def rotate_spline3_wrap(x, degrees):
+    """scipy.ndimage.rotate(x, degrees, axes=(2,3), reshape=False, order=3, mode='grid-wrap') on the device."""
+    _chk(x)
+    x = _c(x)
+    n, c, H, W = x.shape
+    m, off = rotate_affine(degrees, H, W)
     y = torch.empty_like(x)
     ws = torch.empty(n * c * H * W, device=x.device, dtype=torch.float64)
     lib().afd_affine_spline3_wrap(_p(x), _p(y), n * c, H, W, m.ctypes.data, off.ctypes.data, _p(ws), _stream())
     return y
+
+
+def affine_spline3_wrap(x, matrix, offset):
+    """scipy.ndimage.affine_transform(plane, matrix, offset, order=3, mode='grid-wrap') of every (H, W) plane of x (n, C, H, W)
+    on the device: in = matrix @ out + offset in (row, col) order, matrix 2 x 2 and offset 2 host values."""
+    _chk(x)
+    x = _c(x)
+    n, c, H, W = x.shape
+    m = np.ascontiguousarray(np.asarray(matrix, dtype=np.float64).reshape(2, 2))
+    off = np.ascontiguousarray(np.asarray(offset, dtype=np.float64).reshape(2))
+    y = torch.empty_like(x)
+    ws = torch.empty(n * c * H * W, device=x.device, dtype=torch.float64)
+    lib().afd_affine_spline3_wrap(_p(x), _p(y), n * c, H, W, m.ctypes.data, off.ctypes.data, _p(ws), _stream())
+    return y
+
+
+# ---- equivariance scores: prefilter once, resample / compare row-wise (include/afd.h gives the exact expressions) -----------
+def spline3_prefilter_wrap(x, out=None):
+    """fp64 cubic B-spline coefficients (periodic) of every (H, W) plane of x (n, C, H, W) fp32: the prefilter of
+    `rotate_spline3_wrap`, done once for any number of `affine_spline3_wrap_rows` / `eq_terms` calls."""
+    _chk(x)
+    if x.dim() != 4 or not x.is_contiguous():
+        raise AfdError("afdm: spline prefilter: x must be a contiguous (n, C, H, W) tensor")
+    out = torch.empty(x.shape, device=x.device, dtype=torch.float64) if out is None else out
+    if not out.is_cuda or out.dtype != torch.float64 or out.shape != x.shape or not out.is_contiguous():
+        raise AfdError("afdm: spline prefilter: out must be a contiguous fp64 device tensor shaped like x")
+    n, c, H, W = x.shape
+    lib().afd_spline3_prefilter_wrap(_p(x), _p(out), n * c, H, W, _stream())
+    return out
+
+
+def _affine_rows_args(what, coef, img, affine, k, check_range):
+    """Common checks of the row-wise spline entry points -> (n_src, K, rows, C, H, W)."""
+    if not coef.is_cuda or coef.dtype != torch.float64 or coef.dim() != 4 or not coef.is_contiguous():
+        raise AfdError(f"afdm: {what}: coef must be a contiguous (n_src, C, H, W) fp64 device tensor (spline3_prefilter_wrap)")
+    if not affine.is_cuda or affine.dtype != torch.float64 or affine.dim() != 2 or affine.shape[1] != 6 or affine.shape[0] < 1 \
+            or not affine.is_contiguous():
+        raise AfdError(f"afdm: {what}: affine must be a contiguous (K, 6) fp64 device table (Diffusion.equivariance_transforms)")
+    rows = img.numel() if isinstance(img, torch.Tensor) else -1
+    for name, v in (("img", img), ("k", k)):
+        if not isinstance(v, torch.Tensor) or not v.is_cuda or v.dtype != torch.long or v.dim() != 1 or v.numel() != rows \
+                or not v.is_contiguous():
+            raise AfdError(f"afdm: {what}: {name} must be a contiguous int64 device vector, one value per row")
+    n_src, K = coef.shape[0], affine.shape[0]
+    if check_range and rows > 0:
+        lo_i, hi_i, lo_k, hi_k = (int(v) for v in torch.stack([img.min(), img.max(), k.min(), k.max()]).cpu())
+        if lo_i < 0 or hi_i >= n_src:
+            raise AfdError(f"afdm: {what}: img must lie in [0, {n_src}) (got {lo_i} .. {hi_i})")
+        if lo_k < 0 or hi_k >= K:
+            raise AfdError(f"afdm: {what}: k must lie in [0, {K}) (got {lo_k} .. {hi_k})")
+    return (n_src, K, rows) + tuple(coef.shape[1:])
+
+
+def affine_spline3_wrap_rows(coef, img, affine, k, out=None, check_range=True):
+    """Row r = source field img[r] of `coef` (n_src, C, H, W; `spline3_prefilter_wrap`) resampled by transform k[r] of the (K, 6)
+    fp64 device table `affine`, rounded once to fp32: (rows, C, H, W).  Bit for bit what `rotate_spline3_wrap` /
+    `affine_spline3_wrap` return for that field and that transform.  img, k: (rows,) int64 device."""
+    n_src, K, rows, C, H, W = _affine_rows_args("row-wise resampling", coef, img, affine, k, check_range)
+    out = torch.empty((rows, C, H, W), device=coef.device, dtype=torch.float32) if out is None else out
+    if not out.is_cuda or out.dtype != torch.float32 or tuple(out.shape) != (rows, C, H, W) or not out.is_contiguous():
+        raise AfdError(f"afdm: row-wise resampling: out must be a contiguous fp32 device tensor of shape {(rows, C, H, W)}")
+    lib().afd_affine_spline3_wrap_rows(_p(coef), n_src, _p(img), _p(affine), K, _p(k), _p(out), rows, C, H, W, _stream())
+    return out
+
+
+def eq_terms(coef_ref, img, affine, k, g, margin, out=None, check_range=True):
+    """The equivariance sums of each row, a (rows, 3) fp64 device tensor [sum d^2, sum ref^2, masked pixels * C] with
+    ref = field img[r] of `coef_ref` under transform k[r], evaluated in fp64 and never stored, d = double(g[r]) - ref, over the
+    transform's validity mask for `margin` (include/afd.h: afd_eq_terms).  g: (rows, C, H, W) fp32."""
+    n_src, K, rows, C, H, W = _affine_rows_args("equivariance terms", coef_ref, img, affine, k, check_range)
+    _chk(g)
+    if tuple(g.shape) != (rows, C, H, W) or not g.is_contiguous():
+        raise AfdError(f"afdm: equivariance terms: g must be a contiguous fp32 tensor of shape {(rows, C, H, W)}")
+    margin = float(margin)
+    if not (0.0 <= margin < float("inf")):
+        raise AfdError(f"afdm: equivariance terms: margin must be finite and >= 0 (got {margin})")
+    out = torch.empty((rows, 3), device=g.device, dtype=torch.float64) if out is None else out
+    if not out.is_cuda or out.dtype != torch.float64 or tuple(out.shape) != (rows, 3) or not out.is_contiguous():
+        raise AfdError(f"afdm: equivariance terms: out must be a contiguous fp64 device tensor of shape {(rows, 3)}")
+    lib().afd_eq_terms(_p(coef_ref), n_src, _p(img), _p(affine), K, _p(k), _p(g), margin, _p(out), rows, C, H, W, _stream())
+    return out
 
 
 class MseLoss(_Fn):

@@ -134,6 +134,10 @@ def ddpm_run(params):
     # FID/KID image set came from (Diffusion.calc_bpd; "eval_bpd_t_samples": K timesteps per image, "eval_bpd_sigma")
     if params.get("eval_bpd"):
         out["bpd"] = _eval_bpd(params, args, diffusion, gen_model, run_dir, name, v, seed)
+    # optional equivariance scores: params["eval_equivariance"] = the keyword arguments of Diffusion.equivariance (t, transforms,
+    # margin, peak, batch, ...) plus "N" (default 16), the number of training images scored, in dataset order, on the same model
+    if params.get("eval_equivariance"):
+        out["equivariance"] = _eval_equivariance(params, args, diffusion, gen_model, run_dir, name, v, seed)
     return out
 
 
@@ -154,6 +158,27 @@ def _eval_bpd(params, args, diffusion, model, run_dir, name, v, seed):
         fh.write("\n".join(lines) + "\n")
     print("\n".join(lines))
     return float(bpd.mean())
+
+
+def _eval_equivariance(params, args, diffusion, model, run_dir, name, v, seed):
+    import json
+    kw = dict(params["eval_equivariance"])
+    N = int(kw.pop("N", 16))
+    dataset = _loader(name, args)[1]
+    if not 1 <= N <= len(dataset):
+        raise ValueError(f"ddpm_run: eval_equivariance N must lie in [1, {len(dataset)}] (the training set's size; got {N})")
+    images = torch.stack([dataset[i][0] for i in range(N)]).float()
+    set_seed(seed)
+    r = diffusion.equivariance(model, images, **kw)
+    t = kw["t"]
+    table = {"t": [int(t)] if isinstance(t, (int, np.integer)) else [int(a) for a in t],
+             "transforms": [list(sp) for sp in kw["transforms"]], "N": N, "margin": float(kw.get("margin", 4.0)),
+             "peak": float(kw.get("peak", 2.0)), "count": r["count"].tolist(), "eq_db": r["eq_db"].tolist(),
+             "snr_db": r["snr_db"].tolist()}
+    with open(os.path.join(run_dir, f"equivariance_{name}_{v}.json"), "w") as fh:
+        json.dump(table, fh, indent=1)
+    print(json.dumps(table))
+    return table
 
 
 def _load(model_data):
@@ -189,6 +214,14 @@ def bpd_results(model_data, images, **kw):
     model, diffusion, _ = _load(model_data)
     set_seed(model_data["seed"])
     return diffusion.calc_bpd(model, images, **kw)
+
+
+def equivariance_results(model_data, images, **kw):
+    """Load the checkpoint as rotation_results does, seed, and score the model's equivariance on `images`
+    (Diffusion.equivariance; **kw: t, transforms, margin, peak, labels, batch, noise_source, noise_fn).  Returns its dict."""
+    model, diffusion, _ = _load(model_data)
+    set_seed(model_data["seed"])
+    return diffusion.equivariance(model, images, **kw)
 
 
 def shift_results(model_data, shift):

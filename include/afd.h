@@ -484,6 +484,25 @@ int afd_quantize_u8(const float* x, uint8_t* out, long n, afd_stream_t stream);
 size_t afd_rotate_workspace_bytes(long planes, int H, int W);
 int afd_affine_spline3_wrap(const float* x, float* y, long planes, int H, int W, const double* matrix4, const double* offset2,
                             void* workspace, afd_stream_t stream);
+/* ---- equivariance scores (EQ-T / EQ-R, Karras et al. 2021): prefilter once, resample and compare many times ----
+ * The prefilter of afd_affine_spline3_wrap as its own entry: x (planes, H, W) fp32 -> coef, its fp64 cubic B-spline
+ * coefficients (periodic).  afd_affine_spline3_wrap is this call followed by the interpolation. */
+int afd_spline3_prefilter_wrap(const float* x, double* coef, long planes, int H, int W, afd_stream_t stream);
+/* Row-wise resampling.  coef: n_src prefiltered fields of C planes each; affine: K transforms of 6 fp64 device values
+ * [m00, m01, m10, m11, off0, off1] (in = M @ out + off, row / col order); img and k: int64 device arrays of `rows` values, read
+ * on the device: the caller keeps them in [0, n_src) and [0, K) (nothing checks them here).
+ *   out[r] (C, H, W) = field img[r] under transform k[r], rounded once to fp32: afd_affine_spline3_wrap's output for that field
+ *   and that matrix, bit for bit (the same weight and index arithmetic in the same order). */
+int afd_affine_spline3_wrap_rows(const double* coef, long n_src, const int64_t* img, const double* affine, long K, const int64_t* k,
+                                 float* out, long rows, int C, int H, int W, afd_stream_t stream);
+/* The fused comparison, one workgroup per row, in fp64.  ref = field img[r] of coef under transform k[r], evaluated per pixel and
+ * never rounded or stored; the mask of the transform for `margin` (pixels) holds at output pixel o iff o and its unwrapped
+ * source c = M o + off both lie in [margin, H-1-margin] x [margin, W-1-margin] (c: two products and two sums per coordinate,
+ * each rounded, no fused multiply-add).  With d = double(g[r]) - ref over the masked pixels of all C planes:
+ *   out[r] = [sum d^2, sum ref^2, masked pixels * C]      (out: rows x 3 fp64)
+ * Deterministic: fixed per-thread order, fixed wave tree, waves summed in order, no atomics.  Outputs may overlap no input. */
+int afd_eq_terms(const double* coef, long n_src, const int64_t* img, const double* affine, long K, const int64_t* k, const float* g,
+                 double margin, double* out, long rows, int C, int H, int W, afd_stream_t stream);
 
 /* ---- F15: loss + optimiser ------------------------------------------- ddpm_utils.py:489-490,503-507
  * mse: loss_out[0] = mean((pred-target)^2) (deterministic two-stage reduction; workspace >= 4096 floats);
