@@ -42,7 +42,8 @@ def parse_header(path=HEADER):
     return out
 
 
-_VALUE_RETURNING = {"afd_device_count", "afd_tok_supported", "afd_conv3x3_weight_kinds", "afd_conv_wgrad_form"}      # int results, not status codes
+_VALUE_RETURNING = {"afd_device_count", "afd_tok_supported", "afd_conv3x3_weight_kinds", "afd_conv_wgrad_form",
+                    "afd_grad_sqnorm_n_partials"}      # int results, not status codes
 
 
 class AfdError(RuntimeError):

@@ -40,6 +40,11 @@ def ddpm_run(params):
     use_ema = params.get("ema_beta") is not None
     if use_ema:
         args.ema_beta, args.ema_start = params["ema_beta"], params.get("ema_start", 2000)
+    # optional gradient-norm clipping and learning-rate schedule (train() hands them to its TrainStep).  Without the keys nothing
+    # changes, the settings file included.
+    opt_keys = [k for k in ("max_grad_norm", "lr_warmup", "lr_schedule", "lr_min_ratio") if params.get(k) is not None]
+    for k in opt_keys:
+        setattr(args, k, params[k])
     cwd = os.getcwd()
     modelpath = os.path.join(cwd, f"models/DDPM_Uncondtional_{name}_{v}/ckpt_{name}_{v}.pt")
     f_settings = _f_settings(params)
@@ -65,6 +70,8 @@ def ddpm_run(params):
     for k_out, k_in in (("kernel_size", "kernel_size"), ("kaiser_beta", "kaiser_beta"),
                         ("omega_c_down", "omega_c_down"), ("omega_c_up", "omega_c_up")):
         settings[k_out] = f_settings[k_in] if f_settings is not None else "None"
+    for k in opt_keys:
+        settings[k] = params[k]
     text = "\n".join(f"{k}: {val}" for k, val in settings.items())
     print(text)
     run_dir = os.path.join(cwd, f"runs/DDPM_Uncondtional_{name}_{v}")

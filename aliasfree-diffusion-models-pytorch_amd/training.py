@@ -2,7 +2,9 @@
 data parallelism (one process per GPU, RCCL all-reduce of one flat fp32 gradient buffer), and
 hipGraph replay of the whole step.
 """
+import ctypes
 import logging
+import math
 import os
 import weakref
 
@@ -17,13 +19,18 @@ class argument:
     """Attribute bag of run settings (ddpm_utils.py:11-23)."""
 
     def __init__(self, run_name=None, epochs=None, batch_size=None, image_size=None, image_channels=3,
-                 dataset_path=None, device=None, lr=None, noise_steps=None, image_gen_n=4, ema_beta=None, ema_start=2000):
+                 dataset_path=None, device=None, lr=None, noise_steps=None, image_gen_n=4, ema_beta=None, ema_start=2000,
+                 max_grad_norm=None, lr_warmup=0, lr_schedule=None, lr_min_ratio=0.0):
         """ema_beta / ema_start (not in the reference's class): with ema_beta set, `train` keeps an EMA of the weights
-        (EMA(ema_beta), step_start_ema = ema_start)."""
+        (EMA(ema_beta), step_start_ema = ema_start).
+        max_grad_norm: `train` clips the gradient to this global L2 norm.  lr_schedule ("constant" | "linear" | "cosine") /
+        lr_warmup / lr_min_ratio: `train` runs LRSchedule(lr_schedule, lr_warmup, total = epochs * batches, lr_min_ratio);
+        lr_warmup > 0 alone means a warm-up into a constant rate."""
         self.run_name, self.epochs, self.batch_size, self.image_size = run_name, epochs, batch_size, image_size
         self.image_channels, self.dataset_path, self.device, self.lr = image_channels, dataset_path, device, lr
         self.noise_steps, self.image_gen_n = noise_steps, image_gen_n
         self.ema_beta, self.ema_start = ema_beta, ema_start
+        self.max_grad_norm, self.lr_warmup, self.lr_schedule, self.lr_min_ratio = max_grad_norm, lr_warmup, lr_schedule, lr_min_ratio
 
 
 def set_seed(seed):
@@ -98,19 +105,153 @@ class FlatParams:
                 p.grad = self.grad[o:o + p.numel()].view(p.shape)
 
 
+_LR_KINDS = {"constant": 0, "linear": 1, "cosine": 2}      # AFD_LR_* of afd.h
+
+
+def _whole(x, what, who):
+    if isinstance(x, bool) or not isinstance(x, int) or x < 0:
+        raise ValueError(f"{who}: {what} must be an integer >= 0 (got {x!r})")
+    return x
+
+
+class LRSchedule:
+    """Learning-rate factor of the k-th optimiser update (k = 0, 1, ...): linear warm-up over `warmup` updates, then constant,
+    or a linear / cosine decay that reaches `min_ratio` at update `total` and stays there:
+        k < warmup:   k / max(1, warmup)
+        constant:     1
+        otherwise:    pr = min(1, (k - warmup) / max(1, total - warmup)),
+                      base = 0.5 * (1 + cos(pi * pr))  (cosine)  or  1 - pr  (linear),   min_ratio + (1 - min_ratio) * base
+    -- torch.optim.lr_scheduler.LambdaLR with the usual "..._schedule_with_warmup" lambda, evaluated in Python doubles (equal
+    to LambdaLR's param_groups[0]["lr"] bit for bit).  Like LambdaLR it gives lr = 0 for the very first update when warmup > 0.
+    This class is the host mirror; FusedAdamW(lr_schedule=...) evaluates the same formula on the device (afd_adamw_ctl_tick), from
+    its device-resident step counter, so a captured step follows the schedule."""
+
+    def __init__(self, kind="constant", warmup=0, total=None, min_ratio=0.0):
+        who = "LRSchedule"
+        if kind not in _LR_KINDS:
+            raise ValueError(f"{who}: kind must be one of {sorted(_LR_KINDS)} (got {kind!r})")
+        self.kind, self.warmup = kind, _whole(warmup, "warmup", who)
+        if kind == "constant" and total is None:
+            total = self.warmup
+        if total is None:
+            raise ValueError(f"{who}: a {kind} decay needs total (the number of optimiser updates of the run)")
+        self.total = _whole(total, "total", who)
+        if kind != "constant" and self.total < self.warmup:
+            raise ValueError(f"{who}: total < warmup ({self.total} < {self.warmup})")
+        try:
+            ok = 0.0 <= float(min_ratio) <= 1.0
+        except (TypeError, ValueError):
+            ok = False
+        if not ok:
+            raise ValueError(f"{who}: min_ratio must lie in [0, 1] (got {min_ratio!r})")
+        self.min_ratio = float(min_ratio)
+
+    def factor(self, k):
+        if k < self.warmup:
+            return float(k) / float(max(1, self.warmup))
+        if self.kind == "constant":
+            return 1.0
+        pr = min(1.0, float(k - self.warmup) / float(max(1, self.total - self.warmup)))
+        base = 0.5 * (1.0 + math.cos(math.pi * pr)) if self.kind == "cosine" else 1.0 - pr
+        return self.min_ratio + (1.0 - self.min_ratio) * base
+
+    def lr(self, base_lr, k):
+        return base_lr * self.factor(k)
+
+    def __repr__(self):
+        return f"LRSchedule(kind={self.kind!r}, warmup={self.warmup}, total={self.total}, min_ratio={self.min_ratio})"
+
+
+def clip_coefficient(norm, max_norm):
+    """The factor torch.nn.utils.clip_grad_norm_(norm_type=2) scales the gradients by, in Python doubles:
+    min(1, max_norm / (norm + 1e-6)); 1 when max_norm is None or <= 0 (no clipping).  Host mirror of afd_adamw_ctl_tick's step 1
+    (a NaN norm gives NaN there and here, as torch's clamp does)."""
+    if max_norm is None or max_norm <= 0:
+        return 1.0
+    c = float(max_norm) / (float(norm) + 1e-6)
+    return 1.0 if c > 1.0 else c
+
+
+def _check_opt_ctl(who, max_grad_norm, lr_schedule):
+    if max_grad_norm is not None:
+        ok = isinstance(max_grad_norm, (int, float)) and not isinstance(max_grad_norm, bool) and max_grad_norm > 0      # (False for NaN)
+        if not ok:
+            raise ValueError(f"{who}: max_grad_norm must be a number > 0, or None for no clipping (got {max_grad_norm!r})")
+    if lr_schedule is not None and not isinstance(lr_schedule, LRSchedule):
+        raise ValueError(f"{who}: lr_schedule must be an LRSchedule or None (got {type(lr_schedule).__name__})")
+
+
+class _OptCtl(ctypes.Structure):               # afd_opt_ctl of afd.h
+    _fields_ = [("base_lr", ctypes.c_double), ("warmup", ctypes.c_long), ("total", ctypes.c_long), ("kind", ctypes.c_int),
+                ("min_ratio", ctypes.c_double), ("max_norm", ctypes.c_double), ("skip_nonfinite", ctypes.c_int)]
+
+
+CTL_FIELDS = ("lr", "coef", "norm", "skip", "n_skipped", "sq", "index", "factor")      # FusedAdamW.ctl, afd.h
+
+
 class FusedAdamW:
     """torch.optim.AdamW(params, lr) semantics (betas .9/.999, eps 1e-8, weight_decay 0.01 --
     the defaults the reference relies on, ddpm_utils.py:489) as ONE kernel over the flat buffers (their first
     `n_active` elements: see FlatParams).
-    The step counter and bias corrections live on the device so a captured hipGraph replays correctly."""
+    The step counter and bias corrections live on the device so a captured hipGraph replays correctly.
 
-    def __init__(self, model_or_flat, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.01, conditional=False):
+    max_grad_norm / lr_schedule / skip_nonfinite / track_grad_norm: gradient clipping by the global L2 norm
+    (torch.nn.utils.clip_grad_norm_) and a learning-rate schedule (LRSchedule), decided ON THE DEVICE so that they work in a
+    captured step, where `lr` passed by value would be frozen and a host-side clip cannot run at all.  With all four at their
+    defaults the step is the two launches it always was (afd_adamw_tick + afd_adamw_step, or the EMA pair).  Otherwise:
+        [afd_grad_sqnorm_partials]  ->  afd_adamw_ctl_tick  ->  afd_adamw_ctl_step        (at most one launch more)
+    the first only when a norm is needed (max_grad_norm, skip_nonfinite or track_grad_norm).  The norm is that of the gradient
+    the optimiser consumes, grad * grad_scale over the first n_active elements; under data parallelism it is taken after the
+    all-reduce, over the reduced buffer with grad_scale = 1 / world: every rank holds the same bytes and the reduction order is
+    fixed, so every rank computes the same coefficient and NO extra collective is needed.
+    skip_nonfinite: an update whose gradient norm is inf or NaN is dropped whole (no parameter, moment, step count or EMA
+    change) and counted in `n_skipped`.
+    `ctl` is the device buffer (float64, CTL_FIELDS) the tick writes and the step reads; `last_grad_norm`, `last_lr`,
+    `n_skipped` read it back (one D2H copy, hence a sync, per access -- nothing in `step` synchronises)."""
+
+    def __init__(self, model_or_flat, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.01, conditional=False,
+                 max_grad_norm=None, lr_schedule=None, skip_nonfinite=False, track_grad_norm=False):
+        _check_opt_ctl("FusedAdamW", max_grad_norm, lr_schedule)
         self.fp = model_or_flat if isinstance(model_or_flat, FlatParams) else FlatParams(model_or_flat, conditional=conditional)
         self.lr, self.betas, self.eps, self.weight_decay = lr, betas, eps, weight_decay
         dev = self.fp.flat.device
         self.m = torch.zeros_like(self.fp.flat)
         self.v = torch.zeros_like(self.fp.flat)
         self.state = torch.zeros(4, device=dev, dtype=torch.float32)
+        self.max_grad_norm, self.lr_schedule = max_grad_norm, lr_schedule
+        self.skip_nonfinite, self.track_grad_norm = bool(skip_nonfinite), bool(track_grad_norm)
+        self._ctl_on = max_grad_norm is not None or lr_schedule is not None or self.skip_nonfinite or self.track_grad_norm
+        self._need_norm = max_grad_norm is not None or self.skip_nonfinite or self.track_grad_norm
+        self.ctl = self.partials = None
+        if self._ctl_on:
+            self.ctl = torch.zeros(len(CTL_FIELDS), device=dev, dtype=torch.float64)
+            if self._need_norm:
+                self.partials = torch.zeros(lib().afd_grad_sqnorm_n_partials(), device=dev, dtype=torch.float64)
+
+    def _cfg(self):
+        sch = self.lr_schedule or LRSchedule()
+        return _OptCtl(float(self.lr), sch.warmup, sch.total, _LR_KINDS[sch.kind], sch.min_ratio,
+                       float(self.max_grad_norm) if self.max_grad_norm is not None else 0.0, int(self.skip_nonfinite))
+
+    def _read_ctl(self, field):
+        if self.ctl is None:
+            return None
+        return float(self.ctl[CTL_FIELDS.index(field)].item())
+
+    @property
+    def last_grad_norm(self):
+        """L2 norm of the last step's gradient (before clipping); None unless a norm is computed.  One D2H copy."""
+        return self._read_ctl("norm") if self._need_norm else None
+
+    @property
+    def last_lr(self):
+        """The learning rate the last applied update used (the fp32 value).  One D2H copy when a schedule is active."""
+        return float(self.lr) if self.ctl is None else self._read_ctl("lr")
+
+    @property
+    def n_skipped(self):
+        """Updates dropped by skip_nonfinite so far.  One D2H copy."""
+        return 0 if self.ctl is None else int(self._read_ctl("n_skipped"))
 
     def zero_grad(self, set_to_none=False):
         self.fp.zero_grad()
@@ -118,6 +259,22 @@ class FusedAdamW:
     def step(self, grad_scale=1.0, ema=None):
         """ema: an _EMAHome (TrainStep(ema=...)): the same two launches, in their fused EMA form (afd.h)."""
         L, s = lib(), ops._stream()
+        if self._ctl_on:
+            cfg, fp = self._cfg(), self.fp
+            parts, n_parts = None, 0
+            if self._need_norm:
+                parts, n_parts = self.partials.data_ptr(), self.partials.numel()
+                L.afd_grad_sqnorm_partials(fp.grad.data_ptr(), fp.n_active, grad_scale, parts, n_parts, s)
+            es = ema.state.data_ptr() if ema is not None else None
+            L.afd_adamw_ctl_tick(self.state.data_ptr(), self.betas[0], self.betas[1], es, ema.start if ema is not None else 0,
+                                 parts, n_parts, ctypes.byref(cfg), self.ctl.data_ptr(), s)
+            L.afd_adamw_ctl_step(fp.flat.data_ptr(), fp.grad.data_ptr(), self.m.data_ptr(), self.v.data_ptr(), fp.n_active,
+                                 self.state.data_ptr(), self.ctl.data_ptr(), self.betas[0], self.betas[1], self.eps,
+                                 self.weight_decay, grad_scale, ema.flat.data_ptr() if ema is not None else None,
+                                 ema.flat.numel() if ema is not None else 0, es, ema.beta if ema is not None else 0.0,
+                                 ema.one_minus_beta if ema is not None else 0.0, s)
+            ops.bump_param_epoch()
+            return
         if ema is not None:
             L.afd_adamw_ema_tick(self.state.data_ptr(), self.betas[0], self.betas[1], ema.state.data_ptr(), ema.start, s)
             L.afd_adamw_ema_step(self.fp.flat.data_ptr(), self.fp.grad.data_ptr(), self.m.data_ptr(), self.v.data_ptr(),
@@ -431,7 +588,8 @@ class TrainStep:
     B = 16, bit-identical to the eager step.  The noise is drawn outside the replayed list (no generator state in it)."""
 
     def __init__(self, model, diffusion, lr, graph=False, distributed=None, n_buckets=4, overlap_wgrad=None, conditional=False,
-                 p_uncond=0.0, ema=None, ema_model=None, ema_start=2000):
+                 p_uncond=0.0, ema=None, ema_model=None, ema_start=2000, max_grad_norm=None, lr_schedule=None, skip_nonfinite=False,
+                 track_grad_norm=False):
         """conditional=True: the step takes class labels (`step(images, y=labels)`, UNet.forward(x, t, y): ddpm_models.py:276-277)
         and `label_emb` is optimised and exchanged like every other parameter.  With the default (the reference's loop,
         ddpm_utils.py:502, never passes labels) `label_emb` stays untouched, as under the reference's AdamW, and passing y raises.
@@ -442,7 +600,14 @@ class TrainStep:
         in ema_model -- the reference's `ema.step_ema(ema_model, model, step_start_ema=ema_start)` after every optimizer step.  The
         update is fused into the AdamW launch (afd_adamw_ema_tick + afd_adamw_ema_step instead of afd_adamw_tick + afd_adamw_step:
         no extra launch), in every launch mode and under data parallelism; ema.beta is read here, once.  `ema.step` counts the
-        calls to this step (the host mirror of the device counter)."""
+        calls to this step (the host mirror of the device counter).
+        max_grad_norm / lr_schedule (an LRSchedule; `lr` is its base rate) / skip_nonfinite / track_grad_norm: gradient clipping by
+        the global L2 norm and a learning-rate schedule, decided on the device between backward and AdamW (FusedAdamW has the
+        semantics): at most one launch more than the default step, none with all four at their defaults, and the same results in
+        every launch mode, with ema=, with conditional= and under data parallelism (the norm is taken after the all-reduce; no
+        extra collective).  `last_grad_norm`, `last_lr`, `n_skipped` read the device buffer `opt.ctl` (one D2H copy per access).
+        With skip_nonfinite a dropped update does not advance the EMA either, while `ema.step` still counts the call."""
+        _check_opt_ctl("TrainStep", max_grad_norm, lr_schedule)
         if (ema is None) != (ema_model is None):
             raise ValueError("TrainStep: ema and ema_model go together (EMA(beta) and a copy of the model): got only one of them")
         if ema is not None and (isinstance(ema_start, bool) or int(ema_start) != ema_start or ema_start < 0):
@@ -477,7 +642,8 @@ class TrainStep:
         # Re-measured with medians over windows (tools/step_median.py, separate processes): eager 4 / 6 / 8 / 10 / 12 / 16 -> 7.264 / 7.109 /
         # 7.097 / 7.133 / 7.147 / 7.182; captured 8 / 16 / 24 / 32 / 40 / 48 / 64 / 128 -> 7.343 / 7.285 / 7.220 / 7.208 / 7.299 / 7.375 / 7.361 / 7.552
         self.wgrad_batch = 8 if (not graph or graph == "lanes") else 32      # ("lanes" has the eager step's stream semantics)
-        self.opt = FusedAdamW(model, lr=lr, conditional=conditional)
+        self.opt = FusedAdamW(model, lr=lr, conditional=conditional, max_grad_norm=max_grad_norm, lr_schedule=lr_schedule,
+                              skip_nonfinite=skip_nonfinite, track_grad_norm=track_grad_norm)
         self.ema, self._ema_home = ema, None
         if ema is not None:
             h = ema._fast(ema_model, model)          # (model now lives in self.opt's FlatParams)
@@ -505,6 +671,10 @@ class TrainStep:
         self._graph = None
         self._static = None
         self._wino_plan, self._wino_requests = None, None      # ops.WinoStepPlan after the first (recording) step
+
+    last_grad_norm = property(lambda self: self.opt.last_grad_norm, doc=FusedAdamW.last_grad_norm.__doc__)
+    last_lr = property(lambda self: self.opt.last_lr, doc=FusedAdamW.last_lr.__doc__)
+    n_skipped = property(lambda self: self.opt.n_skipped, doc=FusedAdamW.n_skipped.__doc__)
 
     def __del__(self):
         h = getattr(self, "_lanes_handle", None)           # the replay list points into the captured graph: free it first
@@ -601,10 +771,11 @@ class TrainStep:
             st = self._static
             # warm-up outside capture (allocator, lazy init, the Winograd plan's recording step).  These are real steps on
             # the first batch, so everything they change is put back afterwards -- parameters, AdamW moments and step
-            # counter, the EMA buffer and its counter, the device generator -- and under data parallel they stop before the
+            # counter, the clip / schedule control buffer, the EMA buffer and its counter, the device generator -- and under data parallel they stop before the
             # exchange: the first graph call is then exactly one step, like the eager one (and like the reference's).
             fp, opt, h = self.opt.fp, self.opt, self._ema_home
             bufs = (fp.flat, opt.m, opt.v, opt.state) + ((h.flat, h.state) if h is not None else ())
+            bufs += (opt.ctl,) if opt.ctl is not None else ()
             keep = [b.clone() for b in bufs]
             rng = torch.cuda.get_rng_state(images.device)
             s = torch.cuda.Stream()
@@ -660,9 +831,15 @@ def train(args, model_path=None, dataloader=None, model=None, diffusion=None):
     if ema_beta is not None:              # (the reference's conditional recipe: EMA(0.995), ema_model = deepcopy(model))
         import copy
         ema, ema_model = EMA(ema_beta), copy.deepcopy(model)
-    step = TrainStep(model, diffusion, lr=args.lr, graph=False, ema=ema, ema_model=ema_model,
-                     ema_start=getattr(args, "ema_start", 2000))
     n_batches = len(dataloader)
+    kind, warmup = getattr(args, "lr_schedule", None), getattr(args, "lr_warmup", 0) or 0
+    schedule = None
+    if kind is not None or warmup:
+        schedule = LRSchedule(kind or "constant", warmup=warmup, total=args.epochs * n_batches,
+                              min_ratio=getattr(args, "lr_min_ratio", 0.0) or 0.0)
+    step = TrainStep(model, diffusion, lr=args.lr, graph=False, ema=ema, ema_model=ema_model,
+                     ema_start=getattr(args, "ema_start", 2000), max_grad_norm=getattr(args, "max_grad_norm", None),
+                     lr_schedule=schedule)
     loss_all = []
     for epoch in range(args.epochs):
         logging.info(f"Starting epoch {epoch}:")

@@ -535,6 +535,57 @@ int afd_adamw_ema_step(float* p, const float* g, float* m, float* v, long n_acti
                        float beta1, float beta2, float eps, float weight_decay, float grad_scale, float* ema, long n_ema,
                        const int* ema_state, float beta, float one_minus_beta, afd_stream_t stream);
 
+/* ---- gradient-norm clipping + learning-rate schedule, on the device ------ training.FusedAdamW / TrainStep(max_grad_norm=, lr_schedule=)
+ * torch.nn.utils.clip_grad_norm_(norm_type=2) and torch.optim.lr_scheduler.LambdaLR (warm-up, then constant / linear / cosine
+ * decay) between backward and AdamW, with the learning rate and the clip coefficient in DEVICE memory so that a captured step
+ * replays them correctly: [afd_grad_sqnorm_partials ->] afd_adamw_ctl_tick -> afd_adamw_ctl_step, in place of tick + step.
+ *
+ * afd_grad_sqnorm_partials: partials[j] = fp64 sum over slice j of (double)(g[i] * grad_scale)^2, the product formed in fp32 exactly
+ *   as the AdamW kernels form it (the norm of the gradient the optimiser consumes; grad_scale = 1 / world under data parallelism).
+ *   n_partials must equal afd_grad_sqnorm_n_partials() (512); slice j is [j*S, (j+1)*S) with S = 4 * ceil(n / 2048), so slices
+ *   beyond n hold 0.  Deterministic: fixed slice per workgroup, fixed element order per thread, fixed tree, no atomics -- the
+ *   bytes do not depend on the run, the launch grid or the alignment of g (16-byte loads when g is 16-byte aligned, scalar loads
+ *   of the same elements in the same order otherwise).  fp64 squares: |g| ~ 1e20 stays finite; inf / NaN elements give inf / NaN.
+ * afd_adamw_ctl_tick: one workgroup, in this order:
+ *   1. with partials: sq = their sum in index order (fp64), norm = sqrt(sq), and with max_norm > 0
+ *      coef = min(1, max_norm / (norm + 1e-6)) (a NaN norm gives a NaN coef, as torch's clamp does); otherwise coef = 1;
+ *   2. with skip_nonfinite and norm inf / NaN: ctl.skip = 1, ++ctl.n_skipped, ctl.norm / ctl.sq reported, NOTHING else changes
+ *      (no Adam step, no EMA call, lr / coef / index / factor keep their last values); otherwise ctl.skip = 0 and
+ *   3. exactly afd_adamw_tick on adam_state (afd_adamw_ema_tick with ema_state / ema_start when ema_state is not NULL);
+ *   4. k = step - 1 (the 0-based index of this update), lr = (float)(base_lr * factor(k)), factor in fp64:
+ *        k < warmup:       k / max(1, warmup)                         (so lr = 0 at k = 0 when warmup > 0: LambdaLR's semantics)
+ *        kind constant:    1
+ *        otherwise:        pr = min(1, (k - warmup) / max(1, total - warmup)),
+ *                          base = 0.5 * (1 + cos(pi * pr)) (cosine) or 1 - pr (linear), factor = min_ratio + (1 - min_ratio) * base;
+ *   5. ctl = device double[8] {lr (the fp32 value, widened), coef, norm, skip, n_skipped, sq, k, factor}.  n_skipped accumulates:
+ *      zero the buffer once.
+ *   cfg points to HOST memory and is copied into the kernel arguments (captured by value: the schedule is fixed, only its position
+ *   is device state).  Rejected before any device is touched: NULL adam_state / cfg / ctl, base_lr not finite or < 0, warmup < 0,
+ *   unknown kind, total < warmup for a non-constant kind, min_ratio outside [0, 1], NaN max_norm, n_partials outside [1, 1024]
+ *   when partials is given, ema_start < 0 when ema_state is given.
+ * afd_adamw_ctl_step: afd_adamw_step (ema == NULL; n_ema, ema_state, beta, one_minus_beta ignored) or afd_adamw_ema_step with
+ *   lr = (float)ctl.lr and grad_scale * (float)ctl.coef read from the device, the same expressions in the same order otherwise:
+ *   with ctl.lr = lr, ctl.coef = 1, ctl.skip = 0 the results are bit-identical to those entry points.  With ctl.skip != 0 every
+ *   thread returns at once: p, m, v and ema are not written. */
+#define AFD_LR_CONSTANT 0
+#define AFD_LR_LINEAR 1
+#define AFD_LR_COSINE 2
+typedef struct afd_opt_ctl {
+  double base_lr;
+  long warmup, total;      /* in optimiser updates; total is ignored by AFD_LR_CONSTANT */
+  int kind;                /* AFD_LR_* */
+  double min_ratio;        /* the decay ends at base_lr * min_ratio */
+  double max_norm;         /* <= 0: no clipping */
+  int skip_nonfinite;
+} afd_opt_ctl;
+int afd_grad_sqnorm_n_partials(void);
+int afd_grad_sqnorm_partials(const float* g, long n, float grad_scale, double* partials, int n_partials, afd_stream_t stream);
+int afd_adamw_ctl_tick(float* adam_state, float beta1, float beta2, int* ema_state, int ema_start, const double* partials,
+                       int n_partials, const afd_opt_ctl* cfg, double* ctl, afd_stream_t stream);
+int afd_adamw_ctl_step(float* p, const float* g, float* m, float* v, long n_active, const float* adam_state, const double* ctl,
+                       float beta1, float beta2, float eps, float weight_decay, float grad_scale, float* ema, long n_ema,
+                       const int* ema_state, float beta, float one_minus_beta, afd_stream_t stream);
+
 /* ---- two-lane replay of a captured step (csrc/replay.hip) --------------------------------- training.TrainStep(graph="lanes")
  * A step captured by the host framework as a hipGraph (forward, backward with the weight gradients forked to a side stream,
  * AdamW) is re-issued from a C++ loop on TWO REAL STREAMS: afd_replay_build walks the graph once (kernel / memset / flat
