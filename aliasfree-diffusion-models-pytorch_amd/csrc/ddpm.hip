@@ -680,6 +680,132 @@ __global__ void mse_bwd_k(const float* __restrict__ p, const float* __restrict__
   AFD_GRID_STRIDE(i, n) dp[i] = (p[i] - t[i]) * g;
 }
 
+// ---- training objectives: eps / v / x0 prediction with a per-timestep loss weight ----------------------------------------
+// Work item = (row b, segment g): the 256 threads of a workgroup take the 256 quads [4 q, 4 q + 4) of row b with
+// q = 256 g + threadIdx.x, so sqrt(a), sqrt(1 - a) (noise_images_k's two expressions) and w[t_b] are read once per item and
+// are uniform over the workgroup.  VEC (chw % 4 == 0, 16-byte aligned pointers): one 128-bit access per stream; otherwise the
+// same quad element by element -- every thread sees the same values in the same order in both forms, so their results are
+// bit-identical.  Streaming, 12-16 bytes per element: at B = 256, chw = 3072 this is 768 items, three workgroups per CU.
+constexpr int kObjBlocks = 1024;      // cap on the partial sums (the workspace holds 4096 floats, as for mse)
+
+// target: eps (AFD_PRED_EPS), sqrt(a) eps - sqrt(1 - a) x0 (AFD_PRED_V), x0 (AFD_PRED_X0); -> pred - target
+__device__ __forceinline__ float objective_diff(int kind, float p, float x0, float e, float sa, float sb) {
+  if (kind == AFD_PRED_V) {
+    const float l = sa * e, r = sb * x0;
+    return p - (l - r);
+  }
+  return p - (kind == AFD_PRED_X0 ? x0 : e);
+}
+
+// the quad at offset o of a row whose remaining length is `left` (>= 1): four values, zero past the row's end
+template <bool VEC>
+__device__ __forceinline__ float4 load_quad(const float* __restrict__ p, long o, long left) {
+  if (VEC) return *reinterpret_cast<const float4*>(p + o);
+  float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+  v.x = p[o];
+  if (left > 1) v.y = p[o + 1];
+  if (left > 2) v.z = p[o + 2];
+  if (left > 3) v.w = p[o + 3];
+  return v;
+}
+template <bool VEC>
+__device__ __forceinline__ void store_quad(float* p, long o, long left, float4 v) {
+  if (VEC) { *reinterpret_cast<float4*>(p + o) = v; return; }
+  p[o] = v.x;
+  if (left > 1) p[o + 1] = v.y;
+  if (left > 2) p[o + 2] = v.z;
+  if (left > 3) p[o + 3] = v.w;
+}
+
+// part[blockIdx.x] = sum over the workgroup's items of w[t_b] * sum_i (pred - target)^2: per thread in item order, then the
+// workgroup's fixed tree (block_sum); mse_final_k sums the partials.  x0 (eps) is not read for AFD_PRED_EPS (AFD_PRED_X0).
+template <bool VEC>
+__global__ __launch_bounds__(256) void objective_partial_k(const float* __restrict__ pred, const float* __restrict__ x0,
+                                                           const float* __restrict__ eps, const int64_t* __restrict__ t,
+                                                           const float* __restrict__ alpha_hat, const float* __restrict__ w, int kind,
+                                                           float* __restrict__ part, long items, long segs, long chw) {
+  __shared__ float red[16];
+  const float4 zero = make_float4(0.f, 0.f, 0.f, 0.f);
+  float s = 0.f;
+  for (long it = blockIdx.x; it < items; it += gridDim.x) {
+    const long b = it / segs, q = (it - b * segs) * 256 + threadIdx.x;
+    const long tb = t[b], left = chw - 4 * q, o = b * chw + 4 * q;
+    const float ah = alpha_hat[tb];
+    const float sa = sqrtf(ah), sb = sqrtf(1.0f - ah);
+    const float wb = w ? w[tb] : 1.0f;
+    if (left <= 0) continue;
+    const float4 p = load_quad<VEC>(pred, o, left);
+    const float4 x = kind != AFD_PRED_EPS ? load_quad<VEC>(x0, o, left) : zero;
+    const float4 e = kind != AFD_PRED_X0 ? load_quad<VEC>(eps, o, left) : zero;
+    const float dx = objective_diff(kind, p.x, x.x, e.x, sa, sb), dy = objective_diff(kind, p.y, x.y, e.y, sa, sb);
+    const float dz = objective_diff(kind, p.z, x.z, e.z, sa, sb), dw = objective_diff(kind, p.w, x.w, e.w, sa, sb);
+    float r = dx * dx;
+    if (left > 1) r += dy * dy;        // (a value past the row's end may be anything, NaN included: it is never added)
+    if (left > 2) r += dz * dz;
+    if (left > 3) r += dw * dw;
+    s += wb * r;
+  }
+  s = block_sum(s, red);
+  if (threadIdx.x == 0) part[blockIdx.x] = s;
+}
+
+// dpred = (dloss * 2 / (B chw) * w[t_b]) * (pred - target), the target recomputed; with w NULL and AFD_PRED_EPS: mse_bwd_k's values
+template <bool VEC>
+__global__ __launch_bounds__(256) void objective_bwd_k(const float* __restrict__ pred, const float* __restrict__ x0,
+                                                       const float* __restrict__ eps, const int64_t* __restrict__ t,
+                                                       const float* __restrict__ alpha_hat, const float* __restrict__ w, int kind,
+                                                       const float* __restrict__ dloss, float* __restrict__ dpred, long items,
+                                                       long segs, long chw, float two_over_n) {
+  const float4 zero = make_float4(0.f, 0.f, 0.f, 0.f);
+  const float g0 = dloss[0] * two_over_n;
+  for (long it = blockIdx.x; it < items; it += gridDim.x) {
+    const long b = it / segs, q = (it - b * segs) * 256 + threadIdx.x;
+    const long tb = t[b], left = chw - 4 * q, o = b * chw + 4 * q;
+    const float ah = alpha_hat[tb];
+    const float sa = sqrtf(ah), sb = sqrtf(1.0f - ah);
+    const float g = w ? g0 * w[tb] : g0;
+    if (left <= 0) continue;
+    const float4 p = load_quad<VEC>(pred, o, left);
+    const float4 x = kind != AFD_PRED_EPS ? load_quad<VEC>(x0, o, left) : zero;
+    const float4 e = kind != AFD_PRED_X0 ? load_quad<VEC>(eps, o, left) : zero;
+    float4 d;
+    d.x = objective_diff(kind, p.x, x.x, e.x, sa, sb) * g;
+    d.y = objective_diff(kind, p.y, x.y, e.y, sa, sb) * g;
+    d.z = objective_diff(kind, p.z, x.z, e.z, sa, sb) * g;
+    d.w = objective_diff(kind, p.w, x.w, e.w, sa, sb) * g;
+    store_quad<VEC>(dpred, o, left, d);
+  }
+}
+
+// the network's output -> eps, per row t: v: (sqrt(a) v) + (sqrt(1 - a) x_t);  x0: (x_t - sqrt(a) x0) / sqrt(1 - a).
+// eps_out may be `out` itself (elementwise: every thread reads its quad before it writes it), hence no __restrict__ on them.
+template <bool VEC>
+__global__ __launch_bounds__(256) void pred_to_eps_k(const float* out, const float* __restrict__ xt, const int64_t* __restrict__ t,
+                                                     const float* __restrict__ alpha_hat, int kind, float* eps_out, long items,
+                                                     long segs, long chw) {
+  for (long it = blockIdx.x; it < items; it += gridDim.x) {
+    const long b = it / segs, q = (it - b * segs) * 256 + threadIdx.x;
+    const long left = chw - 4 * q, o = b * chw + 4 * q;
+    const float ah = alpha_hat[t[b]];
+    const float sa = sqrtf(ah), sb = sqrtf(1.0f - ah);
+    if (left <= 0) continue;
+    const float4 v = load_quad<VEC>(out, o, left), x = load_quad<VEC>(xt, o, left);
+    float4 e;
+    if (kind == AFD_PRED_V) {
+      { const float l = sa * v.x, r = sb * x.x; e.x = l + r; }
+      { const float l = sa * v.y, r = sb * x.y; e.y = l + r; }
+      { const float l = sa * v.z, r = sb * x.z; e.z = l + r; }
+      { const float l = sa * v.w, r = sb * x.w; e.w = l + r; }
+    } else {
+      { const float l = sa * v.x; e.x = (x.x - l) / sb; }
+      { const float l = sa * v.y; e.y = (x.y - l) / sb; }
+      { const float l = sa * v.z; e.z = (x.z - l) / sb; }
+      { const float l = sa * v.w; e.w = (x.w - l) / sb; }
+    }
+    store_quad<VEC>(eps_out, o, left, e);
+  }
+}
+
 // ---- AdamW (torch.optim.AdamW semantics, decoupled weight decay) ---------------------------
 __global__ void adamw_tick_k(float* state, float b1, float b2) {
   // state = {step, 1 - b1^step, 1 - b2^step, unused}; double keeps the powers exact enough for 1e6 steps
@@ -1232,6 +1358,61 @@ int afd_mse_bwd(const float* pred, const float* target, const float* dloss, floa
   AFD_REQUIRE(pred && target && dloss && dpred && n > 0, "afd_mse_bwd: bad argument");
   hipLaunchKernelGGL(mse_bwd_k, dim3(gs_grid(n)), dim3(256), 0, as_stream(st), pred, target, dloss, dpred, n, 2.0f / (float)n);
   return check_launch("afd_mse_bwd");
+}
+
+// items / segments of the objective kernels' (row, 256-quad segment) walk, and its grid
+static inline long obj_segs(long chw) { return ((chw + 3) / 4 + 255) / 256; }
+static inline int obj_grid(long items) { return (int)(items < kObjBlocks ? items : kObjBlocks); }
+static inline bool kind_ok(int kind) { return kind == AFD_PRED_EPS || kind == AFD_PRED_V || kind == AFD_PRED_X0; }
+
+int afd_objective_loss_fwd(const float* pred, const float* x0, const float* eps, const int64_t* t, const float* alpha_hat,
+                           const float* w, int kind, float* loss_out, float* workspace, long B, long chw, afd_stream_t st) {
+  AFD_REQUIRE(pred && x0 && eps && t && alpha_hat && loss_out && workspace,
+              "afd_objective_loss_fwd: pred, x0, eps, t, alpha_hat, loss_out and workspace must not be NULL");
+  AFD_REQUIRE(kind_ok(kind), "afd_objective_loss_fwd: kind must be AFD_PRED_EPS, AFD_PRED_V or AFD_PRED_X0 (got %d)", kind);
+  AFD_REQUIRE(B > 0 && chw > 0, "afd_objective_loss_fwd: B and chw must be positive (got %ld, %ld)", B, chw);
+  const long segs = obj_segs(chw), items = B * segs;
+  const int nb = obj_grid(items);
+  const float inv_n = 1.0f / (float)(B * chw);
+  if (chw % 4 == 0 && aligned16(pred) && aligned16(x0) && aligned16(eps))
+    hipLaunchKernelGGL(objective_partial_k<true>, dim3(nb), dim3(256), 0, as_stream(st), pred, x0, eps, t, alpha_hat, w, kind,
+                       workspace, items, segs, chw);
+  else
+    hipLaunchKernelGGL(objective_partial_k<false>, dim3(nb), dim3(256), 0, as_stream(st), pred, x0, eps, t, alpha_hat, w, kind,
+                       workspace, items, segs, chw);
+  hipLaunchKernelGGL(mse_final_k, dim3(1), dim3(256), 0, as_stream(st), workspace, loss_out, nb, inv_n);
+  return check_launch("afd_objective_loss_fwd");
+}
+int afd_objective_loss_bwd(const float* pred, const float* x0, const float* eps, const int64_t* t, const float* alpha_hat,
+                           const float* w, int kind, const float* dloss, float* dpred, long B, long chw, afd_stream_t st) {
+  AFD_REQUIRE(pred && x0 && eps && t && alpha_hat && dloss && dpred,
+              "afd_objective_loss_bwd: pred, x0, eps, t, alpha_hat, dloss and dpred must not be NULL");
+  AFD_REQUIRE(kind_ok(kind), "afd_objective_loss_bwd: kind must be AFD_PRED_EPS, AFD_PRED_V or AFD_PRED_X0 (got %d)", kind);
+  AFD_REQUIRE(B > 0 && chw > 0, "afd_objective_loss_bwd: B and chw must be positive (got %ld, %ld)", B, chw);
+  const long segs = obj_segs(chw), items = B * segs;
+  const float two_over_n = 2.0f / (float)(B * chw);
+  if (chw % 4 == 0 && aligned16(pred) && aligned16(x0) && aligned16(eps) && aligned16(dpred))
+    hipLaunchKernelGGL(objective_bwd_k<true>, dim3(obj_grid(items)), dim3(256), 0, as_stream(st), pred, x0, eps, t, alpha_hat, w, kind,
+                       dloss, dpred, items, segs, chw, two_over_n);
+  else
+    hipLaunchKernelGGL(objective_bwd_k<false>, dim3(obj_grid(items)), dim3(256), 0, as_stream(st), pred, x0, eps, t, alpha_hat, w, kind,
+                       dloss, dpred, items, segs, chw, two_over_n);
+  return check_launch("afd_objective_loss_bwd");
+}
+int afd_pred_to_eps(const float* out, const float* x_t, const int64_t* t, const float* alpha_hat, int kind, float* eps_out, long B,
+                    long chw, afd_stream_t st) {
+  AFD_REQUIRE(out && x_t && t && alpha_hat && eps_out, "afd_pred_to_eps: out, x_t, t, alpha_hat and eps_out must not be NULL");
+  AFD_REQUIRE(kind == AFD_PRED_V || kind == AFD_PRED_X0,
+              "afd_pred_to_eps: kind must be AFD_PRED_V or AFD_PRED_X0 (got %d; an eps output needs no conversion)", kind);
+  AFD_REQUIRE(B > 0 && chw > 0, "afd_pred_to_eps: B and chw must be positive (got %ld, %ld)", B, chw);
+  const long segs = obj_segs(chw), items = B * segs;
+  if (chw % 4 == 0 && aligned16(out) && aligned16(x_t) && aligned16(eps_out))
+    hipLaunchKernelGGL(pred_to_eps_k<true>, dim3(obj_grid(items)), dim3(256), 0, as_stream(st), out, x_t, t, alpha_hat, kind, eps_out,
+                       items, segs, chw);
+  else
+    hipLaunchKernelGGL(pred_to_eps_k<false>, dim3(obj_grid(items)), dim3(256), 0, as_stream(st), out, x_t, t, alpha_hat, kind, eps_out,
+                       items, segs, chw);
+  return check_launch("afd_pred_to_eps");
 }
 int afd_adamw_tick(float* state, float b1, float b2, afd_stream_t st) {
   AFD_REQUIRE(state, "afd_adamw_tick: state is NULL");

@@ -40,9 +40,25 @@ def gather_u8(t, counts, group=None, dst=0):
 
 
 class Diffusion:
-    def __init__(self, noise_steps=1000, beta_start=1e-4, beta_end=0.02, img_size=256, device="cuda"):
+    SCHEDULES = ("linear", "cosine")
+    PREDICTIONS = ("eps", "v", "x0")
+    LOSS_WEIGHTINGS = ("min_snr",)
+
+    def __init__(self, noise_steps=1000, beta_start=1e-4, beta_end=0.02, img_size=256, device="cuda", schedule="linear",
+                 cosine_s=0.008, prediction="eps"):
+        """schedule: "linear" (the reference's beta schedule) or "cosine" (Nichol & Dhariwal 2021, offset cosine_s).
+        prediction: what the network's output means -- "eps", "v" = sqrt(a_t) eps - sqrt(1 - a_t) x0 (Salimans & Ho 2022) or "x0".
+        Every sampler and evaluation turns the output into eps with `predict_eps`; `TrainStep` trains towards `training_target`."""
+        if not isinstance(schedule, str) or schedule not in self.SCHEDULES:
+            raise ValueError(f"Diffusion: unknown schedule {schedule!r} ('linear' or 'cosine')")
+        if not isinstance(prediction, str) or prediction not in self.PREDICTIONS:
+            raise ValueError(f"Diffusion: unknown prediction {prediction!r} ('eps', 'v' or 'x0')")
+        if schedule == "cosine" and not (isinstance(cosine_s, (int, float)) and not isinstance(cosine_s, bool)
+                                         and math.isfinite(cosine_s) and cosine_s >= 0):
+            raise ValueError(f"Diffusion: cosine_s must be a finite number >= 0 (got {cosine_s!r})")
         self.noise_steps, self.beta_start, self.beta_end = noise_steps, beta_start, beta_end
         self.img_size, self.device = img_size, device
+        self.schedule, self.cosine_s, self.prediction = schedule, float(cosine_s), prediction
         beta = self.prepare_noise_schedule()                    # host fp32
         alpha = 1.0 - beta
         alpha_hat = torch.cumprod(alpha, dim=0)                 # host ATen cumprod, as the reference (:309): accumulates in double, rounds to fp32
@@ -51,7 +67,58 @@ class Diffusion:
         self._t_cache = {}
 
     def prepare_noise_schedule(self):
+        if self.schedule == "cosine":
+            # f(u) = cos^2(((u / T + s) / (1 + s)) pi / 2) in fp64; beta_t = min(1 - f(t + 1) / f(t), 0.999), rounded once to fp32
+            T, s = self.noise_steps, self.cosine_s
+            f = [math.cos(((u / T + s) / (1.0 + s)) * (math.pi / 2.0)) ** 2 for u in range(T + 1)]       # (libm's cos)
+            return torch.tensor([min(1.0 - f[t + 1] / f[t], 0.999) for t in range(T)], dtype=torch.float64).float()
         return torch.linspace(self.beta_start, self.beta_end, self.noise_steps)
+
+    # Parametrisations and loss weights -----------------------------------------------------------------------------------
+    def _sqrt_tables(self, t, like):
+        """sqrt(a_t), sqrt(1 - a_t) of the rows t, shaped to broadcast over `like` (B, ...), in like's dtype on like's device:
+        from the fp32 alpha_hat widened first, so in fp64 they are the exact table's roots."""
+        ah = self.alpha_hat.to(device=like.device, dtype=like.dtype)[t.to(like.device)]
+        ah = ah.reshape((-1,) + (1,) * (like.dim() - 1))
+        return torch.sqrt(ah), torch.sqrt(1.0 - ah)
+
+    def training_target(self, x0, eps, t):
+        """What the network is trained towards for `self.prediction`, in plain torch ops on the inputs' device and in their
+        dtype: eps, sqrt(a_t) eps - sqrt(1 - a_t) x0 ("v") or x0.  t: (B,) integer timesteps."""
+        if self.prediction == "eps":
+            return eps
+        if self.prediction == "x0":
+            return x0
+        sa, sb = self._sqrt_tables(t, x0)
+        return sa * eps - sb * x0
+
+    def predict_eps(self, model, x_t, t, y=None):
+        """Run the model and return eps.  prediction="eps": exactly model(x_t, t[, y]), the same tensor, no launch.  "v" / "x0":
+        one fused conversion launch (ops.pred_to_eps), in place on the model's output; t is the per-row int64 device tensor
+        the model got, so the conversion captures into the sampling graphs with no host value in it."""
+        out = model(x_t, t) if y is None else model(x_t, t, y)
+        if self.prediction == "eps":
+            return out
+        out = out.contiguous()
+        return ops.pred_to_eps(out, x_t.contiguous(), t, self.alpha_hat, self.prediction, eps_out=out)
+
+    def snr_weights(self, kind="min_snr", gamma=5.0):
+        """(T,) fp64 host table of the loss weight of each timestep for `self.prediction` (Min-SNR-gamma, Hang et al. 2023):
+        with snr_t = a_t / (1 - a_t) from the fp32 alpha_hat, min(snr, gamma) / snr for "eps", min(snr, gamma) for "x0",
+        min(snr, gamma) / (snr + 1) for "v"."""
+        if not isinstance(kind, str) or kind not in self.LOSS_WEIGHTINGS:
+            raise ValueError(f"Diffusion.snr_weights: unknown kind {kind!r} ('min_snr')")
+        if isinstance(gamma, bool) or not isinstance(gamma, (int, float, np.integer, np.floating)) or not gamma > 0 \
+                or not math.isfinite(gamma):
+            raise ValueError(f"Diffusion.snr_weights: gamma must be a finite number > 0 (got {gamma!r})")
+        a = self.alpha_hat.detach().cpu().double()
+        snr = a / (1.0 - a)
+        clipped = torch.clamp(snr, max=float(gamma))
+        if self.prediction == "eps":
+            return clipped / snr
+        if self.prediction == "x0":
+            return clipped
+        return clipped / (snr + 1.0)
 
     # F14 ---------------------------------------------------------------------------------
     def noise_images(self, x, t, eps=None):
@@ -136,7 +203,7 @@ class Diffusion:
                         snaps.append(x)
                     continue
                 if guided:
-                    eps2 = model(xs2, self._t_full(2 * n, i, x.device), y)
+                    eps2 = self.predict_eps(model, xs2, self._t_full(2 * n, i, x.device), y)
                     noise = self._step_noise(x, noise_source, shard, n_all) if i > 1 else None
                     nxt = torch.empty_like(xs2)
                     ops.denoise_step_cfg(x, eps2, noise, self.alpha, self.alpha_hat, self.beta, i, cfg_scale, nxt[:n], nxt[n:])
@@ -145,7 +212,7 @@ class Diffusion:
                         snaps.append(x)
                     continue
                 t = self._t_full(n, i, x.device)
-                eps = model(x, t) if y is None else model(x, t, y)
+                eps = self.predict_eps(model, x, t, y)
                 noise = self._step_noise(x, noise_source, shard, n_all) if i > 1 else None
                 x = ops.denoise_step(x, eps, noise, self.alpha, self.alpha_hat, self.beta, i)
                 if theta_step is not None:
@@ -223,14 +290,14 @@ class Diffusion:
                 for t, tp in pairs[first:]:
                     draw = eta > 0 and tp > 0
                     if guided:
-                        eps2 = model(xs2, self._t_full(2 * n, t, x.device), y)
+                        eps2 = self.predict_eps(model, xs2, self._t_full(2 * n, t, x.device), y)
                         noise = self._step_noise(x, noise_source) if draw else None
                         nxt = torch.empty_like(xs2)
                         ops.ddim_step_cfg(x, eps2, noise, self.alpha_hat, t, tp, eta, cfg_scale, nxt[:n], nxt[n:])
                         xs2, x = nxt, nxt[:n]
                     else:
                         tt = self._t_full(n, t, x.device)
-                        eps = model(x, tt) if y is None else model(x, tt, y)
+                        eps = self.predict_eps(model, x, tt, y)
                         noise = self._step_noise(x, noise_source) if draw else None
                         x = ops.ddim_step(x, eps, noise, self.alpha_hat, t, tp, eta)
                     if self.ddim_snapshot(t, tp):
@@ -254,11 +321,11 @@ class Diffusion:
 
         def one_step():
             if guided:
-                eps2 = model(xs, t_dev, y)
+                eps2 = self.predict_eps(model, xs, t_dev, y)
                 noise = torch.randn_like(xh) if noisy else None
                 ops.ddim_step_cfg_dev(xh, eps2, noise, self.alpha_hat, t_dev, tp_dev, eta, cfg_scale, xh, xs[n:])
                 return
-            eps = model(xs, t_dev) if y is None else model(xs, t_dev, y)
+            eps = self.predict_eps(model, xs, t_dev, y)
             noise = torch.randn_like(xs) if noisy else None
             ops.ddim_step_dev(xs, eps, noise, self.alpha_hat, t_dev, tp_dev, eta, xs)            # in place (elementwise)
 
@@ -376,13 +443,13 @@ class Diffusion:
                     t, tp = pairs[k]
                     prev = x0 if self.dpmpp_order(k, len(pairs)) == 2 else None
                     if guided:
-                        eps2 = model(xs, self._t_full(2 * n, t, x.device), y)
+                        eps2 = self.predict_eps(model, xs, self._t_full(2 * n, t, x.device), y)
                         nxt = torch.empty_like(xs)
                         ops.dpmpp_step_cfg(xs[:n], eps2, prev, table[k], s, nxt[:n], nxt[n:], x0)
                         xs = nxt
                     else:
                         tt = self._t_full(n, t, x.device)
-                        eps = model(xs, tt) if y is None else model(xs, tt, y)
+                        eps = self.predict_eps(model, xs, tt, y)
                         xs = ops.dpmpp_step(xs, eps, prev, table[k], x0_out=x0)[0]
                     if self.ddim_snapshot(t, tp):
                         snaps.append(xs[:n])
@@ -405,10 +472,10 @@ class Diffusion:
 
         def one_step():
             if guided:
-                eps2 = model(xs, t_dev, y)
+                eps2 = self.predict_eps(model, xs, t_dev, y)
                 ops.dpmpp_step_cfg(xh, eps2, x0, coef, cfg_scale, xh, xs[n:], x0)
                 return
-            eps = model(xs, t_dev) if y is None else model(xs, t_dev, y)
+            eps = self.predict_eps(model, xs, t_dev, y)
             ops.dpmpp_step(xs, eps, x0, coef, xs, x0)                         # in place (elementwise)
 
         g = self._capture(one_step, xs)
@@ -446,11 +513,11 @@ class Diffusion:
 
         def one_step():
             if guided:
-                eps2 = model(xs, t_dev, y)
+                eps2 = self.predict_eps(model, xs, t_dev, y)
                 noise = torch.randn_like(xh)
                 ops.denoise_step_cfg_dev(xh, eps2, noise, self.alpha, self.alpha_hat, self.beta, t_dev, cfg_scale, xh, xs[n:])
                 return
-            eps = model(xs, t_dev) if y is None else model(xs, t_dev, y)
+            eps = self.predict_eps(model, xs, t_dev, y)
             noise = torch.randn_like(xs)
             ops.denoise_step_dev(xs, eps, noise, self.alpha, self.alpha_hat, self.beta, t_dev, xs)   # in place (elementwise)
 
@@ -665,7 +732,7 @@ class Diffusion:
                 rows = xs.shape[0]
 
                 def forward(t_rows):
-                    return model(xs, t_rows) if y is None else model(xs, t_rows, y)
+                    return self.predict_eps(model, xs, t_rows, y)
 
                 replay = None
                 first = next(((t, tp) for t, tp in moves if t > tp > 0), None)
@@ -895,7 +962,7 @@ class Diffusion:
                     eps = eps.to(device=dev, dtype=torch.float32).contiguous()
                     rows_i, rows_t = img_d[lo:hi], t_d[lo:hi]
                     xt = ops.noise_images_gather(x0, rows_i, eps, rows_t, self.alpha_hat, check_range=False)
-                    eh = model(xt, rows_t) if y_rows is None else model(xt, rows_t, y_rows[lo:hi])
+                    eh = self.predict_eps(model, xt, rows_t, None if y_rows is None else y_rows[lo:hi])
                     ops.vlb_terms(x0, rows_i, xt, eps, eh.contiguous(), rows_t, coef_d, self.alpha, self.alpha_hat, self.beta,
                                   term[lo:hi], sq[lo:hi], check_range=False)
         finally:
@@ -1004,7 +1071,9 @@ class Diffusion:
         comparison (`ops.eq_terms`).  labels: (n,) int64 for a UNet(num_classes=).  Returns a dict of CPU fp64 tensors: mse,
         power (n, J, K), eq_db = 10 log10(peak^2 / mean_i mse) and snr_db = 10 log10(mean_i power / mean_i mse) (J, K), and
         count (K,).  peak = 2 is StyleGAN3's I_max, the range of x0 in [-1, 1]; snr_db assumes no range.  Fractional shifts and
-        rotations resample with a cubic spline, a mild low-pass: compare scores under the same transforms only."""
+        rotations resample with a cubic spline, a mild low-pass: compare scores under the same transforms only.
+        The score is of the network's raw output, whatever `prediction` says it means (eps, v or x0): it does not go through
+        `predict_eps`, whose x_t term would add a trivially equivariant part."""
         T = self.noise_steps
         ts = [t] if isinstance(t, (int, np.integer)) and not isinstance(t, bool) else t
         if isinstance(ts, (str, bytes, bool)) or not hasattr(ts, "__len__") or len(ts) == 0 or \
@@ -1145,7 +1214,7 @@ class Diffusion:
         with torch.no_grad():
             x = self._initial_noise(n, image_channels, "reference").repeat(K, 1, 1, 1)
             for i in reversed(range(1, self.noise_steps)):
-                eps = model(x, self._t_full(K * n, i, x.device))
+                eps = self.predict_eps(model, x, self._t_full(K * n, i, x.device))
                 noise = torch.randn(n, *x.shape[1:], device=x.device).repeat(K, 1, 1, 1) if i > 1 else None
                 x = ops.denoise_step(x, eps, noise, self.alpha, self.alpha_hat, self.beta, i)
                 for k, th in enumerate(thetas):
@@ -1212,7 +1281,7 @@ class Diffusion:
                     for k in group:                                  # one denoise step of every trajectory of the group
                         with torch.cuda.stream(pool[k - g0]):
                             x = xs[k]
-                            eps = model(x, self._t_full(x.shape[0], i, x.device))
+                            eps = self.predict_eps(model, x, self._t_full(x.shape[0], i, x.device))
                             noise = None if not draw else (torch.randn_like(x) if noise_fn is None else noise_fn(k, i, x.shape))
                             if ddim:
                                 x = ops.ddim_step(x, eps, noise, self.alpha_hat, i, tp, eta)
@@ -1256,7 +1325,7 @@ class Diffusion:
                             nz = torch.zeros_like(xs) if noisy else None
 
                             def one_step(xs=xs, t_dev=t_dev, tp_dev=tp_dev, nz=nz):
-                                eps = model(xs, t_dev)
+                                eps = self.predict_eps(model, xs, t_dev)
                                 if ddim:
                                     ops.ddim_step_dev(xs, eps, nz, self.alpha_hat, t_dev, tp_dev, eta, xs)
                                 else:
@@ -1287,7 +1356,7 @@ class Diffusion:
                                     nz.copy_(noise_fn(k, i, xs.shape))
                                 g.replay()
                             else:                            # the last step adds no noise (ddpm_models.py:370-373)
-                                eps = model(xs, self._t_full(xs.shape[0], i, xs.device))
+                                eps = self.predict_eps(model, xs, self._t_full(xs.shape[0], i, xs.device))
                                 if ddim:
                                     xs.copy_(ops.ddim_step(xs, eps, None, self.alpha_hat, i, 0, eta))
                                 else:
@@ -1333,7 +1402,7 @@ class Diffusion:
         with torch.no_grad():
             x = self._initial_noise(n, image_channels, noise_source)
             for i in reversed(range(1, self.noise_steps)):
-                eps = model(x, self._t_full(n, i, x.device))
+                eps = self.predict_eps(model, x, self._t_full(n, i, x.device))
                 noise = self._step_noise(x, noise_source) if i > 1 else None
                 x = ops.denoise_step(x, eps, noise, self.alpha, self.alpha_hat, self.beta, i)
                 if idx is not None and i in idx:

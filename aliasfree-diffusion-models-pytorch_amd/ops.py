@@ -1554,3 +1554,73 @@ class MseLoss(_Fn):
 
 def mse_loss(target, pred):
     return MseLoss.apply(target, pred)
+
+
+PRED_KINDS = {"eps": 0, "v": 1, "x0": 2}          # AFD_PRED_EPS / AFD_PRED_V / AFD_PRED_X0 of afd.h
+
+
+def _objective_args(what, kind, t, alpha_hat, *tensors):
+    """-> (AFD_PRED_* code, B, chw) after checking the tensors of one of the objective kernels: `tensors` (B, ...) fp32 device
+    tensors of one shape, contiguous; t (B,) int64 on the device; alpha_hat (T,) fp32.  t's values are read unchecked."""
+    if not isinstance(kind, str) or kind not in PRED_KINDS:
+        raise AfdError(f"afdm: {what}: unknown prediction {kind!r} ('eps', 'v' or 'x0')")
+    if any(not isinstance(o, torch.Tensor) for o in (alpha_hat,) + tensors):
+        raise AfdError(f"afdm: {what}: every argument but kind must be a tensor")
+    _chk(alpha_hat, *tensors)
+    first = tensors[0]
+    if first.dim() < 1 or first.numel() == 0:
+        raise AfdError(f"afdm: {what}: needs tensors of shape (B, ...) with at least one element")
+    for o in tensors:
+        if tuple(o.shape) != tuple(first.shape) or not o.is_contiguous():
+            raise AfdError(f"afdm: {what}: every tensor must be contiguous and of shape {tuple(first.shape)}")
+    B = first.shape[0]
+    if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.long or tuple(t.shape) != (B,) or not t.is_contiguous():
+        raise AfdError(f"afdm: {what}: t must be a contiguous int64 device tensor of shape ({B},)")
+    if alpha_hat.dim() != 1 or not alpha_hat.is_contiguous():
+        raise AfdError(f"afdm: {what}: alpha_hat must be a contiguous (T,) table")
+    return PRED_KINDS[kind], B, first.numel() // B
+
+
+class ObjectiveLoss(_Fn):
+    """(1 / (B chw)) sum_b w[t_b] sum_i (pred - target)^2 with the target of `kind` formed inside the kernels from x0, eps and
+    alpha_hat[t_b] (afd.h: afd_objective_loss_fwd / _bwd): two launches forward and one backward, like MseLoss."""
+
+    @staticmethod
+    def forward(ctx, pred, x0, eps, t, alpha_hat, w, kind):
+        pred, x0, eps = _c(pred), _c(x0), _c(eps)
+        code, B, chw = _objective_args("objective loss", kind, t, alpha_hat, pred, x0, eps)
+        if w is not None:
+            _chk(w)
+            if tuple(w.shape) != tuple(alpha_hat.shape) or not w.is_contiguous():
+                raise AfdError(f"afdm: objective loss: w must be a contiguous table of alpha_hat's shape {tuple(alpha_hat.shape)}")
+        loss = torch.empty(1, device=pred.device, dtype=torch.float32)
+        ws = torch.empty(4096, device=pred.device, dtype=torch.float32)
+        lib().afd_objective_loss_fwd(_p(pred), _p(x0), _p(eps), _p(t), _p(alpha_hat), _p(w), code, _p(loss), _p(ws), B, chw, _stream())
+        ctx.save_for_backward(pred, x0, eps, t, alpha_hat, w)
+        ctx.code = code
+        return loss.reshape(())
+
+    @staticmethod
+    def backward(ctx, dloss):
+        pred, x0, eps, t, alpha_hat, w = ctx.saved_tensors
+        dloss = dloss.reshape(1).contiguous()
+        dpred = torch.empty_like(pred)
+        B = pred.shape[0]
+        lib().afd_objective_loss_bwd(_p(pred), _p(x0), _p(eps), _p(t), _p(alpha_hat), _p(w), ctx.code, _p(dloss), _p(dpred), B,
+                                     pred.numel() // B, _stream())
+        return dpred, None, None, None, None, None, None
+
+
+def objective_loss(pred, x0, eps, t, alpha_hat, w=None, kind="eps"):
+    """The training loss of a network whose output `pred` means `kind` ("eps", "v" or "x0"), per-row weights w[t] (a (T,) fp32
+    device table, None = 1), normalised by the element count.  Differentiable in pred only."""
+    return ObjectiveLoss.apply(pred, x0, eps, t, alpha_hat, w, kind)
+
+
+def pred_to_eps(out, x_t, t, alpha_hat, kind, eps_out=None):
+    """The network's output `out` at x_t with per-row timesteps t (int64, on the device) -> eps, one launch (afd.h:
+    afd_pred_to_eps).  kind: "v" or "x0" ("eps" needs no conversion and is an error).  eps_out may be `out` (in place)."""
+    eps_out = torch.empty_like(out) if eps_out is None else eps_out
+    code, B, chw = _objective_args("pred_to_eps", kind, t, alpha_hat, out, x_t, eps_out)
+    lib().afd_pred_to_eps(_p(out), _p(x_t), _p(t), _p(alpha_hat), code, _p(eps_out), B, chw, _stream())
+    return eps_out

@@ -12,7 +12,7 @@ import torch
 
 from .data import get_data, get_data_MNIST, make_collage, save_dataset_MNIST, save_gen_images
 from .diffusion import Diffusion
-from .training import argument, ema_path, set_seed, train
+from .training import argument, diffusion_kwargs, ema_path, set_seed, train
 from .unet import UNet
 
 
@@ -42,7 +42,10 @@ def ddpm_run(params):
         args.ema_beta, args.ema_start = params["ema_beta"], params.get("ema_start", 2000)
     # optional gradient-norm clipping and learning-rate schedule (train() hands them to its TrainStep).  Without the keys nothing
     # changes, the settings file included.
-    opt_keys = [k for k in ("max_grad_norm", "lr_warmup", "lr_schedule", "lr_min_ratio") if params.get(k) is not None]
+    # optional training objective: "noise_schedule" ("linear" | "cosine") and "prediction" ("eps" | "v" | "x0") go to every
+    # Diffusion of the run, "loss_weighting" ("min_snr") and "snr_gamma" to train()'s TrainStep; same rule
+    opt_keys = [k for k in ("max_grad_norm", "lr_warmup", "lr_schedule", "lr_min_ratio", "noise_schedule", "prediction",
+                            "loss_weighting", "snr_gamma") if params.get(k) is not None]
     for k in opt_keys:
         setattr(args, k, params[k])
     cwd = os.getcwd()
@@ -93,7 +96,7 @@ def ddpm_run(params):
     dataloader, dataset = _loader(name, args)
     model = UNet(c_in=args.image_channels, c_out=args.image_channels, image_size=args.image_size, f_settings=f_settings,
                  device=args.device, variant=v).to(args.device)
-    diffusion = Diffusion(noise_steps=args.noise_steps, img_size=args.image_size, device=args.device)
+    diffusion = Diffusion(noise_steps=args.noise_steps, img_size=args.image_size, device=args.device, **diffusion_kwargs(args))
     loss_all = train(args, model_path=modelpath, dataloader=dataloader, model=model, diffusion=diffusion)
     with open(os.path.join(run_dir, f"trining_loss_MNIST_{v}.csv"), "w", newline="") as fh:     # (sic) reference file name
         csv.writer(fh).writerow(loss_all)
@@ -105,7 +108,7 @@ def ddpm_run(params):
     model = UNet(c_in=args.image_channels, c_out=args.image_channels, image_size=args.image_size, f_settings=f_settings,
                  device=args.device, variant=v).to(args.device)
     model.load_state_dict(torch.load(modelpath, weights_only=True))
-    diffusion = Diffusion(noise_steps=args.noise_steps, img_size=args.image_size, device=args.device)
+    diffusion = Diffusion(noise_steps=args.noise_steps, img_size=args.image_size, device=args.device, **diffusion_kwargs(args))
     x, _ = diffusion.sample(model, n=6, image_channels=args.image_channels)
     set_seed(seed)
     denoise_img = diffusion.revert(model, n=1, image_channels=args.image_channels)
@@ -194,7 +197,8 @@ def _load(model_data):
     model = UNet(c_in=args.image_channels, c_out=args.image_channels, image_size=args.image_size,
                  f_settings=model_data["f_settings"], device=args.device, variant=v).to(args.device)
     model.load_state_dict(torch.load(model_data["modelpath"], weights_only=True))
-    return model, Diffusion(noise_steps=args.noise_steps, img_size=args.image_size, device=args.device), args
+    # (a checkpoint trained with another noise schedule or parametrisation is evaluated as such: args.noise_schedule / .prediction)
+    return model, Diffusion(noise_steps=args.noise_steps, img_size=args.image_size, device=args.device, **diffusion_kwargs(args)), args
 
 
 def rotation_results(model_data, thatas):

@@ -13,6 +13,7 @@ import torch.distributed as dist
 
 from . import ops
 from ._lib import lib
+from .diffusion import Diffusion
 
 
 class argument:
@@ -20,17 +21,33 @@ class argument:
 
     def __init__(self, run_name=None, epochs=None, batch_size=None, image_size=None, image_channels=3,
                  dataset_path=None, device=None, lr=None, noise_steps=None, image_gen_n=4, ema_beta=None, ema_start=2000,
-                 max_grad_norm=None, lr_warmup=0, lr_schedule=None, lr_min_ratio=0.0):
+                 max_grad_norm=None, lr_warmup=0, lr_schedule=None, lr_min_ratio=0.0, noise_schedule=None, prediction=None,
+                 loss_weighting=None, snr_gamma=None):
         """ema_beta / ema_start (not in the reference's class): with ema_beta set, `train` keeps an EMA of the weights
         (EMA(ema_beta), step_start_ema = ema_start).
         max_grad_norm: `train` clips the gradient to this global L2 norm.  lr_schedule ("constant" | "linear" | "cosine") /
         lr_warmup / lr_min_ratio: `train` runs LRSchedule(lr_schedule, lr_warmup, total = epochs * batches, lr_min_ratio);
-        lr_warmup > 0 alone means a warm-up into a constant rate."""
+        lr_warmup > 0 alone means a warm-up into a constant rate.
+        noise_schedule ("linear" | "cosine") / prediction ("eps" | "v" | "x0"): `diffusion_kwargs` turns them into the arguments
+        of the run's Diffusion; loss_weighting ("min_snr") / snr_gamma: `train` hands them to its TrainStep.  None = the default."""
         self.run_name, self.epochs, self.batch_size, self.image_size = run_name, epochs, batch_size, image_size
         self.image_channels, self.dataset_path, self.device, self.lr = image_channels, dataset_path, device, lr
         self.noise_steps, self.image_gen_n = noise_steps, image_gen_n
         self.ema_beta, self.ema_start = ema_beta, ema_start
         self.max_grad_norm, self.lr_warmup, self.lr_schedule, self.lr_min_ratio = max_grad_norm, lr_warmup, lr_schedule, lr_min_ratio
+        self.noise_schedule, self.prediction = noise_schedule, prediction
+        self.loss_weighting, self.snr_gamma = loss_weighting, snr_gamma
+
+
+def diffusion_kwargs(args):
+    """The Diffusion arguments named by a run's settings (`args.noise_schedule`, `args.prediction`); empty when both are absent
+    or None, so a run without the keys builds the default Diffusion."""
+    kw = {}
+    if getattr(args, "noise_schedule", None) is not None:
+        kw["schedule"] = args.noise_schedule
+    if getattr(args, "prediction", None) is not None:
+        kw["prediction"] = args.prediction
+    return kw
 
 
 def set_seed(seed):
@@ -589,7 +606,7 @@ class TrainStep:
 
     def __init__(self, model, diffusion, lr, graph=False, distributed=None, n_buckets=4, overlap_wgrad=None, conditional=False,
                  p_uncond=0.0, ema=None, ema_model=None, ema_start=2000, max_grad_norm=None, lr_schedule=None, skip_nonfinite=False,
-                 track_grad_norm=False):
+                 track_grad_norm=False, loss_weighting=None, snr_gamma=5.0):
         """conditional=True: the step takes class labels (`step(images, y=labels)`, UNet.forward(x, t, y): ddpm_models.py:276-277)
         and `label_emb` is optimised and exchanged like every other parameter.  With the default (the reference's loop,
         ddpm_utils.py:502, never passes labels) `label_emb` stays untouched, as under the reference's AdamW, and passing y raises.
@@ -606,8 +623,19 @@ class TrainStep:
         semantics): at most one launch more than the default step, none with all four at their defaults, and the same results in
         every launch mode, with ema=, with conditional= and under data parallelism (the norm is taken after the all-reduce; no
         extra collective).  `last_grad_norm`, `last_lr`, `n_skipped` read the device buffer `opt.ctl` (one D2H copy per access).
-        With skip_nonfinite a dropped update does not advance the EMA either, while `ema.step` still counts the call."""
+        With skip_nonfinite a dropped update does not advance the EMA either, while `ema.step` still counts the call.
+        The objective: the network is trained towards `diffusion.training_target` for `diffusion.prediction` ("eps", "v" or "x0"),
+        and loss_weighting="min_snr" weights each sample's squared error by `diffusion.snr_weights("min_snr", snr_gamma)[t]`:
+          L = (1 / (B C H W)) sum_b w[t_b] sum_i (pred - target)^2
+        normalised by the element count, not by sum w, so data-parallel ranks average losses and gradients exactly as for the
+        plain MSE, with no extra collective.  Anything but eps-prediction without weighting runs ops.objective_loss, which forms
+        the target inside the loss kernels: the same number of launches as ops.mse_loss, in every launch mode.  The weight table
+        is a static device buffer built here, once."""
         _check_opt_ctl("TrainStep", max_grad_norm, lr_schedule)
+        if loss_weighting is not None and not (isinstance(loss_weighting, str) and loss_weighting in Diffusion.LOSS_WEIGHTINGS):
+            raise ValueError(f"TrainStep: unknown loss_weighting {loss_weighting!r} (None or 'min_snr')")
+        if isinstance(snr_gamma, bool) or not isinstance(snr_gamma, (int, float)) or not snr_gamma > 0 or not math.isfinite(snr_gamma):
+            raise ValueError(f"TrainStep: snr_gamma must be a finite number > 0 (got {snr_gamma!r})")
         if (ema is None) != (ema_model is None):
             raise ValueError("TrainStep: ema and ema_model go together (EMA(beta) and a copy of the model): got only one of them")
         if ema is not None and (isinstance(ema_start, bool) or int(ema_start) != ema_start or ema_start < 0):
@@ -622,6 +650,11 @@ class TrainStep:
         self.conditional = conditional
         self.p_uncond = float(p_uncond)
         self.last_labels = None          # the labels the last call trained on, after dropout
+        self.prediction = getattr(diffusion, "prediction", "eps")
+        self.loss_weighting, self.snr_gamma = loss_weighting, float(snr_gamma)
+        self.loss_weights = None         # (T,) fp32 device table w[t], or None for the unweighted loss
+        if loss_weighting is not None:
+            self.loss_weights = diffusion.snr_weights(loss_weighting, snr_gamma).float().to(diffusion.alpha_hat.device).contiguous()
         # weight-gradient kernels on a second stream (ops._GradMode.side): off the critical path of backward, they fill
         # the CUs the dependent chain of small kernels leaves idle.  Measured on MI355X (B=256): eager 12.0 -> 11.1
         # ms/step, captured graph 11.45 -> 11.3 (forks batched 16 layers at a time: every fork is a cross-stream edge
@@ -695,7 +728,10 @@ class TrainStep:
         try:
             x_t, noise = self.diffusion.noise_images(images, t, eps)
             pred = self.model(x_t, t) if y is None else self.model(x_t, t, y)
-            loss = ops.mse_loss(noise, pred)
+            if self.prediction == "eps" and self.loss_weights is None:
+                loss = ops.mse_loss(noise, pred)
+            else:
+                loss = ops.objective_loss(pred, images, noise, t, self.diffusion.alpha_hat, self.loss_weights, self.prediction)
             self.opt.zero_grad()
             overlap = self.ddp is not None and self.ddp.world > 1 and not self.use_graph      # (a captured backward cannot hold the exchange)
             if overlap:
@@ -839,7 +875,8 @@ def train(args, model_path=None, dataloader=None, model=None, diffusion=None):
                               min_ratio=getattr(args, "lr_min_ratio", 0.0) or 0.0)
     step = TrainStep(model, diffusion, lr=args.lr, graph=False, ema=ema, ema_model=ema_model,
                      ema_start=getattr(args, "ema_start", 2000), max_grad_norm=getattr(args, "max_grad_norm", None),
-                     lr_schedule=schedule)
+                     lr_schedule=schedule, loss_weighting=getattr(args, "loss_weighting", None),
+                     snr_gamma=5.0 if getattr(args, "snr_gamma", None) is None else args.snr_gamma)
     loss_all = []
     for epoch in range(args.epochs):
         logging.info(f"Starting epoch {epoch}:")

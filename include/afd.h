@@ -511,6 +511,30 @@ int afd_eq_terms(const double* coef, long n_src, const int64_t* img, const doubl
  * device float[4] {step, bias_corr1, bias_corr2, _} advanced by afd_adamw_tick (graph-replay safe). */
 int afd_mse_fwd(const float* pred, const float* target, float* loss_out, float* workspace, long n, afd_stream_t stream);
 int afd_mse_bwd(const float* pred, const float* target, const float* dloss, float* dpred, long n, afd_stream_t stream);
+
+/* ---- training objectives: what the network's output means, and a per-timestep loss weight -------- Diffusion(prediction=) /
+ * TrainStep(loss_weighting=).  With a = alpha_hat[t[b]], sa = sqrt(a), sb = sqrt(1 - a) (afd_noise_images' two expressions), the
+ * target of row b is eps (AFD_PRED_EPS), sa eps - sb x0 (AFD_PRED_V, Salimans & Ho 2022) or x0 (AFD_PRED_X0); it is formed in
+ * registers, never written.  t: B int64 timesteps on the device, each in [0, T) (read unchecked); w: T floats indexed by t[b],
+ * or NULL for weight 1; pred, x0, eps, dpred: B x chw floats.
+ *   fwd: loss_out[0] = (1 / (B chw)) sum_b w[t[b]] sum_i (pred - target)^2: two launches, a deterministic two-stage sum over a
+ *        fixed number of partials (workspace >= 4096 floats), no atomics: identical bytes run to run;
+ *   bwd: dpred = (dloss[0] * 2 / (B chw) * w[t[b]]) * (pred - target), the target recomputed: one launch.
+ * 128-bit accesses when chw % 4 == 0 and the float pointers are 16-byte aligned, element by element otherwise, with the same
+ * values either way.
+ * afd_pred_to_eps: the network's output `out` at x_t -> eps, one launch; eps_out may be `out` (in place):
+ *   AFD_PRED_V: eps = (sa out) + (sb x_t);   AFD_PRED_X0: eps = (x_t - sa out) / sb;   AFD_PRED_EPS is AFD_EINVAL. */
+#define AFD_PRED_EPS 0
+#define AFD_PRED_V 1
+#define AFD_PRED_X0 2
+int afd_objective_loss_fwd(const float* pred, const float* x0, const float* eps, const int64_t* t, const float* alpha_hat,
+                           const float* w_or_null, int kind, float* loss_out, float* workspace, long B, long chw,
+                           afd_stream_t stream);
+int afd_objective_loss_bwd(const float* pred, const float* x0, const float* eps, const int64_t* t, const float* alpha_hat,
+                           const float* w_or_null, int kind, const float* dloss, float* dpred, long B, long chw,
+                           afd_stream_t stream);
+int afd_pred_to_eps(const float* out, const float* x_t, const int64_t* t, const float* alpha_hat, int kind, float* eps_out, long B,
+                    long chw, afd_stream_t stream);
 int afd_adamw_tick(float* state, float beta1, float beta2, afd_stream_t stream);
 int afd_adamw_step(float* p, const float* g, float* m, float* v, long n, const float* state,
                    float lr, float beta1, float beta2, float eps, float weight_decay, float grad_scale,
