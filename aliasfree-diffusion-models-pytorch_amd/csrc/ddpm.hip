@@ -806,6 +806,330 @@ __global__ __launch_bounds__(256) void pred_to_eps_k(const float* out, const flo
   }
 }
 
+// ---- learned reverse-process variances (Nichol & Dhariwal 2021): hybrid loss, ancestral step, bound ---------------------------
+// The network's output row b holds 2 chw floats: the prediction p (eps, v or x0) and, chw floats later, the coefficient v of
+//   logvar = ((v + 1) / 2) lb_t + (1 - (v + 1) / 2) lbt_t,      lb_t = log beta_t, lbt_t = log beta~_t
+// lv_coef: the (T, 3) fp64 table [lb_t, lbt_t, k_t] of Diffusion.lvar_coefficients, k_t = beta_t^2 / (alpha_t (1 - ah_t)).
+// Every per-element term and dL/dv is evaluated in fp64 from the fp32 inputs (in fp32, -1 + x + exp(-x) cancels), x + expm1(-x)
+// in place of -1 + x + exp(-x).  The device functions below are shared by the loss kernels and the bound kernel.
+__device__ __forceinline__ double lvar_logvar(double v, double lb, double lbt) {
+  const double f = (v + 1.0) / 2.0;
+  const double l = f * lb, r = (1.0 - f) * lbt;
+  return l + r;
+}
+// pred - target in fp64 from the fp32 inputs, sa = sqrt(a), sb = sqrt(1 - a) of the widened a = alpha_hat[t]
+__device__ __forceinline__ double lvar_diff(int kind, float p, float x0, float e, double sa, double sb) {
+  if (kind == AFD_PRED_V) {
+    const double l = sa * (double)e, r = sb * (double)x0;
+    return (double)p - (l - r);
+  }
+  return (double)p - (double)(kind == AFD_PRED_X0 ? x0 : e);
+}
+// (eps_hat - eps)^2 = f2 (pred - target)^2: f2 = 1 (eps), a (v), a / (1 - a) (x0)
+__device__ __forceinline__ double lvar_f2(int kind, double a) {
+  return kind == AFD_PRED_V ? a : (kind == AFD_PRED_X0 ? a / (1.0 - a) : 1.0);
+}
+// the output -> eps in fp32: pred_to_eps_k's expressions
+__device__ __forceinline__ float lvar_eps_hat(int kind, float p, float xt, float sa, float sb) {
+  if (kind == AFD_PRED_V) {
+    const float l = sa * p, r = sb * xt;
+    return l + r;
+  }
+  if (kind == AFD_PRED_X0) {
+    const float l = sa * p;
+    return (xt - l) / sb;
+  }
+  return p;
+}
+// KL(q(x_{t-1} | x_t, x0) || p_theta) per element, t >= 2, nats, with the mean's part in its d-form k_t d^2 exp(-logvar);
+// GRAD: dlv = d term / d logvar
+template <bool GRAD>
+__device__ __forceinline__ double lvar_kl(double d2, double v, double lb, double lbt, double kt, double& dlv) {
+  const double lv = lvar_logvar(v, lb, lbt);
+  const double x = lv - lbt;
+  const double em = expm1(-x);
+  const double q = (kt * d2) * exp(-lv);
+  if (GRAD) dlv = 0.5 * (-em - q);
+  return 0.5 * ((x + em) + q);
+}
+// d Phi / d z of approx_std_normal_cdf
+__device__ __forceinline__ double approx_std_normal_cdf_slope(double z) {
+  const double th = tanh(0.7978845608028654 * (z + 0.044715 * (z * z * z)));
+  return (0.5 * (1.0 - th * th)) * (0.7978845608028654 * (1.0 + (3.0 * 0.044715) * (z * z)));
+}
+// -decoder_log_prob(x, mean, exp(-logvar / 2)) with a per-element logvar; GRAD: dlv = d term / d logvar through the tanh
+// CDFs (z = exp(-logvar / 2) (c -+ 1/255), dz / dlogvar = -z / 2), zero where the 1e-12 clamp is active (as torch.clamp)
+template <bool GRAD>
+__device__ __forceinline__ double lvar_decoder(double x, double mean, double v, double lb, double lbt, double& dlv) {
+  const double inv_stdv = exp(-(lvar_logvar(v, lb, lbt) / 2.0));
+  const double c = x - mean;
+  const double zp = inv_stdv * (c + 1.0 / 255.0), zm = inv_stdv * (c - 1.0 / 255.0);
+  const double cp = approx_std_normal_cdf(zp), cm = approx_std_normal_cdf(zm);
+  const bool lo = x < -0.999, hi = x > 0.999;
+  const double P = lo ? cp : (hi ? 1.0 - cm : cp - cm);
+  if (GRAD) {
+    const double gp = hi ? 0.0 : approx_std_normal_cdf_slope(zp) * zp;
+    const double gm = lo ? 0.0 : approx_std_normal_cdf_slope(zm) * zm;
+    dlv = P >= 1e-12 ? (0.5 * (gp - gm)) / P : 0.0;
+  }
+  return -log(fmax(P, 1e-12));
+}
+// the bound's term of one element (GRAD: and d term / d logvar) and sq = (eps_hat - eps)^2; dec: the row is t = 1
+struct LvarRow {
+  double lb, lbt, kt, sa64, sb64, f2;
+  float sa, sb;            // noise_images_k's two roots
+  CfgCoef dec;             // denoise_step_k's coefficients at step 1
+  bool is_dec;
+};
+__device__ __forceinline__ LvarRow lvar_row(const double* __restrict__ lv_coef, const float* __restrict__ alpha,
+                                            const float* __restrict__ alpha_hat, const float* __restrict__ beta, long t, int kind) {
+  LvarRow w;
+  const float ah = alpha_hat[t];
+  w.sa = sqrtf(ah);
+  w.sb = sqrtf(1.0f - ah);
+  const double a = (double)ah;
+  w.sa64 = sqrt(a);
+  w.sb64 = sqrt(1.0 - a);
+  w.f2 = lvar_f2(kind, a);
+  w.lb = lv_coef[3 * t];
+  w.lbt = lv_coef[3 * t + 1];
+  w.kt = lv_coef[3 * t + 2];
+  w.is_dec = t == 1;
+  w.dec = cfg_coef(alpha, alpha_hat, beta, 1, 0.0f);
+  return w;
+}
+template <bool GRAD>
+__device__ __forceinline__ double lvar_term(const LvarRow& w, int kind, float p, float v, float x0, float e, float xt, double& sq,
+                                            double& dlv) {
+  const double df = lvar_diff(kind, p, x0, e, w.sa64, w.sb64);
+  sq = w.f2 * (df * df);
+  if (w.is_dec) {
+    const float mean = denoise_update(w.dec, xt, lvar_eps_hat(kind, p, xt, w.sa, w.sb), 0.0f, false);
+    return lvar_decoder<GRAD>((double)x0, (double)mean, (double)v, w.lb, w.lbt, dlv);
+  }
+  return lvar_kl<GRAD>(sq, (double)v, w.lb, w.lbt, w.kt, dlv);
+}
+__device__ __forceinline__ float noised(float sa, float sb, float x0, float e) {      // noise_images_k's expression
+  const float l = sa * x0, r = sb * e;
+  return l + r;
+}
+
+// Work items as objective_partial_k.  part_s[blockIdx.x]: objective_partial_k's sum over the p half (L_simple, bit for bit);
+// part_v[blockIdx.x]: the fp64 sum of the bound's terms, per thread in item and element order, then the workgroup's fixed tree.
+template <bool VEC>
+__global__ __launch_bounds__(256) void lvar_partial_k(const float* __restrict__ out2, const float* __restrict__ x0,
+                                                      const float* __restrict__ eps, const int64_t* __restrict__ t,
+                                                      const float* __restrict__ alpha, const float* __restrict__ alpha_hat,
+                                                      const float* __restrict__ beta, const double* __restrict__ lv_coef,
+                                                      const float* __restrict__ w, int kind, float* __restrict__ part_s,
+                                                      double* __restrict__ part_v, long items, long segs, long chw) {
+  __shared__ float red[16];
+  __shared__ double red2[8];
+  float s = 0.f;
+  double sv = 0.0, unused = 0.0;
+  for (long it = blockIdx.x; it < items; it += gridDim.x) {
+    const long b = it / segs, q = (it - b * segs) * 256 + threadIdx.x;
+    const long tb = t[b], left = chw - 4 * q, o = b * chw + 4 * q, op = 2 * b * chw + 4 * q;
+    const LvarRow row = lvar_row(lv_coef, alpha, alpha_hat, beta, tb, kind);
+    const float wb = w ? w[tb] : 1.0f;
+    if (left <= 0) continue;
+    const float4 p = load_quad<VEC>(out2, op, left), v = load_quad<VEC>(out2, op + chw, left);
+    const float4 x = load_quad<VEC>(x0, o, left), e = load_quad<VEC>(eps, o, left);
+    const float dx = objective_diff(kind, p.x, x.x, e.x, row.sa, row.sb), dy = objective_diff(kind, p.y, x.y, e.y, row.sa, row.sb);
+    const float dz = objective_diff(kind, p.z, x.z, e.z, row.sa, row.sb), dw = objective_diff(kind, p.w, x.w, e.w, row.sa, row.sb);
+    float r = dx * dx;
+    if (left > 1) r += dy * dy;
+    if (left > 2) r += dz * dz;
+    if (left > 3) r += dw * dw;
+    s += wb * r;
+    const float pv[4] = {p.x, p.y, p.z, p.w}, vv[4] = {v.x, v.y, v.z, v.w}, xv[4] = {x.x, x.y, x.z, x.w}, ev[4] = {e.x, e.y, e.z, e.w};
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      if (i < left) {
+        double sq, dlv;
+        sv += lvar_term<false>(row, kind, pv[i], vv[i], xv[i], ev[i], noised(row.sa, row.sb, xv[i], ev[i]), sq, dlv);
+      }
+    }
+  }
+  s = block_sum(s, red);
+  block_sum2_f64(sv, unused, red2);
+  if (threadIdx.x == 0) {
+    part_s[blockIdx.x] = s;
+    part_v[blockIdx.x] = sv;
+  }
+}
+// loss_out = {L, L_vlb} in fp32, sums_out (optional) the same two in fp64:
+//   L_simple = mse_final_k's value, L_vlb = sum / (N ln 2), L = L_simple + vlb_scale L_vlb
+__global__ __launch_bounds__(256) void lvar_final_k(const float* __restrict__ part_s, const double* __restrict__ part_v, int nparts,
+                                                    float inv_n, double n_ln2, double vlb_scale, float* __restrict__ loss_out,
+                                                    double* __restrict__ sums_out) {
+  __shared__ float red[16];
+  __shared__ double red2[8];
+  float s = 0.f;
+  double sv = 0.0, unused = 0.0;
+  for (int i = threadIdx.x; i < nparts; i += blockDim.x) {
+    s += part_s[i];
+    sv += part_v[i];
+  }
+  s = block_sum(s, red);
+  block_sum2_f64(sv, unused, red2);
+  if (threadIdx.x == 0) {
+    const double ls = (double)(s * inv_n), lv = sv / n_ln2, l = ls + vlb_scale * lv;
+    loss_out[0] = (float)l;
+    loss_out[1] = (float)lv;
+    if (sums_out) {
+      sums_out[0] = l;
+      sums_out[1] = lv;
+    }
+  }
+}
+// dout2: the p half is objective_bwd_k's dpred (L_simple alone: the mean is stopped in L_vlb); the v half is
+// (float)(dloss gv (d term / d logvar) (lb - lbt) / 2), gv = vlb_scale / (N ln 2), in fp64 and rounded once
+template <bool VEC>
+__global__ __launch_bounds__(256) void lvar_bwd_k(const float* __restrict__ out2, const float* __restrict__ x0,
+                                                  const float* __restrict__ eps, const int64_t* __restrict__ t,
+                                                  const float* __restrict__ alpha, const float* __restrict__ alpha_hat,
+                                                  const float* __restrict__ beta, const double* __restrict__ lv_coef,
+                                                  const float* __restrict__ w, int kind, const float* __restrict__ dloss,
+                                                  float* __restrict__ dout2, long items, long segs, long chw, float two_over_n,
+                                                  double gv) {
+  const float g0 = dloss[0] * two_over_n;
+  const double gd = (double)dloss[0] * gv;
+  for (long it = blockIdx.x; it < items; it += gridDim.x) {
+    const long b = it / segs, q = (it - b * segs) * 256 + threadIdx.x;
+    const long tb = t[b], left = chw - 4 * q, o = b * chw + 4 * q, op = 2 * b * chw + 4 * q;
+    const LvarRow row = lvar_row(lv_coef, alpha, alpha_hat, beta, tb, kind);
+    const float g = w ? g0 * w[tb] : g0;
+    const double gl = gd * ((row.lb - row.lbt) / 2.0);
+    if (left <= 0) continue;
+    const float4 p = load_quad<VEC>(out2, op, left), v = load_quad<VEC>(out2, op + chw, left);
+    const float4 x = load_quad<VEC>(x0, o, left), e = load_quad<VEC>(eps, o, left);
+    float4 d;
+    d.x = objective_diff(kind, p.x, x.x, e.x, row.sa, row.sb) * g;
+    d.y = objective_diff(kind, p.y, x.y, e.y, row.sa, row.sb) * g;
+    d.z = objective_diff(kind, p.z, x.z, e.z, row.sa, row.sb) * g;
+    d.w = objective_diff(kind, p.w, x.w, e.w, row.sa, row.sb) * g;
+    store_quad<VEC>(dout2, op, left, d);
+    const float pv[4] = {p.x, p.y, p.z, p.w}, vv[4] = {v.x, v.y, v.z, v.w}, xv[4] = {x.x, x.y, x.z, x.w}, ev[4] = {e.x, e.y, e.z, e.w};
+    float dv[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      if (i < left) {
+        double sq, dlv;
+        lvar_term<true>(row, kind, pv[i], vv[i], xv[i], ev[i], noised(row.sa, row.sb, xv[i], ev[i]), sq, dlv);
+        dv[i] = (float)(gl * dlv);
+      }
+    }
+    store_quad<VEC>(dout2, op + chw, left, make_float4(dv[0], dv[1], dv[2], dv[3]));
+  }
+}
+
+// out2 (B rows of 2 chw) -> eps_out (B x chw; pred_to_eps_k's conversion, a copy for AFD_PRED_EPS) and, optionally, the v half
+template <bool VEC>
+__global__ __launch_bounds__(256) void split_pred_k(const float* __restrict__ out2, const float* __restrict__ xt,
+                                                    const int64_t* __restrict__ t, const float* __restrict__ alpha_hat, int kind,
+                                                    float* __restrict__ eps_out, float* __restrict__ v_out, long items, long segs,
+                                                    long chw) {
+  for (long it = blockIdx.x; it < items; it += gridDim.x) {
+    const long b = it / segs, q = (it - b * segs) * 256 + threadIdx.x;
+    const long left = chw - 4 * q, o = b * chw + 4 * q, op = 2 * b * chw + 4 * q;
+    const float ah = kind != AFD_PRED_EPS ? alpha_hat[t[b]] : 0.0f;
+    const float sa = sqrtf(ah), sb = sqrtf(1.0f - ah);
+    if (left <= 0) continue;
+    const float4 p = load_quad<VEC>(out2, op, left);
+    float4 r = p;
+    if (kind != AFD_PRED_EPS) {
+      const float4 x = load_quad<VEC>(xt, o, left);
+      r.x = lvar_eps_hat(kind, p.x, x.x, sa, sb);
+      r.y = lvar_eps_hat(kind, p.y, x.y, sa, sb);
+      r.z = lvar_eps_hat(kind, p.z, x.z, sa, sb);
+      r.w = lvar_eps_hat(kind, p.w, x.w, sa, sb);
+    }
+    store_quad<VEC>(eps_out, o, left, r);
+    if (v_out) store_quad<VEC>(v_out, o, left, load_quad<VEC>(out2, op + chw, left));
+  }
+}
+
+// Ancestral step with the learned variance: eps_hat from p (pred_to_eps_k's expression at x, per step), guided (kCfg: out2 holds
+// 2 B rows, conditional then unconditional; cfg_lerp of the two eps; the variance from the conditional row), then
+//   x_out = c1 (x - c2 eps_hat) + (float)exp(logvar / 2) noise,  denoise_step_k's mean; no noise at step 1 or with noise NULL.
+// x_out may be x itself (each thread reads its quad before it writes it); x_out2 (optional) receives the same values.
+__device__ __forceinline__ float lvar_update(const CfgCoef& k, float x, float e, float v, float z, double lb, double lbt, bool has_noise) {
+  const float pe = k.c2 * e;
+  const float inner = x - pe;
+  const float lhs = k.c1 * inner;
+  if (!has_noise) return lhs + 0.0f;
+  const float sd = (float)exp(lvar_logvar((double)v, lb, lbt) / 2.0);
+  return lhs + sd * z;
+}
+template <bool kCfg, bool VEC>
+__global__ __launch_bounds__(256) void lvar_step_k(const float* x, const float* __restrict__ out2, const float* __restrict__ noise,
+                                                   const float* __restrict__ alpha, const float* __restrict__ alpha_hat,
+                                                   const float* __restrict__ beta, const double* __restrict__ lv_coef, int kind,
+                                                   int step_arg, const int64_t* __restrict__ step_dev, float s, float* x_out,
+                                                   float* x_out2, long items, long segs, long chw, long B) {
+  const int step = step_dev ? (int)step_dev[0] : step_arg;
+  const CfgCoef k = cfg_coef(alpha, alpha_hat, beta, step, s);
+  const float ah = alpha_hat[step];
+  const float sa = sqrtf(ah), sb = sqrtf(1.0f - ah);
+  const double lb = lv_coef[3 * (long)step], lbt = lv_coef[3 * (long)step + 1];
+  const bool has_noise = noise != nullptr && step > 1;
+  const float4 zero = make_float4(0.f, 0.f, 0.f, 0.f);
+  for (long it = blockIdx.x; it < items; it += gridDim.x) {
+    const long b = it / segs, q = (it - b * segs) * 256 + threadIdx.x;
+    const long left = chw - 4 * q, o = b * chw + 4 * q, op = 2 * b * chw + 4 * q;
+    if (left <= 0) continue;
+    const float4 xv = load_quad<VEC>(x, o, left), c = load_quad<VEC>(out2, op, left), v = load_quad<VEC>(out2, op + chw, left);
+    const float4 u = kCfg ? load_quad<VEC>(out2, op + 2 * B * chw, left) : c;
+    const float4 z = has_noise ? load_quad<VEC>(noise, o, left) : zero;
+    float4 r;
+    r.x = lvar_update(k, xv.x, denoise_eps<kCfg>(k, lvar_eps_hat(kind, c.x, xv.x, sa, sb), lvar_eps_hat(kind, u.x, xv.x, sa, sb)), v.x, z.x, lb, lbt, has_noise);
+    r.y = lvar_update(k, xv.y, denoise_eps<kCfg>(k, lvar_eps_hat(kind, c.y, xv.y, sa, sb), lvar_eps_hat(kind, u.y, xv.y, sa, sb)), v.y, z.y, lb, lbt, has_noise);
+    r.z = lvar_update(k, xv.z, denoise_eps<kCfg>(k, lvar_eps_hat(kind, c.z, xv.z, sa, sb), lvar_eps_hat(kind, u.z, xv.z, sa, sb)), v.z, z.z, lb, lbt, has_noise);
+    r.w = lvar_update(k, xv.w, denoise_eps<kCfg>(k, lvar_eps_hat(kind, c.w, xv.w, sa, sb), lvar_eps_hat(kind, u.w, xv.w, sa, sb)), v.w, z.w, lb, lbt, has_noise);
+    store_quad<VEC>(x_out, o, left, r);
+    if (x_out2) store_quad<VEC>(x_out2, o, left, r);
+  }
+}
+
+// vlb_terms_k with the per-element variance: one workgroup per row r = (img[r], t[r]); out2: rows of 2 per floats.
+//   sq[r] = sum_j (eps_hat_j - eps_j)^2 (d-form),  term[r] = sum_j lvar_term: the KL terms (t >= 2) or the decoder's (t == 1)
+// x_t is what afd_noise_images_gather wrote.  Each thread sums its quads in index order, x, y, z, w within one.
+template <bool VEC>
+__global__ __launch_bounds__(256) void vlb_terms_lvar_k(const float* __restrict__ x0, const int64_t* __restrict__ img,
+                                                        const float* __restrict__ xt, const float* __restrict__ eps,
+                                                        const float* __restrict__ out2, const int64_t* __restrict__ t,
+                                                        const double* __restrict__ lv_coef, const float* __restrict__ alpha,
+                                                        const float* __restrict__ alpha_hat, const float* __restrict__ beta, int kind,
+                                                        double* __restrict__ term, double* __restrict__ sq, long per) {
+  __shared__ double red[8];
+  const long r = blockIdx.x;
+  const LvarRow row = lvar_row(lv_coef, alpha, alpha_hat, beta, t[r], kind);
+  const long src = img[r] * per, dst = r * per, rp = 2 * r * per;
+  double s_t = 0.0, s_sq = 0.0;
+  for (long q = threadIdx.x; 4 * q < per; q += blockDim.x) {
+    const long left = per - 4 * q;
+    const float4 p = load_quad<VEC>(out2, rp + 4 * q, left), v = load_quad<VEC>(out2, rp + per + 4 * q, left);
+    const float4 x = load_quad<VEC>(x0, src + 4 * q, left), e = load_quad<VEC>(eps, dst + 4 * q, left);
+    const float4 n = row.is_dec ? load_quad<VEC>(xt, dst + 4 * q, left) : x;
+    const float pv[4] = {p.x, p.y, p.z, p.w}, vv[4] = {v.x, v.y, v.z, v.w}, xv[4] = {x.x, x.y, x.z, x.w}, ev[4] = {e.x, e.y, e.z, e.w};
+    const float nv[4] = {n.x, n.y, n.z, n.w};
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      if (i < left) {
+        double d2, dlv;
+        s_t += lvar_term<false>(row, kind, pv[i], vv[i], xv[i], ev[i], nv[i], d2, dlv);
+        s_sq += d2;
+      }
+    }
+  }
+  block_sum2_f64(s_t, s_sq, red);
+  if (threadIdx.x == 0) {
+    term[r] = s_t;
+    sq[r] = s_sq;
+  }
+}
+
 // ---- AdamW (torch.optim.AdamW semantics, decoupled weight decay) ---------------------------
 __global__ void adamw_tick_k(float* state, float b1, float b2) {
   // state = {step, 1 - b1^step, 1 - b2^step, unused}; double keeps the powers exact enough for 1e6 steps
@@ -1413,6 +1737,169 @@ int afd_pred_to_eps(const float* out, const float* x_t, const int64_t* t, const 
     hipLaunchKernelGGL(pred_to_eps_k<false>, dim3(obj_grid(items)), dim3(256), 0, as_stream(st), out, x_t, t, alpha_hat, kind, eps_out,
                        items, segs, chw);
   return check_launch("afd_pred_to_eps");
+}
+
+// ---- learned variances ----------------------------------------------------------------------------------------------------
+// whether the n_out outputs share no memory with each other or with any of the n_in inputs (NULL entries are skipped)
+static inline bool all_apart(const void* const* out, const long* out_b, int n_out, const void* const* in, const long* in_b, int n_in) {
+  for (int i = 0; i < n_out; ++i) {
+    if (!out[i]) continue;
+    for (int j = i + 1; j < n_out; ++j)
+      if (overlaps(out[i], out_b[i], out[j], out_b[j])) return false;
+    for (int j = 0; j < n_in; ++j)
+      if (overlaps(out[i], out_b[i], in[j], in_b[j])) return false;
+  }
+  return true;
+}
+constexpr long kLvarWsFloats = 3 * kObjBlocks;      // kObjBlocks fp32 partials, then kObjBlocks fp64 partials
+
+int afd_lvar_loss_fwd(const float* out2, const float* x0, const float* eps, const int64_t* t, const float* alpha,
+                      const float* alpha_hat, const float* beta, const double* lv_coef, const float* w, int kind, double vlb_scale,
+                      float* loss_out, double* sums_out, float* workspace, long B, long chw, afd_stream_t st) {
+  AFD_REQUIRE(out2 && x0 && eps && t && alpha && alpha_hat && beta && lv_coef && loss_out && workspace,
+              "afd_lvar_loss_fwd: out2, x0, eps, t, alpha, alpha_hat, beta, lv_coef, loss_out and workspace must not be NULL");
+  AFD_REQUIRE(kind_ok(kind), "afd_lvar_loss_fwd: kind must be AFD_PRED_EPS, AFD_PRED_V or AFD_PRED_X0 (got %d)", kind);
+  AFD_REQUIRE(B > 0 && chw > 0, "afd_lvar_loss_fwd: B and chw must be positive (got %ld, %ld)", B, chw);
+  AFD_REQUIRE(std::isfinite(vlb_scale) && vlb_scale >= 0.0, "afd_lvar_loss_fwd: vlb_scale must be finite and >= 0 (got %g)", vlb_scale);
+  AFD_REQUIRE(((uintptr_t)workspace & 7) == 0, "afd_lvar_loss_fwd: workspace must be 8-byte aligned");
+  const long fb = B * chw * (long)sizeof(float);
+  const void* out[] = {loss_out, sums_out, workspace};
+  const long out_b[] = {2 * (long)sizeof(float), 2 * (long)sizeof(double), kLvarWsFloats * (long)sizeof(float)};
+  const void* in[] = {out2, x0, eps, t};
+  const long in_b[] = {2 * fb, fb, fb, B * (long)sizeof(int64_t)};
+  AFD_REQUIRE(all_apart(out, out_b, 3, in, in_b, 4), "afd_lvar_loss_fwd: loss_out, sums_out and workspace must not overlap each other or an input");
+  const long segs = obj_segs(chw), items = B * segs;
+  const int nb = obj_grid(items);
+  double* part_v = reinterpret_cast<double*>(workspace + kObjBlocks);
+  const double n = (double)B * (double)chw;
+  if (chw % 4 == 0 && aligned16(out2) && aligned16(x0) && aligned16(eps))
+    hipLaunchKernelGGL(lvar_partial_k<true>, dim3(nb), dim3(256), 0, as_stream(st), out2, x0, eps, t, alpha, alpha_hat, beta, lv_coef, w,
+                       kind, workspace, part_v, items, segs, chw);
+  else
+    hipLaunchKernelGGL(lvar_partial_k<false>, dim3(nb), dim3(256), 0, as_stream(st), out2, x0, eps, t, alpha, alpha_hat, beta, lv_coef, w,
+                       kind, workspace, part_v, items, segs, chw);
+  hipLaunchKernelGGL(lvar_final_k, dim3(1), dim3(256), 0, as_stream(st), workspace, part_v, nb, 1.0f / (float)(B * chw),
+                     n * 0.6931471805599453, vlb_scale, loss_out, sums_out);
+  return check_launch("afd_lvar_loss_fwd");
+}
+int afd_lvar_loss_bwd(const float* out2, const float* x0, const float* eps, const int64_t* t, const float* alpha,
+                      const float* alpha_hat, const float* beta, const double* lv_coef, const float* w, int kind, double vlb_scale,
+                      const float* dloss, float* dout2, long B, long chw, afd_stream_t st) {
+  AFD_REQUIRE(out2 && x0 && eps && t && alpha && alpha_hat && beta && lv_coef && dloss && dout2,
+              "afd_lvar_loss_bwd: out2, x0, eps, t, alpha, alpha_hat, beta, lv_coef, dloss and dout2 must not be NULL");
+  AFD_REQUIRE(kind_ok(kind), "afd_lvar_loss_bwd: kind must be AFD_PRED_EPS, AFD_PRED_V or AFD_PRED_X0 (got %d)", kind);
+  AFD_REQUIRE(B > 0 && chw > 0, "afd_lvar_loss_bwd: B and chw must be positive (got %ld, %ld)", B, chw);
+  AFD_REQUIRE(std::isfinite(vlb_scale) && vlb_scale >= 0.0, "afd_lvar_loss_bwd: vlb_scale must be finite and >= 0 (got %g)", vlb_scale);
+  const long fb = B * chw * (long)sizeof(float);
+  const void* out[] = {dout2};
+  const long out_b[] = {2 * fb};
+  const void* in[] = {out2, x0, eps, t, dloss};
+  const long in_b[] = {2 * fb, fb, fb, B * (long)sizeof(int64_t), (long)sizeof(float)};
+  AFD_REQUIRE(all_apart(out, out_b, 1, in, in_b, 5), "afd_lvar_loss_bwd: dout2 must not overlap an input");
+  const long segs = obj_segs(chw), items = B * segs;
+  const double n = (double)B * (double)chw;
+  const float two_over_n = 2.0f / (float)(B * chw);
+  const double gv = vlb_scale / (n * 0.6931471805599453);
+  if (chw % 4 == 0 && aligned16(out2) && aligned16(x0) && aligned16(eps) && aligned16(dout2))
+    hipLaunchKernelGGL(lvar_bwd_k<true>, dim3(obj_grid(items)), dim3(256), 0, as_stream(st), out2, x0, eps, t, alpha, alpha_hat, beta,
+                       lv_coef, w, kind, dloss, dout2, items, segs, chw, two_over_n, gv);
+  else
+    hipLaunchKernelGGL(lvar_bwd_k<false>, dim3(obj_grid(items)), dim3(256), 0, as_stream(st), out2, x0, eps, t, alpha, alpha_hat, beta,
+                       lv_coef, w, kind, dloss, dout2, items, segs, chw, two_over_n, gv);
+  return check_launch("afd_lvar_loss_bwd");
+}
+int afd_split_pred(const float* out2, const float* x_t, const int64_t* t, const float* alpha_hat, int kind, float* eps_out,
+                   float* v_out, long B, long chw, afd_stream_t st) {
+  AFD_REQUIRE(out2 && eps_out, "afd_split_pred: out2 and eps_out must not be NULL");
+  AFD_REQUIRE(kind_ok(kind), "afd_split_pred: kind must be AFD_PRED_EPS, AFD_PRED_V or AFD_PRED_X0 (got %d)", kind);
+  AFD_REQUIRE(kind == AFD_PRED_EPS || (x_t && t && alpha_hat), "afd_split_pred: x_t, t and alpha_hat must not be NULL for AFD_PRED_V / AFD_PRED_X0");
+  AFD_REQUIRE(B > 0 && chw > 0, "afd_split_pred: B and chw must be positive (got %ld, %ld)", B, chw);
+  const long fb = B * chw * (long)sizeof(float);
+  const void* out[] = {eps_out, v_out};
+  const long out_b[] = {fb, fb};
+  const void* in[] = {out2, x_t, t};
+  const long in_b[] = {2 * fb, fb, B * (long)sizeof(int64_t)};
+  AFD_REQUIRE(all_apart(out, out_b, 2, in, in_b, 3), "afd_split_pred: eps_out and v_out must not overlap each other, out2, x_t or t");
+  const long segs = obj_segs(chw), items = B * segs;
+  if (chw % 4 == 0 && aligned16(out2) && aligned16(eps_out) && (!x_t || aligned16(x_t)) && (!v_out || aligned16(v_out)))
+    hipLaunchKernelGGL(split_pred_k<true>, dim3(obj_grid(items)), dim3(256), 0, as_stream(st), out2, x_t, t, alpha_hat, kind, eps_out,
+                       v_out, items, segs, chw);
+  else
+    hipLaunchKernelGGL(split_pred_k<false>, dim3(obj_grid(items)), dim3(256), 0, as_stream(st), out2, x_t, t, alpha_hat, kind, eps_out,
+                       v_out, items, segs, chw);
+  return check_launch("afd_split_pred");
+}
+
+// x_out may be x itself, and must otherwise share no memory with x; x_out and x_out2 share none with each other or any other input
+static int launch_lvar_step(bool kCfg, const char* name, const float* x, const float* out2, const float* noise, const float* alpha,
+                            const float* alpha_hat, const float* beta, const double* lv_coef, int kind, int i, const int64_t* t_dev,
+                            bool dev, float s, float* x_out, float* x_out2, long B, long chw, hipStream_t st) {
+  AFD_REQUIRE(x && out2 && alpha && alpha_hat && beta && lv_coef && x_out && (!dev || t_dev),
+              "%s: x, out2, alpha, alpha_hat, beta, lv_coef%s and x_out must not be NULL", name, dev ? ", t_dev" : "");
+  AFD_REQUIRE(kind_ok(kind), "%s: kind must be AFD_PRED_EPS, AFD_PRED_V or AFD_PRED_X0 (got %d)", name, kind);
+  AFD_REQUIRE(B > 0 && chw > 0, "%s: B and chw must be positive (got %ld, %ld)", name, B, chw);
+  AFD_REQUIRE(dev || i >= 1, "%s: need i >= 1 (the step i -> i - 1; got i = %d)", name, i);
+  const long fb = B * chw * (long)sizeof(float);
+  const void* out[] = {x_out, x_out2};
+  const long out_b[] = {fb, fb};
+  const void* in[] = {out2, noise, t_dev, x_out == x ? nullptr : x};
+  const long in_b[] = {(kCfg ? 4 : 2) * fb, fb, (long)sizeof(int64_t), fb};
+  AFD_REQUIRE(all_apart(out, out_b, 2, in, in_b, 4) && !(x_out2 && overlaps(x_out2, fb, x, fb)),
+              "%s: x_out must be x itself or apart from it, and x_out / x_out2 must not overlap each other, out2, noise or t_dev", name);
+  const long segs = obj_segs(chw), items = B * segs;
+  const bool vec = chw % 4 == 0 && aligned16(x) && aligned16(out2) && aligned16(x_out) && (!noise || aligned16(noise)) &&
+                   (!x_out2 || aligned16(x_out2));
+  auto kern = kCfg ? (vec ? lvar_step_k<true, true> : lvar_step_k<true, false>) : (vec ? lvar_step_k<false, true> : lvar_step_k<false, false>);
+  hipLaunchKernelGGL(kern, dim3(obj_grid(items)), dim3(256), 0, st, x, out2, noise, alpha, alpha_hat, beta, lv_coef, kind, i, t_dev, s,
+                     x_out, x_out2, items, segs, chw, B);
+  return check_launch(name);
+}
+int afd_denoise_step_lvar(const float* x, const float* out2, const float* noise, const float* alpha, const float* alpha_hat,
+                          const float* beta, const double* lv_coef, int kind, int i, float* x_out, long B, long chw, afd_stream_t st) {
+  return launch_lvar_step(false, "afd_denoise_step_lvar", x, out2, noise, alpha, alpha_hat, beta, lv_coef, kind, i, nullptr, false, 0.0f,
+                                 x_out, nullptr, B, chw, as_stream(st));
+}
+int afd_denoise_step_lvar_dev(const float* x, const float* out2, const float* noise, const float* alpha, const float* alpha_hat,
+                              const float* beta, const double* lv_coef, int kind, const int64_t* t_dev, float* x_out, long B, long chw,
+                              afd_stream_t st) {
+  return launch_lvar_step(false, "afd_denoise_step_lvar_dev", x, out2, noise, alpha, alpha_hat, beta, lv_coef, kind, 0, t_dev, true, 0.0f,
+                                 x_out, nullptr, B, chw, as_stream(st));
+}
+int afd_denoise_step_lvar_cfg(const float* x, const float* out2, const float* noise, const float* alpha, const float* alpha_hat,
+                              const float* beta, const double* lv_coef, int kind, int i, float cfg_scale, float* x_out, float* x_out2,
+                              long B, long chw, afd_stream_t st) {
+  return launch_lvar_step(true, "afd_denoise_step_lvar_cfg", x, out2, noise, alpha, alpha_hat, beta, lv_coef, kind, i, nullptr, false,
+                                cfg_scale, x_out, x_out2, B, chw, as_stream(st));
+}
+int afd_denoise_step_lvar_cfg_dev(const float* x, const float* out2, const float* noise, const float* alpha, const float* alpha_hat,
+                                  const float* beta, const double* lv_coef, int kind, const int64_t* t_dev, float cfg_scale, float* x_out,
+                                  float* x_out2, long B, long chw, afd_stream_t st) {
+  return launch_lvar_step(true, "afd_denoise_step_lvar_cfg_dev", x, out2, noise, alpha, alpha_hat, beta, lv_coef, kind, 0, t_dev, true,
+                                cfg_scale, x_out, x_out2, B, chw, as_stream(st));
+}
+int afd_vlb_terms_lvar(const float* x0, long n_img, const int64_t* img, const float* x_t, const float* eps, const float* out2,
+                       const int64_t* t, const double* lv_coef, long T, const float* alpha, const float* alpha_hat, const float* beta,
+                       int kind, double* term, double* sq, long rows, long per, afd_stream_t st) {
+  AFD_REQUIRE(x0 && img && x_t && eps && out2 && t && lv_coef && alpha && alpha_hat && beta && term && sq,
+              "afd_vlb_terms_lvar: no pointer may be NULL");
+  AFD_REQUIRE(kind_ok(kind), "afd_vlb_terms_lvar: kind must be AFD_PRED_EPS, AFD_PRED_V or AFD_PRED_X0 (got %d)", kind);
+  AFD_REQUIRE(n_img > 0 && rows > 0 && per > 0 && T >= 2,
+              "afd_vlb_terms_lvar: n_img, rows and per must be positive and T >= 2 (got %ld, %ld, %ld, %ld)", n_img, rows, per, T);
+  AFD_REQUIRE(rows <= 0x7fffffffL, "afd_vlb_terms_lvar: at most 2^31 - 1 rows per call (got %ld)", rows);
+  const long db = rows * (long)sizeof(double), fb = rows * per * (long)sizeof(float), ib = rows * (long)sizeof(int64_t);
+  const long tb = T * (long)sizeof(float);
+  const void* out[] = {term, sq};
+  const long out_b[] = {db, db};
+  const void* in[] = {x0, img, x_t, eps, out2, t, lv_coef, alpha, alpha_hat, beta};
+  const long in_b[] = {n_img * per * (long)sizeof(float), ib, fb, fb, 2 * fb, ib, 3 * T * (long)sizeof(double), tb, tb, tb};
+  AFD_REQUIRE(all_apart(out, out_b, 2, in, in_b, 10), "afd_vlb_terms_lvar: term and sq must not overlap each other or any input");
+  if (per % 4 == 0 && aligned16(x0) && aligned16(x_t) && aligned16(eps) && aligned16(out2))
+    hipLaunchKernelGGL(vlb_terms_lvar_k<true>, dim3((unsigned)rows), dim3(256), 0, as_stream(st), x0, img, x_t, eps, out2, t, lv_coef,
+                       alpha, alpha_hat, beta, kind, term, sq, per);
+  else
+    hipLaunchKernelGGL(vlb_terms_lvar_k<false>, dim3((unsigned)rows), dim3(256), 0, as_stream(st), x0, img, x_t, eps, out2, t, lv_coef,
+                       alpha, alpha_hat, beta, kind, term, sq, per);
+  return check_launch("afd_vlb_terms_lvar");
 }
 int afd_adamw_tick(float* state, float b1, float b2, afd_stream_t st) {
   AFD_REQUIRE(state, "afd_adamw_tick: state is NULL");

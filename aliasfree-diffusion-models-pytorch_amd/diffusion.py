@@ -43,12 +43,22 @@ class Diffusion:
     SCHEDULES = ("linear", "cosine")
     PREDICTIONS = ("eps", "v", "x0")
     LOSS_WEIGHTINGS = ("min_snr",)
+    VARIANCES = ("fixed", "learned")
 
     def __init__(self, noise_steps=1000, beta_start=1e-4, beta_end=0.02, img_size=256, device="cuda", schedule="linear",
-                 cosine_s=0.008, prediction="eps"):
+                 cosine_s=0.008, prediction="eps", variance="fixed"):
         """schedule: "linear" (the reference's beta schedule) or "cosine" (Nichol & Dhariwal 2021, offset cosine_s).
         prediction: what the network's output means -- "eps", "v" = sqrt(a_t) eps - sqrt(1 - a_t) x0 (Salimans & Ho 2022) or "x0".
-        Every sampler and evaluation turns the output into eps with `predict_eps`; `TrainStep` trains towards `training_target`."""
+        Every sampler and evaluation turns the output into eps with `predict_eps`; `TrainStep` trains towards `training_target`.
+        variance: "fixed" (beta_t, the reference's) or "learned" (Nichol & Dhariwal 2021): the network is UNet(c_in=C, c_out=2 C),
+        its first C output channels are the prediction and the next C the coefficient v of
+        log sigma^2 = ((v + 1) / 2) log beta_t + (1 - (v + 1) / 2) log beta~_t per pixel (`lvar_coefficients`).  The DDPM chain
+        (`sample`, `revert`, `sample_sharded`, guided or not, eager or graph=True) then draws with that variance,
+        `calc_bpd(sigma="learned")` scores it and `TrainStep` trains it with the hybrid loss.  Everything that goes through
+        `predict_eps` -- DDIM, DPM-Solver++(2M), `inpaint`, `equivariance`, the sweeps, `sample_shift` and `sample_concurrent` --
+        reads the prediction half alone and keeps its own variance."""
+        if not isinstance(variance, str) or variance not in self.VARIANCES:
+            raise ValueError(f"Diffusion: unknown variance {variance!r} ('fixed' or 'learned')")
         if not isinstance(schedule, str) or schedule not in self.SCHEDULES:
             raise ValueError(f"Diffusion: unknown schedule {schedule!r} ('linear' or 'cosine')")
         if not isinstance(prediction, str) or prediction not in self.PREDICTIONS:
@@ -59,6 +69,8 @@ class Diffusion:
         self.noise_steps, self.beta_start, self.beta_end = noise_steps, beta_start, beta_end
         self.img_size, self.device = img_size, device
         self.schedule, self.cosine_s, self.prediction = schedule, float(cosine_s), prediction
+        self.variance = variance
+        self._lv_dev = None
         beta = self.prepare_noise_schedule()                    # host fp32
         alpha = 1.0 - beta
         alpha_hat = torch.cumprod(alpha, dim=0)                 # host ATen cumprod, as the reference (:309): accumulates in double, rounds to fp32
@@ -92,11 +104,71 @@ class Diffusion:
         sa, sb = self._sqrt_tables(t, x0)
         return sa * eps - sb * x0
 
+    # Learned reverse-process variances (Nichol & Dhariwal 2021) ------------------------------------------------------------------
+    def lvar_coefficients(self):
+        """(T, 3) fp64 host table [lb_t, lbt_t, k_t] of the learned variance, from the fp32 schedule tables widened to fp64; row 0
+        is zeros.  For 1 <= t < T: lb_t = log(beta[t]); lbt_t = log(beta~_t), beta~_t = (1 - ah[t-1]) / (1 - ah[t]) * beta[t]
+        (positive for every t >= 1 under this indexing, so nothing is clipped; lbt_t < lb_t); k_t = beta[t]^2 / (alpha[t] (1 - ah[t])),
+        the KL term's weight of (eps_hat - eps)^2 exp(-logvar)."""
+        T = self.noise_steps
+        if T < 2:
+            raise ValueError(f"Diffusion.lvar_coefficients: needs noise_steps >= 2 (got {T})")
+        b = self.beta.detach().cpu().double().numpy()
+        a = self.alpha.detach().cpu().double().numpy()
+        om = 1.0 - self.alpha_hat.detach().cpu().double().numpy()
+        tab = np.zeros((T, 3), dtype=np.float64)
+        for t in range(1, T):
+            tab[t, 0] = math.log(b[t])
+            tab[t, 1] = math.log(om[t - 1] / om[t] * b[t])
+            tab[t, 2] = b[t] * b[t] / (a[t] * om[t])
+        return torch.from_numpy(tab)
+
+    def _lv(self):
+        """`lvar_coefficients` on the device, built once."""
+        if self._lv_dev is None:
+            self._lv_dev = self.lvar_coefficients().to(self.device).contiguous()
+        return self._lv_dev
+
+    def output_channels(self, image_channels):
+        """The channels the network must emit for C = image_channels: C, or 2 C with variance="learned"."""
+        return 2 * image_channels if self.variance == "learned" else image_channels
+
+    def check_model(self, model, image_channels=None, where="Diffusion"):
+        """ValueError when the model's output layer (`model.outc`) does not emit `output_channels` channels.  image_channels
+        defaults to the model's input channels; a model without `outc` / `inc` is checked on its first output instead."""
+        co = getattr(getattr(model, "outc", None), "out_channels", None)
+        C = image_channels
+        if C is None and hasattr(model, "inc"):
+            C = next((p.shape[1] for p in model.inc.parameters() if p.dim() == 4), None)
+        if co is None or C is None:
+            return
+        self._check_out_channels(co, C, where)
+
+    def _check_out_channels(self, got, C, where):
+        want = self.output_channels(C)
+        if got != want:
+            raise ValueError(f"{where}: the model emits {got} channels but variance={self.variance!r} on {C}-channel images needs "
+                             f"{want}" + (f" (build UNet(c_in={C}, c_out={2 * C}): the prediction and the variance coefficient)"
+                                          if self.variance == "learned" else f" (build UNet(c_in={C}, c_out={C}), or "
+                                          f"Diffusion(variance='learned') for a {2 * C}-channel output)"))
+
+    def _raw_output(self, model, x_t, t, y=None):
+        """The network's contiguous output at x_t, its channel count checked against `output_channels`."""
+        out = model(x_t, t) if y is None else model(x_t, t, y)
+        self._check_out_channels(out.shape[1], x_t.shape[1], "Diffusion")
+        return out.contiguous()
+
     def predict_eps(self, model, x_t, t, y=None):
         """Run the model and return eps.  prediction="eps": exactly model(x_t, t[, y]), the same tensor, no launch.  "v" / "x0":
         one fused conversion launch (ops.pred_to_eps), in place on the model's output; t is the per-row int64 device tensor
-        the model got, so the conversion captures into the sampling graphs with no host value in it."""
+        the model got, so the conversion captures into the sampling graphs with no host value in it.
+        variance="learned": the contiguous eps of the output's prediction half, one launch (ops.split_pred); the coefficient
+        half is not read, so whatever calls this keeps its own, fixed variance."""
+        if self.variance == "learned":
+            return ops.split_pred(self._raw_output(model, x_t, t, y), x_t.contiguous(), t, self.alpha_hat, self.prediction)
         out = model(x_t, t) if y is None else model(x_t, t, y)
+        if out.shape[1] != x_t.shape[1]:
+            self._check_out_channels(out.shape[1], x_t.shape[1], "Diffusion")
         if self.prediction == "eps":
             return out
         out = out.contiguous()
@@ -179,6 +251,8 @@ class Diffusion:
         theta_step = None if theta is None else theta / self.noise_steps
         if graph is None:
             graph = False
+        self.check_model(model, image_channels, "Diffusion.sample")
+        learned = self.variance == "learned"
         self._hint(model)
         model.eval()
         snaps = []
@@ -203,18 +277,29 @@ class Diffusion:
                         snaps.append(x)
                     continue
                 if guided:
-                    eps2 = self.predict_eps(model, xs2, self._t_full(2 * n, i, x.device), y)
+                    t2 = self._t_full(2 * n, i, x.device)
+                    eps2 = self._raw_output(model, xs2, t2, y) if learned else self.predict_eps(model, xs2, t2, y)
                     noise = self._step_noise(x, noise_source, shard, n_all) if i > 1 else None
                     nxt = torch.empty_like(xs2)
-                    ops.denoise_step_cfg(x, eps2, noise, self.alpha, self.alpha_hat, self.beta, i, cfg_scale, nxt[:n], nxt[n:])
+                    if learned:
+                        ops.denoise_step_lvar_cfg(x, eps2, noise, self.alpha, self.alpha_hat, self.beta, self._lv(), self.prediction, i,
+                                                  cfg_scale, nxt[:n], nxt[n:])
+                    else:
+                        ops.denoise_step_cfg(x, eps2, noise, self.alpha, self.alpha_hat, self.beta, i, cfg_scale, nxt[:n], nxt[n:])
                     xs2, x = nxt, nxt[:n]
                     if i % 100 == 0:
                         snaps.append(x)
                     continue
                 t = self._t_full(n, i, x.device)
-                eps = self.predict_eps(model, x, t, y)
-                noise = self._step_noise(x, noise_source, shard, n_all) if i > 1 else None
-                x = ops.denoise_step(x, eps, noise, self.alpha, self.alpha_hat, self.beta, i)
+                if learned:
+                    out2 = self._raw_output(model, x, t, y)
+                    noise = self._step_noise(x, noise_source, shard, n_all) if i > 1 else None
+                    x = ops.denoise_step_lvar(x.contiguous(), out2, noise, self.alpha, self.alpha_hat, self.beta, self._lv(),
+                                              self.prediction, i)
+                else:
+                    eps = self.predict_eps(model, x, t, y)
+                    noise = self._step_noise(x, noise_source, shard, n_all) if i > 1 else None
+                    x = ops.denoise_step(x, eps, noise, self.alpha, self.alpha_hat, self.beta, i)
                 if theta_step is not None:
                     x = self.rotate_2d_matrix(x, theta_step, self.filter)
                 if i % 100 == 0:
@@ -510,8 +595,19 @@ class Diffusion:
         t_dev = torch.full((2 * n if guided else n,), self.noise_steps - 1, device=x.device, dtype=torch.long)
         xs = torch.cat([x, x]) if guided else x.clone()
         xh = xs[:n]
+        learned = self.variance == "learned"
+        lv = self._lv() if learned else None
 
         def one_step():
+            if learned:                                  # the raw 2C output and the learned-variance update, in place as below
+                out2 = self._raw_output(model, xs, t_dev, y)
+                noise = torch.randn_like(xh)
+                if guided:
+                    ops.denoise_step_lvar_cfg_dev(xh, out2, noise, self.alpha, self.alpha_hat, self.beta, lv, self.prediction, t_dev,
+                                                  cfg_scale, xh, xs[n:])
+                else:
+                    ops.denoise_step_lvar_dev(xs, out2, noise, self.alpha, self.alpha_hat, self.beta, lv, self.prediction, t_dev, xs)
+                return
             if guided:
                 eps2 = self.predict_eps(model, xs, t_dev, y)
                 noise = torch.randn_like(xh)
@@ -792,7 +888,7 @@ class Diffusion:
         return g
 
     # Likelihood: the variational bound in bits per dimension (Ho et al. 2020, section 3.3) -----------------------------------
-    VLB_SIGMAS = ("beta", "posterior")
+    VLB_SIGMAS = ("beta", "posterior")           # (calc_bpd also takes "learned" on a learned-variance process)
 
     def vlb_coefficients(self, sigma="beta"):
         """(T, 4) fp64 host table of the bound's coefficients, from the fp32 schedule tables widened to fp64.  Row t (1 <= t < T)
@@ -917,11 +1013,18 @@ class Diffusion:
         labels: (n,) int64 class labels for a UNet(num_classes=K): the bound of log p(x | y); NULL_LABEL rows give the
         unconditional bound.  Returns a dict of CPU fp64 (n,) tensors bpd, prior_bpd, vb_bpd (the KL terms), decoder_bpd
         (bpd is their sum); with return_terms also terms (n, T), nats per t (0 where not evaluated; unscaled), and mse (n, T),
-        the per-element mean of (eps_hat - eps)^2."""
+        the per-element mean of (eps_hat - eps)^2.
+        sigma="learned" (needs variance="learned"): the per-pixel variance the network emits, in L_t and in the decoder
+        (`ops.vlb_terms_lvar`, the terms the hybrid loss trains on).  "beta" / "posterior" on a learned-variance process score its
+        prediction half with those fixed variances."""
         T = self.noise_steps
         if T < 3:
             raise ValueError(f"Diffusion.calc_bpd: needs noise_steps >= 3 (got {T})")
-        coef = self.vlb_coefficients(sigma)
+        learned = isinstance(sigma, str) and sigma == "learned"
+        if learned and self.variance != "learned":
+            raise ValueError(f"Diffusion.calc_bpd: unknown sigma 'learned' for a process with variance={self.variance!r} ('beta' or "
+                             "'posterior'; 'learned' needs Diffusion(variance='learned'))")
+        coef = self.vlb_coefficients("beta" if learned else sigma)           # (the prior column does not depend on sigma)
         if t_samples is not None and (isinstance(t_samples, bool) or not isinstance(t_samples, (int, np.integer))
                                       or not 1 <= t_samples <= T - 1):
             raise ValueError(f"Diffusion.calc_bpd: t_samples must be an int in [1, {T - 1}] or None (got {t_samples!r})")
@@ -930,6 +1033,7 @@ class Diffusion:
         if noise_source not in ("device", "cpu"):
             raise ValueError(f"Diffusion.calc_bpd: noise_source must be 'device' or 'cpu' (got {noise_source!r})")
         x0 = self._bpd_images(model, images)
+        self.check_model(model, images.shape[1], "Diffusion.calc_bpd")
         n, shape = x0.shape[0], tuple(x0.shape[1:])
         per = int(np.prod(shape))
         y = None if labels is None else self._check_labels(model, n, None, labels, "calc_bpd")
@@ -962,6 +1066,11 @@ class Diffusion:
                     eps = eps.to(device=dev, dtype=torch.float32).contiguous()
                     rows_i, rows_t = img_d[lo:hi], t_d[lo:hi]
                     xt = ops.noise_images_gather(x0, rows_i, eps, rows_t, self.alpha_hat, check_range=False)
+                    if learned:
+                        out2 = self._raw_output(model, xt, rows_t, None if y_rows is None else y_rows[lo:hi])
+                        ops.vlb_terms_lvar(x0, rows_i, xt, eps, out2, rows_t, self._lv(), self.alpha, self.alpha_hat, self.beta,
+                                           self.prediction, term[lo:hi], sq[lo:hi], check_range=False)
+                        continue
                     eh = self.predict_eps(model, xt, rows_t, None if y_rows is None else y_rows[lo:hi])
                     ops.vlb_terms(x0, rows_i, xt, eps, eh.contiguous(), rows_t, coef_d, self.alpha, self.alpha_hat, self.beta,
                                   term[lo:hi], sq[lo:hi], check_range=False)
@@ -1073,7 +1182,8 @@ class Diffusion:
         count (K,).  peak = 2 is StyleGAN3's I_max, the range of x0 in [-1, 1]; snr_db assumes no range.  Fractional shifts and
         rotations resample with a cubic spline, a mild low-pass: compare scores under the same transforms only.
         The score is of the network's raw output, whatever `prediction` says it means (eps, v or x0): it does not go through
-        `predict_eps`, whose x_t term would add a trivially equivariant part."""
+        `predict_eps`, whose x_t term would add a trivially equivariant part.  With variance="learned" it is the score of the
+        output's prediction half."""
         T = self.noise_steps
         ts = [t] if isinstance(t, (int, np.integer)) and not isinstance(t, bool) else t
         if isinstance(ts, (str, bytes, bool)) or not hasattr(ts, "__len__") or len(ts) == 0 or \
@@ -1128,12 +1238,14 @@ class Diffusion:
                     rows_t = t0_d[lo:hi]
                     xt = ops.noise_images_gather(x0, img0_d[lo:hi], eps, rows_t, self.alpha_hat, check_range=False)
                     f = model(xt, rows_t) if y is None else model(xt, rows_t, y[img0_d[lo:hi]])
+                    f = f[:, :C] if self.variance == "learned" else f             # the prediction half
                     ops.spline3_prefilter_wrap(xt, coef_x[lo:hi])
                     ops.spline3_prefilter_wrap(f.contiguous(), coef_f[lo:hi])
                 for lo, hi in self.bpd_chunks(len(k), batch):
                     rows_s, rows_k, rows_t = src_d[lo:hi], k_d[lo:hi], t_d[lo:hi]
                     sx = ops.affine_spline3_wrap_rows(coef_x, rows_s, aff_d, rows_k, check_range=False)
                     g = model(sx, rows_t) if y is None else model(sx, rows_t, y[rows_s // J])
+                    g = g[:, :C] if self.variance == "learned" else g
                     ops.eq_terms(coef_f, rows_s, aff_d, rows_k, g.contiguous(), margin, sums[lo:hi], check_range=False)
         finally:
             model.train(was_training)

@@ -1624,3 +1624,173 @@ def pred_to_eps(out, x_t, t, alpha_hat, kind, eps_out=None):
     code, B, chw = _objective_args("pred_to_eps", kind, t, alpha_hat, out, x_t, eps_out)
     lib().afd_pred_to_eps(_p(out), _p(x_t), _p(t), _p(alpha_hat), code, _p(eps_out), B, chw, _stream())
     return eps_out
+
+
+# ---- learned reverse-process variances and the hybrid loss (include/afd.h gives the exact expressions) ----------------------
+def _lvar_args(what, kind, out2, t, alpha_hat, lv_coef, *tensors, rows2=1):
+    """-> (AFD_PRED_* code, B, chw): out2 is the contiguous (rows2 * B, 2C, ...) output of a learned-variance network, `tensors`
+    are contiguous (B, C, ...) fp32 device tensors of one shape (None entries are skipped), t None or (B,) int64 on the device,
+    lv_coef the (T, 3) fp64 device table of `Diffusion.lvar_coefficients`."""
+    if not isinstance(kind, str) or kind not in PRED_KINDS:
+        raise AfdError(f"afdm: {what}: unknown prediction {kind!r} ('eps', 'v' or 'x0')")
+    given = tuple(o for o in tensors if o is not None)
+    if any(not isinstance(o, torch.Tensor) for o in (out2, alpha_hat) + given):
+        raise AfdError(f"afdm: {what}: every argument but kind must be a tensor")
+    _chk(out2, alpha_hat, *given)
+    first = given[0]
+    if first.dim() < 2 or first.numel() == 0:
+        raise AfdError(f"afdm: {what}: needs tensors of shape (B, C, ...) with at least one element")
+    for o in given:
+        if tuple(o.shape) != tuple(first.shape) or not o.is_contiguous():
+            raise AfdError(f"afdm: {what}: every tensor must be contiguous and of shape {tuple(first.shape)}")
+    B, C = first.shape[0], first.shape[1]
+    want = (rows2 * B, 2 * C) + tuple(first.shape[2:])
+    if tuple(out2.shape) != want or not out2.is_contiguous():
+        raise AfdError(f"afdm: {what}: the network's output must be contiguous and of shape {want}: {2 * C} channels, the "
+                       f"prediction's {C} and the variance coefficient's {C} (got {tuple(out2.shape)})")
+    if t is not None and (not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.long or tuple(t.shape) != (B,)
+                          or not t.is_contiguous()):
+        raise AfdError(f"afdm: {what}: t must be a contiguous int64 device tensor of shape ({B},)")
+    if alpha_hat.dim() != 1 or not alpha_hat.is_contiguous():
+        raise AfdError(f"afdm: {what}: alpha_hat must be a contiguous (T,) table")
+    T = alpha_hat.numel()
+    if lv_coef is not None and (not isinstance(lv_coef, torch.Tensor) or not lv_coef.is_cuda or lv_coef.dtype != torch.float64
+                                or tuple(lv_coef.shape) != (T, 3) or not lv_coef.is_contiguous()):
+        raise AfdError(f"afdm: {what}: lv_coef must be the contiguous ({T}, 3) fp64 device table (Diffusion.lvar_coefficients)")
+    return PRED_KINDS[kind], B, first.numel() // B
+
+
+def _lvar_tables(what, alpha, alpha_hat, beta, w=None):
+    _chk(alpha, beta, w)
+    for name, v in (("alpha", alpha), ("beta", beta), ("w", w)):
+        if v is not None and (tuple(v.shape) != tuple(alpha_hat.shape) or not v.is_contiguous()):
+            raise AfdError(f"afdm: {what}: {name} must be a contiguous table of alpha_hat's shape {tuple(alpha_hat.shape)}")
+
+
+def _vlb_scale(what, vlb_scale):
+    if isinstance(vlb_scale, bool) or not isinstance(vlb_scale, (int, float, np.integer, np.floating)) \
+            or not np.isfinite(vlb_scale) or vlb_scale < 0:
+        raise AfdError(f"afdm: {what}: vlb_scale must be a finite number >= 0 (got {vlb_scale!r})")
+    return float(vlb_scale)
+
+
+class LvarLoss(_Fn):
+    """L = L_simple + vlb_scale * L_vlb of a learned-variance output (afd.h: afd_lvar_loss_fwd / _bwd): two launches forward and
+    one backward, like ObjectiveLoss.  Returns (L, L_vlb, sums): two 0-d fp32 tensors and the (2,) fp64 tensor [L, L_vlb]; only L
+    is differentiable."""
+
+    @staticmethod
+    def forward(ctx, out2, x0, eps, t, alpha, alpha_hat, beta, lv_coef, w, kind, vlb_scale):
+        out2, x0, eps = _c(out2), _c(x0), _c(eps)
+        code, B, chw = _lvar_args("learned-variance loss", kind, out2, t, alpha_hat, lv_coef, x0, eps)
+        _lvar_tables("learned-variance loss", alpha, alpha_hat, beta, w)
+        scale = _vlb_scale("learned-variance loss", vlb_scale)
+        aux = torch.empty(2, device=out2.device, dtype=torch.float32)
+        aux64 = torch.empty(2, device=out2.device, dtype=torch.float64)
+        ws = torch.empty(4096, device=out2.device, dtype=torch.float32)
+        lib().afd_lvar_loss_fwd(_p(out2), _p(x0), _p(eps), _p(t), _p(alpha), _p(alpha_hat), _p(beta), _p(lv_coef), _p(w), code, scale,
+                                _p(aux), _p(aux64), _p(ws), B, chw, _stream())
+        ctx.save_for_backward(out2, x0, eps, t, alpha, alpha_hat, beta, lv_coef, w)
+        ctx.code, ctx.scale = code, scale
+        loss, vlb = aux[0], aux[1]
+        ctx.mark_non_differentiable(vlb, aux64)
+        ctx.set_materialize_grads(False)          # (no zero-filled gradients for the two logging outputs: a launch each)
+        return loss, vlb, aux64
+
+    @staticmethod
+    def backward(ctx, dloss, _daux=None, _daux64=None):
+        out2, x0, eps, t, alpha, alpha_hat, beta, lv_coef, w = ctx.saved_tensors
+        dloss = dloss.reshape(1).contiguous()
+        dout2 = torch.empty_like(out2)
+        B = x0.shape[0]
+        lib().afd_lvar_loss_bwd(_p(out2), _p(x0), _p(eps), _p(t), _p(alpha), _p(alpha_hat), _p(beta), _p(lv_coef), _p(w), ctx.code,
+                                ctx.scale, _p(dloss), _p(dout2), B, x0.numel() // B, _stream())
+        return (dout2,) + (None,) * 10
+
+
+def lvar_loss(out2, x0, eps, t, alpha, alpha_hat, beta, lv_coef, w=None, kind="eps", vlb_scale=0.0, return_sums=False):
+    """The hybrid loss L_simple + vlb_scale * L_vlb (Nichol & Dhariwal 2021) of a network whose (B, 2C, ...) output holds the
+    prediction (`kind`) and the variance coefficient.  L_simple is `objective_loss` on the prediction (weights w[t] included);
+    L_vlb is the variational bound's term of each row in bits per dimension, averaged over the batch, with the mean stopped: the
+    prediction's gradient is L_simple's, bit for bit, the coefficient's comes from L_vlb alone.  Returns (loss, L_vlb), two 0-d
+    fp32 device tensors (L_vlb detached, unscaled); return_sums: also the (2,) fp64 device tensor [L, L_vlb]."""
+    loss, vlb, sums = LvarLoss.apply(out2, x0, eps, t, alpha, alpha_hat, beta, lv_coef, w, kind, vlb_scale)
+    if return_sums:
+        return loss, vlb, sums
+    return loss, vlb
+
+
+def split_pred(out2, x_t, t, alpha_hat, kind, eps_out=None, want_v=False):
+    """A learned-variance output (B, 2C, ...) -> the contiguous eps (B, C, ...): the prediction half, converted as `pred_to_eps`
+    does for "v" / "x0" (a copy for "eps"), in one launch; want_v: also the contiguous coefficient half.  Returns eps or (eps, v)."""
+    if not isinstance(x_t, torch.Tensor):
+        raise AfdError("afdm: split_pred: x_t must be a tensor (it gives the shape of eps)")
+    eps_out = torch.empty_like(x_t) if eps_out is None else eps_out
+    out2, x_t = _c(out2), _c(x_t)
+    code, B, chw = _lvar_args("split_pred", kind, out2, t, alpha_hat, None, x_t, eps_out)
+    v_out = torch.empty_like(x_t) if want_v else None
+    lib().afd_split_pred(_p(out2), _p(x_t), _p(t), _p(alpha_hat), code, _p(eps_out), _p(v_out), B, chw, _stream())
+    return (eps_out, v_out) if want_v else eps_out
+
+
+def _lvar_step(name, x, out2, noise, alpha, alpha_hat, beta, lv_coef, kind, step, cfg_scale, out, out2_x, guided):
+    what = "guided learned-variance step" if guided else "learned-variance step"
+    code, B, chw = _lvar_args(what, kind, out2, None, alpha_hat, lv_coef, x, noise, out, out2_x, rows2=2 if guided else 1)
+    _lvar_tables(what, alpha, alpha_hat, beta)
+    if isinstance(step, torch.Tensor):
+        if not step.is_cuda or step.dtype != torch.long or step.numel() < 1:
+            raise AfdError(f"afdm: {what}: t_dev must be an int64 device tensor (element 0 is read)")
+        step = _p(step)
+    else:
+        step = int(step)
+        if not 1 <= step < alpha_hat.numel():
+            raise AfdError(f"afdm: {what} needs 1 <= i < {alpha_hat.numel()} (got {step})")
+    args = (_p(x), _p(out2), _p(noise), _p(alpha), _p(alpha_hat), _p(beta), _p(lv_coef), code, step)
+    if guided:
+        getattr(lib(), name)(*args, float(cfg_scale), _p(out), _p(out2_x), B, chw, _stream())
+    else:
+        getattr(lib(), name)(*args, _p(out), B, chw, _stream())
+    return out
+
+
+def denoise_step_lvar(x, out2, noise, alpha, alpha_hat, beta, lv_coef, kind, i, out=None):
+    """The ancestral step i -> i - 1 with the learned variance: mean as `denoise_step` from the output's prediction half (read
+    as `kind`), plus exp(logvar / 2) * noise from its coefficient half; noise is ignored at i = 1 and may be None.  out may be x."""
+    out = torch.empty_like(x) if out is None else out
+    return _lvar_step("afd_denoise_step_lvar", x, out2, noise, alpha, alpha_hat, beta, lv_coef, kind, i, 0.0, out, None, False)
+
+
+def denoise_step_lvar_dev(x, out2, noise, alpha, alpha_hat, beta, lv_coef, kind, t_dev, out):
+    """denoise_step_lvar with the step index t_dev[0] read on the device (graph-replayable)."""
+    return _lvar_step("afd_denoise_step_lvar_dev", x, out2, noise, alpha, alpha_hat, beta, lv_coef, kind, t_dev, 0.0, out, None, False)
+
+
+def denoise_step_lvar_cfg(x, out2, noise, alpha, alpha_hat, beta, lv_coef, kind, i, cfg_scale, out=None, out_x2=None):
+    """Classifier-free guided `denoise_step_lvar`: out2 is the forward over [conditional rows ; unconditional rows]; the two eps
+    are combined as `denoise_step_cfg` combines them, the variance is the conditional row's.  out may be x; out_x2 (optional)
+    receives the same values."""
+    out = torch.empty_like(x) if out is None else out
+    return _lvar_step("afd_denoise_step_lvar_cfg", x, out2, noise, alpha, alpha_hat, beta, lv_coef, kind, i, cfg_scale, out, out_x2, True)
+
+
+def denoise_step_lvar_cfg_dev(x, out2, noise, alpha, alpha_hat, beta, lv_coef, kind, t_dev, cfg_scale, out, out_x2=None):
+    """denoise_step_lvar_cfg with the step index t_dev[0] read on the device (graph-replayable)."""
+    return _lvar_step("afd_denoise_step_lvar_cfg_dev", x, out2, noise, alpha, alpha_hat, beta, lv_coef, kind, t_dev, cfg_scale, out,
+                      out_x2, True)
+
+
+def vlb_terms_lvar(x0, img, x_t, eps, out2, t, lv_coef, alpha, alpha_hat, beta, kind, term=None, sq=None, check_range=True):
+    """`vlb_terms` for a learned-variance output out2 (rows, 2C, ...): the bound's term of each row, in nats, with the
+    per-element variance, and sum_j (eps_hat - eps)^2, both fp64 (rows,) device tensors (afd.h: afd_vlb_terms_lvar).
+    lv_coef: the (T, 3) fp64 table of `Diffusion.lvar_coefficients` on the device.  Returns (term, sq)."""
+    n_img, rows, per = _rows_args("learned-variance bound terms", x0, img, t, eps, check_range, alpha_hat.numel())
+    code, _, _ = _lvar_args("learned-variance bound terms", kind, out2, None, alpha_hat, lv_coef, eps, x_t)
+    _lvar_tables("learned-variance bound terms", alpha, alpha_hat, beta)
+    term = torch.empty(rows, device=eps.device, dtype=torch.float64) if term is None else term
+    sq = torch.empty(rows, device=eps.device, dtype=torch.float64) if sq is None else sq
+    for v in (term, sq):
+        if not v.is_cuda or v.dtype != torch.float64 or v.numel() != rows or not v.is_contiguous():
+            raise AfdError(f"afdm: learned-variance bound terms: term and sq must be contiguous fp64 device tensors of {rows} values")
+    lib().afd_vlb_terms_lvar(_p(x0), n_img, _p(img), _p(x_t), _p(eps), _p(out2), _p(t), _p(lv_coef), alpha_hat.numel(), _p(alpha),
+                             _p(alpha_hat), _p(beta), code, _p(term), _p(sq), rows, per, _stream())
+    return term, sq

@@ -12,7 +12,7 @@ import torch
 
 from .data import get_data, get_data_MNIST, make_collage, save_dataset_MNIST, save_gen_images
 from .diffusion import Diffusion
-from .training import argument, diffusion_kwargs, ema_path, set_seed, train
+from .training import argument, diffusion_kwargs, ema_path, model_out_channels, set_seed, train
 from .unet import UNet
 
 
@@ -44,8 +44,10 @@ def ddpm_run(params):
     # changes, the settings file included.
     # optional training objective: "noise_schedule" ("linear" | "cosine") and "prediction" ("eps" | "v" | "x0") go to every
     # Diffusion of the run, "loss_weighting" ("min_snr") and "snr_gamma" to train()'s TrainStep; same rule
+    # "variance" ("fixed" | "learned": the UNet then emits 2 * image_channels) goes to every Diffusion and model of the run,
+    # "vlb_lambda" to train()'s TrainStep; same rule
     opt_keys = [k for k in ("max_grad_norm", "lr_warmup", "lr_schedule", "lr_min_ratio", "noise_schedule", "prediction",
-                            "loss_weighting", "snr_gamma") if params.get(k) is not None]
+                            "loss_weighting", "snr_gamma", "variance", "vlb_lambda") if params.get(k) is not None]
     for k in opt_keys:
         setattr(args, k, params[k])
     cwd = os.getcwd()
@@ -83,7 +85,7 @@ def ddpm_run(params):
         fh.write(text)
 
     # smoke forward (the reference does this on the CPU; the HIP engine has no CPU path)
-    net = UNet(c_in=args.image_channels, c_out=args.image_channels, image_size=args.image_size, f_settings=f_settings,
+    net = UNet(c_in=args.image_channels, c_out=model_out_channels(args), image_size=args.image_size, f_settings=f_settings,
                device=args.device, variant=v).to(args.device)
     print(sum(p.numel() for p in net.parameters()))
     x = torch.randn(2, args.image_channels, args.image_size, args.image_size, device=args.device)
@@ -94,7 +96,7 @@ def ddpm_run(params):
     # train
     set_seed(seed)
     dataloader, dataset = _loader(name, args)
-    model = UNet(c_in=args.image_channels, c_out=args.image_channels, image_size=args.image_size, f_settings=f_settings,
+    model = UNet(c_in=args.image_channels, c_out=model_out_channels(args), image_size=args.image_size, f_settings=f_settings,
                  device=args.device, variant=v).to(args.device)
     diffusion = Diffusion(noise_steps=args.noise_steps, img_size=args.image_size, device=args.device, **diffusion_kwargs(args))
     loss_all = train(args, model_path=modelpath, dataloader=dataloader, model=model, diffusion=diffusion)
@@ -105,7 +107,7 @@ def ddpm_run(params):
 
     # reload, sample, revert
     set_seed(seed)
-    model = UNet(c_in=args.image_channels, c_out=args.image_channels, image_size=args.image_size, f_settings=f_settings,
+    model = UNet(c_in=args.image_channels, c_out=model_out_channels(args), image_size=args.image_size, f_settings=f_settings,
                  device=args.device, variant=v).to(args.device)
     model.load_state_dict(torch.load(modelpath, weights_only=True))
     diffusion = Diffusion(noise_steps=args.noise_steps, img_size=args.image_size, device=args.device, **diffusion_kwargs(args))
@@ -127,7 +129,7 @@ def ddpm_run(params):
         gen_kw["sampler"] = params["sample_solver"]
     gen_model = model
     if use_ema:
-        gen_model = UNet(c_in=args.image_channels, c_out=args.image_channels, image_size=args.image_size, f_settings=f_settings,
+        gen_model = UNet(c_in=args.image_channels, c_out=model_out_channels(args), image_size=args.image_size, f_settings=f_settings,
                          device=args.device, variant=v).to(args.device)
         gen_model.load_state_dict(torch.load(ema_path(modelpath), weights_only=True))
     for start in np.arange(0, params["gen_total"], params["gen_per_batch"]):
@@ -141,7 +143,8 @@ def ddpm_run(params):
     if use_ema:
         out["ema_modelpath"] = ema_path(modelpath)
     # optional likelihood: params["eval_bpd"] = N scores the first N training images, in dataset order, on the model the
-    # FID/KID image set came from (Diffusion.calc_bpd; "eval_bpd_t_samples": K timesteps per image, "eval_bpd_sigma")
+    # FID/KID image set came from (Diffusion.calc_bpd; "eval_bpd_t_samples": K timesteps per image, "eval_bpd_sigma": "beta", "posterior" or,
+    # with "variance": "learned", "learned")
     if params.get("eval_bpd"):
         out["bpd"] = _eval_bpd(params, args, diffusion, gen_model, run_dir, name, v, seed)
     # optional equivariance scores: params["eval_equivariance"] = the keyword arguments of Diffusion.equivariance (t, transforms,
@@ -194,7 +197,7 @@ def _eval_equivariance(params, args, diffusion, model, run_dir, name, v, seed):
 def _load(model_data):
     args, v = model_data["args"], model_data["unet_v"]
     set_seed(model_data["seed"])
-    model = UNet(c_in=args.image_channels, c_out=args.image_channels, image_size=args.image_size,
+    model = UNet(c_in=args.image_channels, c_out=model_out_channels(args), image_size=args.image_size,
                  f_settings=model_data["f_settings"], device=args.device, variant=v).to(args.device)
     model.load_state_dict(torch.load(model_data["modelpath"], weights_only=True))
     # (a checkpoint trained with another noise schedule or parametrisation is evaluated as such: args.noise_schedule / .prediction)

@@ -22,14 +22,16 @@ class argument:
     def __init__(self, run_name=None, epochs=None, batch_size=None, image_size=None, image_channels=3,
                  dataset_path=None, device=None, lr=None, noise_steps=None, image_gen_n=4, ema_beta=None, ema_start=2000,
                  max_grad_norm=None, lr_warmup=0, lr_schedule=None, lr_min_ratio=0.0, noise_schedule=None, prediction=None,
-                 loss_weighting=None, snr_gamma=None):
+                 loss_weighting=None, snr_gamma=None, variance=None, vlb_lambda=None):
         """ema_beta / ema_start (not in the reference's class): with ema_beta set, `train` keeps an EMA of the weights
         (EMA(ema_beta), step_start_ema = ema_start).
         max_grad_norm: `train` clips the gradient to this global L2 norm.  lr_schedule ("constant" | "linear" | "cosine") /
         lr_warmup / lr_min_ratio: `train` runs LRSchedule(lr_schedule, lr_warmup, total = epochs * batches, lr_min_ratio);
         lr_warmup > 0 alone means a warm-up into a constant rate.
         noise_schedule ("linear" | "cosine") / prediction ("eps" | "v" | "x0"): `diffusion_kwargs` turns them into the arguments
-        of the run's Diffusion; loss_weighting ("min_snr") / snr_gamma: `train` hands them to its TrainStep.  None = the default."""
+        of the run's Diffusion; loss_weighting ("min_snr") / snr_gamma: `train` hands them to its TrainStep.  None = the default.
+        variance ("fixed" | "learned") goes to the run's Diffusion and doubles the UNet's output channels when "learned"
+        (`model_out_channels`); vlb_lambda is the hybrid loss's weight in `train`'s TrainStep."""
         self.run_name, self.epochs, self.batch_size, self.image_size = run_name, epochs, batch_size, image_size
         self.image_channels, self.dataset_path, self.device, self.lr = image_channels, dataset_path, device, lr
         self.noise_steps, self.image_gen_n = noise_steps, image_gen_n
@@ -37,17 +39,25 @@ class argument:
         self.max_grad_norm, self.lr_warmup, self.lr_schedule, self.lr_min_ratio = max_grad_norm, lr_warmup, lr_schedule, lr_min_ratio
         self.noise_schedule, self.prediction = noise_schedule, prediction
         self.loss_weighting, self.snr_gamma = loss_weighting, snr_gamma
+        self.variance, self.vlb_lambda = variance, vlb_lambda
 
 
 def diffusion_kwargs(args):
-    """The Diffusion arguments named by a run's settings (`args.noise_schedule`, `args.prediction`); empty when both are absent
-    or None, so a run without the keys builds the default Diffusion."""
+    """The Diffusion arguments named by a run's settings (`args.noise_schedule`, `args.prediction`, `args.variance`); empty when
+    all are absent or None, so a run without the keys builds the default Diffusion."""
     kw = {}
     if getattr(args, "noise_schedule", None) is not None:
         kw["schedule"] = args.noise_schedule
     if getattr(args, "prediction", None) is not None:
         kw["prediction"] = args.prediction
+    if getattr(args, "variance", None) is not None:
+        kw["variance"] = args.variance
     return kw
+
+
+def model_out_channels(args):
+    """The UNet's c_out for a run's settings: image_channels, or twice that with variance="learned"."""
+    return args.image_channels * (2 if getattr(args, "variance", None) == "learned" else 1)
 
 
 def set_seed(seed):
@@ -606,7 +616,7 @@ class TrainStep:
 
     def __init__(self, model, diffusion, lr, graph=False, distributed=None, n_buckets=4, overlap_wgrad=None, conditional=False,
                  p_uncond=0.0, ema=None, ema_model=None, ema_start=2000, max_grad_norm=None, lr_schedule=None, skip_nonfinite=False,
-                 track_grad_norm=False, loss_weighting=None, snr_gamma=5.0):
+                 track_grad_norm=False, loss_weighting=None, snr_gamma=5.0, vlb_lambda=0.001):
         """conditional=True: the step takes class labels (`step(images, y=labels)`, UNet.forward(x, t, y): ddpm_models.py:276-277)
         and `label_emb` is optimised and exchanged like every other parameter.  With the default (the reference's loop,
         ddpm_utils.py:502, never passes labels) `label_emb` stays untouched, as under the reference's AdamW, and passing y raises.
@@ -630,7 +640,13 @@ class TrainStep:
         normalised by the element count, not by sum w, so data-parallel ranks average losses and gradients exactly as for the
         plain MSE, with no extra collective.  Anything but eps-prediction without weighting runs ops.objective_loss, which forms
         the target inside the loss kernels: the same number of launches as ops.mse_loss, in every launch mode.  The weight table
-        is a static device buffer built here, once."""
+        is a static device buffer built here, once.
+        With diffusion.variance == "learned" (the model is UNet(c_in=C, c_out=2 C)) the step trains the hybrid loss of Nichol &
+        Dhariwal 2021, L = L_simple + vlb_lambda (T - 1) L_vlb: L_simple is the objective above on the output's prediction half,
+        L_vlb the batch mean of the variational bound's term of each sample's timestep in bits per dimension, with the mean
+        stopped, so it trains the variance half alone (ops.lvar_loss: the same number of launches again, in every launch mode,
+        with loss_weighting=, ema=, clipping, conditional= and under data parallelism; normalised by the element count like
+        L_simple).  `last_vlb` is the last step's L_vlb, a 0-d device tensor.  vlb_lambda is ignored with a fixed variance."""
         _check_opt_ctl("TrainStep", max_grad_norm, lr_schedule)
         if loss_weighting is not None and not (isinstance(loss_weighting, str) and loss_weighting in Diffusion.LOSS_WEIGHTINGS):
             raise ValueError(f"TrainStep: unknown loss_weighting {loss_weighting!r} (None or 'min_snr')")
@@ -646,7 +662,14 @@ class TrainStep:
             raise ValueError(f"TrainStep: p_uncond must lie in [0, 1] (got {p_uncond})")
         if p_uncond > 0 and not conditional:
             raise ValueError("TrainStep: p_uncond > 0 drops class labels, which needs a conditional step (conditional=True)")
+        if isinstance(vlb_lambda, bool) or not isinstance(vlb_lambda, (int, float)) or not vlb_lambda >= 0 or not math.isfinite(vlb_lambda):
+            raise ValueError(f"TrainStep: vlb_lambda must be a finite number >= 0 (got {vlb_lambda!r})")
         self.model, self.diffusion = model, diffusion
+        self.learned = getattr(diffusion, "variance", "fixed") == "learned"
+        self.vlb_lambda = float(vlb_lambda)
+        self.last_vlb = None             # L_vlb of the last step (0-d device tensor; a static buffer under graph=True / "lanes")
+        if hasattr(diffusion, "check_model"):
+            diffusion.check_model(model, None, "TrainStep")
         self.conditional = conditional
         self.p_uncond = float(p_uncond)
         self.last_labels = None          # the labels the last call trained on, after dropout
@@ -728,7 +751,11 @@ class TrainStep:
         try:
             x_t, noise = self.diffusion.noise_images(images, t, eps)
             pred = self.model(x_t, t) if y is None else self.model(x_t, t, y)
-            if self.prediction == "eps" and self.loss_weights is None:
+            if self.learned:
+                d = self.diffusion
+                loss, self.last_vlb = ops.lvar_loss(pred, images, noise, t, d.alpha, d.alpha_hat, d.beta, d._lv(), self.loss_weights,
+                                                    self.prediction, self.vlb_lambda * (d.noise_steps - 1))
+            elif self.prediction == "eps" and self.loss_weights is None:
                 loss = ops.mse_loss(noise, pred)
             else:
                 loss = ops.objective_loss(pred, images, noise, t, self.diffusion.alpha_hat, self.loss_weights, self.prediction)
@@ -876,7 +903,8 @@ def train(args, model_path=None, dataloader=None, model=None, diffusion=None):
     step = TrainStep(model, diffusion, lr=args.lr, graph=False, ema=ema, ema_model=ema_model,
                      ema_start=getattr(args, "ema_start", 2000), max_grad_norm=getattr(args, "max_grad_norm", None),
                      lr_schedule=schedule, loss_weighting=getattr(args, "loss_weighting", None),
-                     snr_gamma=5.0 if getattr(args, "snr_gamma", None) is None else args.snr_gamma)
+                     snr_gamma=5.0 if getattr(args, "snr_gamma", None) is None else args.snr_gamma,
+                     vlb_lambda=0.001 if getattr(args, "vlb_lambda", None) is None else args.vlb_lambda)
     loss_all = []
     for epoch in range(args.epochs):
         logging.info(f"Starting epoch {epoch}:")

@@ -535,6 +535,59 @@ int afd_objective_loss_bwd(const float* pred, const float* x0, const float* eps,
                            afd_stream_t stream);
 int afd_pred_to_eps(const float* out, const float* x_t, const int64_t* t, const float* alpha_hat, int kind, float* eps_out, long B,
                     long chw, afd_stream_t stream);
+
+/* ---- learned reverse-process variances and the hybrid loss (Nichol & Dhariwal 2021) ------ Diffusion(variance="learned") /
+ * TrainStep(vlb_lambda=).  The network's output out2 holds, per row b, 2 chw floats: the prediction p (eps, v or x0 by `kind`)
+ * and, chw floats later, the interpolation coefficient v.  lv_coef: the (T, 3) fp64 device table [lb_t, lbt_t, k_t] of
+ * Diffusion.lvar_coefficients (lb_t = log beta_t, lbt_t = log beta~_t, k_t = beta_t^2 / (alpha_t (1 - ah_t))).  Per element:
+ *   logvar = ((v + 1) / 2) lb_t + (1 - (v + 1) / 2) lbt_t                                     (v is not clamped)
+ *   t >= 2: term = 0.5 (x + expm1(-x) + k_t d^2 exp(-logvar)), x = logvar - lbt_t, d^2 = f2 (p - target)^2 in fp64 with
+ *           f2 = 1 (eps), a (v), a / (1 - a) (x0), a = alpha_hat[t]: the KL term with the means' difference in eps-space;
+ *   t == 1: term = -log p(x0 | x_1), Ho et al.'s discretised Gaussian exactly as afd_vlb_terms', with log_scale = logvar / 2 and
+ *           mean = afd_denoise_step's fp32 expression at i = 1 from x_t (afd_noise_images' expression) and eps_hat
+ *           (afd_pred_to_eps' expression).
+ * Terms and dL/dv are evaluated in fp64 from the fp32 inputs; dL/dv is rounded once to fp32.  With N = B chw:
+ *   L_simple = afd_objective_loss_fwd's value on the p half;  L_vlb = (1 / (N ln 2)) sum term;  L = L_simple + vlb_scale L_vlb
+ * afd_lvar_loss_fwd: loss_out = {L, L_vlb} in fp32, sums_out (may be NULL) the same two in fp64.  Two launches; a deterministic
+ *   two-stage sum (workspace >= 4096 floats, 8-byte aligned), no atomics.
+ * afd_lvar_loss_bwd: one launch writes both halves of dout2: the p half is afd_objective_loss_bwd's dpred bit for bit (the mean is
+ *   stopped in L_vlb), the v half is dloss[0] vlb_scale / (N ln 2) d term / d v, through the tanh CDFs on decoder rows and zero
+ *   where the 1e-12 clamp is active.
+ * afd_split_pred: out2 -> eps_out (B x chw; afd_pred_to_eps' conversion, a copy for AFD_PRED_EPS, where x_t, t and alpha_hat may
+ *   be NULL) and, when v_out is not NULL, the v half; one launch.
+ * afd_denoise_step_lvar[_dev]: x_out = mean + (float)exp(logvar / 2) noise with afd_denoise_step's mean from eps_hat; noise is
+ *   ignored at step 1 and may be NULL.  x: B x chw, out2: B x 2 chw.  _dev reads the step from t_dev[0].  x_out may be x.
+ * afd_denoise_step_lvar_cfg[_dev]: out2 holds 2 B rows, conditional then unconditional; the two eps_hat are combined by
+ *   afd_denoise_step_cfg's lerp, the variance is the conditional row's; x_out2 (may be NULL) receives the same values as x_out.
+ * afd_vlb_terms_lvar: afd_vlb_terms with the per-element variance: term[r] = sum_j term, sq[r] = sum_j d^2, fp64, one workgroup
+ *   per row, the same deterministic reduction; out2: rows x 2 per.
+ * 128-bit accesses when chw % 4 == 0 and the float pointers are 16-byte aligned, element by element otherwise, with the same
+ * values either way.  AFD_EINVAL (nothing written) on sizes <= 0, a bad kind, NULL required pointers, or an output that overlaps
+ * an input it may not alias. */
+int afd_lvar_loss_fwd(const float* out2, const float* x0, const float* eps, const int64_t* t, const float* alpha,
+                      const float* alpha_hat, const float* beta, const double* lv_coef, const float* w_or_null, int kind,
+                      double vlb_scale, float* loss_out, double* sums_out_or_null, float* workspace, long B, long chw,
+                      afd_stream_t stream);
+int afd_lvar_loss_bwd(const float* out2, const float* x0, const float* eps, const int64_t* t, const float* alpha,
+                      const float* alpha_hat, const float* beta, const double* lv_coef, const float* w_or_null, int kind,
+                      double vlb_scale, const float* dloss, float* dout2, long B, long chw, afd_stream_t stream);
+int afd_split_pred(const float* out2, const float* x_t, const int64_t* t, const float* alpha_hat, int kind, float* eps_out,
+                   float* v_out_or_null, long B, long chw, afd_stream_t stream);
+int afd_denoise_step_lvar(const float* x, const float* out2, const float* noise_or_null, const float* alpha, const float* alpha_hat,
+                          const float* beta, const double* lv_coef, int kind, int i, float* x_out, long B, long chw,
+                          afd_stream_t stream);
+int afd_denoise_step_lvar_dev(const float* x, const float* out2, const float* noise_or_null, const float* alpha,
+                              const float* alpha_hat, const float* beta, const double* lv_coef, int kind, const int64_t* t_dev,
+                              float* x_out, long B, long chw, afd_stream_t stream);
+int afd_denoise_step_lvar_cfg(const float* x, const float* out2, const float* noise_or_null, const float* alpha,
+                              const float* alpha_hat, const float* beta, const double* lv_coef, int kind, int i, float cfg_scale,
+                              float* x_out, float* x_out2, long B, long chw, afd_stream_t stream);
+int afd_denoise_step_lvar_cfg_dev(const float* x, const float* out2, const float* noise_or_null, const float* alpha,
+                                  const float* alpha_hat, const float* beta, const double* lv_coef, int kind, const int64_t* t_dev,
+                                  float cfg_scale, float* x_out, float* x_out2, long B, long chw, afd_stream_t stream);
+int afd_vlb_terms_lvar(const float* x0, long n_img, const int64_t* img, const float* x_t, const float* eps, const float* out2,
+                       const int64_t* t, const double* lv_coef, long T, const float* alpha, const float* alpha_hat,
+                       const float* beta, int kind, double* term, double* sq, long rows, long per, afd_stream_t stream);
 int afd_adamw_tick(float* state, float beta1, float beta2, afd_stream_t stream);
 int afd_adamw_step(float* p, const float* g, float* m, float* v, long n, const float* state,
                    float lr, float beta1, float beta2, float eps, float weight_decay, float grad_scale,
