@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstdarg>
+#include <cstdint>
 #include <cstdio>
 #include "../../include/afd.h"
 
@@ -91,6 +92,44 @@ __device__ __forceinline__ float block_sum(float v, float* red) {
   float t = 0.f;
   for (int i = 0; i < nw; ++i) t += red[i];   // fixed order: deterministic
   return t;
+}
+
+// Sum of two fp64 values over a 256-thread workgroup in a fixed order: a shuffle tree inside each wave, then the four waves'
+// partial sums in wave order.  The result is valid in thread 0.  red: 8 doubles of LDS.
+__device__ __forceinline__ void block_sum2_f64(double& a, double& b, double* red) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    a += __shfl_down(a, o, kWave);
+    b += __shfl_down(b, o, kWave);
+  }
+  const int w = threadIdx.x >> 6;
+  if ((threadIdx.x & 63) == 0) {
+    red[2 * w] = a;
+    red[2 * w + 1] = b;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    a = red[0];
+    b = red[1];
+    for (int i = 1; i < (int)(blockDim.x >> 6); ++i) {
+      a += red[2 * i];
+      b += red[2 * i + 1];
+    }
+  }
+}
+
+// grid-stride loop over `total` items
+#define AFD_GRID_STRIDE(i, total) \
+  for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < (total); i += (long)gridDim.x * blockDim.x)
+// (written in the kernel itself: inside a __device__ body, blockDim.x would be read without the kernel's uniform-work-group
+// assumption, one extra load per thread)
+
+// host-side pointer predicates of the launchers: 16-byte alignment (float4 accesses); whether [a, a + abytes) and
+// [b, b + bbytes) share memory (a NULL b overlaps nothing)
+static inline bool aligned16(const void* q) { return ((uintptr_t)q & 15) == 0; }
+static inline bool overlaps(const void* a, long abytes, const void* b, long bbytes) {
+  const uintptr_t pa = (uintptr_t)a, pb = (uintptr_t)b;
+  return b && pa < pb + (uintptr_t)bbytes && pb < pa + (uintptr_t)abytes;
 }
 
 struct Taps {                               // filter taps travel as kernel arguments (no H2D copy)

@@ -9,9 +9,6 @@ static inline int gs_grid(long total, int block = 256) {
   return (int)(g < 1 ? 1 : (g > 32768 ? 32768 : g));
 }
 
-#define AFD_GRID_STRIDE(i, total) \
-  for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < (total); i += (long)gridDim.x * blockDim.x)
-
 // ---- GELU (nn.GELU exact) -----------------------------------------------------------------
 __global__ void gelu_fwd_k(const float* __restrict__ x, float* __restrict__ y, long n4, long n) {
   const float4* x4 = reinterpret_cast<const float4*>(x);

@@ -161,11 +161,6 @@ __global__ __launch_bounds__(256) void eq_terms_k(const double* __restrict__ coe
   if (threadIdx.x == 0) { out[3 * r] = s_d; out[3 * r + 1] = s_r; out[3 * r + 2] = cnt; }
 }
 
-static inline bool overlaps(const void* a, long abytes, const void* b, long bbytes) {
-  const char* pa = static_cast<const char*>(a); const char* pb = static_cast<const char*>(b);
-  return pa < pb + bbytes && pb < pa + abytes;
-}
-
 }  // namespace afd
 using namespace afd;
 

@@ -1,4 +1,5 @@
-// ddpm.hip -- F14/F16 DDPM noise / denoise / quantise, MSE loss, fused AdamW.
+// sampler.hip -- the diffusion math: noising, the sampler steps (DDPM, DDIM, DPM-Solver++(2M), learned variances; plain, guided
+// and masked), renoise, the likelihood bound, the training objectives and quantisation.  (The optimizer is optim.hip.)
 //
 // noise_images / denoise_step / quantize restate the reference's fp32 expression ORDER with one
 // IEEE rounding per torch op (no FMA contraction, correctly rounded sqrt and divide), so given the
@@ -16,11 +17,6 @@ static inline int gs_grid(long total, int block = 256) {
   long g = (total + block - 1) / block;
   return (int)(g < 1 ? 1 : (g > 32768 ? 32768 : g));
 }
-#define AFD_GRID_STRIDE(i, total) \
-  for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < (total); i += (long)gridDim.x * blockDim.x)
-// the same loop's start and stride, taken in a kernel and handed to a __device__ body (inside the body, blockDim.x would be
-// read without the kernel's uniform-work-group assumption: one extra load per thread)
-#define AFD_GRID_START blockIdx.x * (long)blockDim.x + threadIdx.x, (long)gridDim.x * blockDim.x
 
 // x_t = sqrt(ah[t]) * x + sqrt(1 - ah[t]) * eps
 __global__ void noise_images_k(const float* __restrict__ x, const float* __restrict__ eps, const int64_t* __restrict__ t,
@@ -35,62 +31,107 @@ __global__ void noise_images_k(const float* __restrict__ x, const float* __restr
   }
 }
 
-// x' = 1/sqrt(a) * (x - ((1-a)/sqrt(1-ah)) * eps) + sqrt(b) * noise
-__global__ void denoise_step_k(const float* __restrict__ x, const float* __restrict__ eps, const float* __restrict__ noise,
-                               const float* __restrict__ alpha, const float* __restrict__ alpha_hat, const float* __restrict__ beta,
-                               int step_arg, const int64_t* __restrict__ step_dev, float* __restrict__ out, long n) {
-  const int step = step_dev ? (int)step_dev[0] : step_arg;     // device-resident index: a captured graph replays for every i
-  const float a = alpha[step], ah = alpha_hat[step], bt = beta[step];
-  const float c1 = 1.0f / sqrtf(a);
-  const float c2 = (1.0f - a) / sqrtf(1.0f - ah);
-  const float sb = sqrtf(bt);
-  AFD_GRID_STRIDE(i, n) {
-    const float pe = c2 * eps[i];
-    const float inner = x[i] - pe;
-    const float lhs = c1 * inner;
-    const float nz = noise ? sb * noise[i] : 0.0f;       // sqrt(beta) * zeros == +0
-    out[i] = lhs + nz;
-  }
-}
-
-// ---- classifier-free guidance: the guided noise and the update above in one pass ------------------------------------
-// eps2 holds the 2n-row forward: element j of the conditional half at j, of the unconditional half at n + j.
-// e = torch.lerp(e_u, e_c, s) with ATen's scalar formula (aten/src/ATen/native/Lerp.h), one rounding per operation:
+// ---- sampler steps: DDPM and DDIM, plain, guided (kCfg), masked (kMasked) or both, one kernel template --------------------------
+// classifier-free guidance: eps holds the 2n-row forward, element j of the conditional half at j, of the unconditional half at
+// n + j, and e = torch.lerp(e_u, e_c, s) with ATen's scalar formula (aten/src/ATen/native/Lerp.h), one rounding per operation:
 //   |s| < 0.5:  u + s * (c - u)        otherwise:  c - (c - u) * (1 - s)
-// then exactly denoise_step_k's expression.  x_out may alias x (elementwise); x_out2 (optional) receives the same values:
-// the sampler writes both halves of its 2n input buffer, so the next forward needs no concatenation.
-struct CfgCoef {
-  float c1, c2, sb, s, one_minus_s;
+struct Guidance {
+  float s, one_minus_s;
   bool small;
 };
-__device__ __forceinline__ CfgCoef cfg_coef(const float* alpha, const float* alpha_hat, const float* beta, int step, float s) {
-  const float a = alpha[step], ah = alpha_hat[step], bt = beta[step];
-  CfgCoef k;
-  k.c1 = 1.0f / sqrtf(a);
-  k.c2 = (1.0f - a) / sqrtf(1.0f - ah);
-  k.sb = sqrtf(bt);
-  k.s = s;
-  k.one_minus_s = 1.0f - s;
-  k.small = fabsf(s) < 0.5f;
-  return k;
-}
+__device__ __forceinline__ Guidance guidance(float s) { return Guidance{s, 1.0f - s, fabsf(s) < 0.5f}; }
 __device__ __forceinline__ float cfg_lerp(float s, float one_minus_s, bool small, float ec, float eu) {
   const float d = ec - eu;
   return small ? eu + s * d : ec - d * one_minus_s;
 }
-__device__ __forceinline__ float denoise_update(const CfgCoef& k, float x, float e, float nz_in, bool has_noise) {
-  const float pe = k.c2 * e;
-  const float inner = x - pe;
-  const float lhs = k.c1 * inner;
-  const float nz = has_noise ? k.sb * nz_in : 0.0f;
-  return lhs + nz;
-}
 template <bool kCfg>
-__device__ __forceinline__ float denoise_eps(const CfgCoef& k, float ec, float eu) {
-  return kCfg ? cfg_lerp(k.s, k.one_minus_s, k.small, ec, eu) : ec;
+__device__ __forceinline__ float guided_eps(const Guidance& g, float ec, float eu) {
+  return kCfg ? cfg_lerp(g.s, g.one_minus_s, g.small, ec, eu) : ec;
 }
 
-// ---- masked step (inpainting, RePaint): the update above for the generated region, x0 noised to t_prev for the known one --
+// A sampler is a rule type: Args (what its kernel is handed), make(Args) (the coefficients, once per thread before the loop),
+// update(x, e, z, gen_noise) (the per-element expression) and, for the masked form, t_prev() and gen_takes_noise().  Step
+// indices given on the device (the *_dev pointers) let a captured graph replay for every step.
+
+// DDPM, step -> step - 1:  x' = 1/sqrt(a) * (x - ((1-a)/sqrt(1-ah)) * eps) + sqrt(b) * noise
+// masked: the generated region takes no noise at step 1 (the chain's last step)
+struct Ddpm {
+  struct Args {
+    const float *alpha, *alpha_hat, *beta;
+    int step;
+    const int64_t* step_dev;
+  };
+  float c1, c2, sb;
+  int step;
+  __device__ __forceinline__ static Ddpm at(const float* alpha, const float* alpha_hat, const float* beta, int step) {
+    const float a = alpha[step], ah = alpha_hat[step], bt = beta[step];
+    Ddpm k;
+    k.c1 = 1.0f / sqrtf(a);
+    k.c2 = (1.0f - a) / sqrtf(1.0f - ah);
+    k.sb = sqrtf(bt);
+    k.step = step;
+    return k;
+  }
+  __device__ __forceinline__ static Ddpm make(const Args& a) {
+    return at(a.alpha, a.alpha_hat, a.beta, a.step_dev ? (int)a.step_dev[0] : a.step);
+  }
+  __device__ __forceinline__ float update(float x, float e, float nz_in, bool has_noise) const {
+    const float pe = c2 * e;
+    const float inner = x - pe;
+    const float lhs = c1 * inner;
+    const float nz = has_noise ? sb * nz_in : 0.0f;       // sqrt(beta) * zeros == +0
+    return lhs + nz;
+  }
+  __device__ __forceinline__ int t_prev() const { return step > 0 ? step - 1 : 0; }
+  __device__ __forceinline__ bool gen_takes_noise() const { return step > 1; }
+};
+
+// DDIM (Song et al. 2021), one step t -> t_prev of a strided chain.  a_t = alpha_hat[t], a_p = alpha_hat[t_prev]; fp32, one
+// rounding per operation, in this order:
+//   x0  = (x - sqrt(1 - a_t) * e) / sqrt(a_t)
+//   r   = (1 - a_p) / (1 - a_t)        q = 1 - a_t / a_p
+//   var = (eta * eta) * (r * q)        sigma = sqrt(var)        dir = sqrt(max((1 - a_p) - var, 0))
+//   out = ((sqrt(a_p) * x0) + (dir * e)) + (noise ? sigma * noise : +0)
+// The division by sqrt(a_t) stays a division (a reciprocal would round differently).
+// masked: the generated region takes no noise when eta == 0 or t_prev == 0
+struct Ddim {
+  struct Args {
+    const float* alpha_hat;
+    int t, t_prev;
+    const int64_t *t_dev, *t_prev_dev;
+    float eta;
+  };
+  float sq1m_at, sq_at, sq_ap, sigma, dir, eta;
+  int tp;
+  __device__ __forceinline__ static Ddim make(const Args& a) {
+    const int t = a.t_dev ? (int)a.t_dev[0] : a.t;
+    const float eta = a.eta;
+    Ddim k;
+    k.tp = a.t_prev_dev ? (int)a.t_prev_dev[0] : a.t_prev;
+    k.eta = eta;
+    const float a_t = a.alpha_hat[t], a_p = a.alpha_hat[k.tp];
+    k.sq1m_at = sqrtf(1.0f - a_t);
+    k.sq_at = sqrtf(a_t);
+    k.sq_ap = sqrtf(a_p);
+    const float r = (1.0f - a_p) / (1.0f - a_t);
+    const float q = 1.0f - a_t / a_p;
+    const float var = (eta * eta) * (r * q);
+    k.sigma = sqrtf(var);
+    k.dir = sqrtf(fmaxf((1.0f - a_p) - var, 0.0f));
+    return k;
+  }
+  __device__ __forceinline__ float update(float x, float e, float z, bool has_noise) const {
+    const float pe = sq1m_at * e;
+    const float x0 = (x - pe) / sq_at;
+    const float mean = (sq_ap * x0) + (dir * e);
+    const float nz = has_noise ? sigma * z : 0.0f;
+    return mean + nz;
+  }
+  __device__ __forceinline__ int t_prev() const { return tp; }
+  __device__ __forceinline__ bool gen_takes_noise() const { return eta != 0.0f && tp > 0; }
+};
+
+// masked step (inpainting, RePaint): the rule's update for the generated region, x0 noised to t_prev for the known one:
 // known = t_prev == 0 ? x0 : (sqrt(a_p) * x0) + (sqrt(1 - a_p) * z), a_p = alpha_hat[t_prev] (noise_images_k's expression)
 // out   = mask[j] ? known : gen.  One noise tensor z serves both regions (each element reads its z once).
 struct KnownCoef {
@@ -119,278 +160,100 @@ __device__ __forceinline__ float4 masked4(const KnownCoef& k, uchar4 m, float4 x
   return r;
 }
 
-// Bodies shared by the guided (kCfg) and masked (kMasked) kernels, so the generated region cannot drift from the unmasked
-// update.  kMasked: the step is step -> step - 1, and its generated region takes no noise at step 1 (the chain's last step).
-// 16-byte accesses (n % 4 == 0, every float pointer 16-byte aligned, mask 4-byte aligned); n4 = n / 4
-template <bool kCfg, bool kMasked>
-__device__ __forceinline__ void denoise_step_x4_body(long i0, long stride, const float* x, const float* __restrict__ eps, const float* __restrict__ noise,
-                                                     const float* __restrict__ alpha, const float* __restrict__ alpha_hat,
-                                                     const float* __restrict__ beta, int step_arg, const int64_t* __restrict__ step_dev,
-                                                     float s, const float* __restrict__ x0, const uint8_t* __restrict__ mask,
-                                                     float* x_out, float* x_out2, long n4) {
-  const int step = step_dev ? (int)step_dev[0] : step_arg;
-  const CfgCoef k = cfg_coef(alpha, alpha_hat, beta, step, s);
-  const float4* x4 = reinterpret_cast<const float4*>(x);
-  const float4* ec4 = reinterpret_cast<const float4*>(eps);
-  const float4* eu4 = ec4 + n4;                                // read only when kCfg
-  const float4* nz4 = reinterpret_cast<const float4*>(noise);
+// The one loop of the family.  kCfg: eps holds 2n elements and s is the guidance scale.  kMasked: x0 and mask are read.  x_out
+// may alias x (elementwise); x_out2 (optional) receives the same values: the guided sampler writes both halves of its 2n input
+// buffer, so the next forward needs no concatenation.  VEC: 16-byte accesses and n counts float4s (launch_step decides).
+// The loop stays in the kernel: in a __device__ body, blockDim.x would be read without the kernel's uniform-work-group
+// assumption, one extra load per thread.
+template <class Rule, bool kCfg, bool kMasked, bool VEC>
+__global__ __launch_bounds__(256) void step_k(const float* x, const float* __restrict__ eps, const float* __restrict__ noise,
+                                              const typename Rule::Args args, float s, const float* __restrict__ x0,
+                                              const uint8_t* __restrict__ mask, float* x_out, float* x_out2, long n) {
+  const Rule k = Rule::make(args);
+  const Guidance g = guidance(s);
   const bool has_noise = noise != nullptr;
-  const bool gen_noise = kMasked ? has_noise && step > 1 : has_noise;
-  const KnownCoef kn = kMasked ? known_coef(alpha_hat, step > 0 ? step - 1 : 0) : KnownCoef{};
-  for (long i = i0; i < n4; i += stride) {
-    const float4 xv = x4[i], c = ec4[i];
-    const float4 u = kCfg ? eu4[i] : c;
-    const float4 z = has_noise ? nz4[i] : make_float4(0.f, 0.f, 0.f, 0.f);
-    float4 r;
-    r.x = denoise_update(k, xv.x, denoise_eps<kCfg>(k, c.x, u.x), z.x, gen_noise);
-    r.y = denoise_update(k, xv.y, denoise_eps<kCfg>(k, c.y, u.y), z.y, gen_noise);
-    r.z = denoise_update(k, xv.z, denoise_eps<kCfg>(k, c.z, u.z), z.z, gen_noise);
-    r.w = denoise_update(k, xv.w, denoise_eps<kCfg>(k, c.w, u.w), z.w, gen_noise);
-    if (kMasked)
-      r = masked4(kn, reinterpret_cast<const uchar4*>(mask)[i], reinterpret_cast<const float4*>(x0)[i], z, r);
-    reinterpret_cast<float4*>(x_out)[i] = r;
-    if (x_out2) reinterpret_cast<float4*>(x_out2)[i] = r;
-  }
-}
-template <bool kCfg, bool kMasked>
-__device__ __forceinline__ void denoise_step_body(long i0, long stride, const float* x, const float* __restrict__ eps, const float* __restrict__ noise,
-                                                  const float* __restrict__ alpha, const float* __restrict__ alpha_hat,
-                                                  const float* __restrict__ beta, int step_arg, const int64_t* __restrict__ step_dev,
-                                                  float s, const float* __restrict__ x0, const uint8_t* __restrict__ mask,
-                                                  float* x_out, float* x_out2, long n) {
-  const int step = step_dev ? (int)step_dev[0] : step_arg;
-  const CfgCoef k = cfg_coef(alpha, alpha_hat, beta, step, s);
-  const bool has_noise = noise != nullptr;
-  const bool gen_noise = kMasked ? has_noise && step > 1 : has_noise;
-  const KnownCoef kn = kMasked ? known_coef(alpha_hat, step > 0 ? step - 1 : 0) : KnownCoef{};
-  for (long i = i0; i < n; i += stride) {
-    const float z = has_noise ? noise[i] : 0.0f;
-    float r = denoise_update(k, x[i], denoise_eps<kCfg>(k, eps[i], kCfg ? eps[n + i] : 0.0f), z, gen_noise);
-    if (kMasked && mask[i]) r = known_value(kn, x0[i], z);
-    x_out[i] = r;
-    if (x_out2) x_out2[i] = r;
+  const bool gen_noise = kMasked ? has_noise && k.gen_takes_noise() : has_noise;
+  const KnownCoef kn = kMasked ? known_coef(args.alpha_hat, k.t_prev()) : KnownCoef{};
+  auto gen = [&](float xv, float ec, float eu, float z) { return k.update(xv, guided_eps<kCfg>(g, ec, eu), z, gen_noise); };
+  AFD_GRID_STRIDE(i, n) {
+    if (VEC) {
+      const float4 xv = reinterpret_cast<const float4*>(x)[i], c = reinterpret_cast<const float4*>(eps)[i];
+      const float4 u = kCfg ? reinterpret_cast<const float4*>(eps)[n + i] : c;
+      const float4 z = has_noise ? reinterpret_cast<const float4*>(noise)[i] : make_float4(0.f, 0.f, 0.f, 0.f);
+      float4 r = make_float4(gen(xv.x, c.x, u.x, z.x), gen(xv.y, c.y, u.y, z.y), gen(xv.z, c.z, u.z, z.z), gen(xv.w, c.w, u.w, z.w));
+      if (kMasked)
+        r = masked4(kn, reinterpret_cast<const uchar4*>(mask)[i], reinterpret_cast<const float4*>(x0)[i], z, r);
+      reinterpret_cast<float4*>(x_out)[i] = r;
+      if (x_out2) reinterpret_cast<float4*>(x_out2)[i] = r;
+    } else {
+      const float z = has_noise ? noise[i] : 0.0f;
+      float r = gen(x[i], eps[i], kCfg ? eps[n + i] : 0.0f, z);
+      if (kMasked && mask[i]) r = known_value(kn, x0[i], z);
+      x_out[i] = r;
+      if (x_out2) x_out2[i] = r;
+    }
   }
 }
 
-__global__ __launch_bounds__(256) void denoise_step_cfg_x4_k(const float* x, const float* __restrict__ eps2, const float* __restrict__ noise,
-                                                             const float* __restrict__ alpha, const float* __restrict__ alpha_hat,
-                                                             const float* __restrict__ beta, int step_arg, const int64_t* __restrict__ step_dev,
-                                                             float s, float* x_out, float* x_out2, long n4) {
-  denoise_step_x4_body<true, false>(AFD_GRID_START, x, eps2, noise, alpha, alpha_hat, beta, step_arg, step_dev, s, nullptr, nullptr, x_out, x_out2, n4);
+// Launch geometry of the streaming step kernels (these, renoise, DPM++): 16-byte accesses when n % 4 == 0 and every pointer
+// given is 16-byte aligned (an absent optional pointer, NULL, counts as aligned); memory-bound, so at most 2048 workgroups and
+// the loop takes the rest.
+static inline bool vec_ok(long n, std::initializer_list<const void*> ptrs) {
+  for (const void* p : ptrs)
+    if (!aligned16(p)) return false;
+  return n % 4 == 0;
 }
-__global__ __launch_bounds__(256) void denoise_step_cfg_k(const float* x, const float* __restrict__ eps2, const float* __restrict__ noise,
-                                                          const float* __restrict__ alpha, const float* __restrict__ alpha_hat,
-                                                          const float* __restrict__ beta, int step_arg, const int64_t* __restrict__ step_dev,
-                                                          float s, float* x_out, float* x_out2, long n) {
-  denoise_step_body<true, false>(AFD_GRID_START, x, eps2, noise, alpha, alpha_hat, beta, step_arg, step_dev, s, nullptr, nullptr, x_out, x_out2, n);
-}
-// masked DDPM step, plain (eps: n elements) or guided (kCfg, eps: 2n)
-template <bool kCfg>
-__global__ __launch_bounds__(256) void denoise_step_masked_x4_k(const float* x, const float* __restrict__ eps, const float* __restrict__ noise,
-                                                                const float* __restrict__ alpha, const float* __restrict__ alpha_hat,
-                                                                const float* __restrict__ beta, int step_arg,
-                                                                const int64_t* __restrict__ step_dev, float s, const float* __restrict__ x0,
-                                                                const uint8_t* __restrict__ mask, float* x_out, float* x_out2, long n4) {
-  denoise_step_x4_body<kCfg, true>(AFD_GRID_START, x, eps, noise, alpha, alpha_hat, beta, step_arg, step_dev, s, x0, mask, x_out, x_out2, n4);
-}
-template <bool kCfg>
-__global__ __launch_bounds__(256) void denoise_step_masked_k(const float* x, const float* __restrict__ eps, const float* __restrict__ noise,
-                                                             const float* __restrict__ alpha, const float* __restrict__ alpha_hat,
-                                                             const float* __restrict__ beta, int step_arg,
-                                                             const int64_t* __restrict__ step_dev, float s, const float* __restrict__ x0,
-                                                             const uint8_t* __restrict__ mask, float* x_out, float* x_out2, long n) {
-  denoise_step_body<kCfg, true>(AFD_GRID_START, x, eps, noise, alpha, alpha_hat, beta, step_arg, step_dev, s, x0, mask, x_out, x_out2, n);
-}
+static inline long step_grid(long work) { return std::min<long>(2048, std::max<long>(1, (work + 255) / 256)); }
 
-static int launch_denoise_step_cfg(const float* x, const float* eps2, const float* noise, const float* alpha, const float* alpha_hat,
-                                   const float* beta, int i, const int64_t* t_dev, float s, float* x_out, float* x_out2, long n,
-                                   hipStream_t st) {
-  auto a16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
-  const bool vec = n % 4 == 0 && a16(x) && a16(eps2) && a16(x_out) && (!noise || a16(noise)) && (!x_out2 || a16(x_out2));
+template <class Rule, bool kCfg, bool kMasked>
+static void launch_step(const float* x, const float* eps, const float* noise, const typename Rule::Args& args, float s,
+                        const float* x0, const uint8_t* mask, float* x_out, float* x_out2, long n, hipStream_t st) {
+  // The plain DDPM step keeps the geometry it has always had, scalar accesses on up to 32768 workgroups (gs_grid): the 16-byte
+  // form has not been shown to be as fast on the flagship's sampling loop.
+  const bool plain_ddpm = !kCfg && !kMasked && std::is_same<Rule, Ddpm>::value;
+  const bool vec = !plain_ddpm && vec_ok(n, {x, eps, noise, x0, x_out, x_out2}) && (reinterpret_cast<uintptr_t>(mask) & 3) == 0;
   const long work = vec ? n / 4 : n;
-  const int grid = (int)std::min<long>(2048, std::max<long>(1, (work + 255) / 256));      // memory-bound: grid-stride the rest
-  if (vec)
-    hipLaunchKernelGGL(denoise_step_cfg_x4_k, dim3(grid), dim3(256), 0, st, x, eps2, noise, alpha, alpha_hat, beta, i, t_dev, s, x_out,
-                       x_out2, work);
-  else
-    hipLaunchKernelGGL(denoise_step_cfg_k, dim3(grid), dim3(256), 0, st, x, eps2, noise, alpha, alpha_hat, beta, i, t_dev, s, x_out,
-                       x_out2, n);
+  auto kern = vec ? step_k<Rule, kCfg, kMasked, true> : step_k<Rule, kCfg, kMasked, false>;
+  hipLaunchKernelGGL(kern, dim3(plain_ddpm ? gs_grid(n) : step_grid(work)), dim3(256), 0, st, x, eps, noise, args, s, x0, mask, x_out,
+                     x_out2, work);
+}
+
+// ---- the checks of the step family's entry points ----
+// Which of a sampler's eight entry points is being served: its name (for messages), whether the step indices are read on the
+// device, whether eps holds the guided 2n rows, whether x0 / mask select a known region.
+struct StepForm {
+  const char* name;
+  bool dev, cfg, masked;
+};
+// x0 and mask are read by every element while x_out / x_out2 are written: they must not share memory
+static inline bool masked_inputs_apart(const float* x0, const uint8_t* mask, const float* x_out, const float* x_out2, long n) {
+  const long fb = n * (long)sizeof(float);
+  return !overlaps(x0, fb, x_out, fb) && !overlaps(x0, fb, x_out2, fb) && !overlaps(mask, n, x_out, fb) && !overlaps(mask, n, x_out2, fb);
+}
+// The checks both samplers share, before their own: the pointers (tables_ok: the sampler's schedule tables and device indices,
+// named by `tables`), n, and the masked forms' x0 / mask against the outputs.
+static int check_step_buffers(const StepForm& f, bool tables_ok, const char* tables, const float* x, const float* eps,
+                              const float* x0, const uint8_t* mask, const float* x_out, const float* x_out2, long n) {
+  AFD_REQUIRE(x && eps && x_out && tables_ok && (!f.masked || (x0 && mask)), "%s: x, %s%s, %s and x_out must not be NULL", f.name,
+              f.cfg ? "eps2" : "eps", f.masked ? ", x0, mask" : "", tables);
+  AFD_REQUIRE(n > 0, "%s: n must be positive (got %ld)", f.name, n);
+  AFD_REQUIRE(!f.masked || masked_inputs_apart(x0, mask, x_out, x_out2, n), "%s: x0 and mask must not overlap x_out or x_out2", f.name);
   return AFD_OK;
 }
-
-// ---- DDIM (Song et al. 2021): one step t -> t_prev of a strided chain ------------------------------------------------
-// a_t = alpha_hat[t], a_p = alpha_hat[t_prev]; fp32, one rounding per operation, in this order:
-//   x0  = (x - sqrt(1 - a_t) * e) / sqrt(a_t)
-//   r   = (1 - a_p) / (1 - a_t)        q = 1 - a_t / a_p
-//   var = (eta * eta) * (r * q)        sigma = sqrt(var)        dir = sqrt(max((1 - a_p) - var, 0))
-//   out = ((sqrt(a_p) * x0) + (dir * e)) + (noise ? sigma * noise : +0)
-// The division by sqrt(a_t) stays a division (a reciprocal would round differently).  With CFG, e is cfg_lerp of the
-// conditional (j) and unconditional (n + j) halves of eps2 first.  x_out may alias x; x_out2 is optional (nullptr).
-struct DdimCoef {
-  float sq1m_at, sq_at, sq_ap, sigma, dir, s, one_minus_s;
-  bool small;
-};
-__device__ __forceinline__ DdimCoef ddim_coef(const float* alpha_hat, int t, int tp, float eta, float s) {
-  const float a_t = alpha_hat[t], a_p = alpha_hat[tp];
-  DdimCoef k;
-  k.sq1m_at = sqrtf(1.0f - a_t);
-  k.sq_at = sqrtf(a_t);
-  k.sq_ap = sqrtf(a_p);
-  const float r = (1.0f - a_p) / (1.0f - a_t);
-  const float q = 1.0f - a_t / a_p;
-  const float var = (eta * eta) * (r * q);
-  k.sigma = sqrtf(var);
-  k.dir = sqrtf(fmaxf((1.0f - a_p) - var, 0.0f));
-  k.s = s;
-  k.one_minus_s = 1.0f - s;
-  k.small = fabsf(s) < 0.5f;
-  return k;
+// After the sampler's own checks: the known region is x0 noised to t_prev, so it needs the noise unless t_prev == 0.  t_prev < 0:
+// not known on the host (a *_dev form), where the noise is always required.
+static int check_known_noise(const StepForm& f, const float* noise, int t_prev) {
+  AFD_REQUIRE(!f.masked || noise || t_prev == 0, "%s: noise must not be NULL %s(it noises the known region)", f.name,
+              f.dev ? "" : "when t_prev > 0 ");
+  return AFD_OK;
 }
-__device__ __forceinline__ float ddim_update(const DdimCoef& k, float x, float e, float z, bool has_noise) {
-  const float pe = k.sq1m_at * e;
-  const float x0 = (x - pe) / k.sq_at;
-  const float mean = (k.sq_ap * x0) + (k.dir * e);
-  const float nz = has_noise ? k.sigma * z : 0.0f;
-  return mean + nz;
-}
-template <bool kCfg>
-__device__ __forceinline__ float ddim_eps(const DdimCoef& k, float ec, float eu) {
-  return kCfg ? cfg_lerp(k.s, k.one_minus_s, k.small, ec, eu) : ec;
-}
-
-// Bodies shared by the unmasked and masked (kMasked) kernels.  kMasked: the generated region takes no noise when eta == 0 or
-// t_prev == 0; the known region is x0 noised to t_prev (known_value).
-// 16-byte accesses (n % 4 == 0, every float pointer 16-byte aligned, mask 4-byte aligned); n4 = n / 4.  kCfg: eps holds 2n
-// elements.
-template <bool kCfg, bool kMasked>
-__device__ __forceinline__ void ddim_step_x4_body(long i0, long stride, const float* x, const float* __restrict__ eps, const float* __restrict__ noise,
-                                                  const float* __restrict__ alpha_hat, int t_arg, int tp_arg,
-                                                  const int64_t* __restrict__ t_dev, const int64_t* __restrict__ tp_dev, float eta,
-                                                  float s, const float* __restrict__ x0, const uint8_t* __restrict__ mask,
-                                                  float* x_out, float* x_out2, long n4) {
-  const int t = t_dev ? (int)t_dev[0] : t_arg;                 // device-resident indices: a captured graph replays every step
-  const int tp = tp_dev ? (int)tp_dev[0] : tp_arg;
-  const DdimCoef k = ddim_coef(alpha_hat, t, tp, eta, s);
-  const float4* x4 = reinterpret_cast<const float4*>(x);
-  const float4* ec4 = reinterpret_cast<const float4*>(eps);
-  const float4* eu4 = ec4 + n4;                                // read only when kCfg
-  const float4* nz4 = reinterpret_cast<const float4*>(noise);
-  const bool has_noise = noise != nullptr;
-  const bool gen_noise = kMasked ? has_noise && eta != 0.0f && tp > 0 : has_noise;
-  const KnownCoef kn = kMasked ? known_coef(alpha_hat, tp) : KnownCoef{};
-  for (long i = i0; i < n4; i += stride) {
-    const float4 xv = x4[i], c = ec4[i];
-    const float4 u = kCfg ? eu4[i] : c;
-    const float4 z = has_noise ? nz4[i] : make_float4(0.f, 0.f, 0.f, 0.f);
-    float4 r;
-    r.x = ddim_update(k, xv.x, ddim_eps<kCfg>(k, c.x, u.x), z.x, gen_noise);
-    r.y = ddim_update(k, xv.y, ddim_eps<kCfg>(k, c.y, u.y), z.y, gen_noise);
-    r.z = ddim_update(k, xv.z, ddim_eps<kCfg>(k, c.z, u.z), z.z, gen_noise);
-    r.w = ddim_update(k, xv.w, ddim_eps<kCfg>(k, c.w, u.w), z.w, gen_noise);
-    if (kMasked)
-      r = masked4(kn, reinterpret_cast<const uchar4*>(mask)[i], reinterpret_cast<const float4*>(x0)[i], z, r);
-    reinterpret_cast<float4*>(x_out)[i] = r;
-    if (x_out2) reinterpret_cast<float4*>(x_out2)[i] = r;
-  }
-}
-template <bool kCfg, bool kMasked>
-__device__ __forceinline__ void ddim_step_body(long i0, long stride, const float* x, const float* __restrict__ eps, const float* __restrict__ noise,
-                                               const float* __restrict__ alpha_hat, int t_arg, int tp_arg,
-                                               const int64_t* __restrict__ t_dev, const int64_t* __restrict__ tp_dev, float eta, float s,
-                                               const float* __restrict__ x0, const uint8_t* __restrict__ mask, float* x_out,
-                                               float* x_out2, long n) {
-  const int t = t_dev ? (int)t_dev[0] : t_arg;
-  const int tp = tp_dev ? (int)tp_dev[0] : tp_arg;
-  const DdimCoef k = ddim_coef(alpha_hat, t, tp, eta, s);
-  const bool has_noise = noise != nullptr;
-  const bool gen_noise = kMasked ? has_noise && eta != 0.0f && tp > 0 : has_noise;
-  const KnownCoef kn = kMasked ? known_coef(alpha_hat, tp) : KnownCoef{};
-  for (long i = i0; i < n; i += stride) {
-    const float e = ddim_eps<kCfg>(k, eps[i], kCfg ? eps[n + i] : 0.0f);
-    const float z = has_noise ? noise[i] : 0.0f;
-    float r = ddim_update(k, x[i], e, z, gen_noise);
-    if (kMasked && mask[i]) r = known_value(kn, x0[i], z);
-    x_out[i] = r;
-    if (x_out2) x_out2[i] = r;
-  }
-}
-
-template <bool kCfg>
-__global__ __launch_bounds__(256) void ddim_step_x4_k(const float* x, const float* __restrict__ eps, const float* __restrict__ noise,
-                                                      const float* __restrict__ alpha_hat, int t_arg, int tp_arg,
-                                                      const int64_t* __restrict__ t_dev, const int64_t* __restrict__ tp_dev, float eta,
-                                                      float s, float* x_out, float* x_out2, long n4) {
-  ddim_step_x4_body<kCfg, false>(AFD_GRID_START, x, eps, noise, alpha_hat, t_arg, tp_arg, t_dev, tp_dev, eta, s, nullptr, nullptr, x_out, x_out2, n4);
-}
-template <bool kCfg>
-__global__ __launch_bounds__(256) void ddim_step_k(const float* x, const float* __restrict__ eps, const float* __restrict__ noise,
-                                                   const float* __restrict__ alpha_hat, int t_arg, int tp_arg,
-                                                   const int64_t* __restrict__ t_dev, const int64_t* __restrict__ tp_dev, float eta,
-                                                   float s, float* x_out, float* x_out2, long n) {
-  ddim_step_body<kCfg, false>(AFD_GRID_START, x, eps, noise, alpha_hat, t_arg, tp_arg, t_dev, tp_dev, eta, s, nullptr, nullptr, x_out, x_out2, n);
-}
-template <bool kCfg>
-__global__ __launch_bounds__(256) void ddim_step_masked_x4_k(const float* x, const float* __restrict__ eps, const float* __restrict__ noise,
-                                                             const float* __restrict__ alpha_hat, int t_arg, int tp_arg,
-                                                             const int64_t* __restrict__ t_dev, const int64_t* __restrict__ tp_dev,
-                                                             float eta, float s, const float* __restrict__ x0,
-                                                             const uint8_t* __restrict__ mask, float* x_out, float* x_out2, long n4) {
-  ddim_step_x4_body<kCfg, true>(AFD_GRID_START, x, eps, noise, alpha_hat, t_arg, tp_arg, t_dev, tp_dev, eta, s, x0, mask, x_out, x_out2, n4);
-}
-template <bool kCfg>
-__global__ __launch_bounds__(256) void ddim_step_masked_k(const float* x, const float* __restrict__ eps, const float* __restrict__ noise,
-                                                          const float* __restrict__ alpha_hat, int t_arg, int tp_arg,
-                                                          const int64_t* __restrict__ t_dev, const int64_t* __restrict__ tp_dev,
-                                                          float eta, float s, const float* __restrict__ x0,
-                                                          const uint8_t* __restrict__ mask, float* x_out, float* x_out2, long n) {
-  ddim_step_body<kCfg, true>(AFD_GRID_START, x, eps, noise, alpha_hat, t_arg, tp_arg, t_dev, tp_dev, eta, s, x0, mask, x_out, x_out2, n);
-}
-
-template <bool kCfg>
-static void launch_ddim_step(const float* x, const float* eps, const float* noise, const float* alpha_hat, int t, int tp,
-                             const int64_t* t_dev, const int64_t* tp_dev, float eta, float s, float* x_out, float* x_out2, long n,
-                             hipStream_t st) {
-  auto a16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
-  const bool vec = n % 4 == 0 && a16(x) && a16(eps) && a16(x_out) && (!noise || a16(noise)) && (!x_out2 || a16(x_out2));
-  const long work = vec ? n / 4 : n;
-  const int grid = (int)std::min<long>(2048, std::max<long>(1, (work + 255) / 256));      // memory-bound: grid-stride the rest
-  if (vec)
-    hipLaunchKernelGGL(ddim_step_x4_k<kCfg>, dim3(grid), dim3(256), 0, st, x, eps, noise, alpha_hat, t, tp, t_dev, tp_dev, eta, s,
-                       x_out, x_out2, work);
-  else
-    hipLaunchKernelGGL(ddim_step_k<kCfg>, dim3(grid), dim3(256), 0, st, x, eps, noise, alpha_hat, t, tp, t_dev, tp_dev, eta, s,
-                       x_out, x_out2, n);
-}
-
-// one masked launch: the 16-byte kernel when n % 4 == 0 and the pointers allow it, else the scalar one
-static inline long step_grid(long work) { return std::min<long>(2048, std::max<long>(1, (work + 255) / 256)); }
-static inline bool masked_vec(long n, const float* x, const float* eps, const float* noise, const float* x0, const uint8_t* mask,
-                              const float* x_out, const float* x_out2) {
-  auto a16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
-  return n % 4 == 0 && a16(x) && a16(eps) && a16(x0) && a16(x_out) && (!noise || a16(noise)) && (!x_out2 || a16(x_out2)) &&
-         (reinterpret_cast<uintptr_t>(mask) & 3) == 0;
-}
-template <bool kCfg>
-static void launch_denoise_step_masked(const float* x, const float* eps, const float* noise, const float* x0, const uint8_t* mask,
-                                       const float* alpha, const float* alpha_hat, const float* beta, int i, const int64_t* t_dev,
-                                       float s, float* x_out, float* x_out2, long n, hipStream_t st) {
-  if (masked_vec(n, x, eps, noise, x0, mask, x_out, x_out2))
-    hipLaunchKernelGGL(denoise_step_masked_x4_k<kCfg>, dim3(step_grid(n / 4)), dim3(256), 0, st, x, eps, noise, alpha, alpha_hat,
-                       beta, i, t_dev, s, x0, mask, x_out, x_out2, n / 4);
-  else
-    hipLaunchKernelGGL(denoise_step_masked_k<kCfg>, dim3(step_grid(n)), dim3(256), 0, st, x, eps, noise, alpha, alpha_hat, beta, i,
-                       t_dev, s, x0, mask, x_out, x_out2, n);
-}
-template <bool kCfg>
-static void launch_ddim_step_masked(const float* x, const float* eps, const float* noise, const float* x0, const uint8_t* mask,
-                                    const float* alpha_hat, int t, int tp, const int64_t* t_dev, const int64_t* tp_dev, float eta,
-                                    float s, float* x_out, float* x_out2, long n, hipStream_t st) {
-  if (masked_vec(n, x, eps, noise, x0, mask, x_out, x_out2))
-    hipLaunchKernelGGL(ddim_step_masked_x4_k<kCfg>, dim3(step_grid(n / 4)), dim3(256), 0, st, x, eps, noise, alpha_hat, t, tp, t_dev,
-                       tp_dev, eta, s, x0, mask, x_out, x_out2, n / 4);
-  else
-    hipLaunchKernelGGL(ddim_step_masked_k<kCfg>, dim3(step_grid(n)), dim3(256), 0, st, x, eps, noise, alpha_hat, t, tp, t_dev, tp_dev,
-                       eta, s, x0, mask, x_out, x_out2, n);
+template <class Rule>
+static int launch_step_form(const StepForm& f, const float* x, const float* eps, const float* noise, const typename Rule::Args& args,
+                            float s, const float* x0, const uint8_t* mask, float* x_out, float* x_out2, long n, afd_stream_t st) {
+  auto launch = f.cfg ? (f.masked ? launch_step<Rule, true, true> : launch_step<Rule, true, false>)
+                      : (f.masked ? launch_step<Rule, false, true> : launch_step<Rule, false, false>);
+  launch(x, eps, noise, args, s, x0, mask, x_out, x_out2, n, as_stream(st));
+  return check_launch(f.name);
 }
 
 // ---- renoise: q(x_{t_to} | x_{t_from}) of the forward process in one jump (RePaint's up-move) ---------------------------
@@ -425,8 +288,7 @@ __global__ __launch_bounds__(256) void renoise_k(const float* x, const float* __
 // eager loop and graph replay.  x_out may alias x; x0_out may be x0_prev itself (each element reads its x0_prev before it
 // writes x0_out) but overlaps nothing else; x_out2 is optional.  VEC: n % 4 == 0, every pointer 16-byte aligned; n counts float4s.
 struct DpmCoef {
-  float alpha, sigma, A, B0, B1, s, one_minus_s;
-  bool small;
+  float alpha, sigma, A, B0, B1;
 };
 __device__ __forceinline__ float dpmpp_update(const DpmCoef& k, float x, float e, float xp, bool has_prev, float& x0) {
   const float pe = k.sigma * e;
@@ -435,10 +297,6 @@ __device__ __forceinline__ float dpmpp_update(const DpmCoef& k, float x, float e
   const float m = l + r;
   const float p = has_prev ? k.B1 * xp : 0.0f;
   return m + p;
-}
-template <bool kCfg>
-__device__ __forceinline__ float dpmpp_eps(const DpmCoef& k, float ec, float eu) {
-  return kCfg ? cfg_lerp(k.s, k.one_minus_s, k.small, ec, eu) : ec;
 }
 template <bool kCfg, bool VEC>
 __global__ __launch_bounds__(256) void dpmpp_step_k(const float* x, const float* __restrict__ eps, const float* x0_prev,
@@ -450,9 +308,7 @@ __global__ __launch_bounds__(256) void dpmpp_step_k(const float* x, const float*
   k.A = coef[2];
   k.B0 = coef[3];
   k.B1 = coef[4];
-  k.s = s;
-  k.one_minus_s = 1.0f - s;
-  k.small = fabsf(s) < 0.5f;
+  const Guidance g = guidance(s);
   const bool has_prev = x0_prev != nullptr;
   AFD_GRID_STRIDE(i, n) {
     if (VEC) {
@@ -460,16 +316,16 @@ __global__ __launch_bounds__(256) void dpmpp_step_k(const float* x, const float*
       const float4 u = kCfg ? reinterpret_cast<const float4*>(eps)[n + i] : c;
       const float4 p = has_prev ? reinterpret_cast<const float4*>(x0_prev)[i] : make_float4(0.f, 0.f, 0.f, 0.f);
       float4 r, x0;
-      r.x = dpmpp_update(k, xv.x, dpmpp_eps<kCfg>(k, c.x, u.x), p.x, has_prev, x0.x);
-      r.y = dpmpp_update(k, xv.y, dpmpp_eps<kCfg>(k, c.y, u.y), p.y, has_prev, x0.y);
-      r.z = dpmpp_update(k, xv.z, dpmpp_eps<kCfg>(k, c.z, u.z), p.z, has_prev, x0.z);
-      r.w = dpmpp_update(k, xv.w, dpmpp_eps<kCfg>(k, c.w, u.w), p.w, has_prev, x0.w);
+      r.x = dpmpp_update(k, xv.x, guided_eps<kCfg>(g, c.x, u.x), p.x, has_prev, x0.x);
+      r.y = dpmpp_update(k, xv.y, guided_eps<kCfg>(g, c.y, u.y), p.y, has_prev, x0.y);
+      r.z = dpmpp_update(k, xv.z, guided_eps<kCfg>(g, c.z, u.z), p.z, has_prev, x0.z);
+      r.w = dpmpp_update(k, xv.w, guided_eps<kCfg>(g, c.w, u.w), p.w, has_prev, x0.w);
       reinterpret_cast<float4*>(x_out)[i] = r;
       if (x_out2) reinterpret_cast<float4*>(x_out2)[i] = r;
       reinterpret_cast<float4*>(x0_out)[i] = x0;
     } else {
       float x0;
-      const float e = dpmpp_eps<kCfg>(k, eps[i], kCfg ? eps[n + i] : 0.0f);
+      const float e = guided_eps<kCfg>(g, eps[i], kCfg ? eps[n + i] : 0.0f);
       const float r = dpmpp_update(k, x[i], e, has_prev ? x0_prev[i] : 0.0f, has_prev, x0);
       x_out[i] = r;
       if (x_out2) x_out2[i] = r;
@@ -480,11 +336,9 @@ __global__ __launch_bounds__(256) void dpmpp_step_k(const float* x, const float*
 template <bool kCfg>
 static void launch_dpmpp_step(const float* x, const float* eps, const float* x0_prev, const float* coef, float s, float* x_out,
                               float* x_out2, float* x0_out, long n, hipStream_t st) {
-  auto a16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
-  const bool vec = n % 4 == 0 && a16(x) && a16(eps) && a16(x_out) && a16(x0_out) && (!x0_prev || a16(x0_prev)) &&
-                   (!x_out2 || a16(x_out2));
+  const bool vec = vec_ok(n, {x, eps, x0_prev, x_out, x_out2, x0_out});
   const long work = vec ? n / 4 : n;
-  const int grid = (int)std::min<long>(2048, std::max<long>(1, (work + 255) / 256));      // memory-bound: grid-stride the rest
+  const long grid = step_grid(work);
   if (vec)
     hipLaunchKernelGGL((dpmpp_step_k<kCfg, true>), dim3(grid), dim3(256), 0, st, x, eps, x0_prev, coef, s, x_out, x_out2, x0_out, work);
   else
@@ -524,30 +378,6 @@ __global__ __launch_bounds__(256) void noise_images_gather_k(const float* __rest
   }
 }
 
-// Sum of two fp64 values over a 256-thread workgroup in a fixed order: a shuffle tree inside each wave, then the four waves'
-// partial sums in wave order.  The result is valid in thread 0.  red: 8 doubles of LDS.
-__device__ __forceinline__ void block_sum2_f64(double& a, double& b, double* red) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    a += __shfl_down(a, o, kWave);
-    b += __shfl_down(b, o, kWave);
-  }
-  const int w = threadIdx.x >> 6;
-  if ((threadIdx.x & 63) == 0) {
-    red[2 * w] = a;
-    red[2 * w + 1] = b;
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    a = red[0];
-    b = red[1];
-    for (int i = 1; i < (int)(blockDim.x >> 6); ++i) {
-      a += red[2 * i];
-      b += red[2 * i + 1];
-    }
-  }
-}
-
 // Ho et al.'s discretised Gaussian, log p of the 8-bit level x0 under N(mean, exp(2 log_scale)), in fp64: bins of half-width
 // 1/255, the edge bins open below -0.999 and above 0.999, Phi by the tanh approximation, probabilities clamped at 1e-12.
 __device__ __forceinline__ double approx_std_normal_cdf(double x) {
@@ -566,7 +396,7 @@ __device__ __forceinline__ double decoder_log_prob(double x, double mean, double
 //   sq[r]   = sum_j (double(eps_hat_j) - double(eps_j))^2
 //   term[r] = w_t * sq[r] + per * c_t                                                       t != 1: KL(q || p_theta)
 //           = -sum_j decoder_log_prob(x0_j, mean_j, exp(-log_scale_1)),                    t == 1: the decoder
-// with mean_j = denoise_step_k's fp32 expression at step 1 without noise, c1 * (x_t - c2 * eps_hat) (what the sampler returns).
+// with mean_j = Ddpm::update's fp32 expression at step 1 without noise, c1 * (x_t - c2 * eps_hat) (what the sampler returns).
 // Only decoder rows read x0 and x_t.  Each thread sums its elements in index order (x, y, z, w within a float4).
 template <bool VEC>
 __global__ __launch_bounds__(256) void vlb_terms_k(const float* __restrict__ x0, const int64_t* __restrict__ img,
@@ -581,7 +411,7 @@ __global__ __launch_bounds__(256) void vlb_terms_k(const float* __restrict__ x0,
   const long row = r * per;
   double s_sq = 0.0, s_ll = 0.0;
   if (tr == 1) {                                    // uniform per workgroup
-    const CfgCoef k = cfg_coef(alpha, alpha_hat, beta, 1, 0.0f);
+    const Ddpm k = Ddpm::at(alpha, alpha_hat, beta, 1);
     const double inv_stdv = exp(-coef[4 * 1 + 2]);              // row t = 1, log_scale
     const long src = img[r] * per;
     for (long j = threadIdx.x; j < per; j += blockDim.x) {
@@ -594,12 +424,12 @@ __global__ __launch_bounds__(256) void vlb_terms_k(const float* __restrict__ x0,
         for (int q = 0; q < 4; ++q) {
           const double d = (double)hv[q] - (double)ev[q];
           s_sq += d * d;
-          s_ll += decoder_log_prob(vv[q], denoise_update(k, xv[q], hv[q], 0.0f, false), inv_stdv);
+          s_ll += decoder_log_prob(vv[q], k.update(xv[q], hv[q], 0.0f, false), inv_stdv);
         }
       } else {
         const double d = (double)eps_hat[row + j] - (double)eps[row + j];
         s_sq += d * d;
-        s_ll += decoder_log_prob(x0[src + j], denoise_update(k, xt[row + j], eps_hat[row + j], 0.0f, false), inv_stdv);
+        s_ll += decoder_log_prob(x0[src + j], k.update(xt[row + j], eps_hat[row + j], 0.0f, false), inv_stdv);
       }
     }
   } else {
@@ -878,7 +708,7 @@ __device__ __forceinline__ double lvar_decoder(double x, double mean, double v, 
 struct LvarRow {
   double lb, lbt, kt, sa64, sb64, f2;
   float sa, sb;            // noise_images_k's two roots
-  CfgCoef dec;             // denoise_step_k's coefficients at step 1
+  Ddpm dec;                // the DDPM rule at step 1
   bool is_dec;
 };
 __device__ __forceinline__ LvarRow lvar_row(const double* __restrict__ lv_coef, const float* __restrict__ alpha,
@@ -895,7 +725,7 @@ __device__ __forceinline__ LvarRow lvar_row(const double* __restrict__ lv_coef, 
   w.lbt = lv_coef[3 * t + 1];
   w.kt = lv_coef[3 * t + 2];
   w.is_dec = t == 1;
-  w.dec = cfg_coef(alpha, alpha_hat, beta, 1, 0.0f);
+  w.dec = Ddpm::at(alpha, alpha_hat, beta, 1);
   return w;
 }
 template <bool GRAD>
@@ -904,7 +734,7 @@ __device__ __forceinline__ double lvar_term(const LvarRow& w, int kind, float p,
   const double df = lvar_diff(kind, p, x0, e, w.sa64, w.sb64);
   sq = w.f2 * (df * df);
   if (w.is_dec) {
-    const float mean = denoise_update(w.dec, xt, lvar_eps_hat(kind, p, xt, w.sa, w.sb), 0.0f, false);
+    const float mean = w.dec.update(xt, lvar_eps_hat(kind, p, xt, w.sa, w.sb), 0.0f, false);
     return lvar_decoder<GRAD>((double)x0, (double)mean, (double)v, w.lb, w.lbt, dlv);
   }
   return lvar_kl<GRAD>(sq, (double)v, w.lb, w.lbt, w.kt, dlv);
@@ -1052,9 +882,9 @@ __global__ __launch_bounds__(256) void split_pred_k(const float* __restrict__ ou
 
 // Ancestral step with the learned variance: eps_hat from p (pred_to_eps_k's expression at x, per step), guided (kCfg: out2 holds
 // 2 B rows, conditional then unconditional; cfg_lerp of the two eps; the variance from the conditional row), then
-//   x_out = c1 (x - c2 eps_hat) + (float)exp(logvar / 2) noise,  denoise_step_k's mean; no noise at step 1 or with noise NULL.
+//   x_out = c1 (x - c2 eps_hat) + (float)exp(logvar / 2) noise,  Ddpm::update's mean; no noise at step 1 or with noise NULL.
 // x_out may be x itself (each thread reads its quad before it writes it); x_out2 (optional) receives the same values.
-__device__ __forceinline__ float lvar_update(const CfgCoef& k, float x, float e, float v, float z, double lb, double lbt, bool has_noise) {
+__device__ __forceinline__ float lvar_update(const Ddpm& k, float x, float e, float v, float z, double lb, double lbt, bool has_noise) {
   const float pe = k.c2 * e;
   const float inner = x - pe;
   const float lhs = k.c1 * inner;
@@ -1069,7 +899,8 @@ __global__ __launch_bounds__(256) void lvar_step_k(const float* x, const float* 
                                                    int step_arg, const int64_t* __restrict__ step_dev, float s, float* x_out,
                                                    float* x_out2, long items, long segs, long chw, long B) {
   const int step = step_dev ? (int)step_dev[0] : step_arg;
-  const CfgCoef k = cfg_coef(alpha, alpha_hat, beta, step, s);
+  const Ddpm k = Ddpm::at(alpha, alpha_hat, beta, step);
+  const Guidance g = guidance(s);
   const float ah = alpha_hat[step];
   const float sa = sqrtf(ah), sb = sqrtf(1.0f - ah);
   const double lb = lv_coef[3 * (long)step], lbt = lv_coef[3 * (long)step + 1];
@@ -1083,10 +914,10 @@ __global__ __launch_bounds__(256) void lvar_step_k(const float* x, const float* 
     const float4 u = kCfg ? load_quad<VEC>(out2, op + 2 * B * chw, left) : c;
     const float4 z = has_noise ? load_quad<VEC>(noise, o, left) : zero;
     float4 r;
-    r.x = lvar_update(k, xv.x, denoise_eps<kCfg>(k, lvar_eps_hat(kind, c.x, xv.x, sa, sb), lvar_eps_hat(kind, u.x, xv.x, sa, sb)), v.x, z.x, lb, lbt, has_noise);
-    r.y = lvar_update(k, xv.y, denoise_eps<kCfg>(k, lvar_eps_hat(kind, c.y, xv.y, sa, sb), lvar_eps_hat(kind, u.y, xv.y, sa, sb)), v.y, z.y, lb, lbt, has_noise);
-    r.z = lvar_update(k, xv.z, denoise_eps<kCfg>(k, lvar_eps_hat(kind, c.z, xv.z, sa, sb), lvar_eps_hat(kind, u.z, xv.z, sa, sb)), v.z, z.z, lb, lbt, has_noise);
-    r.w = lvar_update(k, xv.w, denoise_eps<kCfg>(k, lvar_eps_hat(kind, c.w, xv.w, sa, sb), lvar_eps_hat(kind, u.w, xv.w, sa, sb)), v.w, z.w, lb, lbt, has_noise);
+    r.x = lvar_update(k, xv.x, guided_eps<kCfg>(g, lvar_eps_hat(kind, c.x, xv.x, sa, sb), lvar_eps_hat(kind, u.x, xv.x, sa, sb)), v.x, z.x, lb, lbt, has_noise);
+    r.y = lvar_update(k, xv.y, guided_eps<kCfg>(g, lvar_eps_hat(kind, c.y, xv.y, sa, sb), lvar_eps_hat(kind, u.y, xv.y, sa, sb)), v.y, z.y, lb, lbt, has_noise);
+    r.z = lvar_update(k, xv.z, guided_eps<kCfg>(g, lvar_eps_hat(kind, c.z, xv.z, sa, sb), lvar_eps_hat(kind, u.z, xv.z, sa, sb)), v.z, z.z, lb, lbt, has_noise);
+    r.w = lvar_update(k, xv.w, guided_eps<kCfg>(g, lvar_eps_hat(kind, c.w, xv.w, sa, sb), lvar_eps_hat(kind, u.w, xv.w, sa, sb)), v.w, z.w, lb, lbt, has_noise);
     store_quad<VEC>(x_out, o, left, r);
     if (x_out2) store_quad<VEC>(x_out2, o, left, r);
   }
@@ -1130,268 +961,6 @@ __global__ __launch_bounds__(256) void vlb_terms_lvar_k(const float* __restrict_
   }
 }
 
-// ---- AdamW (torch.optim.AdamW semantics, decoupled weight decay) ---------------------------
-__global__ void adamw_tick_k(float* state, float b1, float b2) {
-  // state = {step, 1 - b1^step, 1 - b2^step, unused}; double keeps the powers exact enough for 1e6 steps
-  const double step = (double)state[0] + 1.0;
-  state[0] = (float)step;
-  state[1] = (float)(1.0 - pow((double)b1, step));
-  state[2] = (float)(1.0 - pow((double)b2, step));
-}
-__global__ void adamw_step_k(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
-                             long n, const float* __restrict__ state, float lr, float b1, float b2, float eps, float wd, float gscale) {
-  const float bc1 = state[1], bc2 = state[2];
-  const float step_size = lr / bc1, inv_sqrt_bc2 = 1.0f / sqrtf(bc2), decay = 1.0f - lr * wd;
-  AFD_GRID_STRIDE(i, n) {
-    const float gi = g[i] * gscale;
-    const float pi = p[i] * decay;
-    const float mi = m[i] + (gi - m[i]) * (1.0f - b1);            // lerp, as torch does
-    const float vi = v[i] * b2 + gi * gi * (1.0f - b2);
-    const float denom = sqrtf(vi) * inv_sqrt_bc2 + eps;
-    p[i] = pi - step_size * (mi / denom);
-    m[i] = mi; v[i] = vi;
-  }
-}
-
-// ---- EMA of the weights (training.EMA, modules/ddpm_utils.py:26-51) -------------------------------------------------------
-// ema' = copy ? p : (ema * beta) + (p * omb), three roundings in that order (torch's `old * beta + (1 - beta) * new` on fp32
-// tensors; omb = float(1.0 - beta) formed in double on the host).  VEC: every pointer 16-byte aligned -> float4 accesses.
-__device__ __forceinline__ float ema_rule(float e, float p, int copy, float beta, float omb) {
-  if (copy) return p;
-  const float l = e * beta, r = p * omb;
-  return l + r;
-}
-template <bool VEC>
-__device__ __forceinline__ void ema_range(float* __restrict__ ema, const float* __restrict__ p, long lo, long hi, int copy,
-                                          float beta, float omb) {
-  const long tid = blockIdx.x * (long)blockDim.x + threadIdx.x, stride = (long)gridDim.x * blockDim.x;
-  long s = lo;
-  if (VEC && (lo & 3) == 0) {                   // lo % 4 == 0 keeps the 16-byte alignment of the base pointers
-    const long n4 = (hi - lo) >> 2;
-    float4* e4 = reinterpret_cast<float4*>(ema + lo);
-    const float4* p4 = reinterpret_cast<const float4*>(p + lo);
-    for (long k = tid; k < n4; k += stride) {
-      const float4 pv = p4[k];
-      float4 ev = e4[k];
-      ev.x = ema_rule(ev.x, pv.x, copy, beta, omb); ev.y = ema_rule(ev.y, pv.y, copy, beta, omb);
-      ev.z = ema_rule(ev.z, pv.z, copy, beta, omb); ev.w = ema_rule(ev.w, pv.w, copy, beta, omb);
-      e4[k] = ev;
-    }
-    s = lo + 4 * n4;
-  }
-  for (long i = s + tid; i < hi; i += stride) ema[i] = ema_rule(ema[i], p[i], copy, beta, omb);
-}
-template <bool VEC>
-__global__ void ema_step_k(float* __restrict__ ema, const float* __restrict__ p, long n, int copy, float beta, float omb) {
-  ema_range<VEC>(ema, p, 0, n, copy, beta, omb);
-}
-
-// adamw_tick_k's arithmetic, plus the EMA's call counter: ema_state = {calls, copy}; copy = calls < start, then ++calls
-// (the order of EMA.step_ema).  Device-resident so that a replayed step crosses `start` where the eager one would.
-__global__ void adamw_ema_tick_k(float* state, float b1, float b2, int* ema_state, int start) {
-  const double step = (double)state[0] + 1.0;
-  state[0] = (float)step;
-  state[1] = (float)(1.0 - pow((double)b1, step));
-  state[2] = (float)(1.0 - pow((double)b2, step));
-  const int calls = ema_state[0];
-  ema_state[1] = calls < start ? 1 : 0;
-  ema_state[0] = calls + 1;
-}
-
-// one AdamW element, the expressions and order of adamw_step_k
-__device__ __forceinline__ void adamw_elem(float& p, float g, float& m, float& v, float gscale, float decay, float b1, float b2,
-                                           float step_size, float inv_sqrt_bc2, float eps) {
-  const float gi = g * gscale;
-  const float pi = p * decay;
-  const float mi = m + (gi - m) * (1.0f - b1);
-  const float vi = v * b2 + gi * gi * (1.0f - b2);
-  const float denom = sqrtf(vi) * inv_sqrt_bc2 + eps;
-  p = pi - step_size * (mi / denom);
-  m = mi; v = vi;
-}
-
-// AdamW over [0, n_active) with the EMA rule applied to the NEW p, then the EMA rule alone over [n_active, n_ema) (FlatParams'
-// tail: parameters the optimiser never touches, which the reference's EMA still walks).  One pass: p, g, m, v, ema streamed once.
-template <bool VEC>
-__global__ void adamw_ema_step_k(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
-                                 long n_active, const float* __restrict__ state, float lr, float b1, float b2, float eps, float wd,
-                                 float gscale, float* __restrict__ ema, long n_ema, const int* __restrict__ ema_state, float beta,
-                                 float omb) {
-  const float bc1 = state[1], bc2 = state[2];
-  const float step_size = lr / bc1, inv_sqrt_bc2 = 1.0f / sqrtf(bc2), decay = 1.0f - lr * wd;
-  const int copy = ema_state[1];
-  const long tid = blockIdx.x * (long)blockDim.x + threadIdx.x, stride = (long)gridDim.x * blockDim.x;
-  long s = 0;
-  if (VEC) {
-    const long n4 = n_active >> 2;
-    for (long k = tid; k < n4; k += stride) {
-      float4 pv = reinterpret_cast<const float4*>(p)[k];
-      const float4 gv = reinterpret_cast<const float4*>(g)[k];
-      float4 mv = reinterpret_cast<const float4*>(m)[k], vv = reinterpret_cast<const float4*>(v)[k];
-      float4 ev = reinterpret_cast<const float4*>(ema)[k];
-      adamw_elem(pv.x, gv.x, mv.x, vv.x, gscale, decay, b1, b2, step_size, inv_sqrt_bc2, eps);
-      adamw_elem(pv.y, gv.y, mv.y, vv.y, gscale, decay, b1, b2, step_size, inv_sqrt_bc2, eps);
-      adamw_elem(pv.z, gv.z, mv.z, vv.z, gscale, decay, b1, b2, step_size, inv_sqrt_bc2, eps);
-      adamw_elem(pv.w, gv.w, mv.w, vv.w, gscale, decay, b1, b2, step_size, inv_sqrt_bc2, eps);
-      ev.x = ema_rule(ev.x, pv.x, copy, beta, omb); ev.y = ema_rule(ev.y, pv.y, copy, beta, omb);
-      ev.z = ema_rule(ev.z, pv.z, copy, beta, omb); ev.w = ema_rule(ev.w, pv.w, copy, beta, omb);
-      reinterpret_cast<float4*>(p)[k] = pv;
-      reinterpret_cast<float4*>(m)[k] = mv;
-      reinterpret_cast<float4*>(v)[k] = vv;
-      reinterpret_cast<float4*>(ema)[k] = ev;
-    }
-    s = 4 * n4;
-  }
-  for (long i = s + tid; i < n_active; i += stride) {
-    float pi = p[i], mi = m[i], vi = v[i];
-    adamw_elem(pi, g[i], mi, vi, gscale, decay, b1, b2, step_size, inv_sqrt_bc2, eps);
-    p[i] = pi; m[i] = mi; v[i] = vi;
-    ema[i] = ema_rule(ema[i], pi, copy, beta, omb);
-  }
-  ema_range<VEC>(ema, p, n_active, n_ema, copy, beta, omb);
-}
-
-// ---- gradient-norm clipping and the learning-rate schedule, on the device (training.FusedAdamW(max_grad_norm=, lr_schedule=)) ----
-// Squared L2 norm of g * gscale as kGradNormPartials fp64 partial sums.  Workgroup j owns the fixed slice [j*slice, (j+1)*slice)
-// (slice a multiple of 4, chosen from n alone); inside it, thread t takes the quads t, t + 256, ... in ascending order into ONE
-// fp64 accumulator, then the workgroup's fixed tree (block_sum2_f64).  Nothing depends on the grid, on timing or on VEC, which
-// only turns four scalar loads into one 16-byte load: run to run, and aligned against misaligned, the bytes are identical.
-constexpr int kGradNormPartials = 512;      // two 256-thread workgroups per CU; four quads in flight per thread = 32 KiB per CU
-template <bool VEC>
-__device__ __forceinline__ float4 load_quad(const float* __restrict__ g, long q) {
-  if (VEC) return reinterpret_cast<const float4*>(g)[q];
-  return make_float4(g[4 * q], g[4 * q + 1], g[4 * q + 2], g[4 * q + 3]);
-}
-__device__ __forceinline__ void sq_acc(double& s, float g, float gscale) {
-  const float gi = g * gscale;                  // the product adamw_elem forms, in fp32
-  s += (double)gi * (double)gi;                 // (exact in fp64: 48 significant bits)
-}
-__device__ __forceinline__ void sq_acc4(double& s, float4 v, float gscale) {
-  sq_acc(s, v.x, gscale); sq_acc(s, v.y, gscale); sq_acc(s, v.z, gscale); sq_acc(s, v.w, gscale);
-}
-template <bool VEC>
-__global__ void grad_sqnorm_partials_k(const float* __restrict__ g, long n, long slice, float gscale, double* __restrict__ partials) {
-  __shared__ double red[8];
-  const long lo = blockIdx.x * slice;
-  long len = n - lo;
-  len = len < 0 ? 0 : (len > slice ? slice : len);
-  const float* gs = g + lo;
-  const long nq = len >> 2;                     // whole quads of this slice
-  double s = 0.0, unused = 0.0;
-  long q = threadIdx.x;
-  for (; q + 768 < nq; q += 1024) {             // four independent loads, then the four quads in order
-    const float4 a = load_quad<VEC>(gs, q), b = load_quad<VEC>(gs, q + 256), c = load_quad<VEC>(gs, q + 512),
-                 d = load_quad<VEC>(gs, q + 768);
-    sq_acc4(s, a, gscale); sq_acc4(s, b, gscale); sq_acc4(s, c, gscale); sq_acc4(s, d, gscale);
-  }
-  for (; q < nq; q += 256) sq_acc4(s, load_quad<VEC>(gs, q), gscale);
-  if (q == nq)                                  // the end of the buffer inside a quad: its elements, in the thread that quad belongs to
-    for (long i = 4 * nq; i < len; ++i) sq_acc(s, gs[i], gscale);
-  block_sum2_f64(s, unused, red);
-  if (threadIdx.x == 0) partials[blockIdx.x] = s;
-}
-
-// ctl = device double[kCtlDoubles]: what the tick decides and the step reads (afd.h)
-enum { kCtlLr = 0, kCtlCoef, kCtlNorm, kCtlSkip, kCtlNSkipped, kCtlSq, kCtlIndex, kCtlFactor, kCtlDoubles };
-constexpr int kCtlMaxPartials = 1024;
-
-__device__ __forceinline__ double lr_factor(const afd_opt_ctl& c, double k) {
-  if (k < (double)c.warmup) return k / (double)(c.warmup > 1 ? c.warmup : 1);
-  if (c.kind == AFD_LR_CONSTANT) return 1.0;
-  const long span = c.total - c.warmup;
-  double pr = (k - (double)c.warmup) / (double)(span > 1 ? span : 1);
-  pr = pr < 1.0 ? pr : 1.0;
-  const double base = c.kind == AFD_LR_COSINE ? 0.5 * (1.0 + cos(3.141592653589793 * pr)) : 1.0 - pr;
-  return c.min_ratio + (1.0 - c.min_ratio) * base;
-}
-
-// One workgroup: the partials in index order -> norm -> clip coefficient; unless the step is skipped, adamw_tick_k (or
-// adamw_ema_tick_k) and the learning rate of this update.  The partials go through LDS so that thread 0's chain of fp64 adds
-// does not wait on one global load each.
-__global__ void adamw_ctl_tick_k(float* state, float b1, float b2, int* ema_state, int start, const double* __restrict__ partials,
-                                 int n_partials, afd_opt_ctl cfg, double* ctl) {
-  __shared__ double sp[kCtlMaxPartials];
-  for (int i = threadIdx.x; i < n_partials; i += blockDim.x) sp[i] = partials[i];
-  __syncthreads();
-  if (threadIdx.x != 0) return;
-  double sq = 0.0, norm = 0.0, coef = 1.0;
-  if (partials) {
-    for (int i = 0; i < n_partials; ++i) sq += sp[i];
-    norm = sqrt(sq);
-    if (cfg.max_norm > 0.0) {
-      const double c = cfg.max_norm / (norm + 1e-6);
-      coef = c > 1.0 ? 1.0 : c;                 // (a NaN norm gives a NaN coefficient, as torch.clamp(max=1) does)
-    }
-  }
-  ctl[kCtlSq] = sq;
-  ctl[kCtlNorm] = norm;
-  if (cfg.skip_nonfinite && !(fabs(norm) <= 1.79769313486231570e308)) {      // inf or NaN
-    ctl[kCtlSkip] = 1.0;
-    ctl[kCtlNSkipped] += 1.0;
-    return;
-  }
-  const double step = (double)state[0] + 1.0;   // adamw_tick_k
-  state[0] = (float)step;
-  state[1] = (float)(1.0 - pow((double)b1, step));
-  state[2] = (float)(1.0 - pow((double)b2, step));
-  if (ema_state) {                              // adamw_ema_tick_k
-    const int calls = ema_state[0];
-    ema_state[1] = calls < start ? 1 : 0;
-    ema_state[0] = calls + 1;
-  }
-  const double k = (double)state[0] - 1.0, factor = lr_factor(cfg, k);
-  ctl[kCtlLr] = (double)(float)(cfg.base_lr * factor);
-  ctl[kCtlCoef] = coef;
-  ctl[kCtlSkip] = 0.0;
-  ctl[kCtlIndex] = k;
-  ctl[kCtlFactor] = factor;
-}
-
-// adamw_step_k (EMA = false) / adamw_ema_step_k (EMA = true) with lr and the clip coefficient read from ctl; every thread
-// returns before its first access when ctl says skip.
-template <bool VEC, bool EMA>
-__global__ void adamw_ctl_step_k(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
-                                 long n_active, const float* __restrict__ state, const double* __restrict__ ctl, float b1, float b2,
-                                 float eps, float wd, float grad_scale, float* __restrict__ ema, long n_ema,
-                                 const int* __restrict__ ema_state, float beta, float omb) {
-  if (ctl[kCtlSkip] != 0.0) return;
-  const float lr = (float)ctl[kCtlLr], gscale = grad_scale * (float)ctl[kCtlCoef];
-  const float bc1 = state[1], bc2 = state[2];
-  const float step_size = lr / bc1, inv_sqrt_bc2 = 1.0f / sqrtf(bc2), decay = 1.0f - lr * wd;
-  const int copy = EMA ? ema_state[1] : 0;
-  const long tid = blockIdx.x * (long)blockDim.x + threadIdx.x, stride = (long)gridDim.x * blockDim.x;
-  long s = 0;
-  if (VEC) {
-    const long n4 = n_active >> 2;
-    for (long k = tid; k < n4; k += stride) {
-      float4 pv = reinterpret_cast<const float4*>(p)[k];
-      const float4 gv = reinterpret_cast<const float4*>(g)[k];
-      float4 mv = reinterpret_cast<const float4*>(m)[k], vv = reinterpret_cast<const float4*>(v)[k];
-      adamw_elem(pv.x, gv.x, mv.x, vv.x, gscale, decay, b1, b2, step_size, inv_sqrt_bc2, eps);
-      adamw_elem(pv.y, gv.y, mv.y, vv.y, gscale, decay, b1, b2, step_size, inv_sqrt_bc2, eps);
-      adamw_elem(pv.z, gv.z, mv.z, vv.z, gscale, decay, b1, b2, step_size, inv_sqrt_bc2, eps);
-      adamw_elem(pv.w, gv.w, mv.w, vv.w, gscale, decay, b1, b2, step_size, inv_sqrt_bc2, eps);
-      reinterpret_cast<float4*>(p)[k] = pv;
-      reinterpret_cast<float4*>(m)[k] = mv;
-      reinterpret_cast<float4*>(v)[k] = vv;
-      if (EMA) {
-        float4 ev = reinterpret_cast<const float4*>(ema)[k];
-        ev.x = ema_rule(ev.x, pv.x, copy, beta, omb); ev.y = ema_rule(ev.y, pv.y, copy, beta, omb);
-        ev.z = ema_rule(ev.z, pv.z, copy, beta, omb); ev.w = ema_rule(ev.w, pv.w, copy, beta, omb);
-        reinterpret_cast<float4*>(ema)[k] = ev;
-      }
-    }
-    s = 4 * n4;
-  }
-  for (long i = s + tid; i < n_active; i += stride) {
-    float pi = p[i], mi = m[i], vi = v[i];
-    adamw_elem(pi, g[i], mi, vi, gscale, decay, b1, b2, step_size, inv_sqrt_bc2, eps);
-    p[i] = pi; m[i] = mi; v[i] = vi;
-    if (EMA) ema[i] = ema_rule(ema[i], pi, copy, beta, omb);
-  }
-  if (EMA) ema_range<VEC>(ema, p, n_active, n_ema, copy, beta, omb);
-}
-
 }  // namespace afd
 using namespace afd;
 
@@ -1404,179 +973,128 @@ int afd_noise_images(const float* x, const float* eps, const int64_t* t, const f
   hipLaunchKernelGGL(noise_images_k, dim3(gs_grid(total)), dim3(256), 0, as_stream(st), x, eps, t, alpha_hat, x_t, per_sample, total);
   return check_launch("afd_noise_images");
 }
+// ---- sampler steps: afd_denoise_step* (DDPM) and afd_ddim_step* (DDIM) -----------------------------------------------------------
+// DDPM: i >= 0, and i >= 1 for the masked forms (the step i -> i - 1)
+static int ddpm_step(const StepForm& f, const float* x, const float* eps, const float* noise, const float* x0, const uint8_t* mask,
+                     const float* alpha, const float* alpha_hat, const float* beta, int i, const int64_t* t_dev, float s, float* x_out,
+                     float* x_out2, long n, afd_stream_t st) {
+  if (int rc = check_step_buffers(f, alpha && alpha_hat && beta && (!f.dev || t_dev), f.dev ? "alpha, alpha_hat, beta, t_dev" : "alpha, alpha_hat, beta",
+                                  x, eps, x0, mask, x_out, x_out2, n))
+    return rc;
+  AFD_REQUIRE(f.dev || i >= (f.masked ? 1 : 0), "%s: need i >= %d (got i = %d)", f.name, f.masked ? 1 : 0, i);
+  if (int rc = check_known_noise(f, noise, f.dev ? -1 : i - 1)) return rc;
+  return launch_step_form<Ddpm>(f, x, eps, noise, Ddpm::Args{alpha, alpha_hat, beta, i, t_dev}, s, x0, mask, x_out, x_out2, n, st);
+}
 int afd_denoise_step(const float* x, const float* eps_pred, const float* noise, const float* alpha, const float* alpha_hat,
                      const float* beta, int i, float* x_out, long n, afd_stream_t st) {
-  AFD_REQUIRE(x && eps_pred && alpha && alpha_hat && beta && x_out && n > 0 && i >= 0, "afd_denoise_step: bad argument");
-  hipLaunchKernelGGL(denoise_step_k, dim3(gs_grid(n)), dim3(256), 0, as_stream(st), x, eps_pred, noise, alpha, alpha_hat, beta, i, (const int64_t*)nullptr, x_out, n);
-  return check_launch("afd_denoise_step");
+  return ddpm_step({"afd_denoise_step", false, false, false}, x, eps_pred, noise, nullptr, nullptr, alpha, alpha_hat, beta, i, nullptr,
+                   0.0f, x_out, nullptr, n, st);
 }
 int afd_denoise_step_dev(const float* x, const float* eps_pred, const float* noise, const float* alpha, const float* alpha_hat,
                          const float* beta, const int64_t* t_dev, float* x_out, long n, afd_stream_t st) {
-  AFD_REQUIRE(x && eps_pred && alpha && alpha_hat && beta && t_dev && x_out && n > 0, "afd_denoise_step_dev: bad argument");
-  hipLaunchKernelGGL(denoise_step_k, dim3(gs_grid(n)), dim3(256), 0, as_stream(st), x, eps_pred, noise, alpha, alpha_hat, beta, 0, t_dev, x_out, n);
-  return check_launch("afd_denoise_step_dev");
+  return ddpm_step({"afd_denoise_step_dev", true, false, false}, x, eps_pred, noise, nullptr, nullptr, alpha, alpha_hat, beta, 0, t_dev,
+                   0.0f, x_out, nullptr, n, st);
 }
 int afd_denoise_step_cfg(const float* x, const float* eps2, const float* noise, const float* alpha, const float* alpha_hat,
                          const float* beta, int i, float cfg_scale, float* x_out, float* x_out2, long n, afd_stream_t st) {
-  AFD_REQUIRE(x && eps2 && alpha && alpha_hat && beta && x_out && n > 0 && i >= 0, "afd_denoise_step_cfg: bad argument");
-  launch_denoise_step_cfg(x, eps2, noise, alpha, alpha_hat, beta, i, nullptr, cfg_scale, x_out, x_out2, n, as_stream(st));
-  return check_launch("afd_denoise_step_cfg");
+  return ddpm_step({"afd_denoise_step_cfg", false, true, false}, x, eps2, noise, nullptr, nullptr, alpha, alpha_hat, beta, i, nullptr,
+                   cfg_scale, x_out, x_out2, n, st);
 }
 int afd_denoise_step_cfg_dev(const float* x, const float* eps2, const float* noise, const float* alpha, const float* alpha_hat,
                              const float* beta, const int64_t* t_dev, float cfg_scale, float* x_out, float* x_out2, long n,
                              afd_stream_t st) {
-  AFD_REQUIRE(x && eps2 && alpha && alpha_hat && beta && t_dev && x_out && n > 0, "afd_denoise_step_cfg_dev: bad argument");
-  launch_denoise_step_cfg(x, eps2, noise, alpha, alpha_hat, beta, 0, t_dev, cfg_scale, x_out, x_out2, n, as_stream(st));
-  return check_launch("afd_denoise_step_cfg_dev");
+  return ddpm_step({"afd_denoise_step_cfg_dev", true, true, false}, x, eps2, noise, nullptr, nullptr, alpha, alpha_hat, beta, 0, t_dev,
+                   cfg_scale, x_out, x_out2, n, st);
 }
-int afd_ddim_step(const float* x, const float* eps, const float* noise, const float* alpha_hat, int t, int t_prev, float eta,
-                  float* x_out, long n, afd_stream_t st) {
-  AFD_REQUIRE(x && eps && alpha_hat && x_out, "afd_ddim_step: x, eps, alpha_hat and x_out must not be NULL");
-  AFD_REQUIRE(n > 0, "afd_ddim_step: n must be positive (got %ld)", n);
-  AFD_REQUIRE(t_prev >= 0 && t_prev < t, "afd_ddim_step: need 0 <= t_prev < t (got t = %d, t_prev = %d)", t, t_prev);
-  AFD_REQUIRE(eta >= 0.0f, "afd_ddim_step: eta must be >= 0");
-  launch_ddim_step<false>(x, eps, noise, alpha_hat, t, t_prev, nullptr, nullptr, eta, 0.0f, x_out, nullptr, n, as_stream(st));
-  return check_launch("afd_ddim_step");
-}
-int afd_ddim_step_dev(const float* x, const float* eps, const float* noise, const float* alpha_hat, const int64_t* t_dev,
-                      const int64_t* t_prev_dev, float eta, float* x_out, long n, afd_stream_t st) {
-  AFD_REQUIRE(x && eps && alpha_hat && t_dev && t_prev_dev && x_out,
-              "afd_ddim_step_dev: x, eps, alpha_hat, t_dev, t_prev_dev and x_out must not be NULL");
-  AFD_REQUIRE(n > 0, "afd_ddim_step_dev: n must be positive (got %ld)", n);
-  AFD_REQUIRE(eta >= 0.0f, "afd_ddim_step_dev: eta must be >= 0");
-  launch_ddim_step<false>(x, eps, noise, alpha_hat, 0, 0, t_dev, t_prev_dev, eta, 0.0f, x_out, nullptr, n, as_stream(st));
-  return check_launch("afd_ddim_step_dev");
-}
-int afd_ddim_step_cfg(const float* x, const float* eps2, const float* noise, const float* alpha_hat, int t, int t_prev, float eta,
-                      float cfg_scale, float* x_out, float* x_out2, long n, afd_stream_t st) {
-  AFD_REQUIRE(x && eps2 && alpha_hat && x_out, "afd_ddim_step_cfg: x, eps2, alpha_hat and x_out must not be NULL");
-  AFD_REQUIRE(n > 0, "afd_ddim_step_cfg: n must be positive (got %ld)", n);
-  AFD_REQUIRE(t_prev >= 0 && t_prev < t, "afd_ddim_step_cfg: need 0 <= t_prev < t (got t = %d, t_prev = %d)", t, t_prev);
-  AFD_REQUIRE(eta >= 0.0f, "afd_ddim_step_cfg: eta must be >= 0");
-  launch_ddim_step<true>(x, eps2, noise, alpha_hat, t, t_prev, nullptr, nullptr, eta, cfg_scale, x_out, x_out2, n, as_stream(st));
-  return check_launch("afd_ddim_step_cfg");
-}
-int afd_ddim_step_cfg_dev(const float* x, const float* eps2, const float* noise, const float* alpha_hat, const int64_t* t_dev,
-                          const int64_t* t_prev_dev, float eta, float cfg_scale, float* x_out, float* x_out2, long n, afd_stream_t st) {
-  AFD_REQUIRE(x && eps2 && alpha_hat && t_dev && t_prev_dev && x_out,
-              "afd_ddim_step_cfg_dev: x, eps2, alpha_hat, t_dev, t_prev_dev and x_out must not be NULL");
-  AFD_REQUIRE(n > 0, "afd_ddim_step_cfg_dev: n must be positive (got %ld)", n);
-  AFD_REQUIRE(eta >= 0.0f, "afd_ddim_step_cfg_dev: eta must be >= 0");
-  launch_ddim_step<true>(x, eps2, noise, alpha_hat, 0, 0, t_dev, t_prev_dev, eta, cfg_scale, x_out, x_out2, n, as_stream(st));
-  return check_launch("afd_ddim_step_cfg_dev");
-}
-static inline bool aligned16(const void* q) { return ((uintptr_t)q & 15) == 0; }
-
-// ---- masked steps (inpainting) and renoise ---------------------------------------------------------------------------------
-static inline bool overlaps(const void* a, long abytes, const void* b, long bbytes) {
-  const uintptr_t pa = (uintptr_t)a, pb = (uintptr_t)b;
-  return b && pa < pb + (uintptr_t)bbytes && pb < pa + (uintptr_t)abytes;
-}
-// x0 and mask are read by every element while x_out / x_out2 are written: they must not share memory
-static inline bool masked_inputs_apart(const float* x0, const uint8_t* mask, const float* x_out, const float* x_out2, long n) {
-  const long fb = n * (long)sizeof(float);
-  return !overlaps(x0, fb, x_out, fb) && !overlaps(x0, fb, x_out2, fb) && !overlaps(mask, n, x_out, fb) && !overlaps(mask, n, x_out2, fb);
-}
-#define AFD_MASKED_CHECKS(name, x0, mask, x_out, x_out2, n)                                                                   \
-  AFD_REQUIRE(n > 0, name ": n must be positive (got %ld)", n);                                                           \
-  AFD_REQUIRE(masked_inputs_apart(x0, mask, x_out, x_out2, n), name ": x0 and mask must not overlap x_out or x_out2")
-
 int afd_denoise_step_masked(const float* x, const float* eps_pred, const float* noise, const float* x0, const uint8_t* mask,
                             const float* alpha, const float* alpha_hat, const float* beta, int i, float* x_out, long n,
                             afd_stream_t st) {
-  AFD_REQUIRE(x && eps_pred && x0 && mask && alpha && alpha_hat && beta && x_out,
-              "afd_denoise_step_masked: x, eps_pred, x0, mask, alpha, alpha_hat, beta and x_out must not be NULL");
-  AFD_MASKED_CHECKS("afd_denoise_step_masked", x0, mask, x_out, (const float*)nullptr, n);
-  AFD_REQUIRE(i >= 1, "afd_denoise_step_masked: need i >= 1 (the step i -> i - 1; got i = %d)", i);
-  AFD_REQUIRE(noise || i == 1, "afd_denoise_step_masked: noise must not be NULL when i > 1 (it noises the known region)");
-  launch_denoise_step_masked<false>(x, eps_pred, noise, x0, mask, alpha, alpha_hat, beta, i, nullptr, 0.0f, x_out, nullptr, n,
-                                    as_stream(st));
-  return check_launch("afd_denoise_step_masked");
+  return ddpm_step({"afd_denoise_step_masked", false, false, true}, x, eps_pred, noise, x0, mask, alpha, alpha_hat, beta, i, nullptr, 0.0f,
+                   x_out, nullptr, n, st);
 }
 int afd_denoise_step_masked_dev(const float* x, const float* eps_pred, const float* noise, const float* x0, const uint8_t* mask,
                                 const float* alpha, const float* alpha_hat, const float* beta, const int64_t* t_dev, float* x_out,
                                 long n, afd_stream_t st) {
-  AFD_REQUIRE(x && eps_pred && noise && x0 && mask && alpha && alpha_hat && beta && t_dev && x_out,
-              "afd_denoise_step_masked_dev: x, eps_pred, noise, x0, mask, alpha, alpha_hat, beta, t_dev and x_out must not be NULL");
-  AFD_MASKED_CHECKS("afd_denoise_step_masked_dev", x0, mask, x_out, (const float*)nullptr, n);
-  launch_denoise_step_masked<false>(x, eps_pred, noise, x0, mask, alpha, alpha_hat, beta, 0, t_dev, 0.0f, x_out, nullptr, n,
-                                    as_stream(st));
-  return check_launch("afd_denoise_step_masked_dev");
+  return ddpm_step({"afd_denoise_step_masked_dev", true, false, true}, x, eps_pred, noise, x0, mask, alpha, alpha_hat, beta, 0, t_dev, 0.0f,
+                   x_out, nullptr, n, st);
 }
 int afd_denoise_step_masked_cfg(const float* x, const float* eps2, const float* noise, const float* x0, const uint8_t* mask,
                                 const float* alpha, const float* alpha_hat, const float* beta, int i, float cfg_scale, float* x_out,
                                 float* x_out2, long n, afd_stream_t st) {
-  AFD_REQUIRE(x && eps2 && x0 && mask && alpha && alpha_hat && beta && x_out,
-              "afd_denoise_step_masked_cfg: x, eps2, x0, mask, alpha, alpha_hat, beta and x_out must not be NULL");
-  AFD_MASKED_CHECKS("afd_denoise_step_masked_cfg", x0, mask, x_out, x_out2, n);
-  AFD_REQUIRE(i >= 1, "afd_denoise_step_masked_cfg: need i >= 1 (the step i -> i - 1; got i = %d)", i);
-  AFD_REQUIRE(noise || i == 1, "afd_denoise_step_masked_cfg: noise must not be NULL when i > 1 (it noises the known region)");
-  launch_denoise_step_masked<true>(x, eps2, noise, x0, mask, alpha, alpha_hat, beta, i, nullptr, cfg_scale, x_out, x_out2, n,
-                                   as_stream(st));
-  return check_launch("afd_denoise_step_masked_cfg");
+  return ddpm_step({"afd_denoise_step_masked_cfg", false, true, true}, x, eps2, noise, x0, mask, alpha, alpha_hat, beta, i, nullptr,
+                   cfg_scale, x_out, x_out2, n, st);
 }
 int afd_denoise_step_masked_cfg_dev(const float* x, const float* eps2, const float* noise, const float* x0, const uint8_t* mask,
                                     const float* alpha, const float* alpha_hat, const float* beta, const int64_t* t_dev,
                                     float cfg_scale, float* x_out, float* x_out2, long n, afd_stream_t st) {
-  AFD_REQUIRE(x && eps2 && noise && x0 && mask && alpha && alpha_hat && beta && t_dev && x_out,
-              "afd_denoise_step_masked_cfg_dev: x, eps2, noise, x0, mask, alpha, alpha_hat, beta, t_dev and x_out must not be NULL");
-  AFD_MASKED_CHECKS("afd_denoise_step_masked_cfg_dev", x0, mask, x_out, x_out2, n);
-  launch_denoise_step_masked<true>(x, eps2, noise, x0, mask, alpha, alpha_hat, beta, 0, t_dev, cfg_scale, x_out, x_out2, n,
-                                   as_stream(st));
-  return check_launch("afd_denoise_step_masked_cfg_dev");
+  return ddpm_step({"afd_denoise_step_masked_cfg_dev", true, true, true}, x, eps2, noise, x0, mask, alpha, alpha_hat, beta, 0, t_dev,
+                   cfg_scale, x_out, x_out2, n, st);
+}
+
+// DDIM: 0 <= t_prev < t where the host knows them, eta >= 0 (a NaN eta fails the comparison)
+static int ddim_step(const StepForm& f, const float* x, const float* eps, const float* noise, const float* x0, const uint8_t* mask,
+                     const float* alpha_hat, int t, int t_prev, const int64_t* t_dev, const int64_t* t_prev_dev, float eta, float s,
+                     float* x_out, float* x_out2, long n, afd_stream_t st) {
+  if (int rc = check_step_buffers(f, alpha_hat && (!f.dev || (t_dev && t_prev_dev)), f.dev ? "alpha_hat, t_dev, t_prev_dev" : "alpha_hat", x, eps,
+                                  x0, mask, x_out, x_out2, n))
+    return rc;
+  AFD_REQUIRE(f.dev || (t_prev >= 0 && t_prev < t), "%s: need 0 <= t_prev < t (got t = %d, t_prev = %d)", f.name, t, t_prev);
+  AFD_REQUIRE(eta >= 0.0f, "%s: eta must be >= 0", f.name);
+  if (int rc = check_known_noise(f, noise, f.dev ? -1 : t_prev)) return rc;
+  return launch_step_form<Ddim>(f, x, eps, noise, Ddim::Args{alpha_hat, t, t_prev, t_dev, t_prev_dev, eta}, s, x0, mask, x_out, x_out2, n,
+                                st);
+}
+int afd_ddim_step(const float* x, const float* eps, const float* noise, const float* alpha_hat, int t, int t_prev, float eta,
+                  float* x_out, long n, afd_stream_t st) {
+  return ddim_step({"afd_ddim_step", false, false, false}, x, eps, noise, nullptr, nullptr, alpha_hat, t, t_prev, nullptr, nullptr, eta, 0.0f,
+                   x_out, nullptr, n, st);
+}
+int afd_ddim_step_dev(const float* x, const float* eps, const float* noise, const float* alpha_hat, const int64_t* t_dev,
+                      const int64_t* t_prev_dev, float eta, float* x_out, long n, afd_stream_t st) {
+  return ddim_step({"afd_ddim_step_dev", true, false, false}, x, eps, noise, nullptr, nullptr, alpha_hat, 0, 0, t_dev, t_prev_dev, eta, 0.0f,
+                   x_out, nullptr, n, st);
+}
+int afd_ddim_step_cfg(const float* x, const float* eps2, const float* noise, const float* alpha_hat, int t, int t_prev, float eta,
+                      float cfg_scale, float* x_out, float* x_out2, long n, afd_stream_t st) {
+  return ddim_step({"afd_ddim_step_cfg", false, true, false}, x, eps2, noise, nullptr, nullptr, alpha_hat, t, t_prev, nullptr, nullptr, eta,
+                   cfg_scale, x_out, x_out2, n, st);
+}
+int afd_ddim_step_cfg_dev(const float* x, const float* eps2, const float* noise, const float* alpha_hat, const int64_t* t_dev,
+                          const int64_t* t_prev_dev, float eta, float cfg_scale, float* x_out, float* x_out2, long n, afd_stream_t st) {
+  return ddim_step({"afd_ddim_step_cfg_dev", true, true, false}, x, eps2, noise, nullptr, nullptr, alpha_hat, 0, 0, t_dev, t_prev_dev, eta,
+                   cfg_scale, x_out, x_out2, n, st);
 }
 int afd_ddim_step_masked(const float* x, const float* eps, const float* noise, const float* x0, const uint8_t* mask,
                          const float* alpha_hat, int t, int t_prev, float eta, float* x_out, long n, afd_stream_t st) {
-  AFD_REQUIRE(x && eps && x0 && mask && alpha_hat && x_out, "afd_ddim_step_masked: x, eps, x0, mask, alpha_hat and x_out must not be NULL");
-  AFD_MASKED_CHECKS("afd_ddim_step_masked", x0, mask, x_out, (const float*)nullptr, n);
-  AFD_REQUIRE(t_prev >= 0 && t_prev < t, "afd_ddim_step_masked: need 0 <= t_prev < t (got t = %d, t_prev = %d)", t, t_prev);
-  AFD_REQUIRE(eta >= 0.0f, "afd_ddim_step_masked: eta must be >= 0");
-  AFD_REQUIRE(noise || t_prev == 0, "afd_ddim_step_masked: noise must not be NULL when t_prev > 0 (it noises the known region)");
-  launch_ddim_step_masked<false>(x, eps, noise, x0, mask, alpha_hat, t, t_prev, nullptr, nullptr, eta, 0.0f, x_out, nullptr, n,
-                                 as_stream(st));
-  return check_launch("afd_ddim_step_masked");
+  return ddim_step({"afd_ddim_step_masked", false, false, true}, x, eps, noise, x0, mask, alpha_hat, t, t_prev, nullptr, nullptr, eta, 0.0f,
+                   x_out, nullptr, n, st);
 }
 int afd_ddim_step_masked_dev(const float* x, const float* eps, const float* noise, const float* x0, const uint8_t* mask,
                              const float* alpha_hat, const int64_t* t_dev, const int64_t* t_prev_dev, float eta, float* x_out, long n,
                              afd_stream_t st) {
-  AFD_REQUIRE(x && eps && noise && x0 && mask && alpha_hat && t_dev && t_prev_dev && x_out,
-              "afd_ddim_step_masked_dev: x, eps, noise, x0, mask, alpha_hat, t_dev, t_prev_dev and x_out must not be NULL");
-  AFD_MASKED_CHECKS("afd_ddim_step_masked_dev", x0, mask, x_out, (const float*)nullptr, n);
-  AFD_REQUIRE(eta >= 0.0f, "afd_ddim_step_masked_dev: eta must be >= 0");
-  launch_ddim_step_masked<false>(x, eps, noise, x0, mask, alpha_hat, 0, 0, t_dev, t_prev_dev, eta, 0.0f, x_out, nullptr, n,
-                                 as_stream(st));
-  return check_launch("afd_ddim_step_masked_dev");
+  return ddim_step({"afd_ddim_step_masked_dev", true, false, true}, x, eps, noise, x0, mask, alpha_hat, 0, 0, t_dev, t_prev_dev, eta, 0.0f,
+                   x_out, nullptr, n, st);
 }
 int afd_ddim_step_masked_cfg(const float* x, const float* eps2, const float* noise, const float* x0, const uint8_t* mask,
                              const float* alpha_hat, int t, int t_prev, float eta, float cfg_scale, float* x_out, float* x_out2, long n,
                              afd_stream_t st) {
-  AFD_REQUIRE(x && eps2 && x0 && mask && alpha_hat && x_out,
-              "afd_ddim_step_masked_cfg: x, eps2, x0, mask, alpha_hat and x_out must not be NULL");
-  AFD_MASKED_CHECKS("afd_ddim_step_masked_cfg", x0, mask, x_out, x_out2, n);
-  AFD_REQUIRE(t_prev >= 0 && t_prev < t, "afd_ddim_step_masked_cfg: need 0 <= t_prev < t (got t = %d, t_prev = %d)", t, t_prev);
-  AFD_REQUIRE(eta >= 0.0f, "afd_ddim_step_masked_cfg: eta must be >= 0");
-  AFD_REQUIRE(noise || t_prev == 0, "afd_ddim_step_masked_cfg: noise must not be NULL when t_prev > 0 (it noises the known region)");
-  launch_ddim_step_masked<true>(x, eps2, noise, x0, mask, alpha_hat, t, t_prev, nullptr, nullptr, eta, cfg_scale, x_out, x_out2, n,
-                                as_stream(st));
-  return check_launch("afd_ddim_step_masked_cfg");
+  return ddim_step({"afd_ddim_step_masked_cfg", false, true, true}, x, eps2, noise, x0, mask, alpha_hat, t, t_prev, nullptr, nullptr, eta,
+                   cfg_scale, x_out, x_out2, n, st);
 }
 int afd_ddim_step_masked_cfg_dev(const float* x, const float* eps2, const float* noise, const float* x0, const uint8_t* mask,
                                  const float* alpha_hat, const int64_t* t_dev, const int64_t* t_prev_dev, float eta, float cfg_scale,
                                  float* x_out, float* x_out2, long n, afd_stream_t st) {
-  AFD_REQUIRE(x && eps2 && noise && x0 && mask && alpha_hat && t_dev && t_prev_dev && x_out,
-              "afd_ddim_step_masked_cfg_dev: x, eps2, noise, x0, mask, alpha_hat, t_dev, t_prev_dev and x_out must not be NULL");
-  AFD_MASKED_CHECKS("afd_ddim_step_masked_cfg_dev", x0, mask, x_out, x_out2, n);
-  AFD_REQUIRE(eta >= 0.0f, "afd_ddim_step_masked_cfg_dev: eta must be >= 0");
-  launch_ddim_step_masked<true>(x, eps2, noise, x0, mask, alpha_hat, 0, 0, t_dev, t_prev_dev, eta, cfg_scale, x_out, x_out2, n,
-                                as_stream(st));
-  return check_launch("afd_ddim_step_masked_cfg_dev");
+  return ddim_step({"afd_ddim_step_masked_cfg_dev", true, true, true}, x, eps2, noise, x0, mask, alpha_hat, 0, 0, t_dev, t_prev_dev, eta,
+                   cfg_scale, x_out, x_out2, n, st);
 }
+
+// ---- renoise (the inpainting sampler's up-move) -----------------------------------------------------------------------------------
 int afd_renoise(const float* x, const float* noise, const float* alpha_hat, int t_from, int t_to, float* x_out, long n,
                 afd_stream_t st) {
   AFD_REQUIRE(x && noise && alpha_hat && x_out, "afd_renoise: x, noise, alpha_hat and x_out must not be NULL");
   AFD_REQUIRE(n > 0, "afd_renoise: n must be positive (got %ld)", n);
   AFD_REQUIRE(t_from >= 0 && t_from < t_to, "afd_renoise: need 0 <= t_from < t_to (got t_from = %d, t_to = %d)", t_from, t_to);
-  if (n % 4 == 0 && aligned16(x) && aligned16(noise) && aligned16(x_out))
+  if (vec_ok(n, {x, noise, x_out}))
     hipLaunchKernelGGL(renoise_k<true>, dim3(step_grid(n / 4)), dim3(256), 0, as_stream(st), x, noise, alpha_hat, t_from, t_to, x_out,
                        n / 4);
   else
@@ -1847,8 +1365,7 @@ static int launch_lvar_step(bool kCfg, const char* name, const float* x, const f
   AFD_REQUIRE(all_apart(out, out_b, 2, in, in_b, 4) && !(x_out2 && overlaps(x_out2, fb, x, fb)),
               "%s: x_out must be x itself or apart from it, and x_out / x_out2 must not overlap each other, out2, noise or t_dev", name);
   const long segs = obj_segs(chw), items = B * segs;
-  const bool vec = chw % 4 == 0 && aligned16(x) && aligned16(out2) && aligned16(x_out) && (!noise || aligned16(noise)) &&
-                   (!x_out2 || aligned16(x_out2));
+  const bool vec = vec_ok(chw, {x, out2, noise, x_out, x_out2});
   auto kern = kCfg ? (vec ? lvar_step_k<true, true> : lvar_step_k<true, false>) : (vec ? lvar_step_k<false, true> : lvar_step_k<false, false>);
   hipLaunchKernelGGL(kern, dim3(obj_grid(items)), dim3(256), 0, st, x, out2, noise, alpha, alpha_hat, beta, lv_coef, kind, i, t_dev, s,
                      x_out, x_out2, items, segs, chw, B);
@@ -1900,113 +1417,6 @@ int afd_vlb_terms_lvar(const float* x0, long n_img, const int64_t* img, const fl
     hipLaunchKernelGGL(vlb_terms_lvar_k<false>, dim3((unsigned)rows), dim3(256), 0, as_stream(st), x0, img, x_t, eps, out2, t, lv_coef,
                        alpha, alpha_hat, beta, kind, term, sq, per);
   return check_launch("afd_vlb_terms_lvar");
-}
-int afd_adamw_tick(float* state, float b1, float b2, afd_stream_t st) {
-  AFD_REQUIRE(state, "afd_adamw_tick: state is NULL");
-  hipLaunchKernelGGL(adamw_tick_k, dim3(1), dim3(1), 0, as_stream(st), state, b1, b2);
-  return check_launch("afd_adamw_tick");
-}
-int afd_adamw_step(float* p, const float* g, float* m, float* v, long n, const float* state,
-                   float lr, float b1, float b2, float eps, float wd, float gscale, afd_stream_t st) {
-  AFD_REQUIRE(p && g && m && v && state && n > 0, "afd_adamw_step: bad argument");
-  hipLaunchKernelGGL(adamw_step_k, dim3(gs_grid(n)), dim3(256), 0, as_stream(st), p, g, m, v, n, state, lr, b1, b2, eps, wd, gscale);
-  return check_launch("afd_adamw_step");
-}
-
-static inline bool beta_ok(float beta, float omb) { return beta >= 0.0f && beta <= 1.0f && omb >= 0.0f && omb <= 1.0f; }
-int afd_ema_step(float* ema, const float* p, long n, int copy, float beta, float one_minus_beta, afd_stream_t st) {
-  AFD_REQUIRE(ema && p, "afd_ema_step: ema or p is NULL");
-  AFD_REQUIRE(n > 0, "afd_ema_step: n must be positive (got %ld)", n);
-  AFD_REQUIRE(beta_ok(beta, one_minus_beta), "afd_ema_step: beta and 1 - beta must lie in [0, 1] (got %g, %g)", (double)beta,
-              (double)one_minus_beta);
-  const int c = copy != 0;
-  if (aligned16(ema) && aligned16(p))
-    hipLaunchKernelGGL(ema_step_k<true>, dim3(gs_grid((n + 3) / 4)), dim3(256), 0, as_stream(st), ema, p, n, c, beta, one_minus_beta);
-  else
-    hipLaunchKernelGGL(ema_step_k<false>, dim3(gs_grid(n)), dim3(256), 0, as_stream(st), ema, p, n, c, beta, one_minus_beta);
-  return check_launch("afd_ema_step");
-}
-int afd_adamw_ema_tick(float* adam_state, float b1, float b2, int* ema_state, int start, afd_stream_t st) {
-  AFD_REQUIRE(adam_state && ema_state, "afd_adamw_ema_tick: adam_state or ema_state is NULL");
-  AFD_REQUIRE(start >= 0, "afd_adamw_ema_tick: start must be >= 0 (got %d)", start);
-  hipLaunchKernelGGL(adamw_ema_tick_k, dim3(1), dim3(1), 0, as_stream(st), adam_state, b1, b2, ema_state, start);
-  return check_launch("afd_adamw_ema_tick");
-}
-int afd_adamw_ema_step(float* p, const float* g, float* m, float* v, long n_active, const float* adam_state, float lr, float b1,
-                       float b2, float eps, float wd, float gscale, float* ema, long n_ema, const int* ema_state, float beta,
-                       float one_minus_beta, afd_stream_t st) {
-  AFD_REQUIRE(p && g && m && v && adam_state && ema && ema_state, "afd_adamw_ema_step: a pointer is NULL");
-  AFD_REQUIRE(n_active > 0 && n_ema > 0, "afd_adamw_ema_step: n_active and n_ema must be positive (got %ld, %ld)", n_active, n_ema);
-  AFD_REQUIRE(n_active <= n_ema, "afd_adamw_ema_step: n_active > n_ema (%ld > %ld)", n_active, n_ema);
-  AFD_REQUIRE(beta_ok(beta, one_minus_beta), "afd_adamw_ema_step: beta and 1 - beta must lie in [0, 1] (got %g, %g)",
-              (double)beta, (double)one_minus_beta);
-  if (aligned16(p) && aligned16(g) && aligned16(m) && aligned16(v) && aligned16(ema))
-    hipLaunchKernelGGL(adamw_ema_step_k<true>, dim3(gs_grid((n_ema + 3) / 4)), dim3(256), 0, as_stream(st), p, g, m, v, n_active,
-                       adam_state, lr, b1, b2, eps, wd, gscale, ema, n_ema, ema_state, beta, one_minus_beta);
-  else
-    hipLaunchKernelGGL(adamw_ema_step_k<false>, dim3(gs_grid(n_ema)), dim3(256), 0, as_stream(st), p, g, m, v, n_active,
-                       adam_state, lr, b1, b2, eps, wd, gscale, ema, n_ema, ema_state, beta, one_minus_beta);
-  return check_launch("afd_adamw_ema_step");
-}
-
-int afd_grad_sqnorm_n_partials(void) { return kGradNormPartials; }
-int afd_grad_sqnorm_partials(const float* g, long n, float grad_scale, double* partials, int n_partials, afd_stream_t st) {
-  AFD_REQUIRE(g && partials, "afd_grad_sqnorm_partials: g or partials is NULL");
-  AFD_REQUIRE(n > 0, "afd_grad_sqnorm_partials: n must be positive (got %ld)", n);
-  AFD_REQUIRE(n_partials == kGradNormPartials, "afd_grad_sqnorm_partials: n_partials must be afd_grad_sqnorm_n_partials() = %d (got %d)",
-              kGradNormPartials, n_partials);
-  AFD_REQUIRE(!overlaps(partials, kGradNormPartials * (long)sizeof(double), g, n * (long)sizeof(float)),
-              "afd_grad_sqnorm_partials: partials must not overlap g");
-  const long slice = 4 * ((n + 4L * kGradNormPartials - 1) / (4L * kGradNormPartials));
-  if (aligned16(g))
-    hipLaunchKernelGGL(grad_sqnorm_partials_k<true>, dim3(kGradNormPartials), dim3(256), 0, as_stream(st), g, n, slice, grad_scale, partials);
-  else
-    hipLaunchKernelGGL(grad_sqnorm_partials_k<false>, dim3(kGradNormPartials), dim3(256), 0, as_stream(st), g, n, slice, grad_scale, partials);
-  return check_launch("afd_grad_sqnorm_partials");
-}
-int afd_adamw_ctl_tick(float* adam_state, float b1, float b2, int* ema_state, int ema_start, const double* partials, int n_partials,
-                       const afd_opt_ctl* cfg, double* ctl, afd_stream_t st) {
-  AFD_REQUIRE(adam_state && cfg && ctl, "afd_adamw_ctl_tick: adam_state, cfg or ctl is NULL");
-  AFD_REQUIRE(!ema_state || ema_start >= 0, "afd_adamw_ctl_tick: ema_start must be >= 0 (got %d)", ema_start);
-  AFD_REQUIRE(!partials || (n_partials >= 1 && n_partials <= kCtlMaxPartials), "afd_adamw_ctl_tick: n_partials must lie in [1, %d] (got %d)",
-              kCtlMaxPartials, n_partials);
-  AFD_REQUIRE(std::isfinite(cfg->base_lr) && cfg->base_lr >= 0.0, "afd_adamw_ctl_tick: base_lr must be finite and >= 0 (got %g)", cfg->base_lr);
-  AFD_REQUIRE(cfg->warmup >= 0, "afd_adamw_ctl_tick: warmup must be >= 0 (got %ld)", cfg->warmup);
-  AFD_REQUIRE(cfg->kind == AFD_LR_CONSTANT || cfg->kind == AFD_LR_LINEAR || cfg->kind == AFD_LR_COSINE,
-              "afd_adamw_ctl_tick: unknown schedule kind %d", cfg->kind);
-  AFD_REQUIRE(cfg->kind == AFD_LR_CONSTANT || cfg->total >= cfg->warmup, "afd_adamw_ctl_tick: total < warmup (%ld < %ld)", cfg->total,
-              cfg->warmup);
-  AFD_REQUIRE(cfg->min_ratio >= 0.0 && cfg->min_ratio <= 1.0, "afd_adamw_ctl_tick: min_ratio must lie in [0, 1] (got %g)", cfg->min_ratio);
-  AFD_REQUIRE(!std::isnan(cfg->max_norm), "afd_adamw_ctl_tick: max_norm is NaN");
-  hipLaunchKernelGGL(adamw_ctl_tick_k, dim3(1), dim3(256), 0, as_stream(st), adam_state, b1, b2, ema_state, ema_start, partials,
-                     partials ? n_partials : 0, *cfg, ctl);
-  return check_launch("afd_adamw_ctl_tick");
-}
-int afd_adamw_ctl_step(float* p, const float* g, float* m, float* v, long n_active, const float* adam_state, const double* ctl,
-                       float b1, float b2, float eps, float wd, float grad_scale, float* ema, long n_ema, const int* ema_state,
-                       float beta, float one_minus_beta, afd_stream_t st) {
-  AFD_REQUIRE(p && g && m && v && adam_state && ctl, "afd_adamw_ctl_step: a pointer is NULL");
-  AFD_REQUIRE(n_active > 0, "afd_adamw_ctl_step: n_active must be positive (got %ld)", n_active);
-  if (!ema) {
-    if (aligned16(p) && aligned16(g) && aligned16(m) && aligned16(v))
-      hipLaunchKernelGGL((adamw_ctl_step_k<true, false>), dim3(gs_grid((n_active + 3) / 4)), dim3(256), 0, as_stream(st), p, g, m, v,
-                         n_active, adam_state, ctl, b1, b2, eps, wd, grad_scale, (float*)nullptr, 0L, (const int*)nullptr, 0.0f, 0.0f);
-    else
-      hipLaunchKernelGGL((adamw_ctl_step_k<false, false>), dim3(gs_grid(n_active)), dim3(256), 0, as_stream(st), p, g, m, v, n_active,
-                         adam_state, ctl, b1, b2, eps, wd, grad_scale, (float*)nullptr, 0L, (const int*)nullptr, 0.0f, 0.0f);
-    return check_launch("afd_adamw_ctl_step");
-  }
-  AFD_REQUIRE(ema_state, "afd_adamw_ctl_step: ema is given but ema_state is NULL");
-  AFD_REQUIRE(n_ema > 0 && n_active <= n_ema, "afd_adamw_ctl_step: 0 < n_active <= n_ema is required (got %ld, %ld)", n_active, n_ema);
-  AFD_REQUIRE(beta_ok(beta, one_minus_beta), "afd_adamw_ctl_step: beta and 1 - beta must lie in [0, 1] (got %g, %g)", (double)beta,
-              (double)one_minus_beta);
-  if (aligned16(p) && aligned16(g) && aligned16(m) && aligned16(v) && aligned16(ema))
-    hipLaunchKernelGGL((adamw_ctl_step_k<true, true>), dim3(gs_grid((n_ema + 3) / 4)), dim3(256), 0, as_stream(st), p, g, m, v, n_active,
-                       adam_state, ctl, b1, b2, eps, wd, grad_scale, ema, n_ema, ema_state, beta, one_minus_beta);
-  else
-    hipLaunchKernelGGL((adamw_ctl_step_k<false, true>), dim3(gs_grid(n_ema)), dim3(256), 0, as_stream(st), p, g, m, v, n_active,
-                       adam_state, ctl, b1, b2, eps, wd, grad_scale, ema, n_ema, ema_state, beta, one_minus_beta);
-  return check_launch("afd_adamw_ctl_step");
 }
 
 }  // extern "C"

@@ -820,7 +820,6 @@ static size_t chain_lds(int C, int nvec) {
 template <class K> static int set_lds(K kern, size_t lds) { return lds_opt_in(kern, lds); }
 static int g_tok_max_wg = 0;       // test hook (afd_debug_tok_grid): cap on the workgroups of a launch, 0 = by the rule
 static int g_tok_path = 0;         // test hook (afd_debug_tok_path): 0 = by the rule, 1 = never the wide forms, 2 = wide wherever they exist
-static bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 // wide forms: C = 128 always, C = 64 for layers of fewer than 1024 pixel tiles (they exist for C in {64, 128})
 static bool use_wide(int C, long ntile) {
   if (C != 64 && C != 128) return false;

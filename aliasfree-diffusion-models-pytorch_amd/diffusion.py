@@ -3,7 +3,7 @@
 Bit-exactness: the schedule tables are built on the host with the reference's own torch calls (fp32
 linspace; torch.cumprod, which on the CPU accumulates fp32 inputs in double -- DESIGN.md section 4); `sample_timesteps` draws from torch's CPU generator exactly like
 the reference; noise_images / the denoise update / the uint8 quantisation are bit-exact HIP
-restatements (csrc/ddpm.hip).  The sampling loop stays on the device: no per-step H2D copy of `t`
+restatements (csrc/sampler.hip).  The sampling loop stays on the device: no per-step H2D copy of `t`
 (the reference does one per step, :362) and no per-step host sync.
 """
 import logging

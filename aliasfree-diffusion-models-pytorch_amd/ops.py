@@ -1109,66 +1109,24 @@ def noise_images(x, eps, t, alpha_hat):
     return out
 
 
-def denoise_step(x, eps_pred, noise, alpha, alpha_hat, beta, i, out=None):
-    _chk(x, eps_pred, noise)
-    x, eps_pred, noise = _c(x), _c(eps_pred), _c(noise)
-    out = torch.empty_like(x) if out is None else out
-    lib().afd_denoise_step(_p(x), _p(eps_pred), _p(noise), _p(alpha), _p(alpha_hat), _p(beta), int(i), _p(out),
-                           x.numel(), _stream())
-    return out
-
-
-def denoise_step_dev(x, eps_pred, noise, alpha, alpha_hat, beta, t_dev, out):
-    """Denoise update whose step index is t_dev[0] on the device (graph-replayable)."""
-    _chk(x, eps_pred, noise)
-    lib().afd_denoise_step_dev(_p(x), _p(eps_pred), _p(noise), _p(alpha), _p(alpha_hat), _p(beta), _p(t_dev), _p(out),
-                               x.numel(), _stream())
-    return out
-
-
-def _cfg_args(x, eps2, noise, out, out2):
-    _chk(x, eps2, noise, out, out2)
-    n = x.numel()
-    if eps2.numel() != 2 * n or (noise is not None and noise.numel() != n):
-        raise AfdError(f"afdm: guided denoise step needs eps2 of 2 x {n} elements (got {eps2.numel()}) and noise of {n}")
-    for o in (x, eps2, noise, out, out2):
-        if o is not None and not o.is_contiguous():
-            raise AfdError("afdm: guided denoise step: every tensor must be contiguous")
-        if o is not None and o is not eps2 and o.numel() != n:
-            raise AfdError(f"afdm: guided denoise step: x / noise / outputs must hold {n} elements")
-    return n
-
-
-def denoise_step_cfg(x, eps2, noise, alpha, alpha_hat, beta, i, cfg_scale, out=None, out2=None):
-    """Classifier-free guided update: eps2 = the forward over [conditional rows ; unconditional rows] (2n images),
-    e = torch.lerp(eps2[n:], eps2[:n], cfg_scale) and then exactly `denoise_step(x, e, ...)`, in one launch.  `out` may be
-    x (in place); `out2` (optional) receives the same values."""
-    out = torch.empty_like(x) if out is None else out
-    n = _cfg_args(x, eps2, noise, out, out2)
-    lib().afd_denoise_step_cfg(_p(x), _p(eps2), _p(noise), _p(alpha), _p(alpha_hat), _p(beta), int(i), float(cfg_scale), _p(out),
-                               _p(out2), n, _stream())
-    return out
-
-
-def denoise_step_cfg_dev(x, eps2, noise, alpha, alpha_hat, beta, t_dev, cfg_scale, out, out2=None):
-    """denoise_step_cfg with the step index t_dev[0] read on the device (graph-replayable)."""
-    n = _cfg_args(x, eps2, noise, out, out2)
-    lib().afd_denoise_step_cfg_dev(_p(x), _p(eps2), _p(noise), _p(alpha), _p(alpha_hat), _p(beta), _p(t_dev), float(cfg_scale),
-                                   _p(out), _p(out2), n, _stream())
-    return out
-
-
-def _ddim_args(what, x, eps, noise, alpha_hat, out, out2=None, guided=False):
-    _chk(x, eps, noise, alpha_hat, out, out2)
+def _step_args(what, x, eps, noise, table, out, out2=None, guided=False, x0=None, mask=None, masked=False):
+    """The argument check of every step wrapper -> n = x.numel().  eps holds n elements (2n when guided); noise, out, out2 and,
+    when masked, x0 (fp32) and mask (uint8) hold n; `table` (alpha_hat, DPM++'s coef; None: not checked) any number."""
+    _chk(x, eps, noise, table, out, out2, x0)
     n = x.numel()
     ne = 2 * n if guided else n
     if eps.numel() != ne:
         raise AfdError(f"afdm: {what} needs eps{'2' if guided else ''} of {ne} elements (got {eps.numel()})")
-    for o in (x, eps, noise, alpha_hat, out, out2):
+    for o in (x, eps, noise, table, out, out2):
         if o is not None and not o.is_contiguous():
             raise AfdError(f"afdm: {what}: every tensor must be contiguous")
-        if o is not None and o is not eps and o is not alpha_hat and o.numel() != n:
+        if o is not None and o is not eps and o is not table and o.numel() != n:
             raise AfdError(f"afdm: {what}: x / noise / outputs must hold {n} elements")
+    if masked:
+        if x0.numel() != n or not x0.is_contiguous():
+            raise AfdError(f"afdm: {what}: x0 must be a contiguous tensor of {n} elements")
+        if not mask.is_cuda or mask.dtype != torch.uint8 or mask.numel() != n or not mask.is_contiguous():
+            raise AfdError(f"afdm: {what}: mask must be a contiguous uint8 device tensor of {n} elements")
     return n
 
 
@@ -1187,46 +1145,72 @@ def _ddim_dev_t(what, t_dev, t_prev_dev):
             raise AfdError(f"afdm: {what}: t_dev / t_prev_dev must be int64 device tensors (element 0 is read)")
 
 
+def _step(what, x, eps, noise, tables, index, out, eta=None, cfg_scale=None, out2=None, x0=None, mask=None, masked=False, dev=False):
+    """One DDPM step (eta None; tables = (alpha, alpha_hat, beta), index = (i,)) or DDIM step (tables = (alpha_hat,), index =
+    (t, t_prev)): checks the arguments and calls afd_{denoise,ddim}_step[_masked][_cfg][_dev], whose arguments run
+    x, eps, noise, [x0, mask], tables, index, [eta], [cfg_scale], x_out, [x_out2], n, stream.  dev: index holds device tensors."""
+    ddim, guided = eta is not None, cfg_scale is not None
+    out = torch.empty_like(x) if out is None else out
+    n = _step_args(what, x, eps, noise, tables[0] if ddim else None, out, out2, guided, x0, mask, masked)
+    if ddim and dev:
+        _ddim_dev_t(what, *index)
+        eta = float(eta)
+    elif ddim:
+        *index, eta = _ddim_host_t(what, tables[0], *index, eta)
+    index = [_p(v) if dev else int(v) for v in index]
+    name = ("afd_ddim_step" if ddim else "afd_denoise_step") + "_masked" * masked + "_cfg" * guided + "_dev" * dev
+    args = [_p(x), _p(eps), _p(noise)] + ([_p(x0), _p(mask)] if masked else []) + [_p(t) for t in tables] + index
+    args += ([eta] if ddim else []) + ([float(cfg_scale)] if guided else []) + [_p(out)] + ([_p(out2)] if guided else [])
+    getattr(lib(), name)(*args, n, _stream())
+    return out
+
+
+def denoise_step(x, eps_pred, noise, alpha, alpha_hat, beta, i, out=None):
+    return _step("denoise step", _c(x), _c(eps_pred), _c(noise), (alpha, alpha_hat, beta), (i,), out)
+
+
+def denoise_step_dev(x, eps_pred, noise, alpha, alpha_hat, beta, t_dev, out):
+    """Denoise update whose step index is t_dev[0] on the device (graph-replayable)."""
+    return _step("denoise step", x, eps_pred, noise, (alpha, alpha_hat, beta), (t_dev,), out, dev=True)
+
+
+def denoise_step_cfg(x, eps2, noise, alpha, alpha_hat, beta, i, cfg_scale, out=None, out2=None):
+    """Classifier-free guided update: eps2 = the forward over [conditional rows ; unconditional rows] (2n images),
+    e = torch.lerp(eps2[n:], eps2[:n], cfg_scale) and then exactly `denoise_step(x, e, ...)`, in one launch.  `out` may be
+    x (in place); `out2` (optional) receives the same values."""
+    return _step("guided denoise step", x, eps2, noise, (alpha, alpha_hat, beta), (i,), out, cfg_scale=cfg_scale, out2=out2)
+
+
+def denoise_step_cfg_dev(x, eps2, noise, alpha, alpha_hat, beta, t_dev, cfg_scale, out, out2=None):
+    """denoise_step_cfg with the step index t_dev[0] read on the device (graph-replayable)."""
+    return _step("guided denoise step", x, eps2, noise, (alpha, alpha_hat, beta), (t_dev,), out, cfg_scale=cfg_scale, out2=out2, dev=True)
+
+
 def ddim_step(x, eps, noise, alpha_hat, t, t_prev, eta, out=None):
     """DDIM update t -> t_prev (include/afd.h: afd_ddim_step gives the exact expression).  noise: None (the last step, or
     eta = 0) or n standard-normal values scaled by sigma.  `out` may be x (in place)."""
-    out = torch.empty_like(x) if out is None else out
-    n = _ddim_args("DDIM step", x, eps, noise, alpha_hat, out)
-    t, t_prev, eta = _ddim_host_t("DDIM step", alpha_hat, t, t_prev, eta)
-    lib().afd_ddim_step(_p(x), _p(eps), _p(noise), _p(alpha_hat), t, t_prev, eta, _p(out), n, _stream())
-    return out
+    return _step("DDIM step", x, eps, noise, (alpha_hat,), (t, t_prev), out, eta=eta)
 
 
 def ddim_step_dev(x, eps, noise, alpha_hat, t_dev, t_prev_dev, eta, out):
     """ddim_step with t = t_dev[0] and t_prev = t_prev_dev[0] read on the device (graph-replayable)."""
-    n = _ddim_args("DDIM step", x, eps, noise, alpha_hat, out)
-    _ddim_dev_t("DDIM step", t_dev, t_prev_dev)
-    lib().afd_ddim_step_dev(_p(x), _p(eps), _p(noise), _p(alpha_hat), _p(t_dev), _p(t_prev_dev), float(eta), _p(out), n, _stream())
-    return out
+    return _step("DDIM step", x, eps, noise, (alpha_hat,), (t_dev, t_prev_dev), out, eta=eta, dev=True)
 
 
 def ddim_step_cfg(x, eps2, noise, alpha_hat, t, t_prev, eta, cfg_scale, out=None, out2=None):
     """Classifier-free guided DDIM update: e = torch.lerp(eps2[n:], eps2[:n], cfg_scale), then exactly `ddim_step(x, e, ...)`,
     in one launch.  `out` may be x (in place); `out2` (optional) receives the same values."""
-    out = torch.empty_like(x) if out is None else out
-    n = _ddim_args("guided DDIM step", x, eps2, noise, alpha_hat, out, out2, guided=True)
-    t, t_prev, eta = _ddim_host_t("guided DDIM step", alpha_hat, t, t_prev, eta)
-    lib().afd_ddim_step_cfg(_p(x), _p(eps2), _p(noise), _p(alpha_hat), t, t_prev, eta, float(cfg_scale), _p(out), _p(out2), n,
-                            _stream())
-    return out
+    return _step("guided DDIM step", x, eps2, noise, (alpha_hat,), (t, t_prev), out, eta=eta, cfg_scale=cfg_scale, out2=out2)
 
 
 def ddim_step_cfg_dev(x, eps2, noise, alpha_hat, t_dev, t_prev_dev, eta, cfg_scale, out, out2=None):
     """ddim_step_cfg with the step indices read on the device (graph-replayable)."""
-    n = _ddim_args("guided DDIM step", x, eps2, noise, alpha_hat, out, out2, guided=True)
-    _ddim_dev_t("guided DDIM step", t_dev, t_prev_dev)
-    lib().afd_ddim_step_cfg_dev(_p(x), _p(eps2), _p(noise), _p(alpha_hat), _p(t_dev), _p(t_prev_dev), float(eta), float(cfg_scale),
-                                _p(out), _p(out2), n, _stream())
-    return out
+    return _step("guided DDIM step", x, eps2, noise, (alpha_hat,), (t_dev, t_prev_dev), out, eta=eta, cfg_scale=cfg_scale, out2=out2,
+                 dev=True)
 
 
 def _dpmpp_args(what, x, eps, x0_prev, coef, out, x0_out, out2=None, guided=False):
-    n = _ddim_args(what, x, eps, x0_prev, coef, out, out2, guided)
+    n = _step_args(what, x, eps, x0_prev, coef, out, out2, guided)
     _chk(x0_out)
     if coef.numel() != 5:
         raise AfdError(f"afdm: {what} needs coef of 5 values [alpha_t, sigma_t, A, B0, B1] (got {coef.numel()})")
@@ -1327,90 +1311,54 @@ def vlb_prior(x0, half_ah, out=None):
 
 
 # ---- inpainting: masked steps and the renoise up-move (include/afd.h gives the exact expressions) --------------------------
-def _masked_args(what, x, eps, noise, x0, mask, out, out2=None, guided=False):
-    n = _ddim_args(what, x, eps, noise, None, out, out2, guided)
-    _chk(x0)
-    if x0.numel() != n or not x0.is_contiguous():
-        raise AfdError(f"afdm: {what}: x0 must be a contiguous tensor of {n} elements")
-    if not mask.is_cuda or mask.dtype != torch.uint8 or mask.numel() != n or not mask.is_contiguous():
-        raise AfdError(f"afdm: {what}: mask must be a contiguous uint8 device tensor of {n} elements")
-    return n
-
-
 def denoise_step_masked(x, eps, noise, x0, mask, alpha, alpha_hat, beta, i, out=None):
     """Masked DDPM update i -> i - 1: where mask is 0, `denoise_step`; where it is 1, x0 noised to i - 1 with the same noise
     (x0 itself at i == 1, where noise may be None).  `out` may be x (in place)."""
-    out = torch.empty_like(x) if out is None else out
-    n = _masked_args("masked denoise step", x, eps, noise, x0, mask, out)
-    lib().afd_denoise_step_masked(_p(x), _p(eps), _p(noise), _p(x0), _p(mask), _p(alpha), _p(alpha_hat), _p(beta), int(i), _p(out),
-                                  n, _stream())
-    return out
+    return _step("masked denoise step", x, eps, noise, (alpha, alpha_hat, beta), (i,), out, x0=x0, mask=mask, masked=True)
 
 
 def denoise_step_masked_dev(x, eps, noise, x0, mask, alpha, alpha_hat, beta, t_dev, out):
     """denoise_step_masked with the step index t_dev[0] read on the device (graph-replayable); noise is required."""
-    n = _masked_args("masked denoise step", x, eps, noise, x0, mask, out)
-    lib().afd_denoise_step_masked_dev(_p(x), _p(eps), _p(noise), _p(x0), _p(mask), _p(alpha), _p(alpha_hat), _p(beta), _p(t_dev),
-                                      _p(out), n, _stream())
-    return out
+    return _step("masked denoise step", x, eps, noise, (alpha, alpha_hat, beta), (t_dev,), out, x0=x0, mask=mask, masked=True, dev=True)
 
 
 def denoise_step_masked_cfg(x, eps2, noise, x0, mask, alpha, alpha_hat, beta, i, cfg_scale, out=None, out2=None):
     """The guided form of denoise_step_masked (eps2 as for denoise_step_cfg); `out2` (optional) receives the same values."""
-    out = torch.empty_like(x) if out is None else out
-    n = _masked_args("guided masked denoise step", x, eps2, noise, x0, mask, out, out2, guided=True)
-    lib().afd_denoise_step_masked_cfg(_p(x), _p(eps2), _p(noise), _p(x0), _p(mask), _p(alpha), _p(alpha_hat), _p(beta), int(i),
-                                      float(cfg_scale), _p(out), _p(out2), n, _stream())
-    return out
+    return _step("guided masked denoise step", x, eps2, noise, (alpha, alpha_hat, beta), (i,), out, cfg_scale=cfg_scale, out2=out2,
+                 x0=x0, mask=mask, masked=True)
 
 
 def denoise_step_masked_cfg_dev(x, eps2, noise, x0, mask, alpha, alpha_hat, beta, t_dev, cfg_scale, out, out2=None):
-    n = _masked_args("guided masked denoise step", x, eps2, noise, x0, mask, out, out2, guided=True)
-    lib().afd_denoise_step_masked_cfg_dev(_p(x), _p(eps2), _p(noise), _p(x0), _p(mask), _p(alpha), _p(alpha_hat), _p(beta),
-                                          _p(t_dev), float(cfg_scale), _p(out), _p(out2), n, _stream())
-    return out
+    return _step("guided masked denoise step", x, eps2, noise, (alpha, alpha_hat, beta), (t_dev,), out, cfg_scale=cfg_scale, out2=out2,
+                 x0=x0, mask=mask, masked=True, dev=True)
 
 
 def ddim_step_masked(x, eps, noise, x0, mask, alpha_hat, t, t_prev, eta, out=None):
     """Masked DDIM update t -> t_prev: where mask is 0, `ddim_step` (no noise term when eta == 0); where it is 1, x0 noised to
     t_prev with the same noise (x0 itself at t_prev == 0, where noise may be None).  `out` may be x (in place)."""
-    out = torch.empty_like(x) if out is None else out
-    n = _masked_args("masked DDIM step", x, eps, noise, x0, mask, out)
-    t, t_prev, eta = _ddim_host_t("masked DDIM step", alpha_hat, t, t_prev, eta)
-    lib().afd_ddim_step_masked(_p(x), _p(eps), _p(noise), _p(x0), _p(mask), _p(alpha_hat), t, t_prev, eta, _p(out), n, _stream())
-    return out
+    return _step("masked DDIM step", x, eps, noise, (alpha_hat,), (t, t_prev), out, eta=eta, x0=x0, mask=mask, masked=True)
 
 
 def ddim_step_masked_dev(x, eps, noise, x0, mask, alpha_hat, t_dev, t_prev_dev, eta, out):
-    n = _masked_args("masked DDIM step", x, eps, noise, x0, mask, out)
-    _ddim_dev_t("masked DDIM step", t_dev, t_prev_dev)
-    lib().afd_ddim_step_masked_dev(_p(x), _p(eps), _p(noise), _p(x0), _p(mask), _p(alpha_hat), _p(t_dev), _p(t_prev_dev), float(eta),
-                                   _p(out), n, _stream())
-    return out
+    return _step("masked DDIM step", x, eps, noise, (alpha_hat,), (t_dev, t_prev_dev), out, eta=eta, x0=x0, mask=mask, masked=True,
+                 dev=True)
 
 
 def ddim_step_masked_cfg(x, eps2, noise, x0, mask, alpha_hat, t, t_prev, eta, cfg_scale, out=None, out2=None):
-    out = torch.empty_like(x) if out is None else out
-    n = _masked_args("guided masked DDIM step", x, eps2, noise, x0, mask, out, out2, guided=True)
-    t, t_prev, eta = _ddim_host_t("guided masked DDIM step", alpha_hat, t, t_prev, eta)
-    lib().afd_ddim_step_masked_cfg(_p(x), _p(eps2), _p(noise), _p(x0), _p(mask), _p(alpha_hat), t, t_prev, eta, float(cfg_scale),
-                                   _p(out), _p(out2), n, _stream())
-    return out
+    return _step("guided masked DDIM step", x, eps2, noise, (alpha_hat,), (t, t_prev), out, eta=eta, cfg_scale=cfg_scale, out2=out2,
+                 x0=x0, mask=mask, masked=True)
 
 
 def ddim_step_masked_cfg_dev(x, eps2, noise, x0, mask, alpha_hat, t_dev, t_prev_dev, eta, cfg_scale, out, out2=None):
-    n = _masked_args("guided masked DDIM step", x, eps2, noise, x0, mask, out, out2, guided=True)
-    _ddim_dev_t("guided masked DDIM step", t_dev, t_prev_dev)
-    lib().afd_ddim_step_masked_cfg_dev(_p(x), _p(eps2), _p(noise), _p(x0), _p(mask), _p(alpha_hat), _p(t_dev), _p(t_prev_dev),
-                                       float(eta), float(cfg_scale), _p(out), _p(out2), n, _stream())
-    return out
+    return _step("guided masked DDIM step", x, eps2, noise, (alpha_hat,), (t_dev, t_prev_dev), out, eta=eta, cfg_scale=cfg_scale,
+                 out2=out2, x0=x0, mask=mask, masked=True, dev=True)
 
 
 def renoise(x, noise, alpha_hat, t_from, t_to, out=None):
     """q(x_{t_to} | x_{t_from}) in one jump: sqrt(a) * x + sqrt(1 - a) * noise, a = alpha_hat[t_to] / alpha_hat[t_from].
     `out` may be x (in place)."""
     out = torch.empty_like(x) if out is None else out
-    n = _ddim_args("renoise", x, noise, None, alpha_hat, out)
+    n = _step_args("renoise", x, noise, None, alpha_hat, out)
     t_from, t_to = int(t_from), int(t_to)
     if not 0 <= t_from < t_to < alpha_hat.numel():
         raise AfdError(f"afdm: renoise needs 0 <= t_from < t_to < {alpha_hat.numel()} (got {t_from}, {t_to})")
