@@ -1507,25 +1507,37 @@ def mse_loss(target, pred):
 PRED_KINDS = {"eps": 0, "v": 1, "x0": 2}          # AFD_PRED_EPS / AFD_PRED_V / AFD_PRED_X0 of afd.h
 
 
-def _objective_args(what, kind, t, alpha_hat, *tensors):
-    """-> (AFD_PRED_* code, B, chw) after checking the tensors of one of the objective kernels: `tensors` (B, ...) fp32 device
-    tensors of one shape, contiguous; t (B,) int64 on the device; alpha_hat (T,) fp32.  t's values are read unchecked."""
+def _pred_tensors(what, kind, tables, tensors, min_dim, shape):
+    """_objective_args' and _lvar_args' first checks: kind; fp32 device tensors; `tensors` contiguous, of one shape -> the first"""
     if not isinstance(kind, str) or kind not in PRED_KINDS:
         raise AfdError(f"afdm: {what}: unknown prediction {kind!r} ('eps', 'v' or 'x0')")
-    if any(not isinstance(o, torch.Tensor) for o in (alpha_hat,) + tensors):
+    if any(not isinstance(o, torch.Tensor) for o in tables + tensors):
         raise AfdError(f"afdm: {what}: every argument but kind must be a tensor")
-    _chk(alpha_hat, *tensors)
+    _chk(*tables, *tensors)
     first = tensors[0]
-    if first.dim() < 1 or first.numel() == 0:
-        raise AfdError(f"afdm: {what}: needs tensors of shape (B, ...) with at least one element")
+    if first.dim() < min_dim or first.numel() == 0:
+        raise AfdError(f"afdm: {what}: needs tensors of shape {shape} with at least one element")
     for o in tensors:
         if tuple(o.shape) != tuple(first.shape) or not o.is_contiguous():
             raise AfdError(f"afdm: {what}: every tensor must be contiguous and of shape {tuple(first.shape)}")
-    B = first.shape[0]
-    if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.long or tuple(t.shape) != (B,) or not t.is_contiguous():
+    return first
+
+
+def _row_t_and_table(what, t, alpha_hat, B, t_optional=False):
+    """and their last: t a (B,) int64 device tensor (its values are read unchecked; t_optional: or None), alpha_hat a (T,) table"""
+    if not (t is None and t_optional) and (not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.long
+                                           or tuple(t.shape) != (B,) or not t.is_contiguous()):
         raise AfdError(f"afdm: {what}: t must be a contiguous int64 device tensor of shape ({B},)")
     if alpha_hat.dim() != 1 or not alpha_hat.is_contiguous():
         raise AfdError(f"afdm: {what}: alpha_hat must be a contiguous (T,) table")
+
+
+def _objective_args(what, kind, t, alpha_hat, *tensors):
+    """-> (AFD_PRED_* code, B, chw) after checking the tensors of one of the objective kernels: `tensors` (B, ...) fp32 device
+    tensors of one shape, contiguous; t (B,) int64 on the device; alpha_hat (T,) fp32."""
+    first = _pred_tensors(what, kind, (alpha_hat,), tensors, 1, "(B, ...)")
+    B = first.shape[0]
+    _row_t_and_table(what, t, alpha_hat, B)
     return PRED_KINDS[kind], B, first.numel() // B
 
 
@@ -1579,28 +1591,13 @@ def _lvar_args(what, kind, out2, t, alpha_hat, lv_coef, *tensors, rows2=1):
     """-> (AFD_PRED_* code, B, chw): out2 is the contiguous (rows2 * B, 2C, ...) output of a learned-variance network, `tensors`
     are contiguous (B, C, ...) fp32 device tensors of one shape (None entries are skipped), t None or (B,) int64 on the device,
     lv_coef the (T, 3) fp64 device table of `Diffusion.lvar_coefficients`."""
-    if not isinstance(kind, str) or kind not in PRED_KINDS:
-        raise AfdError(f"afdm: {what}: unknown prediction {kind!r} ('eps', 'v' or 'x0')")
-    given = tuple(o for o in tensors if o is not None)
-    if any(not isinstance(o, torch.Tensor) for o in (out2, alpha_hat) + given):
-        raise AfdError(f"afdm: {what}: every argument but kind must be a tensor")
-    _chk(out2, alpha_hat, *given)
-    first = given[0]
-    if first.dim() < 2 or first.numel() == 0:
-        raise AfdError(f"afdm: {what}: needs tensors of shape (B, C, ...) with at least one element")
-    for o in given:
-        if tuple(o.shape) != tuple(first.shape) or not o.is_contiguous():
-            raise AfdError(f"afdm: {what}: every tensor must be contiguous and of shape {tuple(first.shape)}")
+    first = _pred_tensors(what, kind, (out2, alpha_hat), tuple(o for o in tensors if o is not None), 2, "(B, C, ...)")
     B, C = first.shape[0], first.shape[1]
     want = (rows2 * B, 2 * C) + tuple(first.shape[2:])
     if tuple(out2.shape) != want or not out2.is_contiguous():
         raise AfdError(f"afdm: {what}: the network's output must be contiguous and of shape {want}: {2 * C} channels, the "
                        f"prediction's {C} and the variance coefficient's {C} (got {tuple(out2.shape)})")
-    if t is not None and (not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.long or tuple(t.shape) != (B,)
-                          or not t.is_contiguous()):
-        raise AfdError(f"afdm: {what}: t must be a contiguous int64 device tensor of shape ({B},)")
-    if alpha_hat.dim() != 1 or not alpha_hat.is_contiguous():
-        raise AfdError(f"afdm: {what}: alpha_hat must be a contiguous (T,) table")
+    _row_t_and_table(what, t, alpha_hat, B, t_optional=True)
     T = alpha_hat.numel()
     if lv_coef is not None and (not isinstance(lv_coef, torch.Tensor) or not lv_coef.is_cuda or lv_coef.dtype != torch.float64
                                 or tuple(lv_coef.shape) != (T, 3) or not lv_coef.is_contiguous()):
