@@ -544,6 +544,80 @@ __global__ __launch_bounds__(256) void vlb_terms_lvar_k(const float* __restrict_
   }
 }
 
+// ---- progressive distillation (Salimans & Ho 2022): two DDIM steps of a teacher, per row, folded into one student target ------
+// Row b goes t -> t_mid -> t_prev (eta = 0).  With a = alpha_hat[.], al = sqrt(a), sg = sqrt(1 - a); the chain's last level
+// t_prev = 0 is alpha_hat[0], as the DDIM rule of sampler.hip reads it (Ddim::make), so the target matches the sampler's last step:
+//   (x_hat, eps_hat) of a raw output p at z:  eps: (z - sg p) / al, p;   v: al z - sg p, sg z + al p;   x0: p, (z - al p) / sg
+//   z_mid   = al' x_hat_1 + sg' eps_hat_1                               (distill_mid_k;    out1 is the output at (z_t, t))
+//   z_prev  = al'' x_hat_2 + sg'' eps_hat_2                             (distill_target_k; out2 is the output at (z_mid, t_mid))
+//   x_tilde = (z_prev - r z_t) / (al'' - r al),  r = sg'' / sg
+//   eps_tilde = (z_t - al x_tilde) / sg
+// so that one DDIM step from z_t with (x_tilde, eps_tilde) lands on z_prev.  The denominator is sin(phi - phi'') / sg with
+// al = cos(phi), a few 1e-3 between neighbouring levels, and the numerator cancels to the same order: every element is widened
+// to fp64, the roots are taken in fp64 from the fp32 table, and the result is rounded once on the store (as the lvar kernels).
+// An output may be one of the inputs (each thread reads its quad of every input before it writes), hence no __restrict__.
+struct Level64 {
+  double al, sg;
+};
+__device__ __forceinline__ Level64 level64(const float* __restrict__ alpha_hat, long t) {
+  const double a = (double)alpha_hat[t];
+  return Level64{sqrt(a), sqrt(1.0 - a)};
+}
+__device__ __forceinline__ void distill_split(int kind, double p, double z, const Level64& k, double& x, double& e) {
+  if (kind == AFD_PRED_V) {
+    x = k.al * z - k.sg * p;
+    e = k.sg * z + k.al * p;
+  } else if (kind == AFD_PRED_X0) {
+    x = p;
+    e = (z - k.al * p) / k.sg;
+  } else {
+    e = p;
+    x = (z - k.sg * p) / k.al;
+  }
+}
+// the DDIM step (eta = 0) of the raw output p at z, level k -> level n, in fp64
+__device__ __forceinline__ double distill_ddim(int kind, float p, float z, const Level64& k, const Level64& n) {
+  double x, e;
+  distill_split(kind, (double)p, (double)z, k, x, e);
+  return n.al * x + n.sg * e;
+}
+template <bool VEC>
+__global__ __launch_bounds__(256) void distill_mid_k(const float* out1, const float* z_t, const int64_t* __restrict__ t,
+                                                     const int64_t* __restrict__ t_mid, const float* __restrict__ alpha_hat, int kind,
+                                                     float* z_mid, long items, long segs, long chw) {
+  for_row_quads(items, segs, chw, [&](const RowQuad& rq) {
+    const Level64 k = level64(alpha_hat, t[rq.b]), n = level64(alpha_hat, t_mid[rq.b]);
+    if (rq.left <= 0) return;
+    const float4 p = load_quad<VEC>(out1, rq.o, rq.left), z = load_quad<VEC>(z_t, rq.o, rq.left);
+    store_quad<VEC>(z_mid, rq.o, rq.left, quad_map([&](float pi, float zi) { return (float)distill_ddim(kind, pi, zi, k, n); }, p, z));
+  });
+}
+template <bool VEC>
+__global__ __launch_bounds__(256) void distill_target_k(const float* out2, const float* z_mid, const float* z_t,
+                                                        const int64_t* __restrict__ t, const int64_t* __restrict__ t_mid,
+                                                        const int64_t* __restrict__ t_prev, const float* __restrict__ alpha_hat,
+                                                        int kind, float* x_tilde, float* eps_tilde, long items, long segs, long chw) {
+  for_row_quads(items, segs, chw, [&](const RowQuad& rq) {
+    const Level64 k = level64(alpha_hat, t[rq.b]), m = level64(alpha_hat, t_mid[rq.b]), n = level64(alpha_hat, t_prev[rq.b]);
+    const double r = n.sg / k.sg;
+    const double den = n.al - r * k.al;
+    if (rq.left <= 0) return;
+    const float4 p = load_quad<VEC>(out2, rq.o, rq.left), zm = load_quad<VEC>(z_mid, rq.o, rq.left);
+    const float4 z = load_quad<VEC>(z_t, rq.o, rq.left);
+    float xs[4], es[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const double zi = (double)lane(z, i);
+      const double zp = distill_ddim(kind, lane(p, i), lane(zm, i), m, n);
+      const double x = (zp - r * zi) / den;
+      xs[i] = (float)x;
+      es[i] = (float)((zi - k.al * x) / k.sg);
+    }
+    store_quad<VEC>(x_tilde, rq.o, rq.left, make_float4(xs[0], xs[1], xs[2], xs[3]));
+    store_quad<VEC>(eps_tilde, rq.o, rq.left, make_float4(es[0], es[1], es[2], es[3]));
+  });
+}
+
 }  // namespace afd
 using namespace afd;
 
@@ -641,6 +715,45 @@ int afd_pred_to_eps(const float* out, const float* x_t, const int64_t* t, const 
   launch_vec(vec_ok(chw, {out, x_t, eps_out}), pred_to_eps_k<true>, pred_to_eps_k<false>, g.grid, as_stream(st), out, x_t, t, alpha_hat,
              kind, eps_out, g.items, g.segs, chw);
   return check_launch("afd_pred_to_eps");
+}
+
+// ---- progressive distillation -----------------------------------------------------------------------------------------------
+// an output may be one of the B x chw inputs itself (the same pointer); otherwise it shares no memory with it
+static bool same_or_apart(const float* out, long fb, std::initializer_list<const float*> ins) {
+  for (const float* in : ins)
+    if (out != in && overlaps(out, fb, in, fb)) return false;
+  return true;
+}
+int afd_distill_mid(const float* out1, const float* z_t, const int64_t* t, const int64_t* t_mid, const float* alpha_hat, int kind,
+                    float* z_mid, long B, long chw, afd_stream_t st) {
+  AFD_REQUIRE(out1 && z_t && t && t_mid && alpha_hat && z_mid,
+              "afd_distill_mid: out1, z_t, t, t_mid, alpha_hat and z_mid must not be NULL");
+  AFD_REQUIRE_KIND("afd_distill_mid", kind);
+  AFD_REQUIRE_B_CHW("afd_distill_mid", B, chw);
+  const long fb = B * chw * kF, ib = B * kI;
+  AFD_REQUIRE(same_or_apart(z_mid, fb, {out1, z_t}) && all_apart({{z_mid, fb}}, {{t, ib}, {t_mid, ib}}),
+              "afd_distill_mid: z_mid must be out1 or z_t itself or apart from them, and must not overlap t or t_mid");
+  const RowQuadGrid g(B, chw, kObjBlocks);
+  launch_vec(vec_ok(chw, {out1, z_t, z_mid}), distill_mid_k<true>, distill_mid_k<false>, g.grid, as_stream(st), out1, z_t, t, t_mid,
+             alpha_hat, kind, z_mid, g.items, g.segs, chw);
+  return check_launch("afd_distill_mid");
+}
+int afd_distill_target(const float* out2, const float* z_mid, const float* z_t, const int64_t* t, const int64_t* t_mid,
+                       const int64_t* t_prev, const float* alpha_hat, int kind, float* x_tilde, float* eps_tilde, long B, long chw,
+                       afd_stream_t st) {
+  AFD_REQUIRE(out2 && z_mid && z_t && t && t_mid && t_prev && alpha_hat && x_tilde && eps_tilde,
+              "afd_distill_target: out2, z_mid, z_t, t, t_mid, t_prev, alpha_hat, x_tilde and eps_tilde must not be NULL");
+  AFD_REQUIRE_KIND("afd_distill_target", kind);
+  AFD_REQUIRE_B_CHW("afd_distill_target", B, chw);
+  const long fb = B * chw * kF, ib = B * kI;
+  AFD_REQUIRE(same_or_apart(x_tilde, fb, {out2, z_mid, z_t}) && same_or_apart(eps_tilde, fb, {out2, z_mid, z_t}) &&
+                  all_apart({{x_tilde, fb}, {eps_tilde, fb}}, {{t, ib}, {t_mid, ib}, {t_prev, ib}}),
+              "afd_distill_target: x_tilde and eps_tilde must each be an input itself or apart from it, and must not overlap each "
+              "other, t, t_mid or t_prev");
+  const RowQuadGrid g(B, chw, kObjBlocks);
+  launch_vec(vec_ok(chw, {out2, z_mid, z_t, x_tilde, eps_tilde}), distill_target_k<true>, distill_target_k<false>, g.grid, as_stream(st),
+             out2, z_mid, z_t, t, t_mid, t_prev, alpha_hat, kind, x_tilde, eps_tilde, g.items, g.segs, chw);
+  return check_launch("afd_distill_target");
 }
 
 // ---- likelihood (bits/dim) ------------------------------------------------------------------------------------------------

@@ -42,7 +42,7 @@ def gather_u8(t, counts, group=None, dst=0):
 class Diffusion:
     SCHEDULES = ("linear", "cosine")
     PREDICTIONS = ("eps", "v", "x0")
-    LOSS_WEIGHTINGS = ("min_snr",)
+    LOSS_WEIGHTINGS = ("min_snr", "truncated_snr")
     VARIANCES = ("fixed", "learned")
 
     def __init__(self, noise_steps=1000, beta_start=1e-4, beta_end=0.02, img_size=256, device="cuda", schedule="linear",
@@ -175,22 +175,98 @@ class Diffusion:
         return ops.pred_to_eps(out, x_t.contiguous(), t, self.alpha_hat, self.prediction, eps_out=out)
 
     def snr_weights(self, kind="min_snr", gamma=5.0):
-        """(T,) fp64 host table of the loss weight of each timestep for `self.prediction` (Min-SNR-gamma, Hang et al. 2023):
-        with snr_t = a_t / (1 - a_t) from the fp32 alpha_hat, min(snr, gamma) / snr for "eps", min(snr, gamma) for "x0",
-        min(snr, gamma) / (snr + 1) for "v"."""
+        """(T,) fp64 host table of the loss weight of each timestep for `self.prediction`, with snr_t = a_t / (1 - a_t) from the fp32
+        alpha_hat widened to fp64 and c_t the clipped snr:
+          "min_snr" (Min-SNR-gamma, Hang et al. 2023): c = min(snr, gamma);
+          "truncated_snr" (Salimans & Ho 2022, the weight progressive distillation trains with): c = max(snr, 1); gamma is ignored.
+        The weight is c / snr for "eps", c for "x0" and c / (snr + 1) for "v": c on the x0 error in every parametrisation."""
         if not isinstance(kind, str) or kind not in self.LOSS_WEIGHTINGS:
-            raise ValueError(f"Diffusion.snr_weights: unknown kind {kind!r} ('min_snr')")
-        if isinstance(gamma, bool) or not isinstance(gamma, (int, float, np.integer, np.floating)) or not gamma > 0 \
-                or not math.isfinite(gamma):
-            raise ValueError(f"Diffusion.snr_weights: gamma must be a finite number > 0 (got {gamma!r})")
+            raise ValueError(f"Diffusion.snr_weights: unknown kind {kind!r} ('min_snr' or 'truncated_snr')")
         a = self.alpha_hat.detach().cpu().double()
         snr = a / (1.0 - a)
-        clipped = torch.clamp(snr, max=float(gamma))
+        if kind == "truncated_snr":
+            clipped = torch.clamp(snr, min=1.0)
+        else:
+            if isinstance(gamma, bool) or not isinstance(gamma, (int, float, np.integer, np.floating)) or not gamma > 0 \
+                    or not math.isfinite(gamma):
+                raise ValueError(f"Diffusion.snr_weights: gamma must be a finite number > 0 (got {gamma!r})")
+            clipped = torch.clamp(snr, max=float(gamma))
         if self.prediction == "eps":
             return clipped / snr
         if self.prediction == "x0":
             return clipped
         return clipped / (snr + 1.0)
+
+    # Progressive distillation (Salimans & Ho 2022) ---------------------------------------------------------------------------------
+    def distill_levels(self, chain):
+        """The per-step timestep tables of one distillation round.  chain: the teacher's DDIM timesteps, an explicit strictly
+        decreasing sequence of ints in [1, T - 1] of EVEN length 2N (validated as `sample(steps=chain)` validates it).  With the
+        levels L = chain + [0], student step k goes L[2k] -> L[2k + 2] and the teacher covers it through L[2k + 1]:
+        -> (t, t_mid, t_prev), three (N,) int64 host tensors.  ValueError also when alpha_hat does not strictly decrease along the
+        levels (the target's denominator sqrt(a'') - (sigma'' / sigma) sqrt(a) would not be positive)."""
+        if isinstance(chain, (int, np.integer)):
+            raise ValueError("Diffusion.distill_levels: chain must be an explicit sequence of timesteps (e.g. ddim_timesteps(S))")
+        levels = [t for t, _ in self._ddim_pairs(chain, 0.0)] + [0]
+        if len(levels) % 2 != 1:
+            raise ValueError(f"Diffusion.distill_levels: the teacher's chain must have an even number of steps, two per student "
+                             f"step (got {len(levels) - 1})")
+        a = self.alpha_hat.detach().cpu().double()[levels].tolist()      # (level 0 is alpha_hat[0], as the DDIM step reads it)
+        if any(lo >= hi for lo, hi in zip(a, a[1:])):
+            raise ValueError("Diffusion.distill_levels: alpha_hat must strictly decrease with t along the chain's levels")
+        as_t = lambda v: torch.tensor(v, dtype=torch.long)
+        return as_t(levels[0:-1:2]), as_t(levels[1::2]), as_t(levels[2::2])
+
+    @staticmethod
+    def halve_chain(chain):
+        """The student's chain of a teacher's: every second timestep, chain[0::2] (it keeps the first, T - 1 for `ddim_timesteps`)."""
+        return list(chain)[0::2]
+
+    @staticmethod
+    def sample_distill_steps(n, N):
+        """(n,) student step indices in [0, N), from the CPU global generator like `sample_timesteps`."""
+        return torch.randint(0, N, (n,))
+
+    def distill_targets(self, teacher, x0, k, chain, eps=None, y=None):
+        """-> (x_tilde, eps_tilde, t): the distillation target of each row of x0 (B, C, H, W on the device) at student step k[b]
+        of the teacher's `chain` (`distill_levels`).  z_t = noise_images(x0, t, eps), then two deterministic DDIM steps of the
+        frozen teacher at the row's own timesteps, t -> t_mid -> t_prev, folded into the pair (x_tilde, eps_tilde) whose single
+        DDIM step from z_t lands on the teacher's z_prev (ops.distill_mid, ops.distill_target: afd.h has the expressions).  Two
+        forwards and three elementwise launches, under no_grad, the teacher hinted and in eval mode; its mode is put back also
+        after an exception.  TrainStep(x_tilde, t, eps_tilde) re-forms z_t and trains towards training_target(x_tilde, eps_tilde, t).
+        k: (B,) integer tensor (host or device) or a (t, t_mid, t_prev) tuple of (B,) int64 device tensors already gathered
+        (DistillStep).  eps: injected noise, default the device generator's; y: class labels handed to both forwards."""
+        if self.variance == "learned":
+            raise ValueError("Diffusion.distill_targets: variance='learned' is not supported (the student's step is deterministic "
+                             "DDIM; distilling a learned variance is out of scope)")
+        if isinstance(k, tuple):
+            t, t_mid, t_prev = k
+        else:
+            tabs = self.distill_levels(chain)
+            k = torch.as_tensor(k)
+            if k.dtype.is_floating_point or k.dtype == torch.bool or tuple(k.shape) != (x0.shape[0],):
+                raise ValueError(f"Diffusion.distill_targets: k must hold {x0.shape[0]} integer step indices, one per row")
+            kh = k.cpu().long()
+            if int(kh.min()) < 0 or int(kh.max()) >= tabs[0].numel():
+                raise ValueError(f"Diffusion.distill_targets: every step index must lie in [0, {tabs[0].numel()}) (got {kh.tolist()})")
+            t, t_mid, t_prev = (tab[kh].to(x0.device).contiguous() for tab in tabs)
+        was_training = teacher.training
+        hinted = hasattr(teacher, "_t_range")
+        t_range = getattr(teacher, "_t_range", None)
+        self._hint(teacher)
+        try:
+            teacher.eval()
+            with torch.no_grad():
+                x0 = x0.contiguous()
+                z_t, _ = self.noise_images(x0, t, eps)
+                out1 = self._raw_output(teacher, z_t, t, y)
+                z_mid = ops.distill_mid(out1, z_t, t, t_mid, self.alpha_hat, self.prediction)
+                out2 = self._raw_output(teacher, z_mid, t_mid, y)
+                x_tilde, eps_tilde = ops.distill_target(out2, z_mid, z_t, t, t_mid, t_prev, self.alpha_hat, self.prediction)
+        finally:
+            teacher.train(was_training)
+            if hinted:
+                teacher._t_range = t_range
+        return x_tilde, eps_tilde, t
 
     # F14 ---------------------------------------------------------------------------------
     def noise_images(self, x, t, eps=None):

@@ -1586,6 +1586,32 @@ def pred_to_eps(out, x_t, t, alpha_hat, kind, eps_out=None):
     return eps_out
 
 
+# ---- progressive distillation: the teacher's two DDIM steps per row (include/afd.h gives the exact expressions) ---------------
+def distill_mid(out1, z_t, t, t_mid, alpha_hat, kind, out=None):
+    """The teacher's raw output `out1` at (z_t, t) -> z_mid, its deterministic DDIM step t -> t_mid with per-row timesteps (int64,
+    on the device), evaluated in fp64 and rounded once; one launch (afd.h: afd_distill_mid).  kind: "eps", "v" or "x0".  out may
+    be out1 or z_t (in place)."""
+    out = torch.empty_like(out1) if out is None else out
+    code, B, chw = _objective_args("distill_mid", kind, t, alpha_hat, out1, z_t, out)
+    _row_t_and_table("distill_mid", t_mid, alpha_hat, B)
+    lib().afd_distill_mid(_p(out1), _p(z_t), _p(t), _p(t_mid), _p(alpha_hat), code, _p(out), B, chw, _stream())
+    return out
+
+
+def distill_target(out2, z_mid, z_t, t, t_mid, t_prev, alpha_hat, kind, x_out=None, eps_out=None):
+    """The teacher's raw output `out2` at (z_mid, t_mid) -> (x_tilde, eps_tilde): its DDIM step t_mid -> t_prev (t_prev = 0: the
+    chain's last level, alpha_hat[0] as in `ddim_step`) folded with z_t into the (x0, eps) pair whose ONE DDIM step from z_t lands where the teacher's two did; fp64 per
+    element, rounded once; one launch (afd.h: afd_distill_target).  x_out / eps_out may each be one of out2, z_mid, z_t."""
+    x_out = torch.empty_like(out2) if x_out is None else x_out
+    eps_out = torch.empty_like(out2) if eps_out is None else eps_out
+    code, B, chw = _objective_args("distill_target", kind, t, alpha_hat, out2, z_mid, z_t, x_out, eps_out)
+    _row_t_and_table("distill_target", t_mid, alpha_hat, B)
+    _row_t_and_table("distill_target", t_prev, alpha_hat, B)
+    lib().afd_distill_target(_p(out2), _p(z_mid), _p(z_t), _p(t), _p(t_mid), _p(t_prev), _p(alpha_hat), code, _p(x_out), _p(eps_out),
+                             B, chw, _stream())
+    return x_out, eps_out
+
+
 # ---- learned reverse-process variances and the hybrid loss (include/afd.h gives the exact expressions) ----------------------
 def _lvar_args(what, kind, out2, t, alpha_hat, lv_coef, *tensors, rows2=1):
     """-> (AFD_PRED_* code, B, chw): out2 is the contiguous (rows2 * B, 2C, ...) output of a learned-variance network, `tensors`

@@ -12,7 +12,7 @@ import torch
 
 from .data import get_data, get_data_MNIST, make_collage, save_dataset_MNIST, save_gen_images
 from .diffusion import Diffusion
-from .training import argument, diffusion_kwargs, ema_path, model_out_channels, set_seed, train
+from .training import argument, diffusion_kwargs, ema_path, model_out_channels, progressive_distill, set_seed, train
 from .unet import UNet
 
 
@@ -43,13 +43,15 @@ def ddpm_run(params):
     # optional gradient-norm clipping and learning-rate schedule (train() hands them to its TrainStep).  Without the keys nothing
     # changes, the settings file included.
     # optional training objective: "noise_schedule" ("linear" | "cosine") and "prediction" ("eps" | "v" | "x0") go to every
-    # Diffusion of the run, "loss_weighting" ("min_snr") and "snr_gamma" to train()'s TrainStep; same rule
+    # Diffusion of the run, "loss_weighting" ("min_snr" | "truncated_snr") and "snr_gamma" to train()'s TrainStep; same rule
     # "variance" ("fixed" | "learned": the UNet then emits 2 * image_channels) goes to every Diffusion and model of the run,
     # "vlb_lambda" to train()'s TrainStep; same rule
     opt_keys = [k for k in ("max_grad_norm", "lr_warmup", "lr_schedule", "lr_min_ratio", "noise_schedule", "prediction",
                             "loss_weighting", "snr_gamma", "variance", "vlb_lambda") if params.get(k) is not None]
     for k in opt_keys:
         setattr(args, k, params[k])
+    if params.get("distill") is not None:
+        _distill_cfg(params)                                   # a malformed key fails here, not after the training
     cwd = os.getcwd()
     modelpath = os.path.join(cwd, f"models/DDPM_Uncondtional_{name}_{v}/ckpt_{name}_{v}.pt")
     f_settings = _f_settings(params)
@@ -132,6 +134,12 @@ def ddpm_run(params):
         gen_model = UNet(c_in=args.image_channels, c_out=model_out_channels(args), image_size=args.image_size, f_settings=f_settings,
                          device=args.device, variant=v).to(args.device)
         gen_model.load_state_dict(torch.load(ema_path(modelpath), weights_only=True))
+    # optional progressive distillation: params["distill"] = {"start_steps", "end_steps", "iters", "lr"} halves the DDIM chain of
+    # the model the image set is drawn from, round after round (training.progressive_distill; "iters" steps per round, "lr"
+    # defaults to the run's), saves the student beside the checkpoint and draws the image set from it over its own chain, eta = 0
+    distill = None
+    if params.get("distill") is not None:
+        distill, gen_model, gen_kw = _distill(params, args, diffusion, gen_model, modelpath, name, seed)
     for start in np.arange(0, params["gen_total"], params["gen_per_batch"]):
         fileno = np.arange(start, start + params["gen_per_batch"], 1)
         xg, _ = diffusion.sample(gen_model, n=params["gen_per_batch"], image_channels=args.image_channels, **gen_kw)
@@ -142,6 +150,8 @@ def ddpm_run(params):
     out = {"loss_all": loss_all, "sample": x, "revert": denoise_img, "modelpath": modelpath, "gen_dir": gen_dir}
     if use_ema:
         out["ema_modelpath"] = ema_path(modelpath)
+    if distill is not None:
+        out["distill"] = distill
     # optional likelihood: params["eval_bpd"] = N scores the first N training images, in dataset order, on the model the
     # FID/KID image set came from (Diffusion.calc_bpd; "eval_bpd_t_samples": K timesteps per image, "eval_bpd_sigma": "beta", "posterior" or,
     # with "variance": "learned", "learned")
@@ -152,6 +162,32 @@ def ddpm_run(params):
     if params.get("eval_equivariance"):
         out["equivariance"] = _eval_equivariance(params, args, diffusion, gen_model, run_dir, name, v, seed)
     return out
+
+
+def distill_path(model_path, end_steps):
+    """Where `ddpm_run` writes a distilled student beside a checkpoint: ckpt_X.pt -> ckpt_X_distill{end_steps}.pt."""
+    root, ext = os.path.splitext(model_path)
+    return f"{root}_distill{int(end_steps)}{ext}"
+
+
+def _distill_cfg(params):
+    cfg = dict(params["distill"])
+    unknown = sorted(set(cfg) - {"start_steps", "end_steps", "iters", "lr"})
+    if unknown or not {"start_steps", "end_steps", "iters"} <= set(cfg):
+        raise ValueError(f"ddpm_run: distill needs start_steps, end_steps and iters (and optionally lr); got {sorted(cfg)}")
+    return cfg
+
+
+def _distill(params, args, diffusion, model, modelpath, name, seed):
+    """-> (out["distill"], the student, the sampler arguments of the image set)."""
+    cfg = _distill_cfg(params)
+    set_seed(seed)
+    loader = _loader(name, args)[0]
+    student, rounds = progressive_distill(model, diffusion, loader, cfg["start_steps"], cfg["end_steps"], cfg["iters"],
+                                          args.lr if cfg.get("lr") is None else cfg["lr"], args.device)
+    path = distill_path(modelpath, cfg["end_steps"])
+    torch.save(student.state_dict(), path)
+    return {"rounds": rounds, "modelpath": path}, student, {"steps": rounds[-1]["chain"], "eta": 0.0}
 
 
 def _eval_bpd(params, args, diffusion, model, run_dir, name, v, seed):

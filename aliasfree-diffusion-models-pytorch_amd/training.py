@@ -29,7 +29,7 @@ class argument:
         lr_warmup / lr_min_ratio: `train` runs LRSchedule(lr_schedule, lr_warmup, total = epochs * batches, lr_min_ratio);
         lr_warmup > 0 alone means a warm-up into a constant rate.
         noise_schedule ("linear" | "cosine") / prediction ("eps" | "v" | "x0"): `diffusion_kwargs` turns them into the arguments
-        of the run's Diffusion; loss_weighting ("min_snr") / snr_gamma: `train` hands them to its TrainStep.  None = the default.
+        of the run's Diffusion; loss_weighting ("min_snr" | "truncated_snr") / snr_gamma: `train` hands them to its TrainStep.  None = the default.
         variance ("fixed" | "learned") goes to the run's Diffusion and doubles the UNet's output channels when "learned"
         (`model_out_channels`); vlb_lambda is the hybrid loss's weight in `train`'s TrainStep."""
         self.run_name, self.epochs, self.batch_size, self.image_size = run_name, epochs, batch_size, image_size
@@ -635,7 +635,8 @@ class TrainStep:
         extra collective).  `last_grad_norm`, `last_lr`, `n_skipped` read the device buffer `opt.ctl` (one D2H copy per access).
         With skip_nonfinite a dropped update does not advance the EMA either, while `ema.step` still counts the call.
         The objective: the network is trained towards `diffusion.training_target` for `diffusion.prediction` ("eps", "v" or "x0"),
-        and loss_weighting="min_snr" weights each sample's squared error by `diffusion.snr_weights("min_snr", snr_gamma)[t]`:
+        and loss_weighting="min_snr" weights each sample's squared error by `diffusion.snr_weights("min_snr", snr_gamma)[t]`
+        ("truncated_snr": `diffusion.snr_weights("truncated_snr")[t]`, the weight progressive distillation trains with):
           L = (1 / (B C H W)) sum_b w[t_b] sum_i (pred - target)^2
         normalised by the element count, not by sum w, so data-parallel ranks average losses and gradients exactly as for the
         plain MSE, with no extra collective.  Anything but eps-prediction without weighting runs ops.objective_loss, which forms
@@ -649,7 +650,7 @@ class TrainStep:
         L_simple).  `last_vlb` is the last step's L_vlb, a 0-d device tensor.  vlb_lambda is ignored with a fixed variance."""
         _check_opt_ctl("TrainStep", max_grad_norm, lr_schedule)
         if loss_weighting is not None and not (isinstance(loss_weighting, str) and loss_weighting in Diffusion.LOSS_WEIGHTINGS):
-            raise ValueError(f"TrainStep: unknown loss_weighting {loss_weighting!r} (None or 'min_snr')")
+            raise ValueError(f"TrainStep: unknown loss_weighting {loss_weighting!r} (None, 'min_snr' or 'truncated_snr')")
         if isinstance(snr_gamma, bool) or not isinstance(snr_gamma, (int, float)) or not snr_gamma > 0 or not math.isfinite(snr_gamma):
             raise ValueError(f"TrainStep: snr_gamma must be a finite number > 0 (got {snr_gamma!r})")
         if (ema is None) != (ema_model is None):
@@ -881,6 +882,103 @@ class TrainStep:
             self.ddp.begin_step()                       # the replayed backward reported nothing: exchange everything now
             self._update()
         return st["loss"]
+
+
+class DistillStep:
+    """One training step of progressive distillation (Salimans & Ho 2022): the student learns to do in ONE DDIM step what the
+    frozen teacher does in TWO.  Per call: draw a student step index k per row, gather the row timesteps (t, t_mid, t_prev) of
+    `chain` on the device, `diffusion.distill_targets` (two eager teacher forwards under no_grad and three elementwise
+    launches), then the inner TrainStep on (x_tilde, t, eps_tilde): it re-forms z_t = sqrt(a_t) x_tilde + sqrt(1 - a_t) eps_tilde
+    and trains towards diffusion.training_target(x_tilde, eps_tilde, t), so every TrainStep feature (graph=False | True | "lanes",
+    ema=, clipping, schedules, conditional=, data parallelism) works as it is -- the teacher's forwards run outside whatever the
+    inner step captured.  The teacher's parameters are never touched.  `.step` is the inner TrainStep; the student's chain
+    afterwards is `Diffusion.halve_chain(chain)`, sampled with `diffusion.sample(student, steps=that chain)`."""
+
+    def __init__(self, student, teacher, diffusion, chain, lr, loss_weighting="truncated_snr", **train_step_kw):
+        if student is teacher:
+            raise ValueError("DistillStep: student is teacher: the teacher must stay frozen (student = copy.deepcopy(teacher))")
+        if getattr(diffusion, "variance", "fixed") == "learned":
+            raise ValueError("DistillStep: variance='learned' is not supported (the student's step is deterministic DDIM)")
+        levels = diffusion.distill_levels(chain)              # ValueError for an odd, unordered or out-of-range chain
+        if diffusion.prediction == "eps":
+            logging.warning("DistillStep: prediction='eps' is unstable at few sampling steps (Salimans & Ho 2022, section 4); "
+                            "'v' or 'x0' is the parametrisation to distil with")
+        self.student, self.teacher, self.diffusion = student, teacher, diffusion
+        self.chain = [int(v) for v in chain]
+        self.n_steps = levels[0].numel()
+        dev = diffusion.alpha_hat.device
+        self.levels = tuple(tab.to(dev).contiguous() for tab in levels)          # (t, t_mid, t_prev), (N,) int64 each
+        self.step = TrainStep(student, diffusion, lr, loss_weighting=loss_weighting, **train_step_kw)
+
+    def __call__(self, images, k=None, eps=None, y=None):
+        """images (B, C, S, S) on the device; k (B,) student step indices in [0, N) [default: diffusion.sample_distill_steps];
+        eps: injected noise or None (device RNG); y: class labels, handed to the teacher's forwards and the inner step.
+        Returns the inner step's loss, a 0-d device tensor."""
+        B = images.shape[0]
+        if k is None:
+            k = self.diffusion.sample_distill_steps(B, self.n_steps)
+        k = torch.as_tensor(k)
+        if k.dtype.is_floating_point or k.dtype == torch.bool or tuple(k.shape) != (B,):
+            raise ValueError(f"DistillStep: k must hold {B} integer step indices, one per image")
+        if not k.is_cuda and (int(k.min()) < 0 or int(k.max()) >= self.n_steps):
+            raise ValueError(f"DistillStep: every step index must lie in [0, {self.n_steps})")
+        k = k.to(images.device, non_blocking=True).long()
+        rows = tuple(tab[k] for tab in self.levels)
+        x_tilde, eps_tilde, t = self.diffusion.distill_targets(self.teacher, images, rows, self.chain, eps, y)
+        return self.step(x_tilde, t, eps_tilde, y)
+
+
+def progressive_distill(model, diffusion, dataloader, start_steps, end_steps, iters_per_round, lr, device, ema_beta=None,
+                        on_round=None, **train_step_kw):
+    """Progressive distillation: halve the DDIM chain of `model` round after round, from start_steps to end_steps sampling steps.
+    start_steps = end_steps * 2^R with R >= 1 and start_steps <= T - 1 (ValueError otherwise, before any device work).  Round 0's
+    teacher is `model` on chain = diffusion.ddim_timesteps(start_steps); each round makes student = copy.deepcopy(teacher), runs a
+    DistillStep for iters_per_round steps over the loader (cycled; batches are (images, ...) tuples or tensors) with
+    LRSchedule("linear", total=iters_per_round), the paper's per-round decay to zero, then teacher = student and
+    chain = halve_chain(chain).  ema_beta: also keep EMA(ema_beta) of each round's student, fused into its AdamW launch from the
+    first step; the next round's teacher is the student itself, the average is handed to on_round.  on_round(info, student,
+    ema_model) is called after every round.  **train_step_kw go to every round's inner TrainStep (graph=, max_grad_norm=, ...).
+    Single-process.  -> (the last student, [{"steps", "chain", "mean_loss"} per round]); `model` is left as it was."""
+    import copy
+    T = diffusion.noise_steps
+    ok = all(isinstance(v, int) and not isinstance(v, bool) for v in (start_steps, end_steps, iters_per_round))
+    if not ok or end_steps < 1 or iters_per_round < 1:
+        raise ValueError(f"progressive_distill: start_steps, end_steps and iters_per_round must be integers >= 1 "
+                         f"(got {start_steps!r}, {end_steps!r}, {iters_per_round!r})")
+    ratio = start_steps // end_steps
+    if start_steps % end_steps or ratio < 2 or ratio & (ratio - 1):
+        raise ValueError(f"progressive_distill: start_steps must be end_steps * 2^R with R >= 1 (got {start_steps} and {end_steps})")
+    if start_steps > T - 1:
+        raise ValueError(f"progressive_distill: start_steps must lie in [2, {T - 1}] (got {start_steps})")
+    for bad in ("lr_schedule", "ema", "ema_model", "ema_start"):
+        if bad in train_step_kw:
+            raise ValueError(f"progressive_distill: {bad} is set per round here (pass ema_beta for an average)")
+    chain = diffusion.ddim_timesteps(start_steps)
+    teacher, rounds, batches = model, [], None
+    while len(chain) > end_steps:
+        student = copy.deepcopy(teacher)
+        kw = dict(train_step_kw)
+        ema_model = None
+        if ema_beta is not None:
+            ema_model = copy.deepcopy(student)
+            kw.update(ema=EMA(ema_beta), ema_model=ema_model, ema_start=0)
+        step = DistillStep(student, teacher, diffusion, chain, lr, lr_schedule=LRSchedule("linear", total=iters_per_round), **kw)
+        total = torch.zeros((), device=device)
+        for _ in range(iters_per_round):
+            batch = None if batches is None else next(batches, None)
+            if batch is None:                                      # cycle the loader
+                batches = iter(dataloader)
+                batch = next(batches)
+            images = batch[0] if isinstance(batch, (tuple, list)) else batch
+            total += step(images.to(device))
+        chain = Diffusion.halve_chain(chain)
+        info = {"steps": len(chain), "chain": list(chain), "mean_loss": total.item() / iters_per_round}
+        rounds.append(info)
+        logging.info(f"progressive_distill: {2 * len(chain)} -> {len(chain)} steps, mean loss {info['mean_loss']:.6f}")
+        if on_round is not None:
+            on_round(info, student, ema_model)
+        teacher = student
+    return teacher, rounds
 
 
 def train(args, model_path=None, dataloader=None, model=None, diffusion=None):

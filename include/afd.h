@@ -536,6 +536,30 @@ int afd_objective_loss_bwd(const float* pred, const float* x0, const float* eps,
 int afd_pred_to_eps(const float* out, const float* x_t, const int64_t* t, const float* alpha_hat, int kind, float* eps_out, long B,
                     long chw, afd_stream_t stream);
 
+/* ---- progressive distillation (Salimans & Ho 2022): the teacher's two DDIM steps as one target ------ Diffusion.distill_targets /
+ * training.DistillStep.  Row b goes t[b] -> t_mid[b] -> t_prev[b] with eta = 0.  With a = alpha_hat[.], al = sqrt(a), sg = sqrt(1 - a)
+ * (primes: at t_mid, double primes: at t_prev; the chain's last level t_prev[b] == 0 is alpha_hat[0], exactly as afd_ddim_step reads
+ * it, so the target matches the sampler's last step), and (x_hat, eps_hat) of a raw output p of `kind` at z on level (al, sg):
+ *     AFD_PRED_EPS: ((z - sg p) / al, p)     AFD_PRED_V: (al z - sg p, sg z + al p)     AFD_PRED_X0: (p, (z - al p) / sg)
+ * afd_distill_mid:    z_mid = al' x_hat_1 + sg' eps_hat_1, from out1 = the teacher's output at (z_t, t);
+ * afd_distill_target: z_prev = al'' x_hat_2 + sg'' eps_hat_2, from out2 = the teacher's output at (z_mid, t_mid); then
+ *     x_tilde = (z_prev - r z_t) / (al'' - r al), r = sg'' / sg,  eps_tilde = (z_t - al x_tilde) / sg:
+ *     the (x0, eps) pair whose one DDIM step from z_t lands on z_prev, so a TrainStep on (x_tilde, t, eps_tilde) re-forms z_t and
+ *     trains the student's single step towards the teacher's two.
+ * One launch each, no reduction.  Every element is widened to fp64, the roots are taken in fp64 from the fp32 table, everything
+ * is evaluated in fp64 and rounded once on the store (al'' - r al is a few 1e-3 between neighbouring levels and the numerator
+ * cancels to the same order).  t, t_mid, t_prev: B int64 each on the device, in [0, T) with alpha_hat[t] < alpha_hat[t_mid] <
+ * alpha_hat[t_prev], read unchecked; all float tensors B x chw.
+ * Aliasing: every output may be any float input of the same call ITSELF (the same pointer: each thread reads its quad of every
+ * input before it writes); otherwise it must share no memory with it, and x_tilde, eps_tilde must not overlap each other or the
+ * timestep tensors.  128-bit accesses when chw % 4 == 0 and the float pointers are 16-byte aligned, element by element otherwise,
+ * with the same values either way.  AFD_EINVAL (nothing launched) on NULL pointers, sizes <= 0, a bad kind or such an overlap. */
+int afd_distill_mid(const float* out1, const float* z_t, const int64_t* t, const int64_t* t_mid, const float* alpha_hat, int kind,
+                    float* z_mid, long B, long chw, afd_stream_t stream);
+int afd_distill_target(const float* out2, const float* z_mid, const float* z_t, const int64_t* t, const int64_t* t_mid,
+                       const int64_t* t_prev, const float* alpha_hat, int kind, float* x_tilde, float* eps_tilde, long B, long chw,
+                       afd_stream_t stream);
+
 /* ---- learned reverse-process variances and the hybrid loss (Nichol & Dhariwal 2021) ------ Diffusion(variance="learned") /
  * TrainStep(vlb_lambda=).  The network's output out2 holds, per row b, 2 chw floats: the prediction p (eps, v or x0 by `kind`)
  * and, chw floats later, the interpolation coefficient v.  lv_coef: the (T, 3) fp64 device table [lb_t, lbt_t, k_t] of
