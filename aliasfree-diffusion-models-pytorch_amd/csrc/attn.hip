@@ -4,8 +4,10 @@
 // Layout: qkv (B, 3C, L) = the NCHW image of the in-projection, channel = {q,k,v}*C + head*d + j,
 // token index contiguous; o (B, C, L); lse (B, heads, L).
 //
-// Shapes here are d in {2,4,8,16,32,64}, L in {16..4096}.  With d = 8 an MFMA tile would run 50-75 %
-// empty and the exp / max / rescale work is as large as the contractions, so these are VALU kernels:
+// Shapes here are d in {2,4,8,16,32,64}, L in {16..4096}.  The small maps (d in {16,32}, L in {16,32,48,64}) run on
+// the fp32 matrix pipe, one wave per (batch, head) with the whole score tile in registers (attn_small.hip), and d = 8 / 16
+// at L % 256 == 0 on the MFMA passes of attn_mfma.hip.  The kernels of this file serve every other shape: with d = 8 an
+// MFMA tile would run 50-75 % empty and the exp / max / rescale work is as large as the contractions, so they are VALU kernels:
 // a lane owns R query (or key) rows -- their vectors, accumulators and running max / sum live in
 // registers -- while the other operand streams through LDS in 64-row tiles stored [row][d], read with
 // ONE ds_read_b128 per 4 values at a wave-uniform address (broadcast, conflict-free) and reused by
@@ -342,17 +344,29 @@ void attn_mfma8_bwd_dq(const float* qkv, const float* o, const float* d_o, const
 void attn_mfma8_bwd_dkv(const float* qkv, const float* d_o, const float* lse, const float* delta, float* dqkv, int B, int heads, int L,
                         float sc, hipStream_t s);
 }
+namespace afd {   // attn_small.hip: d in {16,32}, L in {16,32,48,64}, one wave per (batch, head) on the fp32 matrix pipe
+bool attn_small_ok(int d, int L);
+void attn_small_fwd_launch(const float* qkv, float* o, float* lse, int B, int heads, int d, int L, float sc, hipStream_t s);
+void attn_small_bwd_launch(const float* qkv, const float* d_o, float* dqkv, int B, int heads, int d, int L, float sc,
+                           hipStream_t s);
+}
 static int g_attn_mfma_bwd_all = 1;   // (afd_debug_attn_rows(10) off / (11) on): the MFMA d = 8 backward also at L = 1024 -- with the K / V tiles
                                       // prefetched through registers it beats the all-VALU pair there too (1.31 vs 1.49 ms at B = 256)
 static int g_attn_rows = 0;      // tuning hook: 0 = default (MFMA path for d = 8 when L % 256 == 0); 1,2,4 force the
                                  // all-VALU kernels with that many rows per lane
 
+static int g_attn_small = 1;          // (afd_debug_attn_rows(30) off / (31) on, the default): the attn_small.hip kernels for their shapes
+static inline bool attn_small_use(int B, int heads, int d, int L) {      // (the pair index b * heads + h is an int there)
+  return g_attn_small && g_attn_rows == 0 && attn_small_ok(d, L) && (long)B * heads <= (1L << 30);
+}
+
 extern "C" {
 
 int afd_debug_attn_rows(int r) {
   if (r == 20 || r == 21) { attn_pv_set(r - 20); return AFD_OK; }                   // rank-8 products of the d = 8 MFMA kernels: vector pipe / fp16 matrix pipe (default)
+  if (r == 30 || r == 31) { g_attn_small = r - 30; return AFD_OK; }                // L <= 64 kernels of attn_small.hip off (the vector kernels) / on (default)
   if (r == 10 || r == 11) { g_attn_mfma_bwd_all = r - 10; return AFD_OK; }         // MFMA d = 8 backward at L = 1024 off / on (default on)
-  AFD_REQUIRE(r == 0 || r == 1 || r == 2 || r == 4, "afd_debug_attn_rows: r must be 0, 1, 2, 4 (rows per lane of the VALU kernels), 10, 11, 20 or 21");
+  AFD_REQUIRE(r == 0 || r == 1 || r == 2 || r == 4, "afd_debug_attn_rows: r must be 0, 1, 2, 4 (rows per lane of the VALU kernels), 10, 11, 20, 21, 30 or 31");
   g_attn_rows = r;
   return AFD_OK;
 }
@@ -364,6 +378,10 @@ int afd_attn_fwd(const float* qkv, float* o, float* lse, int B, int heads, int d
   hipStream_t s = as_stream(st);
   const float sc = 1.0f / sqrtf((float)d);
   if (g_attn_rows == 0 && attn_mfma8_ok(d, L)) { attn_mfma8_fwd(qkv, o, lse, B, heads, d, L, sc, s); return check_launch("afd_attn_fwd"); }
+  if (attn_small_use(B, heads, d, L) && aligned16(qkv)) {       // (its token-contracted operands are float4 loads)
+    attn_small_fwd_launch(qkv, o, lse, B, heads, d, L, sc, s);
+    return check_launch("afd_attn_fwd");
+  }
   // rows per lane by head dim (register budget): 4,4,4,2,2,1
   switch (d) {
     case 2:  launch_fwd<2, 4>(qkv, o, lse, B, heads, L, sc, s); break;
@@ -394,6 +412,10 @@ int afd_attn_bwd(const float* qkv, const float* o, const float* d_o, const float
     attn_mfma8_bwd_dq(qkv, o, d_o, lse, dqkv, delta_ws, B, heads, d, L, sc, s);
     if (d == 8) attn_mfma8_bwd_dkv(qkv, d_o, lse, delta_ws, dqkv, B, heads, L, sc, s);
     else launch_dkv<16, 2>(qkv, d_o, lse, delta_ws, dqkv, B, heads, L, sc, s);       // (the d = 16 dK / dV pass stays on the vector kernel)
+    return check_launch("afd_attn_bwd");
+  }
+  if (attn_small_use(B, heads, d, L) && aligned16(qkv) && aligned16(d_o)) {      // two independent launches (dQ; dK and dV), each with the softmax and delta inside (o, lse, delta_ws unread)
+    attn_small_bwd_launch(qkv, d_o, dqkv, B, heads, d, L, sc, s);
     return check_launch("afd_attn_bwd");
   }
   switch (d) {      // dQ pass: rows per lane 4,4,4,2,2,1
