@@ -336,6 +336,7 @@ template <int D, int R> static void launch_dkv(const float* qkv, const float* d_
 namespace afd {   // attn_mfma.hip: d = 8 / 16 passes with the d-contractions on the matrix cores
 bool attn_mfma8_ok(int d, int L);
 void attn_pv_set(int m);
+void attn_pv16_set(int m);
 bool attn_fused_bwd(const float* qkv, const float* o, const float* d_o, const float* lse, float* dqkv, float* delta, int B, int heads,
                     int d, int L, float sc, hipStream_t s);
 void attn_mfma8_fwd(const float* qkv, float* o, float* lse, int B, int heads, int d, int L, float sc, hipStream_t s);
@@ -364,9 +365,10 @@ extern "C" {
 
 int afd_debug_attn_rows(int r) {
   if (r == 20 || r == 21) { attn_pv_set(r - 20); return AFD_OK; }                   // rank-8 products of the d = 8 MFMA kernels: vector pipe / fp16 matrix pipe (default)
+  if (r == 40 || r == 41) { attn_pv16_set(r - 40); return AFD_OK; }                  // d = 16, L % 256 == 0: the round-2 kernels (40) / P V and the one-pass backward on the fp16 matrix pipe (41, default)
   if (r == 30 || r == 31) { g_attn_small = r - 30; return AFD_OK; }                // L <= 64 kernels of attn_small.hip off (the vector kernels) / on (default)
   if (r == 10 || r == 11) { g_attn_mfma_bwd_all = r - 10; return AFD_OK; }         // MFMA d = 8 backward at L = 1024 off / on (default on)
-  AFD_REQUIRE(r == 0 || r == 1 || r == 2 || r == 4, "afd_debug_attn_rows: r must be 0, 1, 2, 4 (rows per lane of the VALU kernels), 10, 11, 20, 21, 30 or 31");
+  AFD_REQUIRE(r == 0 || r == 1 || r == 2 || r == 4, "afd_debug_attn_rows: r must be 0, 1, 2, 4 (rows per lane of the VALU kernels), 10, 11, 20, 21, 30, 31, 40 or 41");
   g_attn_rows = r;
   return AFD_OK;
 }

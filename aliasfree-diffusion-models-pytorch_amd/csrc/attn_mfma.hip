@@ -1,6 +1,9 @@
 // attn_mfma.hip -- attention core for head dim 8 and 16 (the 16x16 and 32x32 maps: sa1, sa5, sa6 -- 90 % of attention FLOPs)
 // with the two d-contractions of every pass on the matrix cores.  (Written for d = 8; templated on D in round 2: at d = 16
 // a lane half carries 8 of the 16 head dims, so a 32x32x16 MFMA holds ONE cross term and a tile takes six.)
+// The text below describes the round-2 kernels (attn_fwd_mfma, attn_bwd_dq_mfma, attn_bwd_dkv_mfma: behind
+// afd_debug_attn_rows(20) at d = 8 and (40) at d = 16); the default kernels at both head dims, attn_fwd_pv and
+// attn_bwd_fused, also run the rank-d products on the (fp16) matrix pipe and are described where they stand.
 //
 // S^T = K Q^T (and dP^T = V dO^T) are matrix-core products over d = 8 -- at fp32 accuracy on the bf16 path (three
 // v_mfma_f32_32x32x16_bf16 per 32x32 tile on exact three-piece splits of the operands, see split3 below).  Their accumulator layout -- lane = query column (l & 31), the 16 registers = 16 of the 32 keys, the other 16 in
@@ -108,9 +111,14 @@ __device__ __forceinline__ f32x16 dotx3(const bf8 (&a)[3], const bf8 (&b)[3]) {
 // the same with the accumulator starting from c0 (a per-row constant folded into the product: S - lse, dP - delta)
 template <int D>
 __device__ __forceinline__ f32x16 dotx3c(const bf8 (&a)[3], const bf8 (&b)[3], f32x16 c) {
-  static_assert(D == 8, "dotx3c: head dim 8");
+  if (D == 8) {
 #pragma unroll
-  for (int m = 0; m < 3; ++m) c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[m], b[m], c, 0, 0, 0);
+    for (int m = 0; m < 3; ++m) c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[m], b[m], c, 0, 0, 0);
+  } else {
+    constexpr int TA[6] = {0, 1, 0, 2, 1, 0}, TB[6] = {0, 0, 1, 0, 1, 2};
+#pragma unroll
+    for (int m = 0; m < 6; ++m) c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[TA[m]], b[TB[m]], c, 0, 0, 0);
+  }
   return c;
 }
 
@@ -226,7 +234,15 @@ __device__ __forceinline__ float opaque_neg1() {
   asm volatile("s_mov_b32 %0, 0xbf800000" : "=s"(v));
   return v;
 }
-__device__ __forceinline__ void pv_split16(const f32x16& sc, float off, float neg1, h8 (&p1)[2], h8 (&p2)[2]) {
+// SUM (d = 16, where the A operand has no spare row for a ones row): the lane's 16 P' values are also added up, FROM THE
+// ROUNDED PIECES (the sum must be of what multiplies V: the factor 2^14 and the piece rounding cancel only then) -- one
+// v_dot2_f32_f16 against (1, 1) per packed pair and piece, 16 issue slots per tile and lane.  The alternatives: fp32 adds of
+// the pieces read back through v_fma_mix_f32 are 32 slots; MFMAs against a ones operand need both pieces of both k-groups =
+// four more 32x32x16 MFMAs on the ten of a tile for one live output row, and matrix and vector time add in this kernel.
+template <bool SUM = false>
+__device__ __forceinline__ void pv_split16(const f32x16& sc, float off, float neg1, h8 (&p1)[2], h8 (&p2)[2], float* rowsum = nullptr) {
+  const h2v ones = {(_Float16)1.0f, (_Float16)1.0f};
+  float s1 = 0.f, s2 = 0.f;
 #pragma unroll
   for (int g = 0; g < 2; ++g) {
     u32x4 w1, w2;
@@ -237,11 +253,16 @@ __device__ __forceinline__ void pv_split16(const f32x16& sc, float off, float ne
       const h2v c = __builtin_convertvector((f2){__builtin_fmaf((float)a[0], neg1, x0), __builtin_fmaf((float)a[1], neg1, x1)}, h2v);
       w1[q] = __builtin_bit_cast(uint32_t, a);
       w2[q] = __builtin_bit_cast(uint32_t, c);
+      if (SUM) { s1 = __builtin_amdgcn_fdot2(a, ones, s1, false); s2 = __builtin_amdgcn_fdot2(c, ones, s2, false); }
     }
     p1[g] = __builtin_bit_cast(h8, w1);
     p2[g] = __builtin_bit_cast(h8, w2);
   }
+  if (SUM) *rowsum += s1 + s2;
 }
+// d = 16: the row of the fp16 A operands (P V, dK, dV, dQ) that carries piece 1 of head dim d; piece 2 sits 16 rows below.
+// Chosen so that accumulator registers r = 0..7 of a lane half are d = 8 half + r (acc_row: rows 0-3, 8-11 | 4-7, 12-15).
+__device__ __forceinline__ int a_row16(int d) { return (d & 3) + 8 * ((d >> 2) & 1) + 4 * (d >> 3); }
 
 // ------------------------------------------------------------------------------------------------
 // forward, round 3: P V on the fp16 matrix pipe too.
@@ -256,12 +277,17 @@ __device__ __forceinline__ void pv_split16(const f32x16& sc, float off, float ne
 // left on the vector pipe per pair is max/2 + sub + exp + ~2 conversion slots: 7.5 instead of 12.  The piece products
 // v1 p1 + v2 p1 + v1 p2 (+ v2 p2) are exact in the fp32 accumulator; the result is fp32-class (2^-22 per product).
 // Output: lane (query, half) ends with d = 4 half .. 4 half + 3 of its query -- no cross-lane step.
+// d = 16: the two 16-wide pieces fill the 32 rows of A (m = a_row16(d): piece 1, + 16: piece 2), so the four fp16 MFMAs and
+// the accumulator are those of d = 8; S takes six bf16 MFMAs instead of three and the row sum, which has no output row left,
+// is taken from the same rounded pieces on the vector pipe (pv_split16<true>).  A lane ends with d = 8 half .. 8 half + 7
+// in registers r and r + 8.
 // ------------------------------------------------------------------------------------------------
 template <int D>
 __global__ __launch_bounds__(256, 2) void attn_fwd_pv(const float* __restrict__ qkv, float* __restrict__ o,
                                                     float* __restrict__ lse, int heads, int L, float scale) {
-  static_assert(D == 8, "attn_fwd_pv: head dim 8");
-  __shared__ __attribute__((aligned(16))) uint32_t Kp[3 * kTK * 4];            // K pieces (A fragments of S^T)
+  static_assert(D == 8 || D == 16, "attn_fwd_pv: head dim 8 or 16");
+  constexpr int NP = D / 8, NV = D == 8 ? 8 : 16;                              // d-pairs staged per thread; V-weighted accumulator registers
+  __shared__ __attribute__((aligned(16))) uint32_t Kp[3 * NP * kTK * 4];       // K pieces (A fragments of S^T)
   __shared__ __attribute__((aligned(16))) _Float16 Va[2 * 2 * 2 * 32 * 8];     // [key tile][g][half][m][8]: A fragments of P V
   __shared__ float wmax[4];
   const int b = blockIdx.z, h = blockIdx.y, C = heads * D;
@@ -278,12 +304,13 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_pv(const float* __restrict__ 
     for (int d = 0; d < D; ++d) x[d] = qp[(long)d * L + q0 + j * 32 + l31] * (scale * kLog2e);
     row_frags<D>(x, half, bq[j]);
   }
-  // the constant rows of A: ones at m = 16 and 20 (the row sum lands in accumulator register 8 of both lane halves), else 0
-  for (int i = threadIdx.x; i < 2 * 2 * 2 * 16 * 8; i += 256) {
-    const int rec = i >> 3, m = 16 + (rec & 15), blk = rec >> 4;
-    Va[(blk * 32 + m) * 8 + (i & 7)] = (m == 16 || m == 20) ? (_Float16)1.0f : (_Float16)0.0f;
-  }
-  float m[2] = {-INFINITY, -INFINITY};
+  // d = 8: the constant rows of A: ones at m = 16 and 20 (the row sum lands in accumulator register 8 of both lane halves), else 0
+  if (D == 8)
+    for (int i = threadIdx.x; i < 2 * 2 * 2 * 16 * 8; i += 256) {
+      const int rec = i >> 3, m = 16 + (rec & 15), blk = rec >> 4;
+      Va[(blk * 32 + m) * 8 + (i & 7)] = (m == 16 || m == 20) ? (_Float16)1.0f : (_Float16)0.0f;
+    }
+  float m[2] = {-INFINITY, -INFINITY}, l[2] = {0.f, 0.f};               // (l: d = 16 only, this lane's 16 keys of every tile)
   f32x16 acc[2];
 #pragma unroll
   for (int j = 0; j < 2; ++j)
@@ -296,18 +323,22 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_pv(const float* __restrict__ 
   // where this thread's V elements go: key rr = 32 kt + rho, rho = (r & 3) + 8 (r >> 2) + 4 half' -> k-slot (half', j = r & 7) of MFMA g = r >> 3
   const int rho = rr & 31, vh = (rho >> 2) & 1, vr = (rho & 3) + 4 * (rho >> 3);
   const int vbase = ((((rr >> 5) * 2 + (vr >> 3)) * 2 + vh) * 32) * 8 + (vr & 7);       // + m * 8
-  float kreg[2], vreg[2];
+  float kreg[NP][2], vreg[NP][2];                                     // d-pairs (2 jp, 2 jp + 1), jp = jp0 + 4 e
   auto fetch = [&](int k0) {
 #pragma unroll
-    for (int hh = 0; hh < 2; ++hh) {
-      kreg[hh] = kp[(long)(2 * jp0 + hh) * L + k0 + rr];
-      vreg[hh] = vp[(long)(2 * jp0 + hh) * L + k0 + rr];
-    }
+    for (int e = 0; e < NP; ++e)
+#pragma unroll
+      for (int hh = 0; hh < 2; ++hh) {
+        kreg[e][hh] = kp[(long)(2 * (jp0 + 4 * e) + hh) * L + k0 + rr];
+        vreg[e][hh] = vp[(long)(2 * (jp0 + 4 * e) + hh) * L + k0 + rr];
+      }
   };
   fetch(0);
   for (int k0 = 0; k0 < L; k0 += kTK) {
     {
-      const float mv = wave_amax(fmaxf(fabsf(vreg[0]), fabsf(vreg[1])));
+      float mv = fmaxf(fabsf(vreg[0][0]), fabsf(vreg[0][1]));
+      if (D == 16) mv = fmaxf(mv, fmaxf(fabsf(vreg[NP - 1][0]), fabsf(vreg[NP - 1][1])));
+      mv = wave_amax(mv);
       if (lane == 0) wmax[wv] = mv;
     }
     __syncthreads();                                                   // the previous stage's fragment reads are done; the maxima are visible
@@ -318,17 +349,22 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_pv(const float* __restrict__ 
 #pragma unroll
         for (int j = 0; j < 2; ++j)
 #pragma unroll
-          for (int r = 0; r < 8; ++r) acc[j][r] *= f;
+          for (int r = 0; r < NV; ++r) acc[j][r] *= f;
         sv = sn;
       }
     }
-    stage_pieces<D>(Kp, rr, jp0, kreg[0], kreg[1]);
 #pragma unroll
-    for (int hh = 0; hh < 2; ++hh) {
-      _Float16 a, c;
-      h2_split(vreg[hh], sv, a, c);
-      Va[vbase + (2 * jp0 + hh) * 8] = a;
-      Va[vbase + (2 * jp0 + hh + 8) * 8] = c;
+    for (int e = 0; e < NP; ++e) {
+      const int jp = jp0 + 4 * e;
+      stage_pieces<D>(Kp, rr, jp, kreg[e][0], kreg[e][1]);
+#pragma unroll
+      for (int hh = 0; hh < 2; ++hh) {
+        _Float16 a, c;
+        h2_split(vreg[e][hh], sv, a, c);
+        const int m1 = D == 8 ? 2 * jp + hh : a_row16(2 * jp + hh);
+        Va[vbase + m1 * 8] = a;
+        Va[vbase + (m1 + D) * 8] = c;
+      }
     }
     __syncthreads();
     if (k0 + kTK < L) fetch(k0 + kTK);
@@ -349,10 +385,11 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_pv(const float* __restrict__ 
         const float alpha = __builtin_amdgcn_exp2f(m[j] - mn);         // m = -inf first: exp2(-inf) = 0
         m[j] = mn;
 #pragma unroll
-        for (int r = 0; r < 9; ++r) acc[j][r] *= alpha;                // eight sums + the row sum
+        for (int r = 0; r < (D == 8 ? 9 : 16); ++r) acc[j][r] *= alpha;     // d = 8: eight sums + the row sum
         const float off = mn - 14.0f;                                  // P' = 2^14 P
         h8 p1[2], p2[2];
-        pv_split16(sc, off, neg1, p1, p2);
+        if (D == 8) pv_split16(sc, off, neg1, p1, p2);
+        else { l[j] *= alpha; pv_split16<true>(sc, off, neg1, p1, p2, &l[j]); }
         __builtin_amdgcn_s_setprio(2);                                 // matrix-pipe phases issue ahead of the other wave's vector work
         acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(av0, p1[0], acc[j], 0, 0, 0);
         acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(av1, p1[1], acc[j], 0, 0, 0);
@@ -365,12 +402,12 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_pv(const float* __restrict__ 
   const float isv = h2_inv_pow2(sv);
 #pragma unroll
   for (int j = 0; j < 2; ++j) {
-    const float lt = acc[j][8];                                        // 2^14 x the softmax denominator
+    const float lt = D == 8 ? acc[j][8] : l[j] + xhalf(l[j]);           // 2^14 x the softmax denominator
     const float inv = isv / lt;
     const int qi = q0 + j * 32 + l31;
 #pragma unroll
-    for (int i = 0; i < 4; ++i)
-      o[((long)b * C + h * D + 4 * half + i) * L + qi] = (acc[j][i] + acc[j][4 + i]) * inv;
+    for (int i = 0; i < D / 2; ++i)                                    // piece rows m and m + D add
+      o[((long)b * C + h * D + (D / 2) * half + i) * L + qi] = (acc[j][i] + acc[j][D / 2 + i]) * inv;
     if (half == 0) lse[((long)b * heads + h) * L + qi] = (m[j] - 14.0f + __builtin_amdgcn_logf(lt)) * kLn2;   // v_log_f32 = log2
   }
 }
@@ -613,6 +650,15 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkv_mfma(const float* __restr
 // waves' partials meet in LDS in wave order and are added to global memory by this workgroup alone, key block after key block
 // (no other workgroup touches this (batch, head)): deterministic, no atomics, no slabs.  delta = rowsum(dO o O) comes from a
 // small kernel ahead.
+//
+// d = 16 (TJ = 1): the two 16-wide pieces fill the 32 rows of every fp16 A operand (m = a_row16(d), + 16), so dV, dK, the
+// transposition and dQ cost the MFMAs and accumulator registers of d = 8; S and dP take six bf16 MFMAs each (28 per tile).
+// A wave owns ONE key tile and the workgroup walks the keys 128 at a time: with two tiles per wave the images come to 103 KB
+// of LDS and one workgroup per CU, measured 106 us at sa1's shape against 92 us for this form (70 KB, two per CU).
+// dQ = sum_key dS (K - c) with c one constant per (batch, head) and head dim -- the mean of the head's first 256 keys, taken
+// once by the workgroup: every row of dS sums to zero, so the result is the same, but a component of K that is large and
+// nearly constant over the keys (a shifted feature) no longer multiplies the rounding errors of dS: on the +30 row-shift
+// case of tests/test_gpu_attn_d16.py the error of that dQ component falls from 3.5e-4 to 3e-6 (round-2 kernels: 5.5e-5).
 // ------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void attn_delta_k(const float* __restrict__ o, const float* __restrict__ d_o, float* __restrict__ delta,
                                                     int heads, int D, int L, long total) {
@@ -653,22 +699,27 @@ __device__ __forceinline__ void pack16(const f32x16& v, h8 (&p)[2]) {     // fp3
   }
 }
 
-template <int D>
+template <int D, int TJ>
 __global__ __launch_bounds__(256, 2) void attn_bwd_fused(const float* __restrict__ qkv, const float* __restrict__ d_o,
                                                        const float* __restrict__ lse, const float* __restrict__ delta,
                                                        float* __restrict__ dqkv, int heads, int L, float scale) {
-  static_assert(D == 8, "attn_bwd_fused: head dim 8");
-  constexpr int REC = 2 * 2 * 2 * 16;                                  // A-operand records (query / key tile, g, half, m < 16) of one set
-  __shared__ __attribute__((aligned(16))) uint32_t Qp[3 * kTK * 4];   // Q pieces  (bf16x3 A fragments of S)
-  __shared__ __attribute__((aligned(16))) uint32_t Gp[3 * kTK * 4];   // dO pieces (bf16x3 A fragments of dP)
-  __shared__ __attribute__((aligned(16))) _Float16 QA[(REC + 1) * 8]; // fp16 A operands of dK: rows m = d (piece 1), d + 8 (piece 2); + one zero record
-  __shared__ __attribute__((aligned(16))) _Float16 GA[(REC + 1) * 8]; // ... of dV (dO pieces)
-  __shared__ __attribute__((aligned(16))) _Float16 KA[4 * (REC + 1) * 8];   // ... of dQ: this wave's K pieces (per wave)
-  __shared__ __attribute__((aligned(16))) bf8 Bf[4][2][2][3][64];     // bf16x3 B fragments of the wave's key tiles: K (scaled), V
+  static_assert((D == 8 && TJ == 2) || (D == 16 && TJ == 1), "attn_bwd_fused: head dim 8 (two key tiles per wave) or 16 (one)");
+  // d = 8: rows m = d (piece 1), d + 8 (piece 2) of an A operand are live, rows 16..31 read one zero record;
+  // d = 16: m = a_row16(d) and + 16, all 32 rows live, no zero record
+  constexpr int NP = D / 8, ROWS = 2 * D, ZR = D == 8 ? 1 : 0;
+  constexpr int REC = 2 * 2 * 2 * ROWS;                                // A-operand records (query tile, g, half, m < ROWS) of one set
+  constexpr int KREC = TJ * 2 * 2 * ROWS;                              // ... (key tile, g, half, m) of one wave's K image
+  __shared__ __attribute__((aligned(16))) uint32_t Qp[3 * NP * kTK * 4];   // Q pieces  (bf16x3 A fragments of S)
+  __shared__ __attribute__((aligned(16))) uint32_t Gp[3 * NP * kTK * 4];   // dO pieces (bf16x3 A fragments of dP)
+  __shared__ __attribute__((aligned(16))) _Float16 QA[(REC + ZR) * 8]; // fp16 A operands of dK (Q pieces)
+  __shared__ __attribute__((aligned(16))) _Float16 GA[(REC + ZR) * 8]; // ... of dV (dO pieces)
+  __shared__ __attribute__((aligned(16))) _Float16 KA[4 * (KREC + ZR) * 8];   // ... of dQ: this wave's K pieces (per wave)
+  __shared__ __attribute__((aligned(16))) bf8 Bf[4][TJ][2][3][64];    // bf16x3 B fragments of the wave's key tiles: K (scaled), V
   __shared__ __attribute__((aligned(16))) float Ls[kTK];
   __shared__ __attribute__((aligned(16))) float Ds[kTK];
   __shared__ float DQ[4][D][kTK];                                      // the waves' dQ partials of one stage
   __shared__ float wmax[4][4];
+  __shared__ float Kc[D == 16 ? D : 1];                                // d = 16: the constant taken off K in the dQ operand
   const int b = blockIdx.y, h = blockIdx.x, C = heads * D;
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, half = lane >> 5, l31 = lane & 31;
   const float* qp = qkv + ((long)b * 3 * C + h * D) * L;
@@ -681,29 +732,48 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_fused(const float* __restrict
 
   // zero records (rows m >= 16 of every A operand) and the selection matrices of the transposition:
   // Perm[g]: k-slot (half, j) selects column n = acc_row(8 g + j, half)
-  if (threadIdx.x < 8) { QA[REC * 8 + threadIdx.x] = (_Float16)0.f; GA[REC * 8 + threadIdx.x] = (_Float16)0.f; }
-  if (threadIdx.x < 32) KA[(threadIdx.x >> 3) * (REC + 1) * 8 + REC * 8 + (threadIdx.x & 7)] = (_Float16)0.f;
+  if (D == 8) {
+    if (threadIdx.x < 8) { QA[REC * 8 + threadIdx.x] = (_Float16)0.f; GA[REC * 8 + threadIdx.x] = (_Float16)0.f; }
+    if (threadIdx.x < 32) KA[(threadIdx.x >> 3) * (KREC + 1) * 8 + KREC * 8 + (threadIdx.x & 7)] = (_Float16)0.f;
+  }
   h8 perm[2];
 #pragma unroll
   for (int g = 0; g < 2; ++g)
 #pragma unroll
     for (int j = 0; j < 8; ++j) perm[g][j] = (l31 == acc_row(8 * g + j, half)) ? (_Float16)1.0f : (_Float16)0.0f;
-  // A-operand record of this lane for (tile t, group g): rows m >= 16 read the zero record
-  auto a_rec = [&](int t, int g) { return l31 < 16 ? ((t * 2 + g) * 2 + half) * 16 + l31 : REC; };
+  // A-operand record of this lane for (tile t, group g): at d = 8 rows m >= 16 read the zero record zr
+  auto a_rec = [&](int t, int g, int zr) { return (D == 16 || l31 < 16) ? ((t * 2 + g) * 2 + half) * ROWS + l31 : zr; };
   // where a staged row's elements go: row rr = 32 t + rho, rho = (r & 3) + 8 (r >> 2) + 4 half' -> k-slot (half', r & 7) of group r >> 3
   const int jp0 = threadIdx.x >> 6, rr = threadIdx.x & 63;
   const int rho = rr & 31, sh = (rho >> 2) & 1, sr = (rho & 3) + 4 * (rho >> 3);
-  const int sbase = ((((rr >> 5) * 2 + (sr >> 3)) * 2 + sh) * 16) * 8 + (sr & 7);         // + m * 8, m = d or d + 8
+  const int sbase = ((((rr >> 5) * 2 + (sr >> 3)) * 2 + sh) * ROWS) * 8 + (sr & 7);       // + m * 8, m = the rows of d
+  auto row1 = [](int d) { return D == 8 ? d : a_row16(d); };          // piece 1 of head dim d; piece 2: + D
 
+  if (D == 16) {                                                       // c = mean of the head's first 256 keys (DQ is free until the first stage ends)
+    float* part = &DQ[0][0][0];
+    const int d = threadIdx.x >> 4, ch = threadIdx.x & 15;
+    float t = 0.f;
+#pragma unroll
+    for (int i = 0; i < 16; ++i) t += kp[(long)d * L + i * 16 + ch];
+    part[ch * D + d] = t;
+    __syncthreads();
+    if (threadIdx.x < D) {
+      float m = 0.f;
+#pragma unroll
+      for (int c = 0; c < 16; ++c) m += part[c * D + threadIdx.x];
+      Kc[threadIdx.x] = m * (1.0f / 256.0f);
+    }
+    __syncthreads();
+  }
   float sq = __uint_as_float(kH2ScaleCapBits), sg = sq;                // running scales of Q and dO (workgroup)
   const float neg1 = opaque_neg1();
-  for (int kb = 0; kb < L; kb += 256) {
-    const int key0 = kb + wv * 64;
+  for (int kb = 0; kb < L; kb += 128 * TJ) {
+    const int key0 = kb + wv * (32 * TJ);
     // ---- this wave's keys: bf16x3 B fragments (K scaled for the log2-domain scores, V), fp16 A operand of dQ (raw K), |V|_1
     float v1 = 0.f, kmax = 0.f;
-    float xk[2][D];
+    float xk[TJ][D];
 #pragma unroll
-    for (int j = 0; j < 2; ++j) {
+    for (int j = 0; j < TJ; ++j) {
       float xs[D], xv[D];
       float n1 = 0.f;
 #pragma unroll
@@ -711,6 +781,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_fused(const float* __restrict
         xk[j][d] = kp[(long)d * L + key0 + j * 32 + l31];
         xs[d] = xk[j][d] * (scale * kLog2e);
         xv[d] = vp[(long)d * L + key0 + j * 32 + l31];
+        if (D == 16) xk[j][d] -= Kc[d];                                 // the dQ operand is K - c (header comment)
         n1 += fabsf(xv[d]); kmax = fmaxf(kmax, fabsf(xk[j][d]));
       }
       v1 = fmaxf(v1, n1);
@@ -727,36 +798,38 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_fused(const float* __restrict
     if (half == 0) {                                                   // key l31 of tile j: k-slot as above
       const int kh = (l31 >> 2) & 1, kr = (l31 & 3) + 4 * (l31 >> 3);
 #pragma unroll
-      for (int j = 0; j < 2; ++j)
+      for (int j = 0; j < TJ; ++j)
 #pragma unroll
         for (int d = 0; d < D; ++d) {
           _Float16 a, c;
           h2_split(xk[j][d], sk, a, c);
-          const int base = wv * (REC + 1) * 8 + (((j * 2 + (kr >> 3)) * 2 + kh) * 16) * 8 + (kr & 7);
-          KA[base + d * 8] = a; KA[base + (d + 8) * 8] = c;
+          const int base = wv * (KREC + ZR) * 8 + (((j * 2 + (kr >> 3)) * 2 + kh) * ROWS) * 8 + (kr & 7);
+          KA[base + row1(d) * 8] = a; KA[base + (row1(d) + D) * 8] = c;
         }
     }
-    f32x16 accV[2], accK[2];
+    f32x16 accV[TJ], accK[TJ];
 #pragma unroll
-    for (int j = 0; j < 2; ++j)
+    for (int j = 0; j < TJ; ++j)
 #pragma unroll
       for (int r = 0; r < 16; ++r) { accV[j][r] = 0.f; accK[j][r] = 0.f; }
     float sds = __uint_as_float(kH2ScaleCapBits);                      // the running scale of dS for this key block (workgroup-wide: it rides in the staged dO pieces)
 
-    float qreg[2], greg[2], lreg = 0.f, dreg = 0.f;
+    float qreg[NP][2], greg[NP][2], lreg = 0.f, dreg = 0.f;         // d-pairs (2 jp, 2 jp + 1), jp = jp0 + 4 e
     auto fetch = [&](int t0) {
 #pragma unroll
-      for (int hh = 0; hh < 2; ++hh) {
-        qreg[hh] = qp[(long)(2 * jp0 + hh) * L + t0 + rr];
-        greg[hh] = gp[(long)(2 * jp0 + hh) * L + t0 + rr];
-      }
+      for (int e = 0; e < NP; ++e)
+#pragma unroll
+        for (int hh = 0; hh < 2; ++hh) {
+          qreg[e][hh] = qp[(long)(2 * (jp0 + 4 * e) + hh) * L + t0 + rr];
+          greg[e][hh] = gp[(long)(2 * (jp0 + 4 * e) + hh) * L + t0 + rr];
+        }
       if (threadIdx.x < kTK) { lreg = lp[t0 + threadIdx.x] * kLog2e; dreg = dlp[t0 + threadIdx.x]; }
     };
     // the four waves' dQ partials of the stage that ended: added in wave order, into global memory (first key block: stored)
     auto dq_flush = [&](int t0) {
 #pragma unroll
-      for (int it = 0; it < 2; ++it) {
-        const int d = threadIdx.x >> 5, q = (threadIdx.x & 31) + 32 * it;
+      for (int it = 0; it < D / 4; ++it) {
+        const int d = (threadIdx.x >> 5) + 8 * (it >> 1), q = (threadIdx.x & 31) + 32 * (it & 1);
         const float t = ((DQ[0][d][q] + DQ[1][d][q]) + DQ[2][d][q]) + DQ[3][d][q];
         float* dst = dqg + (long)d * L + t0 + q;
         *dst = kb == 0 ? t : *dst + t;
@@ -765,8 +838,13 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_fused(const float* __restrict
     fetch(0);
     for (int t0 = 0; t0 < L; t0 += kTK) {
       {
-        const float mq = wave_amax(fmaxf(fabsf(qreg[0]), fabsf(qreg[1])));
-        const float mg = wave_amax(fmaxf(fabsf(greg[0]), fabsf(greg[1])));
+        float aq = fmaxf(fabsf(qreg[0][0]), fabsf(qreg[0][1])), ag = fmaxf(fabsf(greg[0][0]), fabsf(greg[0][1]));
+        if (D == 16) {
+          aq = fmaxf(aq, fmaxf(fabsf(qreg[NP - 1][0]), fabsf(qreg[NP - 1][1])));
+          ag = fmaxf(ag, fmaxf(fabsf(greg[NP - 1][0]), fabsf(greg[NP - 1][1])));
+        }
+        const float mq = wave_amax(aq);
+        const float mg = wave_amax(ag);
         const float md = wave_amax(fabsf(dreg));                       // (threads >= 64 hold 0)
         if (lane == 0) { wmax[0][wv] = mq; wmax[1][wv] = mg; wmax[2][wv] = md; wmax[3][wv] = v1; }
       }
@@ -783,9 +861,9 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_fused(const float* __restrict
         const float fk = (sqn * h2_inv_pow2(sq)) * (sdc * h2_inv_pow2(sds)), fv = sgn * h2_inv_pow2(sg);
         if (fk != 1.0f || fv != 1.0f) {                                // (uniform per wave)
 #pragma unroll
-          for (int j = 0; j < 2; ++j)
+          for (int j = 0; j < TJ; ++j)
 #pragma unroll
-            for (int r = 0; r < 8; ++r) { accK[j][r] *= fk; accV[j][r] *= fv; }
+            for (int r = 0; r < D; ++r) { accK[j][r] *= fk; accV[j][r] *= fv; }
         }
         sq = sqn; sg = sgn; sds = sdc;
       }
@@ -793,15 +871,20 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_fused(const float* __restrict
       // and both per-query constants start the accumulators of their products -- S - (lse log2(e) - 14) and c dP - c delta leave
       // the matrix pipe ready, one exp2 and one multiply per pair remain on the vector pipe
       const float cds = sds * (1.0f / 16384.0f);
-      stage_pieces<D>(Qp, rr, jp0, qreg[0], qreg[1]);
-      stage_pieces<D>(Gp, rr, jp0, greg[0] * cds, greg[1] * cds);
 #pragma unroll
-      for (int hh = 0; hh < 2; ++hh) {
-        _Float16 a, c;
-        h2_split(qreg[hh], sq, a, c);
-        QA[sbase + (2 * jp0 + hh) * 8] = a; QA[sbase + (2 * jp0 + hh + 8) * 8] = c;
-        h2_split(greg[hh], sg, a, c);
-        GA[sbase + (2 * jp0 + hh) * 8] = a; GA[sbase + (2 * jp0 + hh + 8) * 8] = c;
+      for (int e = 0; e < NP; ++e) {
+        const int jp = jp0 + 4 * e;
+        stage_pieces<D>(Qp, rr, jp, qreg[e][0], qreg[e][1]);
+        stage_pieces<D>(Gp, rr, jp, greg[e][0] * cds, greg[e][1] * cds);
+#pragma unroll
+        for (int hh = 0; hh < 2; ++hh) {
+          _Float16 a, c;
+          const int m1 = row1(2 * jp + hh);
+          h2_split(qreg[e][hh], sq, a, c);
+          QA[sbase + m1 * 8] = a; QA[sbase + (m1 + D) * 8] = c;
+          h2_split(greg[e][hh], sg, a, c);
+          GA[sbase + m1 * 8] = a; GA[sbase + (m1 + D) * 8] = c;
+        }
       }
       if (threadIdx.x < kTK) Ls[threadIdx.x] = 14.0f - lreg;           // (negated: the rows are accumulator start values)
       if (t0 > 0) dq_flush(t0 - kTK);
@@ -813,12 +896,12 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_fused(const float* __restrict
       for (int qt = 0; qt < kTK / 32; ++qt) {
         const h8* qa = reinterpret_cast<const h8*>(QA);
         const h8* ga = reinterpret_cast<const h8*>(GA);
-        const h8* ka = reinterpret_cast<const h8*>(KA) + wv * (REC + 1);
+        const h8* ka = reinterpret_cast<const h8*>(KA) + wv * (KREC + ZR);
         f32x16 accQ;
 #pragma unroll
         for (int r = 0; r < 16; ++r) accQ[r] = 0.f;
 #pragma unroll
-        for (int j = 0; j < 2; ++j) {
+        for (int j = 0; j < TJ; ++j) {
           // (operands are fetched from LDS right where they are used: the accumulators of five products leave few registers)
           f32x16 sc, dp;
 #pragma unroll
@@ -852,7 +935,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_fused(const float* __restrict
           h8 p1[2], p2[2];
           {
             split16(sc, neg1, p1, p2);
-            const h8 ga0 = ga[a_rec(qt, 0)], ga1 = ga[a_rec(qt, 1)];
+            const h8 ga0 = ga[a_rec(qt, 0, REC)], ga1 = ga[a_rec(qt, 1, REC)];
             __builtin_amdgcn_s_setprio(2);                             // matrix-pipe phases issue ahead of the other wave's vector work
             accV[j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ga0, p1[0], accV[j], 0, 0, 0);
             accV[j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ga1, p1[1], accV[j], 0, 0, 0);
@@ -863,7 +946,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_fused(const float* __restrict
           __builtin_amdgcn_sched_barrier(0);
           {
             split16(dp, neg1, p1, p2);
-            const h8 qa0 = qa[a_rec(qt, 0)], qa1 = qa[a_rec(qt, 1)];
+            const h8 qa0 = qa[a_rec(qt, 0, REC)], qa1 = qa[a_rec(qt, 1, REC)];
             __builtin_amdgcn_s_setprio(2);
             accK[j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(qa0, p1[0], accK[j], 0, 0, 0);
             accK[j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(qa1, p1[1], accK[j], 0, 0, 0);
@@ -873,7 +956,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_fused(const float* __restrict
           __builtin_amdgcn_sched_barrier(0);
           // the dS' pieces again, now with lane = query, registers = keys: the tile read as an A operand times the selection
           // matrices (exact: one non-zero product per output), one piece at a time
-          const h8 ka0 = ka[a_rec(j, 0)], ka1 = ka[a_rec(j, 1)];
+          const h8 ka0 = ka[a_rec(j, 0, KREC)], ka1 = ka[a_rec(j, 1, KREC)];
 #pragma unroll
           for (int pc = 0; pc < 2; ++pc) {
             f32x16 t;
@@ -890,21 +973,21 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_fused(const float* __restrict
           __builtin_amdgcn_sched_barrier(0);
         }
 #pragma unroll
-        for (int i = 0; i < 4; ++i) DQ[wv][4 * half + i][qt * 32 + l31] = (accQ[i] + accQ[4 + i]) * udq;
+        for (int i = 0; i < D / 2; ++i) DQ[wv][(D / 2) * half + i][qt * 32 + l31] = (accQ[i] + accQ[D / 2 + i]) * udq;    // piece rows add
       }
     }
     __syncthreads();                                                   // the last stage's dQ partials
     dq_flush(L - kTK);
-    // ---- dK, dV of this key block: lane (key, half) holds d = 4 half .. 4 half + 3
+    // ---- dK, dV of this key block: lane (key, half) holds d = (D / 2) half .. (D / 2) half + D / 2 - 1
     {
       const float uk = (scale * h2_inv_pow2(sds)) * h2_inv_pow2(sq), uv = h2_inv_pow2(sg) * (1.0f / 16384.0f);
 #pragma unroll
-      for (int j = 0; j < 2; ++j) {
+      for (int j = 0; j < TJ; ++j) {
         const int ki = key0 + j * 32 + l31;
 #pragma unroll
-        for (int i = 0; i < 4; ++i) {
-          dqkv[((long)b * 3 * C + C + h * D + 4 * half + i) * L + ki] = (accK[j][i] + accK[j][4 + i]) * uk;
-          dqkv[((long)b * 3 * C + 2 * C + h * D + 4 * half + i) * L + ki] = (accV[j][i] + accV[j][4 + i]) * uv;
+        for (int i = 0; i < D / 2; ++i) {
+          dqkv[((long)b * 3 * C + C + h * D + (D / 2) * half + i) * L + ki] = (accK[j][i] + accK[j][D / 2 + i]) * uk;
+          dqkv[((long)b * 3 * C + 2 * C + h * D + (D / 2) * half + i) * L + ki] = (accV[j][i] + accV[j][D / 2 + i]) * uv;
         }
       }
     }
@@ -920,27 +1003,32 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_fused(const float* __restrict
 // host-side launchers used by attn.hip
 bool attn_mfma8_ok(int d, int L) { return (d == 8 || d == 16) && L % 256 == 0; }
 static int g_attn_pv = 1;           // afd_debug_attn_rows 20 / 21: rank-8 products of the d = 8 kernels on the vector pipe (round 2) / on the fp16 matrix pipe
+static int g_attn_pv16 = 1;         // afd_debug_attn_rows 40 / 41: d = 16 on the round-2 kernels / on attn_fwd_pv<16> and attn_bwd_fused<16, 1>
 void attn_pv_set(int m) { g_attn_pv = m; }
+void attn_pv16_set(int m) { g_attn_pv16 = m; }
 void attn_mfma8_fwd(const float* qkv, float* o, float* lse, int B, int heads, int d, int L, float sc, hipStream_t s) {
   if (d == 8 && g_attn_pv) hipLaunchKernelGGL(attn_fwd_pv<8>, dim3(L / 256, heads, B), dim3(256), 0, s, qkv, o, lse, heads, L, sc);
+  else if (d == 16 && g_attn_pv16) hipLaunchKernelGGL(attn_fwd_pv<16>, dim3(L / 256, heads, B), dim3(256), 0, s, qkv, o, lse, heads, L, sc);
   else if (d == 8) hipLaunchKernelGGL(attn_fwd_mfma<8>, dim3(L / 256, heads, B), dim3(256), 0, s, qkv, o, lse, heads, L, sc);
   else hipLaunchKernelGGL(attn_fwd_mfma<16>, dim3(L / 256, heads, B), dim3(256), 0, s, qkv, o, lse, heads, L, sc);
 }
-// dQ pass (+ delta) for d in {8, 16}; the dK / dV pass on these kernels only at d = 8: at d = 16 one key tile per wave is all
-// the registers hold, every 16-wide Q / dO row read from LDS then serves one tile instead of two and the pass is LDS-bound
-// (measured at sa1's shape: 138 us against 120 for the all-vector kernel with two key rows per lane, which stays)
+// round-2 dQ pass (+ delta) for d in {8, 16}; the dK / dV pass on these kernels only at d = 8: at d = 16 one key tile per wave
+// is all the registers hold, every 16-wide Q / dO row read from LDS then serves one tile instead of two and the pass is
+// LDS-bound (measured at sa1's shape: 138 us against 120 for the all-vector kernel with two key rows per lane, which is
+// what code 40 pairs with this dQ pass; the one-pass kernel reads no fp32 rows at all and does not have that bound)
 void attn_mfma8_bwd_dq(const float* qkv, const float* o, const float* d_o, const float* lse, float* dqkv, float* delta,
                        int B, int heads, int d, int L, float sc, hipStream_t s) {
   if (d == 8) hipLaunchKernelGGL((attn_bwd_dq_mfma<8, 2>), dim3(L / 256, heads, B), dim3(256), 0, s, qkv, o, d_o, lse, dqkv, delta, heads, L, sc);
   else hipLaunchKernelGGL((attn_bwd_dq_mfma<16, 1>), dim3(L / 128, heads, B), dim3(256), 0, s, qkv, o, d_o, lse, dqkv, delta, heads, L, sc);
 }
-// the one-pass backward (d = 8): delta first, then the fused kernel -- one workgroup per (batch, head)
+// the one-pass backward (d = 8, 16): delta first, then the fused kernel -- one workgroup per (batch, head)
 bool attn_fused_bwd(const float* qkv, const float* o, const float* d_o, const float* lse, float* dqkv, float* delta, int B, int heads,
                     int d, int L, float sc, hipStream_t s) {
-  if (d != 8 || !g_attn_pv || L % 256) return false;
+  if (!((d == 8 && g_attn_pv) || (d == 16 && g_attn_pv16)) || L % 256) return false;
   const long total = (long)B * heads * L;
   hipLaunchKernelGGL(attn_delta_k, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, o, d_o, delta, heads, d, L, total);
-  hipLaunchKernelGGL(attn_bwd_fused<8>, dim3(heads, B), dim3(256), 0, s, qkv, d_o, lse, delta, dqkv, heads, L, sc);
+  if (d == 8) hipLaunchKernelGGL((attn_bwd_fused<8, 2>), dim3(heads, B), dim3(256), 0, s, qkv, d_o, lse, delta, dqkv, heads, L, sc);
+  else hipLaunchKernelGGL((attn_bwd_fused<16, 1>), dim3(heads, B), dim3(256), 0, s, qkv, d_o, lse, delta, dqkv, heads, L, sc);
   return true;
 }
 void attn_mfma8_bwd_dkv(const float* qkv, const float* d_o, const float* lse, const float* delta, float* dqkv, int B, int heads, int L,

@@ -263,7 +263,10 @@ int afd_layernorm_c_bwd_partials(const float* x, const float* dy, const float* s
  * o (B,C,L); lse (B,heads,L) saved for backward.  Never materialises the L x L scores. */
 /* tuning hook: force R rows per lane (1, 2, 4) of the all-vector kernels for head dim 8; 0 = default;
  * 10 / 11 = the MFMA two-pass backward for head dim 8 only below L = 1024 / at every L (default);
- * 30 / 31 = head dim 16 / 32 at L in {16,32,48,64}: the all-vector kernels / the one-wave-per-head fp32 matrix-pipe kernels (default) */
+ * 20 / 21 = head dim 8, L % 256 == 0: the rank-8 products on the vector pipe (two-pass backward) / on the fp16 matrix pipe with
+ * the one-pass backward (default);
+ * 30 / 31 = head dim 16 / 32 at L in {16,32,48,64}: the all-vector kernels / the one-wave-per-head fp32 matrix-pipe kernels (default);
+ * 40 / 41 = head dim 16, L % 256 == 0: the same choice as 20 / 21 (41, the fp16 matrix pipe and the one-pass backward, is the default) */
 int afd_debug_attn_rows(int rows);
 int afd_attn_fwd(const float* qkv, float* o, float* lse, int B, int heads, int d, int L, afd_stream_t stream);
 int afd_attn_bwd(const float* qkv, const float* o, const float* d_o, const float* lse, float* dqkv,
