@@ -2,7 +2,8 @@
 
 Public surface = the reference's Python API for the hot path:
 UNet, Diffusion, train, custom_upsample, custom_downsample, circularLowpassKernel, argument,
-set_seed, EMA, plus the engine-side helpers TrainStep / FusedAdamW / GradAllReduce / LRSchedule / DistillStep / progressive_distill.
+set_seed, EMA, plus the engine-side helpers TrainStep / FusedAdamW / GradAllReduce / LRSchedule / DistillStep / progressive_distill /
+LossSecondMomentSampler.
 Device work runs in libafd_hip.so (hand-written gfx950 kernels, C ABI in include/afd.h).
 """
 from ._lib import AfdError, lib  # noqa: F401
@@ -13,7 +14,8 @@ from .ops import NULL_LABEL  # noqa: F401
 from .unet import UNet  # noqa: F401
 from .diffusion import Diffusion  # noqa: F401
 from .training import (argument, set_seed, setup_logging, train, TrainStep, FusedAdamW, FlatParams,  # noqa: F401
-                       GradAllReduce, EMA, LRSchedule, clip_coefficient, DistillStep, progressive_distill)
+                       GradAllReduce, EMA, LRSchedule, clip_coefficient, DistillStep, progressive_distill,
+                       LossSecondMomentSampler)
 
 from .tasks import bpd_results, ddpm_run, equivariance_results, inpaint_results, rotation_results, shift_results  # noqa: F401
 from .data import get_data, get_data_MNIST, save_gen_images, make_collage  # noqa: F401

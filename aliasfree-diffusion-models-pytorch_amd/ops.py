@@ -1631,9 +1631,9 @@ def _lvar_args(what, kind, out2, t, alpha_hat, lv_coef, *tensors, rows2=1):
     return PRED_KINDS[kind], B, first.numel() // B
 
 
-def _lvar_tables(what, alpha, alpha_hat, beta, w=None):
+def _lvar_tables(what, alpha, alpha_hat, beta, w=None, w_name="w"):
     _chk(alpha, beta, w)
-    for name, v in (("alpha", alpha), ("beta", beta), ("w", w)):
+    for name, v in (("alpha", alpha), ("beta", beta), (w_name, w)):
         if v is not None and (tuple(v.shape) != tuple(alpha_hat.shape) or not v.is_contiguous()):
             raise AfdError(f"afdm: {what}: {name} must be a contiguous table of alpha_hat's shape {tuple(alpha_hat.shape)}")
 
@@ -1651,17 +1651,22 @@ class LvarLoss(_Fn):
     is differentiable."""
 
     @staticmethod
-    def forward(ctx, out2, x0, eps, t, alpha, alpha_hat, beta, lv_coef, w, kind, vlb_scale):
+    def forward(ctx, out2, x0, eps, t, alpha, alpha_hat, beta, lv_coef, w, kind, vlb_scale, vw=None):
         out2, x0, eps = _c(out2), _c(x0), _c(eps)
         code, B, chw = _lvar_args("learned-variance loss", kind, out2, t, alpha_hat, lv_coef, x0, eps)
         _lvar_tables("learned-variance loss", alpha, alpha_hat, beta, w)
+        _lvar_tables("learned-variance loss", alpha, alpha_hat, beta, vw, w_name="vw")
         scale = _vlb_scale("learned-variance loss", vlb_scale)
         aux = torch.empty(2, device=out2.device, dtype=torch.float32)
         aux64 = torch.empty(2, device=out2.device, dtype=torch.float64)
         ws = torch.empty(4096, device=out2.device, dtype=torch.float32)
-        lib().afd_lvar_loss_fwd(_p(out2), _p(x0), _p(eps), _p(t), _p(alpha), _p(alpha_hat), _p(beta), _p(lv_coef), _p(w), code, scale,
-                                _p(aux), _p(aux64), _p(ws), B, chw, _stream())
-        ctx.save_for_backward(out2, x0, eps, t, alpha, alpha_hat, beta, lv_coef, w)
+        if vw is None:
+            lib().afd_lvar_loss_fwd(_p(out2), _p(x0), _p(eps), _p(t), _p(alpha), _p(alpha_hat), _p(beta), _p(lv_coef), _p(w), code,
+                                    scale, _p(aux), _p(aux64), _p(ws), B, chw, _stream())
+        else:
+            lib().afd_lvar_loss_fwd_tw(_p(out2), _p(x0), _p(eps), _p(t), _p(alpha), _p(alpha_hat), _p(beta), _p(lv_coef), _p(w), _p(vw),
+                                       code, scale, _p(aux), _p(aux64), _p(ws), B, chw, _stream())
+        ctx.save_for_backward(out2, x0, eps, t, alpha, alpha_hat, beta, lv_coef, w, vw)
         ctx.code, ctx.scale = code, scale
         loss, vlb = aux[0], aux[1]
         ctx.mark_non_differentiable(vlb, aux64)
@@ -1670,25 +1675,126 @@ class LvarLoss(_Fn):
 
     @staticmethod
     def backward(ctx, dloss, _daux=None, _daux64=None):
-        out2, x0, eps, t, alpha, alpha_hat, beta, lv_coef, w = ctx.saved_tensors
+        out2, x0, eps, t, alpha, alpha_hat, beta, lv_coef, w, vw = ctx.saved_tensors
         dloss = dloss.reshape(1).contiguous()
         dout2 = torch.empty_like(out2)
         B = x0.shape[0]
-        lib().afd_lvar_loss_bwd(_p(out2), _p(x0), _p(eps), _p(t), _p(alpha), _p(alpha_hat), _p(beta), _p(lv_coef), _p(w), ctx.code,
-                                ctx.scale, _p(dloss), _p(dout2), B, x0.numel() // B, _stream())
-        return (dout2,) + (None,) * 10
+        if vw is None:
+            lib().afd_lvar_loss_bwd(_p(out2), _p(x0), _p(eps), _p(t), _p(alpha), _p(alpha_hat), _p(beta), _p(lv_coef), _p(w), ctx.code,
+                                    ctx.scale, _p(dloss), _p(dout2), B, x0.numel() // B, _stream())
+        else:
+            lib().afd_lvar_loss_bwd_tw(_p(out2), _p(x0), _p(eps), _p(t), _p(alpha), _p(alpha_hat), _p(beta), _p(lv_coef), _p(w), _p(vw),
+                                       ctx.code, ctx.scale, _p(dloss), _p(dout2), B, x0.numel() // B, _stream())
+        return (dout2,) + (None,) * 11
 
 
-def lvar_loss(out2, x0, eps, t, alpha, alpha_hat, beta, lv_coef, w=None, kind="eps", vlb_scale=0.0, return_sums=False):
+def lvar_loss(out2, x0, eps, t, alpha, alpha_hat, beta, lv_coef, w=None, kind="eps", vlb_scale=0.0, return_sums=False, vw=None):
     """The hybrid loss L_simple + vlb_scale * L_vlb (Nichol & Dhariwal 2021) of a network whose (B, 2C, ...) output holds the
     prediction (`kind`) and the variance coefficient.  L_simple is `objective_loss` on the prediction (weights w[t] included);
     L_vlb is the variational bound's term of each row in bits per dimension, averaged over the batch, with the mean stopped: the
     prediction's gradient is L_simple's, bit for bit, the coefficient's comes from L_vlb alone.  Returns (loss, L_vlb), two 0-d
-    fp32 device tensors (L_vlb detached, unscaled); return_sums: also the (2,) fp64 device tensor [L, L_vlb]."""
-    loss, vlb, sums = LvarLoss.apply(out2, x0, eps, t, alpha, alpha_hat, beta, lv_coef, w, kind, vlb_scale)
+    fp32 device tensors (L_vlb detached, unscaled); return_sums: also the (2,) fp64 device tensor [L, L_vlb].
+    vw (a (T,) fp32 device table, None = 1): vw[t] multiplies each row's bound terms, and with them that row's gradient of the
+    coefficient half -- the timestep sampler's importance weight (afd.h: afd_lvar_loss_fwd_tw / _bwd_tw); vw of ones gives the
+    bits of vw=None."""
+    loss, vlb, sums = LvarLoss.apply(out2, x0, eps, t, alpha, alpha_hat, beta, lv_coef, w, kind, vlb_scale, vw)
     if return_sums:
         return loss, vlb, sums
     return loss, vlb
+
+
+# ---- loss-aware timestep sampling (include/afd.h and DESIGN.md section 6m give the semantics) ------------------------------------
+def _rows_out(what, rows, B, device):
+    if rows is None:
+        return torch.empty(B, device=device, dtype=torch.float64)
+    if not isinstance(rows, torch.Tensor) or not rows.is_cuda or rows.dtype != torch.float64 or tuple(rows.shape) != (B,) \
+            or not rows.is_contiguous():
+        raise AfdError(f"afdm: {what}: out must be a contiguous fp64 device tensor of shape ({B},)")
+    return rows
+
+
+def loss_rows(pred, x0, eps, t, alpha_hat, w=None, kind="eps", out=None):
+    """Row b's share of `objective_loss`, times B: (1 / chw) w[t_b] sum_i (pred - target)^2 with the difference formed as the
+    loss kernels form it and summed in fp64 -> (B,) fp64 device tensor; one launch (afd.h: afd_loss_rows).  No gradient."""
+    pred, x0, eps = _c(pred), _c(x0), _c(eps)
+    code, B, chw = _objective_args("loss_rows", kind, t, alpha_hat, pred, x0, eps)
+    if w is not None:
+        _chk(w)
+        if tuple(w.shape) != tuple(alpha_hat.shape) or not w.is_contiguous():
+            raise AfdError(f"afdm: loss_rows: w must be a contiguous table of alpha_hat's shape {tuple(alpha_hat.shape)}")
+    out = _rows_out("loss_rows", out, B, pred.device)
+    lib().afd_loss_rows(_p(pred), _p(x0), _p(eps), _p(t), _p(alpha_hat), _p(w), code, _p(out), B, chw, _stream())
+    return out
+
+
+def lvar_loss_rows(out2, x0, eps, t, alpha, alpha_hat, beta, lv_coef, w=None, kind="eps", vlb_scale=0.0, out=None):
+    """Row b's share of `lvar_loss`, times B: `loss_rows` on the prediction half plus (vlb_scale / (chw ln 2)) sum_i term_i
+    -> (B,) fp64 device tensor; one launch (afd.h: afd_lvar_loss_rows).  No gradient."""
+    out2, x0, eps = _c(out2), _c(x0), _c(eps)
+    code, B, chw = _lvar_args("lvar_loss_rows", kind, out2, t, alpha_hat, lv_coef, x0, eps)
+    if t is None or lv_coef is None:
+        raise AfdError("afdm: lvar_loss_rows: t and lv_coef must be given")
+    _lvar_tables("lvar_loss_rows", alpha, alpha_hat, beta, w)
+    scale = _vlb_scale("lvar_loss_rows", vlb_scale)
+    out = _rows_out("lvar_loss_rows", out, B, out2.device)
+    lib().afd_lvar_loss_rows(_p(out2), _p(x0), _p(eps), _p(t), _p(alpha), _p(alpha_hat), _p(beta), _p(lv_coef), _p(w), code, scale,
+                             _p(out), B, chw, _stream())
+    return out
+
+
+def _dev_table(what, name, v, dtype, shape):
+    if not isinstance(v, torch.Tensor) or not v.is_cuda or v.dtype != dtype or tuple(v.shape) != shape or not v.is_contiguous():
+        raise AfdError(f"afdm: {what}: {name} must be a contiguous {dtype} device tensor of shape {shape}")
+
+
+def tsampler_tick(t, rows, hist, count, lo, uniform_prob, w_base, prob, cdf, wtab, vwtab, warm):
+    """The timestep sampler's update + refresh, one launch of one workgroup (afd.h: afd_tsampler_tick): folds the batch (t (B,)
+    int64, rows (B,) fp64) into hist (T, H) fp64 / count (T,) int32 in batch order and rebuilds prob (T,) fp64, cdf (T - lo,)
+    fp64, wtab (T,) fp32 = w_base * iw (w_base None: 1), vwtab (T,) fp32 = iw (may be None) and warm (1,) int32, all in place."""
+    what = "tsampler_tick"
+    if not isinstance(hist, torch.Tensor) or hist.dim() != 2:
+        raise AfdError(f"afdm: {what}: hist must be a (T, H) tensor")
+    T, H = hist.shape
+    if isinstance(lo, bool) or not isinstance(lo, int) or not 0 <= lo < T:
+        raise AfdError(f"afdm: {what}: lo must be an integer in [0, {T}) (got {lo!r})")
+    if isinstance(uniform_prob, bool) or not isinstance(uniform_prob, (int, float)) or not 0.0 <= uniform_prob < 1.0:
+        raise AfdError(f"afdm: {what}: uniform_prob must lie in [0, 1) (got {uniform_prob!r})")
+    if not isinstance(rows, torch.Tensor) or rows.dim() != 1 or rows.numel() == 0:
+        raise AfdError(f"afdm: {what}: rows must be a (B,) tensor with at least one element")
+    B = rows.numel()
+    _dev_table(what, "rows", rows, torch.float64, (B,))
+    _dev_table(what, "t", t, torch.long, (B,))
+    _dev_table(what, "hist", hist, torch.float64, (T, H))
+    _dev_table(what, "count", count, torch.int32, (T,))
+    _dev_table(what, "prob", prob, torch.float64, (T,))
+    _dev_table(what, "cdf", cdf, torch.float64, (T - lo,))
+    _dev_table(what, "wtab", wtab, torch.float32, (T,))
+    _dev_table(what, "warm", warm, torch.int32, (1,))
+    if w_base is not None:
+        _dev_table(what, "w_base", w_base, torch.float32, (T,))
+    if vwtab is not None:
+        _dev_table(what, "vwtab", vwtab, torch.float32, (T,))
+    lib().afd_tsampler_tick(_p(t), _p(rows), B, _p(hist), _p(count), T, H, lo, float(uniform_prob), _p(w_base), _p(prob), _p(cdf),
+                            _p(wtab), _p(vwtab), _p(warm), _stream())
+
+
+def tsampler_draw(cdf, u, lo, out=None):
+    """t = lo + searchsorted(cdf, u, side="right"), clamped to the last timestep: cdf (n,) fp64 as `tsampler_tick` writes it, u (B,)
+    fp64 in [0, 1), both on the device -> (B,) int64 device tensor; one launch (afd.h: afd_tsampler_draw)."""
+    what = "tsampler_draw"
+    if not isinstance(cdf, torch.Tensor) or cdf.dim() != 1 or cdf.numel() == 0 or not isinstance(u, torch.Tensor) or u.dim() != 1 \
+            or u.numel() == 0:
+        raise AfdError(f"afdm: {what}: cdf and u must be 1-d tensors with at least one element")
+    if isinstance(lo, bool) or not isinstance(lo, int) or lo < 0:
+        raise AfdError(f"afdm: {what}: lo must be an integer >= 0 (got {lo!r})")
+    n, B = cdf.numel(), u.numel()
+    _dev_table(what, "cdf", cdf, torch.float64, (n,))
+    _dev_table(what, "u", u, torch.float64, (B,))
+    if out is None:
+        out = torch.empty(B, device=u.device, dtype=torch.long)
+    _dev_table(what, "out", out, torch.long, (B,))
+    lib().afd_tsampler_draw(_p(cdf), _p(u), lo, lo + n, _p(out), B, _stream())
+    return out
 
 
 def split_pred(out2, x_t, t, alpha_hat, kind, eps_out=None, want_v=False):

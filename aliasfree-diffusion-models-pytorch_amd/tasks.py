@@ -46,8 +46,10 @@ def ddpm_run(params):
     # Diffusion of the run, "loss_weighting" ("min_snr" | "truncated_snr") and "snr_gamma" to train()'s TrainStep; same rule
     # "variance" ("fixed" | "learned": the UNet then emits 2 * image_channels) goes to every Diffusion and model of the run,
     # "vlb_lambda" to train()'s TrainStep; same rule
+    # "t_sampler" ("loss_second_moment"), "t_sampler_history" and "t_sampler_uniform_prob" to train()'s timestep sampler; same rule
     opt_keys = [k for k in ("max_grad_norm", "lr_warmup", "lr_schedule", "lr_min_ratio", "noise_schedule", "prediction",
-                            "loss_weighting", "snr_gamma", "variance", "vlb_lambda") if params.get(k) is not None]
+                            "loss_weighting", "snr_gamma", "variance", "vlb_lambda", "t_sampler", "t_sampler_history",
+                            "t_sampler_uniform_prob") if params.get(k) is not None]
     for k in opt_keys:
         setattr(args, k, params[k])
     if params.get("distill") is not None:

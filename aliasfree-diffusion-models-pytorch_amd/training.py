@@ -22,7 +22,8 @@ class argument:
     def __init__(self, run_name=None, epochs=None, batch_size=None, image_size=None, image_channels=3,
                  dataset_path=None, device=None, lr=None, noise_steps=None, image_gen_n=4, ema_beta=None, ema_start=2000,
                  max_grad_norm=None, lr_warmup=0, lr_schedule=None, lr_min_ratio=0.0, noise_schedule=None, prediction=None,
-                 loss_weighting=None, snr_gamma=None, variance=None, vlb_lambda=None):
+                 loss_weighting=None, snr_gamma=None, variance=None, vlb_lambda=None, t_sampler=None, t_sampler_history=None,
+                 t_sampler_uniform_prob=None):
         """ema_beta / ema_start (not in the reference's class): with ema_beta set, `train` keeps an EMA of the weights
         (EMA(ema_beta), step_start_ema = ema_start).
         max_grad_norm: `train` clips the gradient to this global L2 norm.  lr_schedule ("constant" | "linear" | "cosine") /
@@ -31,7 +32,9 @@ class argument:
         noise_schedule ("linear" | "cosine") / prediction ("eps" | "v" | "x0"): `diffusion_kwargs` turns them into the arguments
         of the run's Diffusion; loss_weighting ("min_snr" | "truncated_snr") / snr_gamma: `train` hands them to its TrainStep.  None = the default.
         variance ("fixed" | "learned") goes to the run's Diffusion and doubles the UNet's output channels when "learned"
-        (`model_out_channels`); vlb_lambda is the hybrid loss's weight in `train`'s TrainStep."""
+        (`model_out_channels`); vlb_lambda is the hybrid loss's weight in `train`'s TrainStep.
+        t_sampler ("loss_second_moment") / t_sampler_history / t_sampler_uniform_prob: `train` draws the timesteps from a
+        LossSecondMomentSampler(history_per_term, uniform_prob) and saves its state beside the checkpoint."""
         self.run_name, self.epochs, self.batch_size, self.image_size = run_name, epochs, batch_size, image_size
         self.image_channels, self.dataset_path, self.device, self.lr = image_channels, dataset_path, device, lr
         self.noise_steps, self.image_gen_n = noise_steps, image_gen_n
@@ -40,6 +43,7 @@ class argument:
         self.noise_schedule, self.prediction = noise_schedule, prediction
         self.loss_weighting, self.snr_gamma = loss_weighting, snr_gamma
         self.variance, self.vlb_lambda = variance, vlb_lambda
+        self.t_sampler, self.t_sampler_history, self.t_sampler_uniform_prob = t_sampler, t_sampler_history, t_sampler_uniform_prob
 
 
 def diffusion_kwargs(args):
@@ -595,6 +599,118 @@ class GradAllReduce:
         return self.finish()
 
 
+T_SAMPLERS = ("loss_second_moment",)
+
+
+class LossSecondMomentSampler:
+    """Loss-aware timestep sampling (Nichol & Dhariwal 2021, section 3.3): t is drawn with p_t proportional to
+    sqrt(E[l_t^2]), estimated from the last `history_per_term` row losses seen at each timestep, mixed with `uniform_prob` of the
+    uniform distribution; the loss of a row is then weighted by iw_t = 1 / (n p_t), which keeps the step loss an unbiased
+    estimate of the uniform-t loss.  Until every timestep in [1, T) has a full history the draw is uniform and iw_t = 1 exactly.
+    DESIGN.md section 6m has the semantics.
+
+    Everything lives on the device and is decided there: `update` is one launch of one workgroup (afd_tsampler_tick) that folds
+    a batch of (t, row loss) into the history and rebuilds the distribution and the two tables the loss kernels read (`wtab` =
+    base weight * iw, `vwtab` = iw), `draw` is one launch (afd_tsampler_draw); nothing here synchronises.  TrainStep(t_sampler=)
+    drives it.  `probabilities`, `weights`, `warmed_up` and `loss_by_timestep` read the device buffers (a copy and, for the two
+    host values, a sync per access)."""
+
+    LO = 1              # the smallest timestep Diffusion.sample_timesteps returns
+
+    def __init__(self, diffusion, history_per_term=10, uniform_prob=0.001):
+        who = "LossSecondMomentSampler"
+        if isinstance(history_per_term, bool) or not isinstance(history_per_term, int) or history_per_term < 1:
+            raise ValueError(f"{who}: history_per_term must be an integer >= 1 (got {history_per_term!r})")
+        if isinstance(uniform_prob, bool) or not isinstance(uniform_prob, (int, float)) or not 0.0 <= uniform_prob < 1.0:
+            raise ValueError(f"{who}: uniform_prob must lie in [0, 1) (got {uniform_prob!r})")
+        T = int(diffusion.noise_steps)
+        if T < 2:
+            raise ValueError(f"{who}: needs noise_steps >= 2 (got {T})")
+        self.T, self.H, self.uniform_prob = T, history_per_term, float(uniform_prob)
+        dev = diffusion.alpha_hat.device
+        self.device = dev
+        self.hist = torch.zeros(T, self.H, device=dev, dtype=torch.float64)
+        self.count = torch.zeros(T, device=dev, dtype=torch.int32)
+        self.prob = torch.zeros(T, device=dev, dtype=torch.float64)
+        self.cdf = torch.zeros(T - self.LO, device=dev, dtype=torch.float64)
+        self.wtab = torch.zeros(T, device=dev, dtype=torch.float32)
+        self.vwtab = torch.zeros(T, device=dev, dtype=torch.float32)
+        self.warm = torch.zeros(1, device=dev, dtype=torch.int32)
+        self.w_base = None          # (T,) fp32 device table of the loss's own weights (TrainStep(loss_weighting=)), or None for 1
+        self._rows = {}             # B -> the (B,) fp64 buffer the step's row-loss launch writes (static under a captured step)
+        self._refresh()
+
+    def buffers(self):
+        """Every device buffer a step changes: what a captured step's warm-up saves and puts back."""
+        return (self.hist, self.count, self.prob, self.cdf, self.wtab, self.vwtab, self.warm)
+
+    def rows_buffer(self, B):
+        if B not in self._rows:
+            self._rows[B] = torch.zeros(B, device=self.device, dtype=torch.float64)
+        return self._rows[B]
+
+    def _refresh(self):
+        """Rebuild the distribution and the tables from the history as it stands: a tick whose one row is skipped (NaN)."""
+        t = torch.full((1,), self.LO, device=self.device, dtype=torch.long)
+        self.update(t, torch.full((1,), float("nan"), device=self.device, dtype=torch.float64))
+
+    def set_base_weights(self, w_base):
+        """w_base: the (T,) fp32 device table the loss multiplies each row by apart from the importance weight, or None."""
+        if w_base is not None and (not isinstance(w_base, torch.Tensor) or tuple(w_base.shape) != (self.T,)):
+            raise ValueError(f"LossSecondMomentSampler: w_base must be a ({self.T},) tensor or None")
+        self.w_base = None if w_base is None else w_base.to(self.device, torch.float32).contiguous()
+        self._refresh()
+
+    def draw(self, n, u=None, out=None):
+        """n timesteps in [1, T) from the current distribution -> (n,) int64 device tensor (`out` when given).  u: (n,) fp64 device
+        tensor in [0, 1) [default: torch.rand on the device, so torch's CPU generator does not advance]."""
+        if u is None:
+            u = torch.rand(n, device=self.device, dtype=torch.float64)
+        if not isinstance(u, torch.Tensor) or tuple(u.shape) != (n,):
+            raise ValueError(f"LossSecondMomentSampler.draw: u must hold {n} values")
+        return ops.tsampler_draw(self.cdf, u, self.LO, out)
+
+    def update(self, t, rows):
+        """Fold a batch into the history, in batch order, and rebuild the distribution: t (B,) int64, rows (B,) fp64 row losses
+        with the importance weight removed (ops.loss_rows / ops.lvar_loss_rows), both on the device.  Non-finite rows are skipped."""
+        ops.tsampler_tick(t, rows, self.hist, self.count, self.LO, self.uniform_prob, self.w_base, self.prob, self.cdf, self.wtab,
+                          self.vwtab, self.warm)
+
+    def probabilities(self):
+        """(T,) fp64 device copy of p_t (p_0 = 0)."""
+        return self.prob.clone()
+
+    def weights(self):
+        """(T,) fp32 device copy of the importance weights iw_t = 1 / (n p_t) (1 before warm-up and at t = 0)."""
+        return self.vwtab.clone()
+
+    @property
+    def warmed_up(self):
+        """Whether every timestep in [1, T) has a full history.  One D2H copy."""
+        return bool(self.warm.item())
+
+    def loss_by_timestep(self):
+        """The per-timestep loss record: ((T,) fp64 mean of each timestep's history, NaN where nothing was seen; (T,) int32
+        counts), device copies."""
+        count = self.count.clone()
+        seen = torch.arange(self.H, device=self.device)[None, :] < count[:, None]
+        mean = (self.hist * seen).sum(dim=1) / count.to(torch.float64)
+        return torch.where(count > 0, mean, torch.full_like(mean, float("nan"))), count
+
+    def state_dict(self):
+        return {"hist": self.hist.cpu(), "count": self.count.cpu(), "history_per_term": self.H, "uniform_prob": self.uniform_prob}
+
+    def load_state_dict(self, state):
+        hist, count = torch.as_tensor(state["hist"]), torch.as_tensor(state["count"])
+        if tuple(hist.shape) != (self.T, self.H) or tuple(count.shape) != (self.T,) or int(state["history_per_term"]) != self.H:
+            raise ValueError(f"LossSecondMomentSampler.load_state_dict: the state is for another (T, history_per_term) than "
+                             f"({self.T}, {self.H})")
+        self.uniform_prob = float(state["uniform_prob"])
+        self.hist.copy_(hist.to(torch.float64))
+        self.count.copy_(count.to(torch.int32))
+        self._refresh()
+
+
 def label_dropout_mask(n, p_uncond):
     """(n,) bool mask of the samples whose class label a classifier-free-guidance step drops (replaces by NULL_LABEL): each
     with probability p_uncond, drawn from torch's CPU global generator like Diffusion.sample_timesteps."""
@@ -616,7 +732,7 @@ class TrainStep:
 
     def __init__(self, model, diffusion, lr, graph=False, distributed=None, n_buckets=4, overlap_wgrad=None, conditional=False,
                  p_uncond=0.0, ema=None, ema_model=None, ema_start=2000, max_grad_norm=None, lr_schedule=None, skip_nonfinite=False,
-                 track_grad_norm=False, loss_weighting=None, snr_gamma=5.0, vlb_lambda=0.001):
+                 track_grad_norm=False, loss_weighting=None, snr_gamma=5.0, vlb_lambda=0.001, t_sampler=None):
         """conditional=True: the step takes class labels (`step(images, y=labels)`, UNet.forward(x, t, y): ddpm_models.py:276-277)
         and `label_emb` is optimised and exchanged like every other parameter.  With the default (the reference's loop,
         ddpm_utils.py:502, never passes labels) `label_emb` stays untouched, as under the reference's AdamW, and passing y raises.
@@ -647,7 +763,16 @@ class TrainStep:
         L_vlb the batch mean of the variational bound's term of each sample's timestep in bits per dimension, with the mean
         stopped, so it trains the variance half alone (ops.lvar_loss: the same number of launches again, in every launch mode,
         with loss_weighting=, ema=, clipping, conditional= and under data parallelism; normalised by the element count like
-        L_simple).  `last_vlb` is the last step's L_vlb, a 0-d device tensor.  vlb_lambda is ignored with a fixed variance."""
+        L_simple).  `last_vlb` is the last step's L_vlb, a 0-d device tensor.  vlb_lambda is ignored with a fixed variance.
+        t_sampler: None (the step as it always was: t from torch's CPU generator, uniform), "loss_second_moment" or a
+        LossSecondMomentSampler: the timesteps are drawn on the device with p_t proportional to sqrt(E[l_t^2]) and every row's
+        loss is weighted by iw_t = 1 / ((T - 1) p_t), through the tables the loss kernels already read (w = wtab, and vw = vwtab
+        for the bound's terms).  Two launches more than the default step, both inside whatever is captured: the per-row losses
+        after the loss forward (ops.loss_rows / ops.lvar_loss_rows on the detached output) and the sampler's tick after backward,
+        on the main stream behind the loss backward that reads wtab.  The draw runs outside any captured work and writes the
+        step's static t buffer.  A caller-supplied t is used as it is and still gets wtab[t].  The loss returned, and `last_vlb`,
+        are then the importance-weighted estimates.  Not with data parallelism (each rank would need the others' (t, l): one
+        more collective) -- ValueError."""
         _check_opt_ctl("TrainStep", max_grad_norm, lr_schedule)
         if loss_weighting is not None and not (isinstance(loss_weighting, str) and loss_weighting in Diffusion.LOSS_WEIGHTINGS):
             raise ValueError(f"TrainStep: unknown loss_weighting {loss_weighting!r} (None, 'min_snr' or 'truncated_snr')")
@@ -665,6 +790,12 @@ class TrainStep:
             raise ValueError("TrainStep: p_uncond > 0 drops class labels, which needs a conditional step (conditional=True)")
         if isinstance(vlb_lambda, bool) or not isinstance(vlb_lambda, (int, float)) or not vlb_lambda >= 0 or not math.isfinite(vlb_lambda):
             raise ValueError(f"TrainStep: vlb_lambda must be a finite number >= 0 (got {vlb_lambda!r})")
+        if t_sampler is not None and not isinstance(t_sampler, LossSecondMomentSampler) \
+                and not (isinstance(t_sampler, str) and t_sampler in T_SAMPLERS):
+            raise ValueError(f"TrainStep: unknown t_sampler {t_sampler!r} (None, 'loss_second_moment' or a LossSecondMomentSampler)")
+        if t_sampler is not None and (distributed if distributed is not None else dist.is_initialized()):
+            raise ValueError("TrainStep: t_sampler does not work with data parallelism (every rank would need the other ranks' "
+                             "timesteps and row losses: one more collective)")
         self.model, self.diffusion = model, diffusion
         self.learned = getattr(diffusion, "variance", "fixed") == "learned"
         self.vlb_lambda = float(vlb_lambda)
@@ -679,6 +810,11 @@ class TrainStep:
         self.loss_weights = None         # (T,) fp32 device table w[t], or None for the unweighted loss
         if loss_weighting is not None:
             self.loss_weights = diffusion.snr_weights(loss_weighting, snr_gamma).float().to(diffusion.alpha_hat.device).contiguous()
+        self.t_sampler = LossSecondMomentSampler(diffusion) if isinstance(t_sampler, str) else t_sampler
+        if self.t_sampler is not None:
+            if self.t_sampler.T != diffusion.noise_steps:
+                raise ValueError(f"TrainStep: the t_sampler was built for {self.t_sampler.T} noise steps, the diffusion has {diffusion.noise_steps}")
+            self.t_sampler.set_base_weights(self.loss_weights)
         # weight-gradient kernels on a second stream (ops._GradMode.side): off the critical path of backward, they fill
         # the CUs the dependent chain of small kernels leaves idle.  Measured on MI355X (B=256): eager 12.0 -> 11.1
         # ms/step, captured graph 11.45 -> 11.3 (forks batched 16 layers at a time: every fork is a cross-stream edge
@@ -752,7 +888,20 @@ class TrainStep:
         try:
             x_t, noise = self.diffusion.noise_images(images, t, eps)
             pred = self.model(x_t, t) if y is None else self.model(x_t, t, y)
-            if self.learned:
+            ts, rows = self.t_sampler, None
+            if ts is not None:
+                # the loss through the sampler's tables; the rows' own losses (importance weight removed) feed the tick below
+                d, rows = self.diffusion, ts.rows_buffer(images.shape[0])
+                if self.learned:
+                    scale = self.vlb_lambda * (d.noise_steps - 1)
+                    loss, self.last_vlb = ops.lvar_loss(pred, images, noise, t, d.alpha, d.alpha_hat, d.beta, d._lv(), ts.wtab,
+                                                        self.prediction, scale, vw=ts.vwtab)
+                    ops.lvar_loss_rows(pred.detach(), images, noise, t, d.alpha, d.alpha_hat, d.beta, d._lv(), self.loss_weights,
+                                       self.prediction, scale, out=rows)
+                else:
+                    loss = ops.objective_loss(pred, images, noise, t, d.alpha_hat, ts.wtab, self.prediction)
+                    ops.loss_rows(pred.detach(), images, noise, t, d.alpha_hat, self.loss_weights, self.prediction, out=rows)
+            elif self.learned:
                 d = self.diffusion
                 loss, self.last_vlb = ops.lvar_loss(pred, images, noise, t, d.alpha, d.alpha_hat, d.beta, d._lv(), self.loss_weights,
                                                     self.prediction, self.vlb_lambda * (d.noise_steps - 1))
@@ -776,6 +925,8 @@ class TrainStep:
                         loss.backward()
                 if overlap:
                     self.ddp.backward_done()
+            if ts is not None:
+                ts.update(t, rows)                     # on the main stream: behind the loss backward, which reads wtab
         finally:
             if W.recording is not None and W.recording is self._wino_requests:
                 W.recording = None
@@ -807,7 +958,11 @@ class TrainStep:
         if y is not None and not self.conditional:
             raise ValueError("TrainStep: class labels were passed but the step was built with conditional=False: label_emb sits "
                              "outside the optimised range (FlatParams) and would never be updated; build TrainStep(..., conditional=True)")
-        if t is None:
+        drawn = False                               # t was drawn on the device, straight into the captured step's static buffer
+        if t is None and self.t_sampler is not None:
+            drawn = self._graph is not None
+            t = self.t_sampler.draw(images.shape[0], out=self._static["t"] if drawn else None)
+        elif t is None:
             t = self.diffusion.sample_timesteps(images.shape[0])
         t = t.to(images.device, non_blocking=True)
         if y is not None:
@@ -840,6 +995,7 @@ class TrainStep:
             fp, opt, h = self.opt.fp, self.opt, self._ema_home
             bufs = (fp.flat, opt.m, opt.v, opt.state) + ((h.flat, h.state) if h is not None else ())
             bufs += (opt.ctl,) if opt.ctl is not None else ()
+            bufs += self.t_sampler.buffers() if self.t_sampler is not None else ()
             keep = [b.clone() for b in bufs]
             rng = torch.cuda.get_rng_state(images.device)
             s = torch.cuda.Stream()
@@ -868,7 +1024,8 @@ class TrainStep:
             raise ValueError("TrainStep(graph=True): the step was captured " + ("without" if st["y"] is None else "with") +
                              " class labels; `y` must be passed (or omitted) on every call alike")
         st["images"].copy_(images)
-        st["t"].copy_(t)
+        if not drawn:
+            st["t"].copy_(t)
         if y is not None:
             st["y"].copy_(y)
         if eps is not None:
@@ -899,6 +1056,8 @@ class DistillStep:
             raise ValueError("DistillStep: student is teacher: the teacher must stay frozen (student = copy.deepcopy(teacher))")
         if getattr(diffusion, "variance", "fixed") == "learned":
             raise ValueError("DistillStep: variance='learned' is not supported (the student's step is deterministic DDIM)")
+        if train_step_kw.get("t_sampler") is not None:
+            raise ValueError("DistillStep: t_sampler is not supported (the step draws positions of the chain, not timesteps)")
         levels = diffusion.distill_levels(chain)              # ValueError for an odd, unordered or out-of-range chain
         if diffusion.prediction == "eps":
             logging.warning("DistillStep: prediction='eps' is unstable at few sampling steps (Salimans & Ho 2022, section 4); "
@@ -998,7 +1157,12 @@ def train(args, model_path=None, dataloader=None, model=None, diffusion=None):
     if kind is not None or warmup:
         schedule = LRSchedule(kind or "constant", warmup=warmup, total=args.epochs * n_batches,
                               min_ratio=getattr(args, "lr_min_ratio", 0.0) or 0.0)
-    step = TrainStep(model, diffusion, lr=args.lr, graph=False, ema=ema, ema_model=ema_model,
+    t_sampler = getattr(args, "t_sampler", None)
+    if isinstance(t_sampler, str) and t_sampler in T_SAMPLERS:
+        hist, up = getattr(args, "t_sampler_history", None), getattr(args, "t_sampler_uniform_prob", None)
+        t_sampler = LossSecondMomentSampler(diffusion, history_per_term=10 if hist is None else hist,
+                                            uniform_prob=0.001 if up is None else up)
+    step = TrainStep(model, diffusion, lr=args.lr, graph=False, ema=ema, ema_model=ema_model, t_sampler=t_sampler,
                      ema_start=getattr(args, "ema_start", 2000), max_grad_norm=getattr(args, "max_grad_norm", None),
                      lr_schedule=schedule, loss_weighting=getattr(args, "loss_weighting", None),
                      snr_gamma=5.0 if getattr(args, "snr_gamma", None) is None else args.snr_gamma,
@@ -1026,6 +1190,8 @@ def train(args, model_path=None, dataloader=None, model=None, diffusion=None):
             torch.save(model.state_dict(), model_path)
             if ema is not None:
                 torch.save(ema_model.state_dict(), ema_path(model_path))
+            if step.t_sampler is not None:
+                torch.save(step.t_sampler.state_dict(), t_sampler_path(model_path))
     return loss_all
 
 
@@ -1033,3 +1199,9 @@ def ema_path(model_path):
     """Where `train` writes the EMA weights beside a checkpoint: ckpt_X.pt -> ckpt_X_ema.pt."""
     root, ext = os.path.splitext(model_path)
     return f"{root}_ema{ext}"
+
+
+def t_sampler_path(model_path):
+    """Where `train` writes the timestep sampler's state beside a checkpoint: ckpt_X.pt -> ckpt_X_tsampler.pt."""
+    root, ext = os.path.splitext(model_path)
+    return f"{root}_tsampler{ext}"

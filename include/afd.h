@@ -616,6 +616,45 @@ int afd_denoise_step_lvar_cfg_dev(const float* x, const float* out2, const float
 int afd_vlb_terms_lvar(const float* x0, long n_img, const int64_t* img, const float* x_t, const float* eps, const float* out2,
                        const int64_t* t, const double* lv_coef, long T, const float* alpha, const float* alpha_hat,
                        const float* beta, int kind, double* term, double* sq, long rows, long per, afd_stream_t stream);
+
+/* ---- loss-aware timestep sampling (Nichol & Dhariwal 2021, loss-second-moment resampling), on the device ------ training.
+ * LossSecondMomentSampler / TrainStep(t_sampler=).  State: hist (T, H) fp64, the last H row losses seen at each timestep, and
+ * count (T) int32; lo is the smallest timestep that is drawn, n = T - lo (DESIGN.md section 6m has the semantics in full).
+ * afd_loss_rows / afd_lvar_loss_rows: the inputs of afd_objective_loss_fwd / afd_lvar_loss_fwd; rows[b] (B doubles) is row b's
+ *   share of that loss, times B:  (1 / chw) w[t[b]] sum_i d_i^2  [+ (vlb_scale / (chw ln 2)) sum_i term_i],  with d_i = pred -
+ *   target formed by the loss kernels' own fp32 expression and everything after it in fp64.  One launch, one workgroup per row, a
+ *   fixed summation tree, no atomics: identical bytes run to run; 128-bit accesses when chw % 4 == 0 and the float pointers are
+ *   16-byte aligned, element by element otherwise, with the same values either way.  rows must not overlap an input.
+ * afd_tsampler_tick: ONE launch of ONE workgroup.  Update: the rows b = 0 .. B - 1 in order; a row whose loss is not finite (or
+ *   whose t lies outside [0, T)) is skipped; hist[t[b]] takes rows[b] at position count[t[b]]++, or, when it is full, shifts left
+ *   by one and takes it last.  Refresh: warm[0] = (count[t] == H for every t in [lo, T)); with q_t = sqrt(mean_j hist[t][j]^2),
+ *     warm and 0 < sum q < inf:  prob[t] = (q_t / sum q) (1 - uniform_prob) + uniform_prob / n,  iw_t = 1 / (n prob[t])
+ *     otherwise:                 prob[t] = 1 / n,  iw_t = 1 exactly;                  t < lo: prob[t] = 0, iw_t = 1
+ *   cdf (n doubles) = the inclusive prefix sum of prob over [lo, T) divided by its last value, the last entry exactly 1;
+ *   wtab[t] = (float)(w_base[t] iw_t) (w_base NULL: 1), vwtab[t] = (float)iw_t (vwtab may be NULL): the tables the loss kernels
+ *   read as w and vw.  fp64 throughout, every sum in a fixed order.  Any T, H and B.
+ * afd_tsampler_draw: t_out[b] = lo + the first k with u[b] < cdf[k] (u: B doubles in [0, 1)), clamped to T - 1; one launch.
+ * afd_lvar_loss_fwd_tw / _bwd_tw: afd_lvar_loss_fwd / _bwd with a second table vw (T floats, or NULL for 1): vw[t[b]] multiplies
+ *   each of row b's bound terms (forward) and row b's dL/dv (backward).  afd_lvar_loss_fwd / _bwd are these with NULL.
+ * AFD_EINVAL (nothing launched) on NULL required pointers, sizes <= 0, H < 1, uniform_prob outside [0, 1), lo outside [0, T),
+ * a bad kind.  t is read on the device, unchecked by the row kernels. */
+int afd_loss_rows(const float* pred, const float* x0, const float* eps, const int64_t* t, const float* alpha_hat,
+                  const float* w_or_null, int kind, double* rows, long B, long chw, afd_stream_t stream);
+int afd_lvar_loss_rows(const float* out2, const float* x0, const float* eps, const int64_t* t, const float* alpha,
+                       const float* alpha_hat, const float* beta, const double* lv_coef, const float* w_or_null, int kind,
+                       double vlb_scale, double* rows, long B, long chw, afd_stream_t stream);
+int afd_tsampler_tick(const int64_t* t, const double* rows, long B, double* hist, int* count, long T, long H, long lo,
+                      double uniform_prob, const float* w_base_or_null, double* prob, double* cdf, float* wtab,
+                      float* vwtab_or_null, int* warm, afd_stream_t stream);
+int afd_tsampler_draw(const double* cdf, const double* u, long lo, long T, int64_t* t_out, long B, afd_stream_t stream);
+int afd_lvar_loss_fwd_tw(const float* out2, const float* x0, const float* eps, const int64_t* t, const float* alpha,
+                         const float* alpha_hat, const float* beta, const double* lv_coef, const float* w_or_null,
+                         const float* vw_or_null, int kind, double vlb_scale, float* loss_out, double* sums_out_or_null,
+                         float* workspace, long B, long chw, afd_stream_t stream);
+int afd_lvar_loss_bwd_tw(const float* out2, const float* x0, const float* eps, const int64_t* t, const float* alpha,
+                         const float* alpha_hat, const float* beta, const double* lv_coef, const float* w_or_null,
+                         const float* vw_or_null, int kind, double vlb_scale, const float* dloss, float* dout2, long B, long chw,
+                         afd_stream_t stream);
 int afd_adamw_tick(float* state, float beta1, float beta2, afd_stream_t stream);
 int afd_adamw_step(float* p, const float* g, float* m, float* v, long n, const float* state,
                    float lr, float beta1, float beta2, float eps, float weight_decay, float grad_scale,
