@@ -3,7 +3,7 @@
 Public surface = the reference's Python API for the hot path:
 UNet, Diffusion, train, custom_upsample, custom_downsample, circularLowpassKernel, argument,
 set_seed, EMA, plus the engine-side helpers TrainStep / FusedAdamW / GradAllReduce / LRSchedule / DistillStep / progressive_distill /
-LossSecondMomentSampler.
+LossSecondMomentSampler / DeviceDataset / DeviceLoader.
 Device work runs in libafd_hip.so (hand-written gfx950 kernels, C ABI in include/afd.h).
 """
 from ._lib import AfdError, lib  # noqa: F401
@@ -18,6 +18,7 @@ from .training import (argument, set_seed, setup_logging, train, TrainStep, Fuse
                        LossSecondMomentSampler)
 
 from .tasks import bpd_results, ddpm_run, equivariance_results, inpaint_results, rotation_results, shift_results  # noqa: F401
-from .data import get_data, get_data_MNIST, save_gen_images, make_collage  # noqa: F401
+from .data import (get_data, get_data_MNIST, save_gen_images, make_collage, DeviceDataset, DeviceLoader,  # noqa: F401
+                   get_data_device, get_data_MNIST_device)
 
 __version__ = "0.1.0"

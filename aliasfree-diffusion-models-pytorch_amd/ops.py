@@ -1871,3 +1871,36 @@ def vlb_terms_lvar(x0, img, x_t, eps, out2, t, lv_coef, alpha, alpha_hat, beta, 
     lib().afd_vlb_terms_lvar(_p(x0), n_img, _p(img), _p(x_t), _p(eps), _p(out2), _p(t), _p(lv_coef), alpha_hat.numel(), _p(alpha),
                              _p(alpha_hat), _p(beta), code, _p(term), _p(sq), rows, per, _stream())
     return term, sq
+
+
+def batch_gather(data, idx, flip=None, table=None, labels=None, x=None):
+    """One batch out of a device-resident store, one launch (afd.h: afd_batch_gather_u8 / _f32): data (N, C, H, W) uint8 (with
+    table (C, 256) fp32) or fp32, idx (B,) int64 (a view is fine), flip None or (B,) uint8, labels None or (N,) int64, all on the
+    device -> (x (B, C, H, W) fp32, y (B,) int64 or None).  x: where to write (a contiguous fp32 tensor of that shape, or a view
+    that is); a fresh tensor by default."""
+    what = "batch_gather"
+    if not isinstance(data, torch.Tensor) or not data.is_cuda or data.dim() != 4 or not data.is_contiguous() \
+            or data.dtype not in (torch.uint8, torch.float32):
+        raise AfdError(f"afdm: {what}: data must be a contiguous (N, C, H, W) uint8 or fp32 device tensor")
+    N, C, H, W = data.shape
+    if not isinstance(idx, torch.Tensor) or not idx.is_cuda or idx.dtype != torch.long or idx.dim() != 1 or idx.numel() == 0 \
+            or not idx.is_contiguous():
+        raise AfdError(f"afdm: {what}: idx must be a contiguous (B,) int64 device tensor with at least one element")
+    B = idx.numel()
+    u8 = data.dtype == torch.uint8
+    if u8:
+        _dev_table(what, "table", table, torch.float32, (C, 256))
+    if flip is not None:
+        _dev_table(what, "flip", flip, torch.uint8, (B,))
+    y = None
+    if labels is not None:
+        _dev_table(what, "labels", labels, torch.long, (N,))
+        y = torch.empty(B, device=data.device, dtype=torch.long)
+    if x is None:
+        x = torch.empty(B, C, H, W, device=data.device, dtype=torch.float32)
+    _dev_table(what, "x", x, torch.float32, (B, C, H, W))
+    if u8:
+        lib().afd_batch_gather_u8(_p(data), N, C, H, W, _p(idx), _p(flip), _p(table), _p(x), _p(labels), _p(y), B, _stream())
+    else:
+        lib().afd_batch_gather_f32(_p(data), N, C, H, W, _p(idx), _p(flip), _p(x), _p(labels), _p(y), B, _stream())
+    return x, y

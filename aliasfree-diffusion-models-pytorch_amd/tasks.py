@@ -10,7 +10,8 @@ import os
 import numpy as np
 import torch
 
-from .data import get_data, get_data_MNIST, make_collage, save_dataset_MNIST, save_gen_images
+from .data import (DeviceDataset, get_data, get_data_MNIST, get_data_device, get_data_MNIST_device, make_collage, save_dataset_MNIST,
+                   save_gen_images)
 from .diffusion import Diffusion
 from .training import argument, diffusion_kwargs, ema_path, model_out_channels, progressive_distill, set_seed, train
 from .unet import UNet
@@ -23,8 +24,30 @@ def _f_settings(params):
             "omega_c_down": params["f_down"], "omega_c_up": params["f_up"]}
 
 
-def _loader(dataset_name, args):
-    return get_data_MNIST(args) if dataset_name == "MNIST" else get_data(args)
+DATA_KEYS = ("device_loader", "flip_prob", "dataset_cache")
+
+
+def _loader(dataset_name, args, params=None):
+    """(loader, dataset) of a run: the host loaders, or with params["device_loader"] the data set in device memory and a
+    DeviceLoader over it (params["flip_prob"]: horizontal flips, seeded by the run's seed; params["dataset_cache"]: the .npz an
+    image-folder data set is kept in between runs)."""
+    params = params or {}
+    if not params.get("device_loader"):
+        for k in ("flip_prob", "dataset_cache"):
+            if params.get(k):
+                raise ValueError(f"ddpm_run: {k} needs device_loader: True (the host loaders have neither flips nor a cache)")
+        return get_data_MNIST(args) if dataset_name == "MNIST" else get_data(args)
+    kw = {"flip_prob": params.get("flip_prob") or 0.0, "seed": params.get("seed")}
+    if dataset_name == "MNIST":
+        return get_data_MNIST_device(args, **kw)
+    return get_data_device(args, cache=params.get("dataset_cache"), **kw)
+
+
+def _first_images(dataset, N):
+    """The first N training images, in data set order: (N, C, H, W) float."""
+    if isinstance(dataset, DeviceDataset):
+        return dataset.batch(torch.arange(N))[0]
+    return torch.stack([dataset[i][0] for i in range(N)])
 
 
 def ddpm_run(params):
@@ -52,6 +75,10 @@ def ddpm_run(params):
                             "t_sampler_uniform_prob") if params.get(k) is not None]
     for k in opt_keys:
         setattr(args, k, params[k])
+    # optional device-resident data set: "device_loader": True keeps the training set in device memory and assembles every batch
+    # there (data.DeviceLoader: the host loader's order and values), "flip_prob" mirrors rows left-right, "dataset_cache" names the
+    # .npz an image-folder data set is kept in; same rule
+    data_keys = [k for k in DATA_KEYS if params.get(k) is not None]
     if params.get("distill") is not None:
         _distill_cfg(params)                                   # a malformed key fails here, not after the training
     cwd = os.getcwd()
@@ -79,7 +106,7 @@ def ddpm_run(params):
     for k_out, k_in in (("kernel_size", "kernel_size"), ("kaiser_beta", "kaiser_beta"),
                         ("omega_c_down", "omega_c_down"), ("omega_c_up", "omega_c_up")):
         settings[k_out] = f_settings[k_in] if f_settings is not None else "None"
-    for k in opt_keys:
+    for k in opt_keys + data_keys:
         settings[k] = params[k]
     text = "\n".join(f"{k}: {val}" for k, val in settings.items())
     print(text)
@@ -99,7 +126,7 @@ def ddpm_run(params):
 
     # train
     set_seed(seed)
-    dataloader, dataset = _loader(name, args)
+    dataloader, dataset = _loader(name, args, params)
     model = UNet(c_in=args.image_channels, c_out=model_out_channels(args), image_size=args.image_size, f_settings=f_settings,
                  device=args.device, variant=v).to(args.device)
     diffusion = Diffusion(noise_steps=args.noise_steps, img_size=args.image_size, device=args.device, **diffusion_kwargs(args))
@@ -141,7 +168,7 @@ def ddpm_run(params):
     # defaults to the run's), saves the student beside the checkpoint and draws the image set from it over its own chain, eta = 0
     distill = None
     if params.get("distill") is not None:
-        distill, gen_model, gen_kw = _distill(params, args, diffusion, gen_model, modelpath, name, seed)
+        distill, gen_model, gen_kw = _distill(params, args, diffusion, gen_model, modelpath, name, seed, dataloader)
     for start in np.arange(0, params["gen_total"], params["gen_per_batch"]):
         fileno = np.arange(start, start + params["gen_per_batch"], 1)
         xg, _ = diffusion.sample(gen_model, n=params["gen_per_batch"], image_channels=args.image_channels, **gen_kw)
@@ -157,12 +184,13 @@ def ddpm_run(params):
     # optional likelihood: params["eval_bpd"] = N scores the first N training images, in dataset order, on the model the
     # FID/KID image set came from (Diffusion.calc_bpd; "eval_bpd_t_samples": K timesteps per image, "eval_bpd_sigma": "beta", "posterior" or,
     # with "variance": "learned", "learned")
+    dev_set = dataset if isinstance(dataset, DeviceDataset) else None      # (the host path loads its data set again, as before)
     if params.get("eval_bpd"):
-        out["bpd"] = _eval_bpd(params, args, diffusion, gen_model, run_dir, name, v, seed)
+        out["bpd"] = _eval_bpd(params, args, diffusion, gen_model, run_dir, name, v, seed, dev_set)
     # optional equivariance scores: params["eval_equivariance"] = the keyword arguments of Diffusion.equivariance (t, transforms,
     # margin, peak, batch, ...) plus "N" (default 16), the number of training images scored, in dataset order, on the same model
     if params.get("eval_equivariance"):
-        out["equivariance"] = _eval_equivariance(params, args, diffusion, gen_model, run_dir, name, v, seed)
+        out["equivariance"] = _eval_equivariance(params, args, diffusion, gen_model, run_dir, name, v, seed, dev_set)
     return out
 
 
@@ -180,11 +208,11 @@ def _distill_cfg(params):
     return cfg
 
 
-def _distill(params, args, diffusion, model, modelpath, name, seed):
-    """-> (out["distill"], the student, the sampler arguments of the image set)."""
+def _distill(params, args, diffusion, model, modelpath, name, seed, device_loader=None):
+    """-> (out["distill"], the student, the sampler arguments of the image set).  device_loader: the run's DeviceLoader, if any."""
     cfg = _distill_cfg(params)
     set_seed(seed)
-    loader = _loader(name, args)[0]
+    loader = device_loader if params.get("device_loader") else _loader(name, args)[0]
     student, rounds = progressive_distill(model, diffusion, loader, cfg["start_steps"], cfg["end_steps"], cfg["iters"],
                                           args.lr if cfg.get("lr") is None else cfg["lr"], args.device)
     path = distill_path(modelpath, cfg["end_steps"])
@@ -192,12 +220,13 @@ def _distill(params, args, diffusion, model, modelpath, name, seed):
     return {"rounds": rounds, "modelpath": path}, student, {"steps": rounds[-1]["chain"], "eta": 0.0}
 
 
-def _eval_bpd(params, args, diffusion, model, run_dir, name, v, seed):
+def _eval_bpd(params, args, diffusion, model, run_dir, name, v, seed, dataset=None):
     N, K, sigma = int(params["eval_bpd"]), params.get("eval_bpd_t_samples"), params.get("eval_bpd_sigma", "beta")
-    dataset = _loader(name, args)[1]
+    if dataset is None:
+        dataset = _loader(name, args)[1]
     if not 1 <= N <= len(dataset):
         raise ValueError(f"ddpm_run: eval_bpd must lie in [1, {len(dataset)}] (the training set's size; got {N})")
-    images = torch.stack([dataset[i][0] for i in range(N)])
+    images = _first_images(dataset, N)
     set_seed(seed)
     r = diffusion.calc_bpd(model, images, sigma=sigma, t_samples=K)
     bpd = r["bpd"].numpy()
@@ -211,14 +240,15 @@ def _eval_bpd(params, args, diffusion, model, run_dir, name, v, seed):
     return float(bpd.mean())
 
 
-def _eval_equivariance(params, args, diffusion, model, run_dir, name, v, seed):
+def _eval_equivariance(params, args, diffusion, model, run_dir, name, v, seed, dataset=None):
     import json
     kw = dict(params["eval_equivariance"])
     N = int(kw.pop("N", 16))
-    dataset = _loader(name, args)[1]
+    if dataset is None:
+        dataset = _loader(name, args)[1]
     if not 1 <= N <= len(dataset):
         raise ValueError(f"ddpm_run: eval_equivariance N must lie in [1, {len(dataset)}] (the training set's size; got {N})")
-    images = torch.stack([dataset[i][0] for i in range(N)]).float()
+    images = _first_images(dataset, N).float()
     set_seed(seed)
     r = diffusion.equivariance(model, images, **kw)
     t = kw["t"]

@@ -743,6 +743,25 @@ int afd_replay_build(void* hip_graph, void** out_handle, int* counts);
 int afd_replay_run(void* handle, afd_stream_t main_stream, afd_stream_t side_stream);
 int afd_replay_free(void* handle);
 
+/* ---- batch assembly from a device-resident data set (csrc/loader.hip) ------------------------- data.DeviceDataset.batch
+ * data is a contiguous (N, C, H, W) store of uint8 pixels or of floats, idx B indices into it (int64, 8-byte aligned: it may be
+ * a view into a longer permutation), flip NULL or B bytes (non-zero: mirror that row left-right), labels / y N and B int64
+ * class labels, NULL together.  ONE launch writes, for row b with i = idx[b] and w' = flip[b] ? W - 1 - w : w,
+ *     u8:   x[b, c, h, w] = table[c * 256 + data[i, c, h, w']]          table: (C, 256) floats, filled on the host
+ *     f32:  x[b, c, h, w] = data[i, c, h, w']   as 32-bit words: NaN payloads, infinities and -0.0 survive
+ *     y[b] = labels[i]
+ * No arithmetic touches a pixel, so the u8 form returns exactly the floats the table holds.  An index outside [0, N) reads
+ * nothing outside data: that row of x is quiet NaN (0x7fc00000) and y[b] = INT64_MIN; indices may repeat.
+ * 16 source bytes per lane (one 128-bit load; four / one 128-bit stores) when a row of data is a multiple of 16 bytes and data
+ * and x are 16-byte aligned; element by element otherwise, with the same values either way.  x (4-byte aligned) must not
+ * overlap an input or y.  AFD_EINVAL (nothing launched) on NULL required pointers, sizes <= 0, labels without y or y without
+ * labels, misaligned x / idx, an overlapping x, or more than 2^31 - 1 output planes (B C). */
+int afd_batch_gather_u8(const uint8_t* data, long N, long C, long H, long W, const int64_t* idx, const uint8_t* flip_or_null,
+                        const float* table, float* x, const int64_t* labels_or_null, int64_t* y_or_null, long B,
+                        afd_stream_t stream);
+int afd_batch_gather_f32(const float* data, long N, long C, long H, long W, const int64_t* idx, const uint8_t* flip_or_null,
+                         float* x, const int64_t* labels_or_null, int64_t* y_or_null, long B, afd_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
