@@ -10,7 +10,7 @@ from ._lib import AfdError, lib  # noqa: F401
 from .filters import circularLowpassKernel, custom_downsample, custom_upsample  # noqa: F401
 from .blocks import (SelfAttention, DoubleConv, DoubleConv_F, DoubleConv_F4, Down, Down_F, Down_FF, Down_FFF,  # noqa: F401
                      Down_F4, Up, Up_F, Up_FF, Up_FFF, Up_F4)
-from .ops import NULL_LABEL  # noqa: F401
+from .ops import NULL_LABEL, nn_search  # noqa: F401
 from .unet import UNet  # noqa: F401
 from .diffusion import Diffusion  # noqa: F401
 from .training import (argument, set_seed, setup_logging, train, TrainStep, FusedAdamW, FlatParams,  # noqa: F401

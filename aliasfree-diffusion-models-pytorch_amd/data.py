@@ -106,7 +106,9 @@ class DeviceDataset:
     images: (N, C, H, W) uint8 pixels, normalised on the way out through `table` = normalisation_table(C, mean, std) -- bit for
     bit what ImageFolder.__getitem__ returns for those pixels -- or float32 values that are handed out as they are (mean and std
     are then unused).  labels: None or (N,) int64.  `.images`, `.labels`, `.table` live on `device`.
-    device="cpu" runs `batch` as plain torch indexing: the same values, and the oracle of the kernels' tests."""
+    device="cpu" runs `batch` as plain torch indexing: the same values, and the oracle of the kernels' tests.
+    `nearest` / `self_nearest` search the store for the nearest images of a set of queries; on
+    device="cpu" they are a plain torch brute force, the oracle of that kernel's tests."""
 
     def __init__(self, images, labels=None, mean=0.5, std=0.5, device="cuda", classes=None):
         if isinstance(images, np.ndarray):
@@ -166,6 +168,83 @@ class DeviceDataset:
         y = self.labels[safe]
         y[bad] = INT64_MIN
         return x, y
+
+    def nearest(self, queries, k=1, exclude=None):
+        """For each query image the k images of the store of smallest squared L2 distance, ascending, ties to the lower index
+        (ops.nn_search: afd_nn_search_u8 / afd_nn_search_f32).  queries: (n, C, H, W) of the store's
+        dtype -- raw pixels for a uint8 store, values on the store's scale for a float32 one; exclude: None or (n,) int64, query q
+        skips image exclude[q] (negative: nothing).  -> (dist (n, k), idx (n, k) int64) on the store's device: dist is the exact
+        sum of squared pixel differences as int64 (uint8), or the fp64 sum rounded once to float32, a NaN distance reported as
+        the canonical NaN and ranked last (float32).  A slot with no image left has idx -1 and dist -1 / +inf."""
+        what = "DeviceDataset.nearest"
+        if isinstance(queries, np.ndarray):
+            queries = torch.from_numpy(queries)
+        if not isinstance(queries, torch.Tensor) or queries.dtype != self.images.dtype:
+            raise ValueError(f"{what}: queries must be a tensor of the store's dtype {self.images.dtype} (got "
+                             f"{getattr(queries, 'dtype', type(queries).__name__)})")
+        if queries.dim() != 4 or tuple(queries.shape[1:]) != tuple(self.images.shape[1:]):
+            raise ValueError(f"{what}: queries must have the shape (n, {', '.join(str(s) for s in self.images.shape[1:])}) "
+                             f"(got {tuple(queries.shape)})")
+        n = queries.shape[0]
+        if n < 1:
+            raise ValueError(f"{what}: queries must hold at least one image (n >= 1)")
+        if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 1 <= k <= 16:
+            raise ValueError(f"{what}: k must be an int in [1, 16] (got {k!r})")
+        if exclude is not None and (not isinstance(exclude, torch.Tensor) or exclude.dtype != torch.long or tuple(exclude.shape) != (n,)):
+            raise ValueError(f"{what}: exclude must be None or an int64 tensor of shape ({n},)")
+        if self.images.dtype == torch.uint8 and self.images[0].numel() > 32768:
+            raise ValueError(f"{what}: a uint8 image holds at most 32768 elements (C H W = {self.images[0].numel()})")
+        queries = queries.detach().to(self.device).contiguous()
+        exclude = None if exclude is None else exclude.to(self.device).contiguous()
+        if self.device.type == "cpu":
+            return self._nearest_torch(queries, int(k), exclude)
+        from . import ops
+        with torch.cuda.device(self.device):
+            return ops.nn_search(self.images, queries, int(k), exclude)
+
+    def self_nearest(self, k=1, batch=1024):
+        """Leave-one-out: nearest(images, k, exclude = own index) over the whole store, `batch` queries at a time.  The
+        distribution that the distances of generated samples are read against."""
+        if isinstance(batch, bool) or not isinstance(batch, (int, np.integer)) or batch < 1:
+            raise ValueError(f"DeviceDataset.self_nearest: batch must be an integer >= 1 (got {batch!r})")
+        own = torch.arange(len(self), device=self.device)
+        parts = [self.nearest(self.images[a:a + batch], k, own[a:a + batch]) for a in range(0, len(self), int(batch))]
+        return torch.cat([p[0] for p in parts]), torch.cat([p[1] for p in parts])
+
+    def _nearest_torch(self, queries, k, exclude):
+        """Brute force in plain torch: int64 sums of squared differences (uint8) or fp64 sums rounded once to float32, then a stable
+        sort by distance (NaN last), so equal distances keep their index order."""
+        N, n = len(self), queries.shape[0]
+        u8 = self.images.dtype == torch.uint8
+        data = self.images.reshape(N, -1)
+        data = data.to(torch.int16) if u8 else data.double()
+        q = queries.reshape(n, -1)
+        q = q.to(torch.int16) if u8 else q.double()
+        d = torch.empty(n, N, dtype=torch.long if u8 else torch.float32, device=data.device)
+        step = max(1, (1 << 24) // max(1, data.numel()))
+        for a in range(0, n, step):
+            diff = data[None] - q[a:a + step, None]
+            if u8:
+                diff = diff.to(torch.int32)
+                d[a:a + step] = (diff * diff).sum(-1, dtype=torch.long)
+            else:
+                d[a:a + step] = (diff * diff).sum(-1).float()
+        if not u8:
+            d[torch.isnan(d)] = float("nan")                       # the canonical quiet NaN
+        order = torch.sort(d, dim=1, stable=True)[1]
+        if exclude is not None:                                    # the excluded row goes behind every candidate, order kept
+            out = order == exclude.view(n, 1)
+            order = order.gather(1, torch.sort(out.to(torch.uint8), dim=1, stable=True)[1])
+            avail = N - out.sum(1)
+        else:
+            avail = torch.full((n,), N, device=d.device)
+        idx = torch.full((n, k), -1, dtype=torch.long, device=d.device)
+        dist = torch.full((n, k), -1 if u8 else float("inf"), dtype=d.dtype, device=d.device)
+        m = min(k, N)
+        keep = torch.arange(m, device=d.device).view(1, m) < avail.view(n, 1)
+        idx[:, :m] = torch.where(keep, order[:, :m], idx[:, :m])
+        dist[:, :m] = torch.where(keep, d.gather(1, order[:, :m]), dist[:, :m])
+        return dist, idx
 
     @classmethod
     def from_folder(cls, root, size, cache=None, device="cuda", mean=0.5, std=0.5):

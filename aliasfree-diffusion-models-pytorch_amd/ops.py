@@ -1904,3 +1904,54 @@ def batch_gather(data, idx, flip=None, table=None, labels=None, x=None):
     else:
         lib().afd_batch_gather_f32(_p(data), N, C, H, W, _p(idx), _p(flip), _p(x), _p(labels), _p(y), B, _stream())
     return x, y
+
+
+NN_MAX_K = 16
+NN_MAX_D_U8 = 32768
+NN_WORKSPACE_LIMIT = 64 << 20
+
+
+def nn_group(N, D, n, k, f32):
+    """How many queries one afd_nn_search_* launch takes so that its workspace stays within NN_WORKSPACE_LIMIT: the workspace is
+    linear in the number of queries, so this is the limit over the bytes one query needs (at least 1, at most n)."""
+    per = int(lib().afd_nn_search_workspace_bytes(N, D, 1, k, int(f32)))
+    if per <= 0:
+        raise AfdError(f"afdm: nn_search: sizes out of range (N = {N}, D = {D}, n = {n}, k = {k})")
+    return max(1, min(n, NN_WORKSPACE_LIMIT // per))
+
+
+def nn_search(data, queries, k=1, exclude=None):
+    """For each query row the k rows of `data` of smallest squared L2 distance, ascending, ties to the lower index (afd.h:
+    afd_nn_search_u8 / _f32).  data (N, D) or (N, C, H, W), queries (n, D) or (n, C, H, W) of the same row size and dtype, uint8
+    (exact int64 distances, D <= 32768) or fp32 (fp64 sums rounded once to fp32), contiguous, on the device; exclude None or (n,)
+    int64 on the device: query q skips row exclude[q] (negative: nothing).  -> (dist (n, k) int64 / fp32, idx (n, k) int64); a
+    slot with no candidate left holds idx -1 and dist -1 / +inf.  The queries go through in groups that share one workspace of
+    at most NN_WORKSPACE_LIMIT bytes."""
+    what = "nn_search"
+    for name, v in (("data", data), ("queries", queries)):
+        if not isinstance(v, torch.Tensor) or not v.is_cuda or v.dim() not in (2, 4) or not v.is_contiguous() or v.numel() == 0 \
+                or v.dtype not in (torch.uint8, torch.float32):
+            raise AfdError(f"afdm: {what}: {name} must be a non-empty contiguous 2-D or 4-D uint8 or fp32 device tensor")
+    N, n = data.shape[0], queries.shape[0]
+    D = data.numel() // N
+    if queries.dtype != data.dtype or queries.numel() // n != D:
+        raise AfdError(f"afdm: {what}: queries must have data's dtype and row size ({data.dtype}, {D})")
+    if isinstance(k, bool) or not isinstance(k, int) or not 1 <= k <= NN_MAX_K:
+        raise AfdError(f"afdm: {what}: k must be an int in [1, {NN_MAX_K}] (got {k!r})")
+    f32 = data.dtype == torch.float32
+    if not f32 and D > NN_MAX_D_U8:
+        raise AfdError(f"afdm: {what}: a uint8 row holds at most {NN_MAX_D_U8} elements (got D = {D})")
+    if exclude is not None:
+        _dev_table(what, "exclude", exclude, torch.long, (n,))
+    idx = torch.empty(n, k, device=data.device, dtype=torch.long)
+    dist = torch.empty(n, k, device=data.device, dtype=torch.float32 if f32 else torch.long)
+    group = nn_group(N, D, n, k, f32)
+    nbytes = int(lib().afd_nn_search_workspace_bytes(N, D, group, k, int(f32)))
+    ws = torch.empty(nbytes // 8, device=data.device, dtype=torch.long)
+    fn = lib().afd_nn_search_f32 if f32 else lib().afd_nn_search_u8
+    qflat = queries.view(n, D)
+    for a in range(0, n, group):
+        b = min(n, a + group)
+        fn(_p(data), N, D, _p(qflat[a:b]), b - a, None if exclude is None else _p(exclude[a:b]), k, _p(idx[a:b]), _p(dist[a:b]), _p(ws),
+           nbytes, _stream())
+    return dist, idx

@@ -10,8 +10,8 @@ import os
 import numpy as np
 import torch
 
-from .data import (DeviceDataset, get_data, get_data_MNIST, get_data_device, get_data_MNIST_device, make_collage, save_dataset_MNIST,
-                   save_gen_images)
+from .data import (DeviceDataset, get_data, get_data_MNIST, get_data_device, get_data_MNIST_device, make_collage,
+                   normalisation_table, save_dataset_MNIST, save_gen_images)
 from .diffusion import Diffusion
 from .training import argument, diffusion_kwargs, ema_path, model_out_channels, progressive_distill, set_seed, train
 from .unet import UNet
@@ -81,6 +81,8 @@ def ddpm_run(params):
     data_keys = [k for k in DATA_KEYS if params.get(k) is not None]
     if params.get("distill") is not None:
         _distill_cfg(params)                                   # a malformed key fails here, not after the training
+    if params.get("eval_nearest") is not None:
+        _nearest_cfg(params)
     cwd = os.getcwd()
     modelpath = os.path.join(cwd, f"models/DDPM_Uncondtional_{name}_{v}/ckpt_{name}_{v}.pt")
     f_settings = _f_settings(params)
@@ -169,10 +171,14 @@ def ddpm_run(params):
     distill = None
     if params.get("distill") is not None:
         distill, gen_model, gen_kw = _distill(params, args, diffusion, gen_model, modelpath, name, seed, dataloader)
+    nearest_n = _nearest_cfg(params)["n"] if params.get("eval_nearest") is not None else 0
+    generated = []                                             # the first eval_nearest["n"] images of the set, uint8 as sampled
     for start in np.arange(0, params["gen_total"], params["gen_per_batch"]):
         fileno = np.arange(start, start + params["gen_per_batch"], 1)
         xg, _ = diffusion.sample(gen_model, n=params["gen_per_batch"], image_channels=args.image_channels, **gen_kw)
         save_gen_images(gen_dir, xg, fileno)
+        if start < nearest_n:
+            generated.append(xg[:nearest_n - start])
     make_collage(gen_dir, gen_dir, params["collage_n_per_image"], params["collage_n"], args.image_size)
     torch.cuda.empty_cache()
     gc.collect()
@@ -191,6 +197,11 @@ def ddpm_run(params):
     # margin, peak, batch, ...) plus "N" (default 16), the number of training images scored, in dataset order, on the same model
     if params.get("eval_equivariance"):
         out["equivariance"] = _eval_equivariance(params, args, diffusion, gen_model, run_dir, name, v, seed, dev_set)
+    # optional nearest training images: params["eval_nearest"] = {"n": ..., "k": ...} (k defaults to 5) searches the training set
+    # for the k nearest neighbours of the first n generated images, and of the first n training images (leave-one-out) as the
+    # baseline the distances are read against (DeviceDataset.nearest)
+    if params.get("eval_nearest") is not None:
+        out["nearest"] = _eval_nearest(params, args, torch.cat(generated), run_dir, name, v, dev_set)
     return out
 
 
@@ -218,6 +229,54 @@ def _distill(params, args, diffusion, model, modelpath, name, seed, device_loade
     path = distill_path(modelpath, cfg["end_steps"])
     torch.save(student.state_dict(), path)
     return {"rounds": rounds, "modelpath": path}, student, {"steps": rounds[-1]["chain"], "eta": 0.0}
+
+
+def _nearest_cfg(params):
+    cfg = params["eval_nearest"]
+    if not isinstance(cfg, dict) or set(cfg) - {"n", "k"} or "n" not in cfg:
+        raise ValueError(f"ddpm_run: eval_nearest needs n (and optionally k); got "
+                         f"{sorted(cfg) if isinstance(cfg, dict) else type(cfg).__name__}")
+    cfg = {"n": cfg["n"], "k": cfg.get("k", 5)}
+    for key, hi, why in (("n", params["gen_total"], "gen_total, the size of the generated set"), ("k", 16, "16")):
+        val = cfg[key]
+        if isinstance(val, bool) or not isinstance(val, (int, np.integer)) or not 1 <= val <= hi:
+            raise ValueError(f"ddpm_run: eval_nearest {key} must be an int in [1, {why}] (got {val!r})")
+        cfg[key] = int(val)
+    return cfg
+
+
+def _eval_nearest(params, args, generated, run_dir, name, v, dataset=None):
+    from .imageio_utils import save_images
+    cfg = _nearest_cfg(params)
+    n, k = cfg["n"], cfg["k"]
+    if dataset is None:                                        # the host loaders' data set, moved to the device once
+        host = _loader(name, args)[1]
+        dataset = (DeviceDataset.from_tensor_dataset(host, device=args.device) if name == "MNIST" else
+                   DeviceDataset.from_folder(args.dataset_path, args.image_size, device=args.device))
+    if not n <= len(dataset):
+        raise ValueError(f"ddpm_run: eval_nearest n must lie in [1, {len(dataset)}] (the training set's size; got {n})")
+    C = dataset.images.shape[1]
+    queries = generated[:n].to(dataset.device)
+    if dataset.images.dtype != torch.uint8:                    # a float store: the samples on its scale, as the loader maps pixels
+        queries = normalisation_table(C).to(dataset.device)[torch.arange(C, device=dataset.device).view(1, C, 1, 1), queries.long()]
+    dist, idx = dataset.nearest(queries, k)
+    own = torch.arange(n, device=dataset.device)
+    base_dist, base_idx = dataset.nearest(dataset.images[:n], k, exclude=own)
+    res = {"dist": dist.cpu().numpy(), "idx": idx.cpu().numpy(), "baseline_dist": base_dist.cpu().numpy(),
+           "baseline_idx": base_idx.cpu().numpy()}
+    np.savez(os.path.join(run_dir, f"nearest_{name}_{v}.npz"), **res)
+    # one row per sample: the sample, then its k neighbours (a slot with no neighbour left is black)
+    rows = torch.where(idx < 0, torch.arange(n, device=idx.device).view(n, 1) - n, idx)
+    pool = torch.cat([dataset.images, dataset.images.new_zeros((n,) + tuple(dataset.images.shape[1:]))])
+    neigh = pool[rows.reshape(-1)]
+    if neigh.dtype != torch.uint8:                             # back to pixels, as the samplers do: (x clamped to [-1, 1] + 1) / 2 * 255
+        neigh = ((neigh.clamp(-1, 1) + 1) / 2 * 255).to(torch.uint8)
+    neigh = neigh.view(n, k, *neigh.shape[1:])
+    grid = torch.cat([generated[:n].to(neigh.device).unsqueeze(1), neigh], dim=1).reshape(n * (k + 1), *neigh.shape[2:])
+    save_images(grid.cpu(), os.path.join(run_dir, f"nearest_{name}_{v}.jpg"), nrow=k + 1)
+    print(f"nearest: median distance {np.median(res['dist'][:, 0]):.6g} (samples), {np.median(res['baseline_dist'][:, 0]):.6g} "
+          f"(training images, leave-one-out)")
+    return res
 
 
 def _eval_bpd(params, args, diffusion, model, run_dir, name, v, seed, dataset=None):

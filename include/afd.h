@@ -762,6 +762,31 @@ int afd_batch_gather_u8(const uint8_t* data, long N, long C, long H, long W, con
 int afd_batch_gather_f32(const float* data, long N, long C, long H, long W, const int64_t* idx, const uint8_t* flip_or_null,
                          float* x, const int64_t* labels_or_null, int64_t* y_or_null, long B, afd_stream_t stream);
 
+/* ---- nearest store rows of a set of queries (csrc/nearest.hip) ------------------------------- data.DeviceDataset.nearest
+ * data is a contiguous (N, D) store, queries n rows of the same D and element type, 1 <= k <= 16, exclude NULL or n int64:
+ * query q skips store row exclude[q] (a negative value skips nothing).  For query q, idx[q * k + t] and dist[q * k + t], t = 0 ..
+ * k - 1, are the k store rows of smallest squared L2 distance, ascending; ties go to the lower store index, so the order is total
+ * and the result depends on no tiling, partition or launch order.  A slot with no candidate left (k exceeds the rows available)
+ * holds idx -1 and dist -1 (u8) / +inf (f32).
+ *     u8:   dist = sum_j (a_j - b_j)^2 in pixel units, exact, int64.  D <= 32768, so that int32 holds every partial sum: with
+ *           a' = a - 128 (byte ^ 0x80 as int8) the sum is sum a'^2 + sum b'^2 - 2 sum a'b', the cross term on the i8 matrix pipe.
+ *     f32:  dist = sum_j ((double)a_j - (double)b_j)^2 summed in fp64 and rounded once to fp32, ranked by (its bits, index); a NaN
+ *           distance is reported as the canonical quiet NaN (0x7fc00000) and ranks after +inf, by index.
+ * Each search workgroup leaves the k smallest (distance bits << 32 | index) keys of its chunk of the store in the workspace, a
+ * second kernel merges the chunks: two launches on `stream`, no allocation, no host synchronisation, no memset (the workspace
+ * needs no initial contents), so a call can be captured into a graph.  afd_nn_search_workspace_bytes: the bytes one call needs
+ * (at most 512 n k 8; 0 for sizes the search rejects).  u8 data and queries need no alignment: a D that is no multiple of 16, or a
+ * pointer that is not 16-byte aligned, takes byte loads instead of 16-byte ones, with the same result.
+ * AFD_EINVAL (nothing launched) on a NULL data / queries / idx / dist / workspace, N, D or n <= 0, k outside [1, 16], D > 32768
+ * (u8), N or n >= 2^31, idx / exclude / workspace not 8-byte aligned, dist not aligned to its element, f32 data / queries not
+ * 4-byte aligned, a workspace smaller than afd_nn_search_workspace_bytes, or idx / dist / workspace overlapping an input or each
+ * other. */
+size_t afd_nn_search_workspace_bytes(long N, long D, long n, long k, int f32);
+int afd_nn_search_u8(const uint8_t* data, long N, long D, const uint8_t* queries, long n, const int64_t* exclude_or_null, long k,
+                     int64_t* idx, int64_t* dist, void* workspace, size_t workspace_bytes, afd_stream_t stream);
+int afd_nn_search_f32(const float* data, long N, long D, const float* queries, long n, const int64_t* exclude_or_null, long k,
+                      int64_t* idx, float* dist, void* workspace, size_t workspace_bytes, afd_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
