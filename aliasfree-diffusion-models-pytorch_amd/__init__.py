@@ -11,13 +11,15 @@ from .filters import circularLowpassKernel, custom_downsample, custom_upsample  
 from .blocks import (SelfAttention, DoubleConv, DoubleConv_F, DoubleConv_F4, Down, Down_F, Down_FF, Down_FFF,  # noqa: F401
                      Down_F4, Up, Up_F, Up_FF, Up_FFF, Up_F4)
 from .ops import NULL_LABEL, nn_search  # noqa: F401
+from .spectrum import compare_spectra, hann_window, power_spectrum, spectrum_bins  # noqa: F401
 from .unet import UNet  # noqa: F401
 from .diffusion import Diffusion  # noqa: F401
 from .training import (argument, set_seed, setup_logging, train, TrainStep, FusedAdamW, FlatParams,  # noqa: F401
                        GradAllReduce, EMA, LRSchedule, clip_coefficient, DistillStep, progressive_distill,
                        LossSecondMomentSampler)
 
-from .tasks import bpd_results, ddpm_run, equivariance_results, inpaint_results, rotation_results, shift_results  # noqa: F401
+from .tasks import (bpd_results, ddpm_run, equivariance_results, inpaint_results, rotation_results, shift_results,  # noqa: F401
+                    spectrum_results)
 from .data import (get_data, get_data_MNIST, save_gen_images, make_collage, DeviceDataset, DeviceLoader,  # noqa: F401
                    get_data_device, get_data_MNIST_device)
 

@@ -108,7 +108,8 @@ class DeviceDataset:
     are then unused).  labels: None or (N,) int64.  `.images`, `.labels`, `.table` live on `device`.
     device="cpu" runs `batch` as plain torch indexing: the same values, and the oracle of the kernels' tests.
     `nearest` / `self_nearest` search the store for the nearest images of a set of queries; on
-    device="cpu" they are a plain torch brute force, the oracle of that kernel's tests."""
+    device="cpu" they are a plain torch brute force, the oracle of that kernel's tests.
+    `power_spectrum` is the mean power spectrum of the store's images."""
 
     def __init__(self, images, labels=None, mean=0.5, std=0.5, device="cuda", classes=None):
         if isinstance(images, np.ndarray):
@@ -210,6 +211,15 @@ class DeviceDataset:
         own = torch.arange(len(self), device=self.device)
         parts = [self.nearest(self.images[a:a + batch], k, own[a:a + batch]) for a in range(0, len(self), int(batch))]
         return torch.cat([p[0] for p in parts]), torch.cat([p[1] for p in parts])
+
+    def power_spectrum(self, window="hann", remove_mean=True, n=None):
+        """The mean power spectrum of the first n images of the store (None: all of them), read through the store's own table:
+        spectrum.power_spectrum's dict (afd_power_spectrum_u8 / _f32 on the device, plain torch on device="cpu"; DESIGN.md
+        section 6p)."""
+        from .spectrum import power_spectrum
+        if n is not None and (isinstance(n, bool) or not isinstance(n, (int, np.integer)) or not 1 <= n <= len(self)):
+            raise ValueError(f"DeviceDataset.power_spectrum: n must be None or an int in [1, {len(self)}] (got {n!r})")
+        return power_spectrum(self.images if n is None else self.images[:int(n)], self.table, window, remove_mean)
 
     def _nearest_torch(self, queries, k, exclude):
         """Brute force in plain torch: int64 sums of squared differences (uint8) or fp64 sums rounded once to float32, then a stable

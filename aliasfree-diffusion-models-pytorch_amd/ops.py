@@ -1955,3 +1955,51 @@ def nn_search(data, queries, k=1, exclude=None):
         fn(_p(data), N, D, _p(qflat[a:b]), b - a, None if exclude is None else _p(exclude[a:b]), k, _p(idx[a:b]), _p(dist[a:b]), _p(ws),
            nbytes, _stream())
     return dist, idx
+
+
+SPECTRUM_MAX_SIDE = 64
+
+
+def power_spectrum(images, table=None, win_h=None, win_w=None, remove_mean=True, bins=None, R=None, want_power=True):
+    """Mean power spectrum of a set of images in fp64 (afd.h: afd_power_spectrum_u8 / _f32).  images (n, C, H, W) uint8 (read
+    through table (C, 256) fp32) or fp32, contiguous, on the device, H and W at most 64; win_h (H,) / win_w (W,) fp64 or None (1);
+    remove_mean: subtract each plane's own mean first; bins (H, W // 2 + 1) int32 with values in [-1, R) and R: the radial sums are
+    wanted; want_power: the (C, H, W // 2 + 1) spectrum is wanted.  -> (power or None, radial (C, R) or None), fresh fp64 tensors:
+    radial[c][r] is the SUM of m(v) power[c][u][v] over bins == r, for the caller to divide by its counts."""
+    what = "power_spectrum"
+    if not isinstance(images, torch.Tensor) or not images.is_cuda or images.dim() != 4 or not images.is_contiguous() or images.numel() == 0 \
+            or images.dtype not in (torch.uint8, torch.float32):
+        raise AfdError(f"afdm: {what}: images must be a non-empty contiguous (n, C, H, W) uint8 or fp32 device tensor")
+    n, C, H, W = images.shape
+    if not (1 <= H <= SPECTRUM_MAX_SIDE and 1 <= W <= SPECTRUM_MAX_SIDE):
+        raise AfdError(f"afdm: {what}: H and W must lie in [1, {SPECTRUM_MAX_SIDE}] (got {H}, {W})")
+    u8 = images.dtype == torch.uint8
+    if u8:
+        _dev_table(what, "table", table, torch.float32, (C, 256))
+    elif table is not None:
+        raise AfdError(f"afdm: {what}: table goes with uint8 images only")
+    if win_h is not None:
+        _dev_table(what, "win_h", win_h, torch.float64, (H,))
+    if win_w is not None:
+        _dev_table(what, "win_w", win_w, torch.float64, (W,))
+    Wh = W // 2 + 1
+    if (bins is None) != (R is None):
+        raise AfdError(f"afdm: {what}: bins and R go together")
+    if bins is None and not want_power:
+        raise AfdError(f"afdm: {what}: nothing to compute (want_power is False and no bins are given)")
+    if bins is not None:
+        _dev_table(what, "bins", bins, torch.int32, (H, Wh))
+        if isinstance(R, bool) or not isinstance(R, int) or R < 1:
+            raise AfdError(f"afdm: {what}: R must be an int >= 1 (got {R!r})")
+    nbytes = int(lib().afd_spectrum_workspace_bytes(n, C, H, W))
+    if nbytes <= 0:
+        raise AfdError(f"afdm: {what}: sizes out of range (n = {n}, C = {C}, H = {H}, W = {W})")
+    power = torch.empty(C, H, Wh, device=images.device, dtype=torch.float64) if want_power else None
+    radial = torch.empty(C, R, device=images.device, dtype=torch.float64) if bins is not None else None
+    ws = torch.empty(nbytes // 8, device=images.device, dtype=torch.float64)
+    tail = (n, C, H, W, _p(win_h), _p(win_w), int(bool(remove_mean)), _p(bins), R or 0, _p(power), _p(radial), _p(ws), nbytes, _stream())
+    if u8:
+        lib().afd_power_spectrum_u8(_p(images), _p(table), *tail)
+    else:
+        lib().afd_power_spectrum_f32(_p(images), *tail)
+    return power, radial

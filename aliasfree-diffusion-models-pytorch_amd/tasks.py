@@ -83,6 +83,8 @@ def ddpm_run(params):
         _distill_cfg(params)                                   # a malformed key fails here, not after the training
     if params.get("eval_nearest") is not None:
         _nearest_cfg(params)
+    if params.get("eval_spectrum") is not None:
+        _spectrum_cfg(params)
     cwd = os.getcwd()
     modelpath = os.path.join(cwd, f"models/DDPM_Uncondtional_{name}_{v}/ckpt_{name}_{v}.pt")
     f_settings = _f_settings(params)
@@ -172,13 +174,15 @@ def ddpm_run(params):
     if params.get("distill") is not None:
         distill, gen_model, gen_kw = _distill(params, args, diffusion, gen_model, modelpath, name, seed, dataloader)
     nearest_n = _nearest_cfg(params)["n"] if params.get("eval_nearest") is not None else 0
-    generated = []                                             # the first eval_nearest["n"] images of the set, uint8 as sampled
+    spectrum_n = _spectrum_cfg(params)["n"] if params.get("eval_spectrum") is not None else 0
+    keep_n = max(nearest_n, spectrum_n)
+    generated = []                                             # the first images of the set that an evaluation asks for, uint8 as sampled
     for start in np.arange(0, params["gen_total"], params["gen_per_batch"]):
         fileno = np.arange(start, start + params["gen_per_batch"], 1)
         xg, _ = diffusion.sample(gen_model, n=params["gen_per_batch"], image_channels=args.image_channels, **gen_kw)
         save_gen_images(gen_dir, xg, fileno)
-        if start < nearest_n:
-            generated.append(xg[:nearest_n - start])
+        if start < keep_n:
+            generated.append(xg[:keep_n - start])
     make_collage(gen_dir, gen_dir, params["collage_n_per_image"], params["collage_n"], args.image_size)
     torch.cuda.empty_cache()
     gc.collect()
@@ -202,6 +206,10 @@ def ddpm_run(params):
     # baseline the distances are read against (DeviceDataset.nearest)
     if params.get("eval_nearest") is not None:
         out["nearest"] = _eval_nearest(params, args, torch.cat(generated), run_dir, name, v, dev_set)
+    # optional power spectra: params["eval_spectrum"] = {"n": ..., "window": "hann" | None} sets the mean power spectrum of the first
+    # n generated images against that of the first n training images (spectrum.power_spectrum / compare_spectra)
+    if params.get("eval_spectrum") is not None:
+        out["spectrum"] = _eval_spectrum(params, args, torch.cat(generated), run_dir, name, v, dev_set)
     return out
 
 
@@ -245,14 +253,20 @@ def _nearest_cfg(params):
     return cfg
 
 
+def _training_store(name, args, dataset=None):
+    """The run's DeviceDataset, or the host loaders' data set moved to the device once."""
+    if dataset is not None:
+        return dataset
+    host = _loader(name, args)[1]
+    return (DeviceDataset.from_tensor_dataset(host, device=args.device) if name == "MNIST" else
+            DeviceDataset.from_folder(args.dataset_path, args.image_size, device=args.device))
+
+
 def _eval_nearest(params, args, generated, run_dir, name, v, dataset=None):
     from .imageio_utils import save_images
     cfg = _nearest_cfg(params)
     n, k = cfg["n"], cfg["k"]
-    if dataset is None:                                        # the host loaders' data set, moved to the device once
-        host = _loader(name, args)[1]
-        dataset = (DeviceDataset.from_tensor_dataset(host, device=args.device) if name == "MNIST" else
-                   DeviceDataset.from_folder(args.dataset_path, args.image_size, device=args.device))
+    dataset = _training_store(name, args, dataset)
     if not n <= len(dataset):
         raise ValueError(f"ddpm_run: eval_nearest n must lie in [1, {len(dataset)}] (the training set's size; got {n})")
     C = dataset.images.shape[1]
@@ -276,6 +290,49 @@ def _eval_nearest(params, args, generated, run_dir, name, v, dataset=None):
     save_images(grid.cpu(), os.path.join(run_dir, f"nearest_{name}_{v}.jpg"), nrow=k + 1)
     print(f"nearest: median distance {np.median(res['dist'][:, 0]):.6g} (samples), {np.median(res['baseline_dist'][:, 0]):.6g} "
           f"(training images, leave-one-out)")
+    return res
+
+
+def _spectrum_cfg(params):
+    cfg = params["eval_spectrum"]
+    if not isinstance(cfg, dict) or set(cfg) - {"n", "window"} or "n" not in cfg:
+        raise ValueError(f"ddpm_run: eval_spectrum needs n (and optionally window); got "
+                         f"{sorted(cfg) if isinstance(cfg, dict) else type(cfg).__name__}")
+    n, window = cfg["n"], cfg.get("window", "hann")
+    if isinstance(n, bool) or not isinstance(n, (int, np.integer)) or not 1 <= n <= params["gen_total"]:
+        raise ValueError(f"ddpm_run: eval_spectrum n must be an int in [1, gen_total, the size of the generated set] (got {n!r})")
+    if window is not None and window != "hann":
+        raise ValueError(f"ddpm_run: eval_spectrum window must be 'hann' or None (got {window!r})")
+    if params.get("image_size") is not None and not 1 <= params["image_size"] <= 64:
+        raise ValueError(f"ddpm_run: eval_spectrum takes images of at most 64 x 64 (image_size is {params['image_size']})")
+    return {"n": int(n), "window": window}
+
+
+def _spectrum_pair(train, generated, window, remove_mean=True):
+    """The spectra of a DeviceDataset's first images and of as many generated uint8 images, and their comparison, as numpy arrays.
+    A uint8 store and the samples go through the store's table; beside a float store the samples go through normalisation_table,
+    as the loader maps pixels."""
+    from .spectrum import compare_spectra, power_spectrum
+    n, C = generated.shape[0], generated.shape[1]
+    ref = train.power_spectrum(window=window, remove_mean=remove_mean, n=n)
+    table = train.table if train.table is not None else normalisation_table(C)
+    gen = power_spectrum(generated.to(train.device), table, window=window, remove_mean=remove_mean)
+    db, lsd, hf_ratio = compare_spectra(ref, gen)
+    return {"power_train": ref["power"].cpu().numpy(), "power_gen": gen["power"].cpu().numpy(), "radial_train": ref["radial"].cpu().numpy(),
+            "radial_gen": gen["radial"].cpu().numpy(), "counts": ref["counts"].cpu().numpy(), "db": db.numpy(), "lsd": np.float64(lsd),
+            "hf_ratio": np.float64(hf_ratio)}
+
+
+def _eval_spectrum(params, args, generated, run_dir, name, v, dataset=None):
+    cfg = _spectrum_cfg(params)
+    n = cfg["n"]
+    dataset = _training_store(name, args, dataset)
+    if not n <= len(dataset):
+        raise ValueError(f"ddpm_run: eval_spectrum n must lie in [1, {len(dataset)}] (the training set's size; got {n})")
+    res = _spectrum_pair(dataset, generated[:n], cfg["window"])
+    np.savez(os.path.join(run_dir, f"spectrum_{name}_{v}.npz"), **res)
+    print(f"spectrum: log-spectral distance {res['lsd']:.4f} dB, high-frequency energy ratio {res['hf_ratio']:.4f} "
+          f"({n} samples against {n} training images)")
     return res
 
 
@@ -355,6 +412,20 @@ def bpd_results(model_data, images, **kw):
     model, diffusion, _ = _load(model_data)
     set_seed(model_data["seed"])
     return diffusion.calc_bpd(model, images, **kw)
+
+
+def spectrum_results(model_data, images, n, window="hann", remove_mean=True, **kw):
+    """Load the checkpoint as rotation_results does, seed, draw n samples (Diffusion.sample; **kw: steps, eta, sampler, ...) and set
+    their mean power spectrum against that of the first n of `images`: a DeviceDataset, or (N, C, H, W) uint8 pixels or float32
+    values on the loader's scale.  Returns the arrays ddpm_run writes for params["eval_spectrum"]: power_train, power_gen,
+    radial_train, radial_gen, counts, db, lsd, hf_ratio."""
+    if isinstance(n, bool) or not isinstance(n, (int, np.integer)) or not 1 <= n <= len(images):
+        raise ValueError(f"spectrum_results: n must be an int in [1, {len(images)}] (the number of images; got {n!r})")
+    model, diffusion, args = _load(model_data)
+    train = images if isinstance(images, DeviceDataset) else DeviceDataset(images[:n], device=args.device)
+    set_seed(model_data["seed"])
+    x, _ = diffusion.sample(model, n=int(n), image_channels=args.image_channels, **kw)
+    return _spectrum_pair(train, x, window, remove_mean)
 
 
 def equivariance_results(model_data, images, **kw):

@@ -787,6 +787,37 @@ int afd_nn_search_u8(const uint8_t* data, long N, long D, const uint8_t* queries
 int afd_nn_search_f32(const float* data, long N, long D, const float* queries, long n, const int64_t* exclude_or_null, long k,
                       int64_t* idx, float* dist, void* workspace, size_t workspace_bytes, afd_stream_t stream);
 
+/* ---- mean power spectrum of a set of images, in fp64 (csrc/spectrum.hip) ----------------------- spectrum.power_spectrum
+ * images is a contiguous (n, C, H, W) set, 1 <= H, W <= 64 (odd and non-square planes included), of uint8 pixels read through
+ * table (C, 256) floats (data.normalisation_table) or of floats taken as they are; every value is widened to double and everything
+ * after that is fp64.  Per plane: remove_mean != 0 subtracts the plane's own mean, then the plane is multiplied by
+ * win_h[y] * win_w[x] (either pointer may be NULL: 1), and F = its 2-D DFT in numpy's convention and rfft2 layout, u in [0, H),
+ * v in [0, Wh), Wh = W / 2 + 1.
+ *     power[c][u][v] = (1 / n) sum_i |F_{i,c}[u][v]|^2                                                   (C, H, Wh)
+ *     radial[c][r]   = sum over (u, v) with bins[u][v] == r of m(v) power[c][u][v]                       (C, R)
+ * m(v) = 1 for v = 0 and, for an even W, v = W / 2, else 2 (the mirrored half of the full spectrum); bins is (H, Wh) int32 with
+ * values in [-1, R), -1 leaves a coefficient out.  radial is a weighted SUM: the caller divides by its counts.  Either of power
+ * and radial may be NULL, not both; bins and R are read only when radial is given.  A NaN or an infinity in a plane propagates
+ * to its channel's outputs; nothing is clamped.
+ * The DFT is two matrix products on the fp64 matrix pipe with twiddles looked up at (j k) mod N in a table of cos and sin of
+ * 2 pi m / N built in fp64 from an integer quadrant and remainder.  Workgroup (slice, channel) sums |F|^2 over its images in
+ * registers and leaves one partial in the workspace; a second kernel folds the partials in a fixed tree, divides by n once and
+ * reduces radial in a fixed order: two launches on `stream`, no atomics, no allocation, no memset (the workspace needs no initial
+ * contents), no synchronisation, so a call can be captured into a graph and repeats bit for bit.  The number of slices depends
+ * on (n, C) alone.  afd_spectrum_workspace_bytes: the bytes one call needs (at most 768 H Wh 8 for C <= 768; 0 for sizes the
+ * call rejects).
+ * AFD_EINVAL (nothing launched) on a NULL images / workspace / table (u8), power and radial both NULL, radial without bins or
+ * with R <= 0, n or C <= 0, H or W outside [1, 64], n >= 2^31, C >= 2^31 or n C > 2^40, power / radial / win_h / win_w /
+ * workspace not 8-byte aligned, bins / table / f32 images not 4-byte aligned, a workspace smaller than
+ * afd_spectrum_workspace_bytes, or power / radial / workspace overlapping an input or each other. */
+size_t afd_spectrum_workspace_bytes(long n, long C, long H, long W);
+int afd_power_spectrum_u8(const uint8_t* images, const float* table, long n, long C, long H, long W, const double* win_h_or_null,
+                          const double* win_w_or_null, int remove_mean, const int* bins_or_null, long R, double* power_or_null,
+                          double* radial_or_null, void* workspace, size_t workspace_bytes, afd_stream_t stream);
+int afd_power_spectrum_f32(const float* images, long n, long C, long H, long W, const double* win_h_or_null,
+                           const double* win_w_or_null, int remove_mean, const int* bins_or_null, long R, double* power_or_null,
+                           double* radial_or_null, void* workspace, size_t workspace_bytes, afd_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
