@@ -6,6 +6,7 @@ the reference; noise_images / the denoise update / the uint8 quantisation are bi
 restatements (csrc/sampler.hip).  The sampling loop stays on the device: no per-step H2D copy of `t`
 (the reference does one per step, :362) and no per-step host sync.
 """
+import contextlib
 import logging
 import math
 
@@ -249,23 +250,13 @@ class Diffusion:
             if int(kh.min()) < 0 or int(kh.max()) >= tabs[0].numel():
                 raise ValueError(f"Diffusion.distill_targets: every step index must lie in [0, {tabs[0].numel()}) (got {kh.tolist()})")
             t, t_mid, t_prev = (tab[kh].to(x0.device).contiguous() for tab in tabs)
-        was_training = teacher.training
-        hinted = hasattr(teacher, "_t_range")
-        t_range = getattr(teacher, "_t_range", None)
-        self._hint(teacher)
-        try:
-            teacher.eval()
-            with torch.no_grad():
-                x0 = x0.contiguous()
-                z_t, _ = self.noise_images(x0, t, eps)
-                out1 = self._raw_output(teacher, z_t, t, y)
-                z_mid = ops.distill_mid(out1, z_t, t, t_mid, self.alpha_hat, self.prediction)
-                out2 = self._raw_output(teacher, z_mid, t_mid, y)
-                x_tilde, eps_tilde = ops.distill_target(out2, z_mid, z_t, t, t_mid, t_prev, self.alpha_hat, self.prediction)
-        finally:
-            teacher.train(was_training)
-            if hinted:
-                teacher._t_range = t_range
+        with self._model_scope(teacher, leave_training=False):
+            x0 = x0.contiguous()
+            z_t, _ = self.noise_images(x0, t, eps)
+            out1 = self._raw_output(teacher, z_t, t, y)
+            z_mid = ops.distill_mid(out1, z_t, t, t_mid, self.alpha_hat, self.prediction)
+            out2 = self._raw_output(teacher, z_mid, t_mid, y)
+            x_tilde, eps_tilde = ops.distill_target(out2, z_mid, z_t, t, t_mid, t_prev, self.alpha_hat, self.prediction)
         return x_tilde, eps_tilde, t
 
     # F14 ---------------------------------------------------------------------------------
@@ -312,6 +303,17 @@ class Diffusion:
             z = torch.randn(shape, device=x.device)
         return z if shard is None else z[shard[0]:shard[1]].contiguous()
 
+    def _chunk_noise(self, shape, noise_source, noise_fn=None):
+        """The fp32 noise of one chunk of rows of `calc_bpd` / `equivariance`, on the device: noise_fn(shape) when given, else
+        drawn from the device generator (noise_source "device") or from the CPU generator and copied ("cpu")."""
+        if noise_fn is not None:
+            eps = noise_fn(shape)
+        elif noise_source == "device":
+            eps = torch.randn(shape, device=self.device)
+        else:
+            eps = torch.randn(shape).to(self.device)
+        return eps.to(device=self.device, dtype=torch.float32).contiguous()
+
     def _loop(self, model, n, image_channels, theta=None, noise_source="reference", graph=None, shard=None, labels=None,
               cfg_scale=0.0):
         """Shared body of sample / revert.  noise_source: 'reference' (x_T from the CPU generator,
@@ -323,65 +325,46 @@ class Diffusion:
         with or without replay), not by host launches.
         labels: (n,) int64 device tensor (checked by `sample`) or None.  With labels and cfg_scale > 0 (classifier-free
         guidance) every step runs ONE forward over 2n rows [x ; x] with labels [labels ; NULL_LABEL] and the fused guided
-        update writes both halves of the next 2n input; the noise drawn is that of n images, as without labels."""
+        update writes both halves of that 2n-row state in place; the noise drawn is that of n images, as without labels.
+        The state lives in xs (n rows, or those 2n) and one local `step` serves the eager iterations and the capture."""
         theta_step = None if theta is None else theta / self.noise_steps
-        if graph is None:
-            graph = False
         self.check_model(model, image_channels, "Diffusion.sample")
         learned = self.variance == "learned"
-        self._hint(model)
-        model.eval()
+        forward = self._raw_output if learned else self.predict_eps      # learned: the raw 2C output goes to the update
         snaps = []
-        with torch.no_grad():
+        with self._model_scope(model):
             x = self._initial_noise(n, image_channels, noise_source, shard)
             n_all, n = n, x.shape[0]
-            guided = labels is not None and cfg_scale > 0
-            y = labels
-            if guided:                                   # built once per trajectory
-                y = torch.cat([labels, torch.full_like(labels, ops.NULL_LABEL)])
+            y, s = self._guided(labels, cfg_scale)
+            xs = torch.cat([x, x]) if s > 0 else x
+            rows = xs.shape[0]
+
+            def step(t_rows, t, draw):
+                out = forward(model, xs, t_rows, y)
+                self._update(xs, n, out, draw() if draw else None, t, learned=learned, cfg_scale=s)
+
+            replay = None
             if graph and theta is None and noise_source != "cpu" and shard is None:
-                x = self._graph_steps(model, x, snaps, y, cfg_scale if guided else 0.0)
-                first_eager = 1
-            else:
-                first_eager = self.noise_steps - 1
-            xs2 = torch.cat([x, x]) if guided else None
-            for i in reversed(range(1, first_eager + 1)):
-                if n == 0:                               # an empty shard still consumes the shared noise stream
+                t_dev = torch.full((rows,), self.noise_steps - 1, device=x.device, dtype=torch.long)
+                g = self._capture(lambda: step(t_dev, t_dev, lambda: torch.randn_like(xs[:n])), xs)
+
+                def replay(i):
+                    t_dev.fill_(i)
+                    g.replay()
+            for i in reversed(range(1, self.noise_steps)):
+                if n == 0:                                   # an empty shard still consumes the shared noise stream
                     if i > 1:
                         self._step_noise(x, noise_source, shard, n_all)
-                    if i % 100 == 0:
-                        snaps.append(x)
-                    continue
-                if guided:
-                    t2 = self._t_full(2 * n, i, x.device)
-                    eps2 = self._raw_output(model, xs2, t2, y) if learned else self.predict_eps(model, xs2, t2, y)
-                    noise = self._step_noise(x, noise_source, shard, n_all) if i > 1 else None
-                    nxt = torch.empty_like(xs2)
-                    if learned:
-                        ops.denoise_step_lvar_cfg(x, eps2, noise, self.alpha, self.alpha_hat, self.beta, self._lv(), self.prediction, i,
-                                                  cfg_scale, nxt[:n], nxt[n:])
-                    else:
-                        ops.denoise_step_cfg(x, eps2, noise, self.alpha, self.alpha_hat, self.beta, i, cfg_scale, nxt[:n], nxt[n:])
-                    xs2, x = nxt, nxt[:n]
-                    if i % 100 == 0:
-                        snaps.append(x)
-                    continue
-                t = self._t_full(n, i, x.device)
-                if learned:
-                    out2 = self._raw_output(model, x, t, y)
-                    noise = self._step_noise(x, noise_source, shard, n_all) if i > 1 else None
-                    x = ops.denoise_step_lvar(x.contiguous(), out2, noise, self.alpha, self.alpha_hat, self.beta, self._lv(),
-                                              self.prediction, i)
+                elif replay is not None and i > 1:           # the last step draws no noise: it runs eagerly
+                    replay(i)
                 else:
-                    eps = self.predict_eps(model, x, t, y)
-                    noise = self._step_noise(x, noise_source, shard, n_all) if i > 1 else None
-                    x = ops.denoise_step(x, eps, noise, self.alpha, self.alpha_hat, self.beta, i)
-                if theta_step is not None:
-                    x = self.rotate_2d_matrix(x, theta_step, self.filter)
+                    step(self._t_full(rows, i, x.device), i,
+                         (lambda: self._step_noise(xs[:n], noise_source, shard, n_all)) if i > 1 else None)
+                    if theta_step is not None:
+                        xs = self.rotate_2d_matrix(xs, theta_step, self.filter)
                 if i % 100 == 0:
-                    snaps.append(x)
-        model.train()        # the reference leaves the model in train mode (:379)
-        self._unhint(model)
+                    snaps.append(xs[:n].clone())
+            x = xs[:n].clone()
         snaps.append(x)
         return x, snaps
 
@@ -432,83 +415,39 @@ class Diffusion:
     def _ddim_loop(self, model, n, image_channels, pairs, eta, noise_source="reference", graph=None, labels=None, cfg_scale=0.0):
         """`_loop` over the DDIM steps `pairs` (see `sample`).  x_T is drawn as in `_loop`; with eta > 0 every step but the
         last draws the noise of n images (`_step_noise`), with eta == 0 none is drawn.  graph: capture one step (forward,
-        noise, ddim_step_dev) and replay it for every step but the last, which runs eagerly."""
-        self._hint(model)
-        try:
-            model.eval()
-            snaps = []
-            with torch.no_grad():
-                x = self._initial_noise(n, image_channels, noise_source)
-                guided = labels is not None and cfg_scale > 0
-                y = labels
-                if guided:
-                    y = torch.cat([labels, torch.full_like(labels, ops.NULL_LABEL)])
-                first = 0
-                if graph and noise_source != "cpu" and len(pairs) > 1:
-                    x = self._ddim_graph_steps(model, x, snaps, pairs[:-1], eta, y, cfg_scale if guided else 0.0)
-                    first = len(pairs) - 1
-                xs2 = torch.cat([x, x]) if guided else None
-                for t, tp in pairs[first:]:
-                    draw = eta > 0 and tp > 0
-                    if guided:
-                        eps2 = self.predict_eps(model, xs2, self._t_full(2 * n, t, x.device), y)
-                        noise = self._step_noise(x, noise_source) if draw else None
-                        nxt = torch.empty_like(xs2)
-                        ops.ddim_step_cfg(x, eps2, noise, self.alpha_hat, t, tp, eta, cfg_scale, nxt[:n], nxt[n:])
-                        xs2, x = nxt, nxt[:n]
-                    else:
-                        tt = self._t_full(n, t, x.device)
-                        eps = self.predict_eps(model, x, tt, y)
-                        noise = self._step_noise(x, noise_source) if draw else None
-                        x = ops.ddim_step(x, eps, noise, self.alpha_hat, t, tp, eta)
-                    if self.ddim_snapshot(t, tp):
-                        snaps.append(x)
-        finally:
-            model.train()
-            self._unhint(model)
+        noise, the update with t and t_prev read on the device) and replay it for every step but the last, which runs eagerly."""
+        snaps = []
+        with self._model_scope(model):
+            x = self._initial_noise(n, image_channels, noise_source)
+            y, s = self._guided(labels, cfg_scale)
+            xs = torch.cat([x, x]) if s > 0 else x
+            rows = xs.shape[0]
+
+            def step(t_rows, t, tp, draw):
+                eps = self.predict_eps(model, xs, t_rows, y)
+                self._update(xs, n, eps, draw() if draw else None, t, tp, eta=eta, cfg_scale=s)
+
+            replay = None
+            if graph and noise_source != "cpu" and len(pairs) > 1:
+                t_dev = torch.full((rows,), pairs[0][0], device=x.device, dtype=torch.long)
+                tp_dev = torch.full((1,), pairs[0][1], device=x.device, dtype=torch.long)
+                g = self._capture(lambda: step(t_dev, t_dev, tp_dev, (lambda: torch.randn_like(xs[:n])) if eta > 0 else None), xs)
+
+                def replay(t, tp):
+                    t_dev.fill_(t)
+                    tp_dev.fill_(tp)
+                    g.replay()
+            for t, tp in pairs:
+                if replay is not None and tp > 0:
+                    replay(t, tp)
+                else:
+                    step(self._t_full(rows, t, x.device), t, tp,
+                         (lambda: self._step_noise(xs[:n], noise_source)) if eta > 0 and tp > 0 else None)
+                if self.ddim_snapshot(t, tp):
+                    snaps.append(xs[:n].clone())
+            x = xs[:n].clone()
         snaps.append(x)
         return x, snaps
-
-    def _ddim_graph_steps(self, model, x, snaps, pairs, eta, y=None, cfg_scale=0.0):
-        """The DDIM steps `pairs` (all but the chain's last) by replaying one captured step; t_dev (the forward's rows) and
-        t_prev_dev are filled on the host before each replay.  Returns x after the last of them."""
-        n = x.shape[0]
-        guided = cfg_scale > 0
-        noisy = eta > 0
-        t_dev = torch.full((2 * n if guided else n,), pairs[0][0], device=x.device, dtype=torch.long)
-        tp_dev = torch.full((1,), pairs[0][1], device=x.device, dtype=torch.long)
-        xs = torch.cat([x, x]) if guided else x.clone()
-        xh = xs[:n]
-
-        def one_step():
-            if guided:
-                eps2 = self.predict_eps(model, xs, t_dev, y)
-                noise = torch.randn_like(xh) if noisy else None
-                ops.ddim_step_cfg_dev(xh, eps2, noise, self.alpha_hat, t_dev, tp_dev, eta, cfg_scale, xh, xs[n:])
-                return
-            eps = self.predict_eps(model, xs, t_dev, y)
-            noise = torch.randn_like(xs) if noisy else None
-            ops.ddim_step_dev(xs, eps, noise, self.alpha_hat, t_dev, tp_dev, eta, xs)            # in place (elementwise)
-
-        side = torch.cuda.Stream()
-        side.wait_stream(torch.cuda.current_stream())
-        keep = xs.clone()
-        rng = torch.cuda.get_rng_state(x.device)
-        with torch.cuda.stream(side):
-            one_step()                                   # warm-up; its effect (and its noise draw) is undone below
-        torch.cuda.current_stream().wait_stream(side)
-        xs.copy_(keep)
-        torch.cuda.set_rng_state(rng, x.device)
-        g = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(g):
-            one_step()
-        for t, tp in pairs:
-            t_dev.fill_(t)
-            tp_dev.fill_(tp)
-            g.replay()
-            if self.ddim_snapshot(t, tp):
-                snaps.append(xh.clone())
-        return xh.clone()
 
     # DPM-Solver++(2M) (Lu et al. 2022): a second-order multistep solver of the probability-flow ODE ------------------------
     def _logsnr(self):
@@ -582,72 +521,44 @@ class Diffusion:
         (2n rows when guided).  The x0 of the previous step is the solver's state, updated in place by the kernel.  graph:
         capture one step (forward and update, reading the step's coefficients from a static device buffer) and replay it for
         every step but the last, which runs eagerly."""
-        self._hint(model)
-        try:
-            model.eval()
-            snaps = []
-            with torch.no_grad():
-                x = self._initial_noise(n, image_channels, noise_source)
-                table = self.dpmpp_coefficients(pairs).to(x.device)          # once per trajectory
-                guided = labels is not None and cfg_scale > 0
-                s = cfg_scale if guided else 0.0
-                y = labels
-                if guided:
-                    y = torch.cat([labels, torch.full_like(labels, ops.NULL_LABEL)])
-                xs = torch.cat([x, x]) if guided else x
-                x0 = torch.zeros_like(x)                                      # the solver state: the previous step's x0
-                first = 0
-                if graph and len(pairs) > 1:
-                    xs = self._dpmpp_graph_steps(model, xs, n, x0, snaps, pairs[:-1], table, y, s)
-                    first = len(pairs) - 1
-                for k in range(first, len(pairs)):
-                    t, tp = pairs[k]
-                    prev = x0 if self.dpmpp_order(k, len(pairs)) == 2 else None
-                    if guided:
-                        eps2 = self.predict_eps(model, xs, self._t_full(2 * n, t, x.device), y)
-                        nxt = torch.empty_like(xs)
-                        ops.dpmpp_step_cfg(xs[:n], eps2, prev, table[k], s, nxt[:n], nxt[n:], x0)
-                        xs = nxt
-                    else:
-                        tt = self._t_full(n, t, x.device)
-                        eps = self.predict_eps(model, xs, tt, y)
-                        xs = ops.dpmpp_step(xs, eps, prev, table[k], x0_out=x0)[0]
-                    if self.ddim_snapshot(t, tp):
-                        snaps.append(xs[:n])
-                x = xs[:n]
-        finally:
-            model.train()
-            self._unhint(model)
+        snaps = []
+        with self._model_scope(model):
+            x = self._initial_noise(n, image_channels, noise_source)
+            table = self.dpmpp_coefficients(pairs).to(x.device)          # once per trajectory
+            y, s = self._guided(labels, cfg_scale)
+            xs = torch.cat([x, x]) if s > 0 else x
+            rows = xs.shape[0]
+            x0 = torch.zeros_like(x)                                      # the solver state: the previous step's x0
+
+            def step(t_rows, coef, prev):
+                eps = self.predict_eps(model, xs, t_rows, y)
+                if s > 0:
+                    ops.dpmpp_step_cfg(xs[:n], eps, prev, coef, s, xs[:n], xs[n:], x0)
+                else:
+                    ops.dpmpp_step(xs, eps, prev, coef, xs, x0)           # in place (elementwise)
+
+            replay = None
+            if graph and len(pairs) > 1:
+                t_dev = torch.full((rows,), pairs[0][0], device=x.device, dtype=torch.long)
+                coef = table[0].clone()
+                # the captured step always reads x0: it starts at zero, so the first-order first step (B1 = 0) adds B1 * 0 = +0
+                g = self._capture(lambda: step(t_dev, coef, x0), xs)
+                x0.zero_()                                                # undo the warm-up's state as well
+
+                def replay(k):
+                    t_dev.fill_(pairs[k][0])
+                    coef.copy_(table[k])
+                    g.replay()
+            for k, (t, tp) in enumerate(pairs):
+                if replay is not None and tp > 0:
+                    replay(k)
+                else:
+                    step(self._t_full(rows, t, x.device), table[k], x0 if self.dpmpp_order(k, len(pairs)) == 2 else None)
+                if self.ddim_snapshot(t, tp):
+                    snaps.append(xs[:n].clone())
+            x = xs[:n].clone()
         snaps.append(x)
         return x, snaps
-
-    def _dpmpp_graph_steps(self, model, xs, n, x0, snaps, pairs, table, y=None, cfg_scale=0.0):
-        """The DPM++ steps `pairs` (all but the chain's last) by replaying one captured step.  Before each replay t_dev (the
-        forward's rows) and the static coefficient buffer are filled from the host's step index; the state x0 starts at zero,
-        so the first-order first step (B1 = 0) adds B1 * 0 = +0.  Returns a fresh xs after the last of them; x0 holds that step's x0."""
-        guided = cfg_scale > 0
-        xs = xs.clone()
-        t_dev = torch.full((xs.shape[0],), pairs[0][0], device=xs.device, dtype=torch.long)
-        coef = table[0].clone()
-        xh = xs[:n]
-
-        def one_step():
-            if guided:
-                eps2 = self.predict_eps(model, xs, t_dev, y)
-                ops.dpmpp_step_cfg(xh, eps2, x0, coef, cfg_scale, xh, xs[n:], x0)
-                return
-            eps = self.predict_eps(model, xs, t_dev, y)
-            ops.dpmpp_step(xs, eps, x0, coef, xs, x0)                         # in place (elementwise)
-
-        g = self._capture(one_step, xs)
-        x0.zero_()                                                            # undo the warm-up's state as well
-        for k, (t, tp) in enumerate(pairs):
-            t_dev.fill_(t)
-            coef.copy_(table[k])
-            g.replay()
-            if self.ddim_snapshot(t, tp):
-                snaps.append(xh.clone())
-        return xs.clone()
 
     def _hint(self, model):
         """Tell the model the range of the timesteps this process will pass (all of them in [0, noise_steps)): lets the
@@ -662,55 +573,33 @@ class Diffusion:
         if hasattr(model, "_t_range"):
             model._t_range = None
 
-    def _graph_steps(self, model, x, snaps, y=None, cfg_scale=0.0):
-        """Steps i = T-1 .. 2 by replaying one captured step; returns x after step 2.  y: class labels of the forward's rows
-        (2n of them when cfg_scale > 0: the captured step is then the 2n-row forward and the fused guided update, which writes
-        both halves of the static 2n input)."""
-        n = x.shape[0]
-        guided = cfg_scale > 0
-        t_dev = torch.full((2 * n if guided else n,), self.noise_steps - 1, device=x.device, dtype=torch.long)
-        xs = torch.cat([x, x]) if guided else x.clone()
-        xh = xs[:n]
-        learned = self.variance == "learned"
-        lv = self._lv() if learned else None
+    @contextlib.contextmanager
+    def _model_scope(self, model, leave_training=True):
+        """What every loop over the model runs in: the model hinted (`_hint`) and in eval mode, under no_grad.  On the way out,
+        also after an exception: leave_training (the samplers) puts the model in train mode, as the reference leaves it (:379),
+        and clears the hint; otherwise (the evaluations) the mode and the hint come back as they were found."""
+        found = None if leave_training else (model.training, getattr(model, "_t_range", None))
+        self._hint(model)
+        try:
+            model.eval()
+            with torch.no_grad():
+                yield
+        finally:
+            if leave_training:
+                model.train()
+                self._unhint(model)
+            else:
+                model.train(found[0])
+                if hasattr(model, "_t_range"):
+                    model._t_range = found[1]
 
-        def one_step():
-            if learned:                                  # the raw 2C output and the learned-variance update, in place as below
-                out2 = self._raw_output(model, xs, t_dev, y)
-                noise = torch.randn_like(xh)
-                if guided:
-                    ops.denoise_step_lvar_cfg_dev(xh, out2, noise, self.alpha, self.alpha_hat, self.beta, lv, self.prediction, t_dev,
-                                                  cfg_scale, xh, xs[n:])
-                else:
-                    ops.denoise_step_lvar_dev(xs, out2, noise, self.alpha, self.alpha_hat, self.beta, lv, self.prediction, t_dev, xs)
-                return
-            if guided:
-                eps2 = self.predict_eps(model, xs, t_dev, y)
-                noise = torch.randn_like(xh)
-                ops.denoise_step_cfg_dev(xh, eps2, noise, self.alpha, self.alpha_hat, self.beta, t_dev, cfg_scale, xh, xs[n:])
-                return
-            eps = self.predict_eps(model, xs, t_dev, y)
-            noise = torch.randn_like(xs)
-            ops.denoise_step_dev(xs, eps, noise, self.alpha, self.alpha_hat, self.beta, t_dev, xs)   # in place (elementwise)
-
-        side = torch.cuda.Stream()
-        side.wait_stream(torch.cuda.current_stream())
-        keep = xs.clone()
-        rng = torch.cuda.get_rng_state(x.device)
-        with torch.cuda.stream(side):
-            one_step()                                   # warm-up (allocator, lazy init); its effect is undone below
-        torch.cuda.current_stream().wait_stream(side)
-        xs.copy_(keep)
-        torch.cuda.set_rng_state(rng, x.device)          # ... including its noise draw: the replays consume the stream the eager loop would
-        g = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(g):
-            one_step()
-        for i in reversed(range(2, self.noise_steps)):
-            t_dev.fill_(i)
-            g.replay()
-            if i % 100 == 0:
-                snaps.append(xh.clone())
-        return xh.clone()
+    @staticmethod
+    def _guided(labels, cfg_scale):
+        """-> (y, s), built once per trajectory.  Classifier-free guidance (labels and cfg_scale > 0): y = [labels ; NULL_LABEL],
+        the labels of the 2n rows [x ; x] of the one forward per step, and s = cfg_scale.  Otherwise y = labels and s = 0."""
+        if labels is not None and cfg_scale > 0:
+            return torch.cat([labels, torch.full_like(labels, ops.NULL_LABEL)]), cfg_scale
+        return labels, 0.0
 
     def _check_labels(self, model, n, theta, labels, where="sample"):
         if theta is not None:
@@ -776,6 +665,10 @@ class Diffusion:
             x, snaps = self._loop(model, n, image_channels, theta, noise_source, graph, labels=labels, cfg_scale=float(cfg_scale))
         else:
             x, snaps = self._ddim_loop(model, n, image_channels, pairs, float(eta), noise_source, graph, labels, float(cfg_scale))
+        return self._finish(x, snaps, return_float)
+
+    def _finish(self, x, snaps, return_float):
+        """What `sample` and `inpaint` return: the final x and the snapshots, quantised; with return_float also x itself."""
         self.last_float_snapshots = snaps          # pre-quantisation x at i % 100 == 0 and the final x (parity tests)
         xq = ops.quantize_u8(x)
         rq = ops.quantize_u8(torch.cat(snaps))
@@ -856,92 +749,67 @@ class Diffusion:
             raise ValueError("Diffusion.inpaint: cfg_scale needs class labels")
         x, snaps = self._inpaint_loop(model, x0, m, moves, None if pairs is None else float(eta), noise_source, graph, labels,
                                       float(cfg_scale))
-        self.last_float_snapshots = snaps
-        xq = ops.quantize_u8(x)
-        rq = ops.quantize_u8(torch.cat(snaps))
-        if return_float:
-            return xq, rq, x
-        return xq, rq
+        return self._finish(x, snaps, return_float)
 
-    def _masked_update(self, xs, n, eps, z, x0, mask, t, tp, eta, cfg_scale, t_dev=None, tp_dev=None):
-        """One masked down-move, in place on xs[:n] (and on xs[n:] too when guided).  eta None: DDPM; t_dev: the _dev form."""
-        x = xs[:n]
-        out2 = xs[n:] if cfg_scale > 0 else None
-        if eta is None:
-            if cfg_scale > 0 and t_dev is not None:
-                ops.denoise_step_masked_cfg_dev(x, eps, z, x0, mask, self.alpha, self.alpha_hat, self.beta, t_dev, cfg_scale, x, out2)
-            elif cfg_scale > 0:
-                ops.denoise_step_masked_cfg(x, eps, z, x0, mask, self.alpha, self.alpha_hat, self.beta, t, cfg_scale, x, out2)
-            elif t_dev is not None:
-                ops.denoise_step_masked_dev(x, eps, z, x0, mask, self.alpha, self.alpha_hat, self.beta, t_dev, x)
-            else:
-                ops.denoise_step_masked(x, eps, z, x0, mask, self.alpha, self.alpha_hat, self.beta, t, x)
-        elif cfg_scale > 0 and t_dev is not None:
-            ops.ddim_step_masked_cfg_dev(x, eps, z, x0, mask, self.alpha_hat, t_dev, tp_dev, eta, cfg_scale, x, out2)
-        elif cfg_scale > 0:
-            ops.ddim_step_masked_cfg(x, eps, z, x0, mask, self.alpha_hat, t, tp, eta, cfg_scale, x, out2)
-        elif t_dev is not None:
-            ops.ddim_step_masked_dev(x, eps, z, x0, mask, self.alpha_hat, t_dev, tp_dev, eta, x)
+    def _update(self, xs, n, out, z, t, tp=None, eta=None, learned=False, cfg_scale=0.0, x0=None, mask=None):
+        """One update of the state xs, in place: its n rows, or both halves of the 2n rows [x ; x] of a guided forward
+        (cfg_scale > 0).  out: that forward's output (eps; with `learned` the raw 2C output); z: the step's noise of n images, or
+        None.  eta None: the DDPM step t -> t - 1, with the fixed or (`learned`) the network's variance; otherwise the DDIM step
+        t -> tp.  x0 and mask: the masked form of `inpaint`.  t and tp: host ints, or int64 device tensors (the graph-replayable
+        _dev form).  One launch: the wrapper these facts name, ops.{denoise,ddim}_step[_lvar][_masked][_cfg][_dev]."""
+        ddim, masked, guided, dev = eta is not None, mask is not None, cfg_scale > 0, isinstance(t, torch.Tensor)
+        if learned and (ddim or masked):
+            raise NotImplementedError("Diffusion: the learned variance is drawn by the unmasked DDPM step alone")
+        step = getattr(ops, ("ddim_step" if ddim else "denoise_step") + "_lvar" * learned + "_masked" * masked + "_cfg" * guided
+                       + "_dev" * dev)
+        x = xs[:n] if guided else xs
+        args = [x, out, z] + ([x0, mask] if masked else [])
+        if ddim:
+            args += [self.alpha_hat, t, tp, eta]
         else:
-            ops.ddim_step_masked(x, eps, z, x0, mask, self.alpha_hat, t, tp, eta, x)
+            args += [self.alpha, self.alpha_hat, self.beta] + ([self._lv(), self.prediction] if learned else []) + [t]
+        step(*args, *([cfg_scale, x, xs[n:]] if guided else [x]))
 
     def _inpaint_loop(self, model, x0, mask, moves, eta, noise_source, graph, labels, cfg_scale):
         """`inpaint`'s trajectory over `moves`.  The state lives in xs: n rows, or the 2n rows [x ; x] of the guided forward,
-        which every update writes in place (both halves)."""
+        which every update writes in place (both halves).  eta None: DDPM updates."""
         n, c = x0.shape[0], x0.shape[1]
-        guided = labels is not None and cfg_scale > 0
-        s = cfg_scale if guided else 0.0
-        self._hint(model)
-        try:
-            model.eval()
-            snaps = []
-            with torch.no_grad():
-                x = self._initial_noise(n, c, noise_source)
-                y = labels
-                if guided:
-                    y = torch.cat([labels, torch.full_like(labels, ops.NULL_LABEL)])
-                xs = torch.cat([x, x]) if guided else x
-                rows = xs.shape[0]
+        snaps = []
+        with self._model_scope(model):
+            x = self._initial_noise(n, c, noise_source)
+            y, s = self._guided(labels, cfg_scale)
+            xs = torch.cat([x, x]) if s > 0 else x
+            rows = xs.shape[0]
 
-                def forward(t_rows):
-                    return self.predict_eps(model, xs, t_rows, y)
+            def step(t_rows, t, tp, draw):
+                eps = self.predict_eps(model, xs, t_rows, y)
+                self._update(xs, n, eps, draw() if draw else None, t, tp, eta=eta, cfg_scale=s, x0=x0, mask=mask)
 
-                replay = None
-                first = next(((t, tp) for t, tp in moves if t > tp > 0), None)
-                if graph and noise_source != "cpu" and first is not None:
-                    t_dev = torch.full((rows,), first[0], device=x.device, dtype=torch.long)
-                    tp_dev = torch.full((1,), first[1], device=x.device, dtype=torch.long)
+            replay = None
+            first = next(((t, tp) for t, tp in moves if t > tp > 0), None)
+            if graph and noise_source != "cpu" and first is not None:
+                t_dev = torch.full((rows,), first[0], device=x.device, dtype=torch.long)
+                tp_dev = torch.full((1,), first[1], device=x.device, dtype=torch.long)
+                g = self._capture(lambda: step(t_dev, t_dev, tp_dev, lambda: torch.randn_like(xs[:n])), xs)
 
-                    def one_step():
-                        eps = forward(t_dev)
-                        z = torch.randn_like(xs[:n])
-                        self._masked_update(xs, n, eps, z, x0, mask, None, None, eta, s, t_dev, tp_dev)
-
-                    g = self._capture(one_step, xs)
-
-                    def replay(t, tp):
-                        t_dev.fill_(t)
-                        tp_dev.fill_(tp)
-                        g.replay()
-                for t, tp in moves:
-                    if tp > t:                                   # up-move: renoise the whole image from level t to tp
-                        z = self._step_noise(xs[:n], noise_source)
-                        ops.renoise(xs[:n], z, self.alpha_hat, t, tp, out=xs[:n])
-                        if guided:
-                            xs[n:].copy_(xs[:n])
-                        continue
-                    if replay is not None and tp > 0:
-                        replay(t, tp)
-                    else:
-                        eps = forward(self._t_full(rows, t, x.device))
-                        z = self._step_noise(xs[:n], noise_source) if tp > 0 else None
-                        self._masked_update(xs, n, eps, z, x0, mask, t, tp, eta, s)
-                    if self.ddim_snapshot(t, tp):
-                        snaps.append(xs[:n].clone())
-                x = xs[:n].clone()
-        finally:
-            model.train()
-            self._unhint(model)
+                def replay(t, tp):
+                    t_dev.fill_(t)
+                    tp_dev.fill_(tp)
+                    g.replay()
+            for t, tp in moves:
+                if tp > t:                                   # up-move: renoise the whole image from level t to tp
+                    z = self._step_noise(xs[:n], noise_source)
+                    ops.renoise(xs[:n], z, self.alpha_hat, t, tp, out=xs[:n])
+                    if s > 0:
+                        xs[n:].copy_(xs[:n])
+                    continue
+                if replay is not None and tp > 0:
+                    replay(t, tp)
+                else:
+                    step(self._t_full(rows, t, x.device), t, tp, (lambda: self._step_noise(xs[:n], noise_source)) if tp > 0 else None)
+                if self.ddim_snapshot(t, tp):
+                    snaps.append(xs[:n].clone())
+            x = xs[:n].clone()
         snaps.append(x)
         return x, snaps
 
@@ -1126,34 +994,19 @@ class Diffusion:
         term = torch.empty(len(t), device=dev, dtype=torch.float64)
         sq = torch.empty_like(term)
         prior = ops.vlb_prior(x0, 0.5 * float(self.alpha_hat[T - 1]))
-        was_training, hint = model.training, getattr(model, "_t_range", None)
-        self._hint(model)
-        try:
-            model.eval()
-            with torch.no_grad():
-                for lo, hi in self.bpd_chunks(len(t), batch):
-                    cs = (hi - lo,) + shape
-                    if noise_fn is not None:
-                        eps = noise_fn(cs)
-                    elif noise_source == "device":
-                        eps = torch.randn(cs, device=dev)
-                    else:
-                        eps = torch.randn(cs).to(dev)
-                    eps = eps.to(device=dev, dtype=torch.float32).contiguous()
-                    rows_i, rows_t = img_d[lo:hi], t_d[lo:hi]
-                    xt = ops.noise_images_gather(x0, rows_i, eps, rows_t, self.alpha_hat, check_range=False)
-                    if learned:
-                        out2 = self._raw_output(model, xt, rows_t, None if y_rows is None else y_rows[lo:hi])
-                        ops.vlb_terms_lvar(x0, rows_i, xt, eps, out2, rows_t, self._lv(), self.alpha, self.alpha_hat, self.beta,
-                                           self.prediction, term[lo:hi], sq[lo:hi], check_range=False)
-                        continue
-                    eh = self.predict_eps(model, xt, rows_t, None if y_rows is None else y_rows[lo:hi])
-                    ops.vlb_terms(x0, rows_i, xt, eps, eh.contiguous(), rows_t, coef_d, self.alpha, self.alpha_hat, self.beta,
-                                  term[lo:hi], sq[lo:hi], check_range=False)
-        finally:
-            model.train(was_training)
-            if hasattr(model, "_t_range"):
-                model._t_range = hint
+        with self._model_scope(model, leave_training=False):
+            for lo, hi in self.bpd_chunks(len(t), batch):
+                eps = self._chunk_noise((hi - lo,) + shape, noise_source, noise_fn)
+                rows_i, rows_t = img_d[lo:hi], t_d[lo:hi]
+                xt = ops.noise_images_gather(x0, rows_i, eps, rows_t, self.alpha_hat, check_range=False)
+                if learned:
+                    out2 = self._raw_output(model, xt, rows_t, None if y_rows is None else y_rows[lo:hi])
+                    ops.vlb_terms_lvar(x0, rows_i, xt, eps, out2, rows_t, self._lv(), self.alpha, self.alpha_hat, self.beta,
+                                       self.prediction, term[lo:hi], sq[lo:hi], check_range=False)
+                    continue
+                eh = self.predict_eps(model, xt, rows_t, None if y_rows is None else y_rows[lo:hi])
+                ops.vlb_terms(x0, rows_i, xt, eps, eh.contiguous(), rows_t, coef_d, self.alpha, self.alpha_hat, self.beta,
+                              term[lo:hi], sq[lo:hi], check_range=False)
         prior_nats = prior.cpu().numpy() + per * float(coef[0, 3])
         return self.bpd_combine(n, per, img, t, term.cpu().numpy(), sq.cpu().numpy(), prior_nats, K, return_terms)
 
@@ -1297,36 +1150,21 @@ class Diffusion:
         coef_x = torch.empty((n * J,) + shape, device=dev, dtype=torch.float64)
         coef_f = torch.empty_like(coef_x)
         sums = torch.empty((len(k), 3), device=dev, dtype=torch.float64)
-        was_training, hint = model.training, getattr(model, "_t_range", None)
-        self._hint(model)
-        try:
-            model.eval()
-            with torch.no_grad():
-                for lo, hi in self.bpd_chunks(n * J, batch):
-                    cs = (hi - lo,) + shape
-                    if noise_fn is not None:
-                        eps = noise_fn(cs)
-                    elif noise_source == "device":
-                        eps = torch.randn(cs, device=dev)
-                    else:
-                        eps = torch.randn(cs).to(dev)
-                    eps = eps.to(device=dev, dtype=torch.float32).contiguous()
-                    rows_t = t0_d[lo:hi]
-                    xt = ops.noise_images_gather(x0, img0_d[lo:hi], eps, rows_t, self.alpha_hat, check_range=False)
-                    f = model(xt, rows_t) if y is None else model(xt, rows_t, y[img0_d[lo:hi]])
-                    f = f[:, :C] if self.variance == "learned" else f             # the prediction half
-                    ops.spline3_prefilter_wrap(xt, coef_x[lo:hi])
-                    ops.spline3_prefilter_wrap(f.contiguous(), coef_f[lo:hi])
-                for lo, hi in self.bpd_chunks(len(k), batch):
-                    rows_s, rows_k, rows_t = src_d[lo:hi], k_d[lo:hi], t_d[lo:hi]
-                    sx = ops.affine_spline3_wrap_rows(coef_x, rows_s, aff_d, rows_k, check_range=False)
-                    g = model(sx, rows_t) if y is None else model(sx, rows_t, y[rows_s // J])
-                    g = g[:, :C] if self.variance == "learned" else g
-                    ops.eq_terms(coef_f, rows_s, aff_d, rows_k, g.contiguous(), margin, sums[lo:hi], check_range=False)
-        finally:
-            model.train(was_training)
-            if hasattr(model, "_t_range"):
-                model._t_range = hint
+        with self._model_scope(model, leave_training=False):
+            for lo, hi in self.bpd_chunks(n * J, batch):
+                eps = self._chunk_noise((hi - lo,) + shape, noise_source, noise_fn)
+                rows_t = t0_d[lo:hi]
+                xt = ops.noise_images_gather(x0, img0_d[lo:hi], eps, rows_t, self.alpha_hat, check_range=False)
+                f = model(xt, rows_t) if y is None else model(xt, rows_t, y[img0_d[lo:hi]])
+                f = f[:, :C] if self.variance == "learned" else f             # the prediction half
+                ops.spline3_prefilter_wrap(xt, coef_x[lo:hi])
+                ops.spline3_prefilter_wrap(f.contiguous(), coef_f[lo:hi])
+            for lo, hi in self.bpd_chunks(len(k), batch):
+                rows_s, rows_k, rows_t = src_d[lo:hi], k_d[lo:hi], t_d[lo:hi]
+                sx = ops.affine_spline3_wrap_rows(coef_x, rows_s, aff_d, rows_k, check_range=False)
+                g = model(sx, rows_t) if y is None else model(sx, rows_t, y[rows_s // J])
+                g = g[:, :C] if self.variance == "learned" else g
+                ops.eq_terms(coef_f, rows_s, aff_d, rows_k, g.contiguous(), margin, sums[lo:hi], check_range=False)
         return self.equivariance_combine(n, J, K, C, sums.cpu().numpy(), peak)
 
     def sample_sharded(self, model, n, image_channels, theta=None, noise_source="reference", group=None, dst=0, steps=None):
@@ -1396,10 +1234,8 @@ class Diffusion:
         K = len(thetas)
         if K == 0:                                       # (a rank of the sharded sweep that holds no angle)
             return [], []
-        self._hint(model)
-        model.eval()
         snaps = [[] for _ in range(K)]
-        with torch.no_grad():
+        with self._model_scope(model):
             x = self._initial_noise(n, image_channels, "reference").repeat(K, 1, 1, 1)
             for i in reversed(range(1, self.noise_steps)):
                 eps = self.predict_eps(model, x, self._t_full(K * n, i, x.device))
@@ -1411,8 +1247,6 @@ class Diffusion:
                 if i % 100 == 0:
                     for k in range(K):
                         snaps[k].append(x[k * n:(k + 1) * n].clone())
-        model.train()
-        self._unhint(model)
         xs, results = [], []
         for k in range(K):
             xk = x[k * n:(k + 1) * n]
@@ -1433,129 +1267,78 @@ class Diffusion:
         steps / eta: DDIM over a strided chain, as for `sample`; noise_fn is then called with i = the step's t (and not at
         all after x_T when eta == 0)."""
         pairs = self._check_ddim("sample_concurrent", steps, eta)
-        run = self._sample_concurrent_graphs if graph else self._sample_concurrent_eager
-        self._hint(model)
-        model.eval()
-        if pairs is None:                                    # the DDPM chain
-            out = run(model, n, image_channels, batch, streams, noise_fn, [(i, i - 1) for i in reversed(range(1, self.noise_steps))])
-            model.train()
-            self._unhint(model)
-            return out
-        try:
-            return run(model, n, image_channels, batch, streams, noise_fn, pairs, float(eta))
-        finally:
-            model.train()
-            self._unhint(model)
-
-    def _sample_concurrent_eager(self, model, n, image_channels, batch, streams, noise_fn, pairs, eta=None):
-        """pairs: the (t, t_prev) steps; eta None = DDPM updates (pairs are then (i, i - 1)), else DDIM with that eta."""
-        ddim = eta is not None
+        eta = None if pairs is None else float(eta)          # None: DDPM updates over the full chain
+        if pairs is None:
+            pairs = [(i, i - 1) for i in reversed(range(1, self.noise_steps))]
+        noisy = eta is None or eta > 0
+        shape = (image_channels, self.img_size, self.img_size)
         sizes = [min(batch, n - o) for o in range(0, n, batch)]
         pool = [torch.cuda.Stream() for _ in range(max(1, min(streams, len(sizes))))]
         cur = torch.cuda.current_stream()
         xs_out, snaps_out = [None] * len(sizes), [None] * len(sizes)
-        with torch.no_grad():
+        slots = {}                                           # graph: (batch size, stream) -> (xs, t, t_prev, noise, graph), captured once
+
+        def slot(b, st):
+            """The static buffers of a trajectory of b images on stream st and its captured step, which reads its noise from nz."""
+            xs = torch.zeros(b, *shape, device=self.device)
+            t_dev = torch.full((b,), self.noise_steps - 1, device=self.device, dtype=torch.long)
+            tp_dev = torch.full((1,), pairs[0][1], device=self.device, dtype=torch.long) if eta is not None else None
+            nz = torch.zeros_like(xs) if noisy else None
+
+            def one_step():
+                self._update(xs, b, self.predict_eps(model, xs, t_dev), nz, t_dev, tp_dev, eta=eta)
+            # not `_capture`: the warm-up (allocator, cached weight transforms) runs on the trajectory's own stream, which also
+            # captures, and needs no undo: it draws nothing and xs is overwritten with x_T afterwards
+            one_step()
+            st.synchronize()
+            g = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(g, stream=st):
+                one_step()
+            return xs, t_dev, tp_dev, nz, g
+
+        def advance(k, key, x, i, tp):
+            """One step (i -> tp) of trajectory k, in place on x; the last step adds no noise (ddpm_models.py:370-373) and is eager."""
+            if graph and tp > 0:
+                _, t_dev, tp_dev, nz, g = slots[key]
+                t_dev.fill_(i)
+                if tp_dev is not None:
+                    tp_dev.fill_(tp)
+                if nz is None:
+                    pass
+                elif noise_fn is None:
+                    nz.normal_()
+                else:
+                    nz.copy_(noise_fn(k, i, x.shape))
+                g.replay()
+                return
+            eps = self.predict_eps(model, x, self._t_full(x.shape[0], i, x.device))
+            noise = None if not (noisy and tp > 0) else (torch.randn_like(x) if noise_fn is None else noise_fn(k, i, x.shape))
+            self._update(x, x.shape[0], eps, noise, i, tp, eta=eta)
+
+        with self._model_scope(model):
             for g0 in range(0, len(sizes), len(pool)):
                 group = list(range(g0, min(g0 + len(pool), len(sizes))))
                 xs, snaps = {}, {k: [] for k in group}
                 for k in group:
                     st = pool[k - g0]
                     st.wait_stream(cur)
-                    with torch.cuda.stream(st):
-                        xs[k] = torch.randn(sizes[k], image_channels, self.img_size, self.img_size, device=self.device) \
-                            if noise_fn is None else noise_fn(k, self.noise_steps, (sizes[k], image_channels, self.img_size, self.img_size))
-                for i, tp in pairs:
-                    draw = tp > 0 and (not ddim or eta > 0)
-                    for k in group:                                  # one denoise step of every trajectory of the group
-                        with torch.cuda.stream(pool[k - g0]):
-                            x = xs[k]
-                            eps = self.predict_eps(model, x, self._t_full(x.shape[0], i, x.device))
-                            noise = None if not draw else (torch.randn_like(x) if noise_fn is None else noise_fn(k, i, x.shape))
-                            if ddim:
-                                x = ops.ddim_step(x, eps, noise, self.alpha_hat, i, tp, eta)
-                            else:
-                                x = ops.denoise_step(x, eps, noise, self.alpha, self.alpha_hat, self.beta, i)
-                            if self.ddim_snapshot(i, tp):
-                                snaps[k].append(x)
-                            xs[k] = x
-                for k in group:
-                    with torch.cuda.stream(pool[k - g0]):
-                        snaps[k].append(xs[k])
-                        xs_out[k] = ops.quantize_u8(xs[k])
-                        snaps_out[k] = ops.quantize_u8(torch.cat(snaps[k]))
-                    cur.wait_stream(pool[k - g0])
-        for t in xs_out + snaps_out:
-            t.record_stream(cur)
-        return torch.cat(xs_out), torch.cat(snaps_out)
-
-    def _sample_concurrent_graphs(self, model, n, image_channels, batch, streams, noise_fn, pairs, eta=None):
-        ddim = eta is not None
-        noisy = not ddim or eta > 0
-        sizes = [min(batch, n - o) for o in range(0, n, batch)]
-        pool = [torch.cuda.Stream() for _ in range(max(1, min(streams, len(sizes))))]
-        cur = torch.cuda.current_stream()
-        xs_out, snaps_out = [None] * len(sizes), [None] * len(sizes)
-        shape = (image_channels, self.img_size, self.img_size)
-        slots = {}                                           # (batch size, stream) -> (x, t, t_prev, noise, graph), captured once
-        with torch.no_grad():
-            for g0 in range(0, len(sizes), len(pool)):
-                group = list(range(g0, min(g0 + len(pool), len(sizes))))
-                state, snaps = {}, {k: [] for k in group}
-                for k in group:
-                    st = pool[k - g0]
-                    st.wait_stream(cur)
                     key = (sizes[k], k - g0)
                     with torch.cuda.stream(st):
-                        if key not in slots:
-                            xs = torch.zeros(sizes[k], *shape, device=self.device)
-                            t_dev = torch.full((sizes[k],), self.noise_steps - 1, device=self.device, dtype=torch.long)
-                            tp_dev = torch.full((1,), pairs[0][1], device=self.device, dtype=torch.long) if ddim else None
-                            nz = torch.zeros_like(xs) if noisy else None
-
-                            def one_step(xs=xs, t_dev=t_dev, tp_dev=tp_dev, nz=nz):
-                                eps = self.predict_eps(model, xs, t_dev)
-                                if ddim:
-                                    ops.ddim_step_dev(xs, eps, nz, self.alpha_hat, t_dev, tp_dev, eta, xs)
-                                else:
-                                    ops.denoise_step_dev(xs, eps, nz, self.alpha, self.alpha_hat, self.beta, t_dev, xs)
-                            one_step()                       # warm-up outside capture (allocator, cached weight transforms)
-                            st.synchronize()
-                            g = torch.cuda.CUDAGraph()
-                            with torch.cuda.graph(g, stream=st):
-                                one_step()
-                            slots[key] = (xs, t_dev, tp_dev, nz, g)
-                        xs = slots[key][0]
-                        xs.copy_(torch.randn(sizes[k], *shape, device=self.device) if noise_fn is None
-                                 else noise_fn(k, self.noise_steps, (sizes[k], *shape)))
-                    state[k] = slots[key]
+                        if graph and key not in slots:
+                            slots[key] = slot(sizes[k], st)
+                        x_T = torch.randn(sizes[k], *shape, device=self.device) if noise_fn is None \
+                            else noise_fn(k, self.noise_steps, (sizes[k], *shape))
+                        xs[k] = slots[key][0].copy_(x_T) if graph else x_T.clone()      # (noise_fn's tensor is not written to)
                 for i, tp in pairs:
-                    for k in group:
-                        xs, t_dev, tp_dev, nz, g = state[k]
+                    for k in group:                                  # one denoise step of every trajectory of the group
                         with torch.cuda.stream(pool[k - g0]):
-                            if tp > 0:
-                                t_dev.fill_(i)
-                                if tp_dev is not None:
-                                    tp_dev.fill_(tp)
-                                if nz is None:
-                                    pass
-                                elif noise_fn is None:
-                                    nz.normal_()
-                                else:
-                                    nz.copy_(noise_fn(k, i, xs.shape))
-                                g.replay()
-                            else:                            # the last step adds no noise (ddpm_models.py:370-373)
-                                eps = self.predict_eps(model, xs, self._t_full(xs.shape[0], i, xs.device))
-                                if ddim:
-                                    xs.copy_(ops.ddim_step(xs, eps, None, self.alpha_hat, i, 0, eta))
-                                else:
-                                    xs.copy_(ops.denoise_step(xs, eps, None, self.alpha, self.alpha_hat, self.beta, 1))
+                            advance(k, (sizes[k], k - g0), xs[k], i, tp)
                             if self.ddim_snapshot(i, tp):
-                                snaps[k].append(xs.clone())
+                                snaps[k].append(xs[k].clone())
                 for k in group:
                     with torch.cuda.stream(pool[k - g0]):
-                        xs = state[k][0]
-                        xs_out[k] = ops.quantize_u8(xs)
-                        snaps_out[k] = ops.quantize_u8(torch.cat(snaps[k] + [xs]))
+                        xs_out[k] = ops.quantize_u8(xs[k])
+                        snaps_out[k] = ops.quantize_u8(torch.cat(snaps[k] + [xs[k]]))
                     cur.wait_stream(pool[k - g0])
         for t in xs_out + snaps_out:
             t.record_stream(cur)
@@ -1585,9 +1368,7 @@ class Diffusion:
         if shift is not None:
             dur = np.abs(shift) / self.noise_steps
             idx = set(np.round(np.arange(0, self.noise_steps, dur)).astype(int)[1:].tolist())
-        self._hint(model)
-        model.eval()
-        with torch.no_grad():
+        with self._model_scope(model):
             x = self._initial_noise(n, image_channels, noise_source)
             for i in reversed(range(1, self.noise_steps)):
                 eps = self.predict_eps(model, x, self._t_full(n, i, x.device))
@@ -1595,8 +1376,6 @@ class Diffusion:
                 x = ops.denoise_step(x, eps, noise, self.alpha, self.alpha_hat, self.beta, i)
                 if idx is not None and i in idx:
                     x = self.shift_2d_matrix(x, 1 * np.sign(shift), 0, self.device)
-        model.train()
-        self._unhint(model)
         return ops.quantize_u8(x)
 
     # F17 (Config E): the reference rotates on the CPU with scipy every step (D2H, single-threaded spline,

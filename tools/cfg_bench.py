@@ -4,7 +4,7 @@ in this process (run the configurations as separate processes).
 uncond: the unconditional step (timestep tables on, as Diffusion.sample runs it); cond: labels, cfg_scale = 0 (one n-row
 forward with the label embedding, so the time embedding is computed every step); cfg: guidance as Diffusion.sample runs it
 (ONE 2n-row forward + afd_denoise_step_cfg writing both halves of the 2n input); cfg2: guidance the upstream way (two n-row
-forwards, torch.lerp, ops.denoise_step).  --graph: the step captured once and replayed, as Diffusion._graph_steps does."""
+forwards, torch.lerp, ops.denoise_step).  --graph: the step captured once and replayed, as Diffusion.sample(graph=True) does (Diffusion._capture)."""
 import gc
 import math
 import os
