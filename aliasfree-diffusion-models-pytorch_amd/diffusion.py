@@ -15,6 +15,7 @@ import torch
 import torch.distributed as dist
 
 from . import ops
+from .filters import circularLowpassKernel
 
 
 def shard_range(n, rank, world):
@@ -54,9 +55,10 @@ class Diffusion:
         variance: "fixed" (beta_t, the reference's) or "learned" (Nichol & Dhariwal 2021): the network is UNet(c_in=C, c_out=2 C),
         its first C output channels are the prediction and the next C the coefficient v of
         log sigma^2 = ((v + 1) / 2) log beta_t + (1 - (v + 1) / 2) log beta~_t per pixel (`lvar_coefficients`).  The DDPM chain
-        (`sample`, `revert`, `sample_sharded`, guided or not, eager or graph=True) then draws with that variance,
+        (`sample`, `revert`, `sample_sharded`, `ilvr`, guided or not, eager or graph=True) then draws with that variance,
         `calc_bpd(sigma="learned")` scores it and `TrainStep` trains it with the hybrid loss.  Everything that goes through
-        `predict_eps` -- DDIM, DPM-Solver++(2M), `inpaint`, `equivariance`, the sweeps, `sample_shift` and `sample_concurrent` --
+        `predict_eps` -- DDIM (also under `ilvr`), DPM-Solver++(2M), `inpaint`, `equivariance`, the sweeps, `sample_shift` and
+        `sample_concurrent` --
         reads the prediction half alone and keeps its own variance."""
         if not isinstance(variance, str) or variance not in self.VARIANCES:
             raise ValueError(f"Diffusion: unknown variance {variance!r} ('fixed' or 'learned')")
@@ -807,6 +809,137 @@ class Diffusion:
                     replay(t, tp)
                 else:
                     step(self._t_full(rows, t, x.device), t, tp, (lambda: self._step_noise(xs[:n], noise_source)) if tp > 0 else None)
+                if self.ddim_snapshot(t, tp):
+                    snaps.append(xs[:n].clone())
+            x = xs[:n].clone()
+        snaps.append(x)
+        return x, snaps
+
+    # Reference-guided sampling (ILVR, Choi et al. 2021) ------------------------------------------------------------------------------
+    def _ilvr_operator(self, where, factor, taps):
+        """-> (ops.Taps, levels) of phi = 4^levels up2^levels(down2^levels(.)): factor = 2^levels; taps None = the default filter."""
+        if self.img_size not in ops.REFINE_SIDES:
+            raise NotImplementedError(f"Diffusion.{where}: img_size must be a power of two in [4, 64] (got {self.img_size})")
+        if isinstance(factor, bool) or not isinstance(factor, (int, np.integer)) or factor < 2 or factor & (factor - 1) \
+                or 2 * factor > self.img_size:
+            raise ValueError(f"Diffusion.{where}: factor must be a power of two in [2, {self.img_size // 2}] (got {factor!r})")
+        if taps is None:
+            taps = circularLowpassKernel(math.pi / 2, 9, beta=8)
+        k = taps.detach().cpu().numpy() if isinstance(taps, torch.Tensor) else np.asarray(taps)
+        if k.ndim != 2 or k.shape[0] != k.shape[1] or k.shape[0] % 2 == 0 or k.shape[0] > 15 or k.dtype.kind not in "fiu":
+            raise ValueError(f"Diffusion.{where}: taps must be an (N, N) array of numbers with N odd and at most 15 "
+                             f"(got shape {tuple(k.shape)}): an even N shifts the image by half a pixel per pass")
+        return ops.Taps(k), int(factor).bit_length() - 1
+
+    def _ilvr_reference(self, reference):
+        if not isinstance(reference, torch.Tensor) or reference.dtype != torch.float32:
+            raise ValueError("Diffusion.ilvr: reference must be an fp32 tensor")
+        if reference.dim() != 4 or reference.shape[0] < 1 or tuple(reference.shape[2:]) != (self.img_size, self.img_size):
+            raise ValueError(f"Diffusion.ilvr: reference must have shape (n, C, {self.img_size}, {self.img_size}) "
+                             f"(got {tuple(reference.shape)})")
+        return reference.to(self.device).contiguous()
+
+    def reference_from_lowres(self, low, factor, taps=None):
+        """A full-size reference for `ilvr` from low-resolution images: 4^L up2^L(low) with factor = 2^L, through the filtered
+        upsampler (ops.FiltUp2).  low: fp32 (n, C, img_size / factor, img_size / factor); taps as for `ilvr`.  For low =
+        down2^L(v) this is ops.lowpass_project(v): `ilvr` on it super-resolves.  Returns the reference on the device."""
+        k, levels = self._ilvr_operator("reference_from_lowres", factor, taps)
+        side = self.img_size >> levels
+        if not isinstance(low, torch.Tensor) or low.dtype != torch.float32:
+            raise ValueError("Diffusion.reference_from_lowres: low must be an fp32 tensor")
+        if low.dim() != 4 or low.shape[0] < 1 or tuple(low.shape[2:]) != (side, side):
+            raise ValueError(f"Diffusion.reference_from_lowres: low must have shape (n, C, {side}, {side}) (got {tuple(low.shape)})")
+        x = low.to(self.device).contiguous()
+        with torch.no_grad():
+            for _ in range(levels):
+                x = ops.FiltUp2.apply(x, k)
+            return x.mul_(float(4 ** levels))
+
+    def ilvr(self, model, reference, factor=4, t_stop=0, taps=None, steps=None, eta=0.0, labels=None, cfg_scale=0.0,
+             noise_source="reference", graph=None, return_float=False):
+        """Draw samples that share the coarse content of `reference` (ILVR, Choi et al. 2021): no retraining.  After the update of
+        a move t -> t_prev the state's low frequencies are replaced by those of the reference noised to t_prev,
+            x <- x + phi(y - x),   y ~ q(x_t_prev | reference)   (y = reference at t_prev = 0),
+        with phi = 4^L up2^L(down2^L(.)) (factor = 2^L) built from the filtered resamplers: one fused launch per move
+        (ops.lowpass_refine).
+        reference: fp32 (n, C, img_size, img_size) in [-1, 1]; img_size must be a power of two in [4, 64].
+        factor: a power of two, 2 <= factor <= img_size / 2; the larger, the less of the reference is kept.
+        t_stop: an int in [0, T]; a move is refined when t_prev >= t_stop (0: every move, the last included; >= T - 1: none, and
+        the result, the snapshots and the generators' positions are `sample`'s, bit for bit).
+        taps: None = circularLowpassKernel(pi / 2, 9, beta=8); otherwise an (N, N) array or tensor, N odd and at most 15.  Symmetric
+        taps (taps == taps.T, and the same read backwards) are what makes up2 the transpose of down2, hence phi symmetric positive
+        semi-definite with eigenvalues at most about 1: the refinement then never expands.  Asymmetric taps are accepted and
+        carry no such promise.
+        steps / eta / labels / cfg_scale / noise_source / graph: as for `sample` (DDPM with steps=None, the learned variance
+        included, or DDIM; there is no DPM-Solver++ form: its multistep history would be stale after a refinement).  Each move
+        draws the step's noise exactly where `sample` draws it; a refined move with t_prev > 0 then draws the noise of n images
+        for the reference.  graph=True captures one refined move (forward, both draws, update, refinement with t_prev read on the
+        device) and, when t_stop > 0, one unrefined move, and replays them; the last move runs eagerly.  Snapshots as `sample`
+        (`ddim_snapshot`).  Returns what `sample` returns."""
+        logging.info(f"Sampling {reference.shape[0] if isinstance(reference, torch.Tensor) else '?'} images guided by a reference....")
+        k, levels = self._ilvr_operator("ilvr", factor, taps)
+        ref = self._ilvr_reference(reference)
+        T = self.noise_steps
+        if isinstance(t_stop, bool) or not isinstance(t_stop, (int, np.integer)) or not 0 <= t_stop <= T:
+            raise ValueError(f"Diffusion.ilvr: t_stop must be an int in [0, {T}] (got {t_stop!r})")
+        pairs = self._check_ddim("ilvr", steps, eta)
+        n = ref.shape[0]
+        if labels is not None:
+            labels = self._check_labels(model, n, None, labels, "ilvr")
+        elif cfg_scale:
+            raise ValueError("Diffusion.ilvr: cfg_scale needs class labels")
+        moves = [(t, t - 1) for t in range(T - 1, 0, -1)] if pairs is None else pairs
+        x, snaps = self._ilvr_loop(model, ref, k, levels, int(t_stop), moves, None if pairs is None else float(eta), noise_source,
+                                   graph, labels, float(cfg_scale))
+        return self._finish(x, snaps, return_float)
+
+    def _ilvr_loop(self, model, ref, taps, levels, t_stop, moves, eta, noise_source, graph, labels, cfg_scale):
+        """`ilvr`'s trajectory over `moves`, [(t, t_prev)] descending to 0.  eta None: DDPM updates (with the network's variance
+        when it is learned), otherwise DDIM.  The state lives in xs as in `_inpaint_loop`; a refined move adds one launch that
+        writes both halves of a guided state."""
+        n, c = ref.shape[0], ref.shape[1]
+        self.check_model(model, c, "Diffusion.ilvr")
+        learned = eta is None and self.variance == "learned"
+        forward = self._raw_output if learned else self.predict_eps      # learned: the raw 2C output goes to the update
+        takes_noise = eta is None or eta > 0
+        snaps = []
+        with self._model_scope(model):
+            x = self._initial_noise(n, c, noise_source)
+            y, s = self._guided(labels, cfg_scale)
+            xs = torch.cat([x, x]) if s > 0 else x
+            rows = xs.shape[0]
+
+            def step(t_rows, t, tp, draw, draw_ref, refined):
+                out = forward(model, xs, t_rows, y)
+                self._update(xs, n, out, draw() if draw else None, t, tp, eta=eta, learned=learned, cfg_scale=s)
+                if refined:
+                    refine = ops.lowpass_refine_dev if isinstance(tp, torch.Tensor) else ops.lowpass_refine
+                    refine(xs[:n], ref, draw_ref() if draw_ref else None, self.alpha_hat, tp, taps, levels, out=xs[:n],
+                           out2=xs[n:] if s > 0 else None)
+
+            replay = None
+            first = next(((t, tp) for t, tp in moves if tp > 0), None)
+            if graph and noise_source != "cpu" and first is not None:
+                t_dev = torch.full((rows,), first[0], device=x.device, dtype=torch.long)
+                tp_dev = torch.full((1,), first[1], device=x.device, dtype=torch.long)
+                dev_draw = lambda: torch.randn_like(xs[:n])
+                graphs = {}                                  # one capture per kind of move (refined or not), made when first needed
+
+                def replay(t, tp, refined):
+                    if refined not in graphs:
+                        graphs[refined] = self._capture(
+                            lambda: step(t_dev, t_dev, tp_dev, dev_draw if takes_noise else None, dev_draw, refined), xs)
+                    t_dev.fill_(t)
+                    tp_dev.fill_(tp)
+                    graphs[refined].replay()
+            host_draw = lambda: self._step_noise(xs[:n], noise_source)
+            for t, tp in moves:
+                refined = tp >= t_stop
+                if replay is not None and tp > 0:            # the last move draws no noise: it runs eagerly
+                    replay(t, tp, refined)
+                else:
+                    step(self._t_full(rows, t, x.device), t, tp, host_draw if takes_noise and tp > 0 else None,
+                         host_draw if tp > 0 else None, refined)
                 if self.ddim_snapshot(t, tp):
                     snaps.append(xs[:n].clone())
             x = xs[:n].clone()

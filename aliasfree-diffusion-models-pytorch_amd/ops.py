@@ -1366,6 +1366,57 @@ def renoise(x, noise, alpha_hat, t_from, t_to, out=None):
     return out
 
 
+# ---- reference-guided sampling (ILVR): the fused low-pass refinement (include/afd.h gives the exact expressions) -------------
+REFINE_SIDES = (4, 8, 16, 32, 64)
+
+
+def _refine_args(what, x, ref, noise, alpha_hat, taps, levels, out, out2):
+    """The argument check of the refine wrappers -> (taps, levels, planes, S).  x: (..., S, S), S a power of two in [4, 64];
+    ref, noise (or None), out and out2 (or None) hold as many elements; taps: an N x N filter, N odd and at most 15."""
+    _step_args(what, x, ref, noise, alpha_hat, out, out2)
+    if x.dim() < 2 or x.shape[-1] != x.shape[-2] or x.shape[-1] not in REFINE_SIDES:
+        raise AfdError(f"afdm: {what} needs square planes (..., S, S) with S a power of two in [4, 64] (got shape {tuple(x.shape)})")
+    S = int(x.shape[-1])
+    taps = Taps.of(taps)
+    if taps.N % 2 == 0 or taps.N > 15:
+        raise AfdError(f"afdm: {what} needs an N x N filter with N odd and at most 15 (got N = {taps.N}): an even N shifts the image")
+    if isinstance(levels, bool) or not isinstance(levels, (int, np.integer)) or levels < 1 or (S >> int(levels)) < 2:
+        raise AfdError(f"afdm: {what} needs an int levels >= 1 with S / 2^levels >= 2 (got levels = {levels!r}, S = {S})")
+    return taps, int(levels), x.numel() // (S * S), S
+
+
+def lowpass_refine(x, ref, noise, alpha_hat, t_prev, taps, levels, out=None, out2=None):
+    """ILVR's refinement x + phi(known - x) in one launch: phi = 4^levels up2^levels(down2^levels(.)) with `taps` (an N x N array,
+    tensor or ops.Taps), known = ref noised to t_prev with `noise` (ref itself at t_prev == 0, where noise may be None).
+    x: (..., S, S).  `out` may be x (in place); `out2` (optional) receives the same values."""
+    out = torch.empty_like(x) if out is None else out
+    taps, levels, planes, S = _refine_args("low-pass refine", x, ref, noise, alpha_hat, taps, levels, out, out2)
+    t_prev = int(t_prev)
+    if not 0 <= t_prev < alpha_hat.numel():
+        raise AfdError(f"afdm: low-pass refine needs 0 <= t_prev < {alpha_hat.numel()} (got {t_prev})")
+    lib().afd_lowpass_refine(_p(x), _p(ref), _p(noise), _p(alpha_hat), t_prev, taps.ptr, taps.N, levels, _p(out), _p(out2), planes, S,
+                             _stream())
+    return out
+
+
+def lowpass_refine_dev(x, ref, noise, alpha_hat, t_prev_dev, taps, levels, out, out2=None):
+    """lowpass_refine with t_prev = t_prev_dev[0] read on the device (graph-replayable); noise is required (ignored at 0)."""
+    taps, levels, planes, S = _refine_args("low-pass refine", x, ref, noise, alpha_hat, taps, levels, out, out2)
+    if not t_prev_dev.is_cuda or t_prev_dev.dtype != torch.long or t_prev_dev.numel() < 1:
+        raise AfdError("afdm: low-pass refine: t_prev_dev must be an int64 device tensor (element 0 is read)")
+    lib().afd_lowpass_refine_dev(_p(x), _p(ref), _p(noise), _p(alpha_hat), _p(t_prev_dev), taps.ptr, taps.N, levels, _p(out), _p(out2),
+                                 planes, S, _stream())
+    return out
+
+
+def lowpass_project(v, taps, levels):
+    """phi(v) = 4^levels up2^levels(down2^levels(v)) with `taps`: the refine launch with x = 0, t_prev = 0 and ref = v."""
+    _chk(v)
+    zero = torch.zeros_like(v, memory_format=torch.contiguous_format)
+    # (t_prev = 0 reads no schedule: the first zero stands in for the table, whose pointer must not be NULL)
+    return lowpass_refine(zero, _c(v), None, zero.view(-1)[:1], 0, taps, levels, out=zero)
+
+
 def quantize_u8(x):
     _chk(x)
     x = _c(x)

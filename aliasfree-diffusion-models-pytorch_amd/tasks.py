@@ -406,6 +406,14 @@ def inpaint_results(model_data, images, mask, **kw):
     return diffusion.inpaint(model, images, mask, **kw)
 
 
+def ilvr_results(model_data, reference, **kw):
+    """Load the checkpoint as rotation_results does, seed, and draw samples that keep the coarse content of `reference`
+    (Diffusion.ilvr; **kw: factor, t_stop, taps, steps, eta, labels, cfg_scale, noise_source, graph, return_float)."""
+    model, diffusion, _ = _load(model_data)
+    set_seed(model_data["seed"])
+    return diffusion.ilvr(model, reference, **kw)
+
+
 def bpd_results(model_data, images, **kw):
     """Load the checkpoint as rotation_results does, seed, and score `images` in bits/dim (Diffusion.calc_bpd; **kw: labels,
     sigma, t_samples, batch, noise_source, noise_fn, return_terms).  Returns calc_bpd's dict."""

@@ -479,6 +479,26 @@ int afd_ddim_step_masked_cfg_dev(const float* x, const float* eps2, const float*
  * Requires 0 <= t_from < t_to (t_to is not checked against the table's length) and n > 0.  x_out may alias x. */
 int afd_renoise(const float* x, const float* noise, const float* alpha_hat, int t_from, int t_to, float* x_out, long n,
                 afd_stream_t stream);
+/* ---- reference-guided sampling (ILVR, Choi et al. 2021): the low-pass refinement after a sampler step ----
+ * With one N x N filter (N odd, N <= 15), D = afd_filt_down2_fwd and U = afd_filt_up2_fwd, both with these taps, and L = levels:
+ *   phi(v) = 4^L U^L(D^L(v))                                  (factor 2^L; the 4 per level undoes up2's DC gain of 1/4)
+ * Per S x S plane (`planes` of them, contiguous; S a power of two in [4, 64], L >= 1, S / 2^L >= 2), one workgroup per plane:
+ *   known = ref                                               if t_prev == 0
+ *           (sqrt(a) * ref) + (sqrt(1 - a) * noise)           otherwise, a = alpha_hat[t_prev] (afd_noise_images' order, fp32,
+ *                                                             one rounding per operation)
+ *   out   = x + 4^L r,   r = U^L(D^L(known - x))              (x_out2, when given, receives the same values)
+ * The tap sums run in the general resamplers' order (a outer, b inner, ascending; U visits only the taps that land on a
+ * sample), each step a fused multiply-add; no atomics, so the same bits from call to call.  For symmetric taps U = D^T and phi is
+ * symmetric positive semi-definite.  noise may be NULL only when t_prev == 0 on the host form and never on the _dev form.
+ * x_out may be x itself (the plane is read before it is written) and is otherwise apart from it; ref and noise must not overlap
+ * x_out or x_out2.  Requires t_prev >= 0 (not checked against the table's length) and planes > 0. */
+int afd_lowpass_refine(const float* x, const float* ref, const float* noise /* NULL only when t_prev == 0 */, const float* alpha_hat,
+                       int t_prev, const float* taps /* HOST float[N*N] */, int N, int levels, float* x_out,
+                       float* x_out2 /* or NULL */, long planes, int S, afd_stream_t stream);
+/* same with t_prev = t_prev_dev[0] read on the device (graph-replayable; the index is not checked; 0 => known = ref) */
+int afd_lowpass_refine_dev(const float* x, const float* ref, const float* noise, const float* alpha_hat, const int64_t* t_prev_dev,
+                           const float* taps /* HOST float[N*N] */, int N, int levels, float* x_out, float* x_out2 /* or NULL */,
+                           long planes, int S, afd_stream_t stream);
 int afd_quantize_u8(const float* x, uint8_t* out, long n, afd_stream_t stream);
 
 /* ---- F17 (Config E): scipy.ndimage.rotate(order=3, mode='grid-wrap', prefilter=True) per (H,W) plane ----
