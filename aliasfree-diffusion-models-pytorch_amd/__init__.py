@@ -12,14 +12,16 @@ from .blocks import (SelfAttention, DoubleConv, DoubleConv_F, DoubleConv_F4, Dow
                      Down_F4, Up, Up_F, Up_FF, Up_FFF, Up_F4)
 from .ops import NULL_LABEL, nn_search  # noqa: F401
 from .spectrum import compare_spectra, hann_window, power_spectrum, spectrum_bins  # noqa: F401
+from .fidelity import (FeatureStats, extract_features, feature_stats, fidelity, frechet_distance, inception_score,  # noqa: F401
+                       kernel_distance, mmd_indices, mmd_sums)
 from .unet import UNet  # noqa: F401
 from .diffusion import Diffusion  # noqa: F401
 from .training import (argument, set_seed, setup_logging, train, TrainStep, FusedAdamW, FlatParams,  # noqa: F401
                        GradAllReduce, EMA, LRSchedule, clip_coefficient, DistillStep, progressive_distill,
                        LossSecondMomentSampler)
 
-from .tasks import (bpd_results, ddpm_run, equivariance_results, ilvr_results, inpaint_results, rotation_results,  # noqa: F401
-                    shift_results, spectrum_results)
+from .tasks import (bpd_results, ddpm_run, equivariance_results, fidelity_results, ilvr_results, inpaint_results,  # noqa: F401
+                    rotation_results, shift_results, spectrum_results)
 from .data import (get_data, get_data_MNIST, save_gen_images, make_collage, DeviceDataset, DeviceLoader,  # noqa: F401
                    get_data_device, get_data_MNIST_device)
 

@@ -109,7 +109,8 @@ class DeviceDataset:
     device="cpu" runs `batch` as plain torch indexing: the same values, and the oracle of the kernels' tests.
     `nearest` / `self_nearest` search the store for the nearest images of a set of queries; on
     device="cpu" they are a plain torch brute force, the oracle of that kernel's tests.
-    `power_spectrum` is the mean power spectrum of the store's images."""
+    `power_spectrum` is the mean power spectrum of the store's images.
+    `feature_stats` is the mean and covariance of an extractor's features of the store's images, for FID."""
 
     def __init__(self, images, labels=None, mean=0.5, std=0.5, device="cuda", classes=None):
         if isinstance(images, np.ndarray):
@@ -220,6 +221,29 @@ class DeviceDataset:
         if n is not None and (isinstance(n, bool) or not isinstance(n, (int, np.integer)) or not 1 <= n <= len(self)):
             raise ValueError(f"DeviceDataset.power_spectrum: n must be None or an int in [1, {len(self)}] (got {n!r})")
         return power_spectrum(self.images if n is None else self.images[:int(n)], self.table, window, remove_mean)
+
+    def pixels(self, n=None):
+        """The first n images of the store (None: all) as uint8 pixels: a uint8 store's own bytes; a float32 store's values mapped
+        back from [-1, 1], (x clamped + 1) * 127.5 rounded to the nearest pixel value."""
+        if n is not None and (isinstance(n, bool) or not isinstance(n, (int, np.integer)) or not 1 <= n <= len(self)):
+            raise ValueError(f"DeviceDataset.pixels: n must be None or an int in [1, {len(self)}] (got {n!r})")
+        x = self.images if n is None else self.images[:int(n)]
+        return x if x.dtype == torch.uint8 else ((x.clamp(-1, 1) + 1) * 127.5).round().to(torch.uint8)
+
+    def feature_stats(self, extractor, n=None, batch=256):
+        """fidelity.FeatureStats of the features `extractor` makes of the first n images of the store (None: all), read as
+        pixels(n), `batch` images at a time (fidelity.extract_features; afd_feature_moments_f32 on the device, plain torch on
+        device="cpu").  Its state() can be saved and reused as a training set's reference statistics."""
+        from .fidelity import FeatureStats, extract_features, load_extractor
+        images, extractor = self.pixels(n), load_extractor(extractor, self.device)
+        if isinstance(batch, bool) or not isinstance(batch, (int, np.integer)) or batch < 1:
+            raise ValueError(f"DeviceDataset.feature_stats: batch must be an integer >= 1 (got {batch!r})")
+        stats = None
+        for a in range(0, images.shape[0], int(batch)):
+            f = extract_features(extractor, images[a:a + int(batch)], int(batch))[0]
+            stats = FeatureStats(f.shape[1], self.device) if stats is None else stats
+            stats.update(f)
+        return stats
 
     def _nearest_torch(self, queries, k, exclude):
         """Brute force in plain torch: int64 sums of squared differences (uint8) or fp64 sums rounded once to float32, then a stable

@@ -2054,3 +2054,72 @@ def power_spectrum(images, table=None, win_h=None, win_w=None, remove_mean=True,
     else:
         lib().afd_power_spectrum_f32(_p(images), *tail)
     return power, radial
+
+
+MMD_MAX_DEGREE = 8
+MMD_MAX_M = 1 << 16
+
+
+def feature_moments(features, sum=None, outer=None):
+    """Sum and sum of outer products of a feature set in fp64 (afd.h: afd_feature_moments_f32).  features (n, D) fp32 on the device
+    (made contiguous if it is not); sum (D,) and outer (D, D): contiguous fp64 device tensors to ADD to, given together, or None
+    for fresh ones.  -> (sum, outer): sum[c] = sum_r x[r][c], outer[i][j] = sum_r x[r][i] x[r][j], outer symmetric bit for bit."""
+    what = "feature_moments"
+    if not isinstance(features, torch.Tensor) or not features.is_cuda or features.dim() != 2 or features.numel() == 0 \
+            or features.dtype != torch.float32:
+        raise AfdError(f"afdm: {what}: features must be a non-empty (n, D) fp32 device tensor")
+    features = _c(features.detach())
+    n, D = features.shape
+    if (sum is None) != (outer is None):
+        raise AfdError(f"afdm: {what}: sum and outer go together")
+    accumulate = sum is not None
+    if accumulate:
+        _dev_table(what, "sum", sum, torch.float64, (D,))
+        _dev_table(what, "outer", outer, torch.float64, (D, D))
+    else:
+        sum = torch.empty(D, device=features.device, dtype=torch.float64)
+        outer = torch.empty(D, D, device=features.device, dtype=torch.float64)
+    nbytes = int(lib().afd_feature_moments_workspace_bytes(n, D))
+    if nbytes <= 0:
+        raise AfdError(f"afdm: {what}: sizes out of range (n = {n}, D = {D})")
+    ws = torch.empty(nbytes // 8, device=features.device, dtype=torch.float64)
+    lib().afd_feature_moments_f32(_p(features), n, D, _p(sum), _p(outer), int(accumulate), _p(ws), nbytes, _stream())
+    return sum, outer
+
+
+def poly_mmd_sums(a, b, ia, ib, degree, gamma, coef0, check_range=True):
+    """The three kernel sums of a polynomial-kernel MMD per subset, in fp64 (afd.h: afd_poly_mmd_sums_f32).  a (na, D) and b (nb, D)
+    fp32 on the device (made contiguous if they are not), ia and ib (S, m) int64 row indices into a and b on the device, m >= 2;
+    k(x, y) = (gamma x.y + coef0)^degree, degree an int in [1, 8].  -> sums (S, 3) fp64: the sum of k over i != j within a's rows,
+    the same within b's, and over all (i, j) between them.  check_range: the indices are checked against na and nb first (one
+    synchronising read); without it an index out of range makes its row NaN."""
+    what = "poly_mmd_sums"
+    for name, v in (("a", a), ("b", b)):
+        if not isinstance(v, torch.Tensor) or not v.is_cuda or v.dim() != 2 or v.numel() == 0 or v.dtype != torch.float32:
+            raise AfdError(f"afdm: {what}: {name} must be a non-empty (n, D) fp32 device tensor")
+    if a.shape[1] != b.shape[1]:
+        raise AfdError(f"afdm: {what}: a and b must have one row size (got {a.shape[1]} and {b.shape[1]})")
+    a, b = _c(a.detach()), _c(b.detach())
+    (na, D), nb = a.shape, b.shape[0]
+    for name, v in (("ia", ia), ("ib", ib)):
+        if not isinstance(v, torch.Tensor) or not v.is_cuda or v.dtype != torch.long or v.dim() != 2 or not v.is_contiguous():
+            raise AfdError(f"afdm: {what}: {name} must be a contiguous (S, m) int64 device tensor")
+    S, m = ia.shape
+    if tuple(ib.shape) != (S, m) or S < 1 or not 2 <= m <= MMD_MAX_M:
+        raise AfdError(f"afdm: {what}: ia and ib must have one shape (S, m) with S >= 1 and m in [2, {MMD_MAX_M}] (got {tuple(ia.shape)} "
+                       f"and {tuple(ib.shape)})")
+    if isinstance(degree, bool) or not isinstance(degree, (int, np.integer)) or not 1 <= degree <= MMD_MAX_DEGREE:
+        raise AfdError(f"afdm: {what}: degree must be an int in [1, {MMD_MAX_DEGREE}] (got {degree!r})")
+    if check_range:
+        lo, hi = torch.stack([ia.amin(), ib.amin()]).tolist(), torch.stack([ia.amax(), ib.amax()]).tolist()
+        if lo[0] < 0 or hi[0] >= na or lo[1] < 0 or hi[1] >= nb:
+            raise AfdError(f"afdm: {what}: an index lies outside its array (ia in [{lo[0]}, {hi[0]}] for {na} rows, ib in [{lo[1]}, {hi[1]}] "
+                           f"for {nb} rows)")
+    nbytes = int(lib().afd_poly_mmd_workspace_bytes(S, m, D))
+    if nbytes <= 0:
+        raise AfdError(f"afdm: {what}: sizes out of range (S = {S}, m = {m}, D = {D})")
+    sums = torch.empty(S, 3, device=a.device, dtype=torch.float64)
+    ws = torch.empty(nbytes // 8, device=a.device, dtype=torch.float64)
+    lib().afd_poly_mmd_sums_f32(_p(a), na, _p(b), nb, D, _p(ia), _p(ib), S, m, int(degree), float(gamma), float(coef0), _p(sums), _p(ws),
+                                nbytes, _stream())
+    return sums

@@ -85,6 +85,8 @@ def ddpm_run(params):
         _nearest_cfg(params)
     if params.get("eval_spectrum") is not None:
         _spectrum_cfg(params)
+    if params.get("eval_fidelity") is not None:
+        _fidelity_cfg(params)
     cwd = os.getcwd()
     modelpath = os.path.join(cwd, f"models/DDPM_Uncondtional_{name}_{v}/ckpt_{name}_{v}.pt")
     f_settings = _f_settings(params)
@@ -175,7 +177,8 @@ def ddpm_run(params):
         distill, gen_model, gen_kw = _distill(params, args, diffusion, gen_model, modelpath, name, seed, dataloader)
     nearest_n = _nearest_cfg(params)["n"] if params.get("eval_nearest") is not None else 0
     spectrum_n = _spectrum_cfg(params)["n"] if params.get("eval_spectrum") is not None else 0
-    keep_n = max(nearest_n, spectrum_n)
+    fidelity_n = _fidelity_cfg(params)["n"] if params.get("eval_fidelity") is not None else 0
+    keep_n = max(nearest_n, spectrum_n, fidelity_n)
     generated = []                                             # the first images of the set that an evaluation asks for, uint8 as sampled
     for start in np.arange(0, params["gen_total"], params["gen_per_batch"]):
         fileno = np.arange(start, start + params["gen_per_batch"], 1)
@@ -210,6 +213,11 @@ def ddpm_run(params):
     # n generated images against that of the first n training images (spectrum.power_spectrum / compare_spectra)
     if params.get("eval_spectrum") is not None:
         out["spectrum"] = _eval_spectrum(params, args, torch.cat(generated), run_dir, name, v, dev_set)
+    # optional FID / KID / Inception Score: params["eval_fidelity"] = {"n": ..., "extractor": a callable, the path of a TorchScript
+    # file or "pixels", "kid_subsets": ..., "kid_subset_size": ...} scores the first n generated images against the first n training
+    # images through the extractor (fidelity.fidelity)
+    if params.get("eval_fidelity") is not None:
+        out["fidelity"] = _eval_fidelity(params, args, torch.cat(generated), run_dir, name, v, dev_set)
     return out
 
 
@@ -336,6 +344,51 @@ def _eval_spectrum(params, args, generated, run_dir, name, v, dataset=None):
     return res
 
 
+def _fidelity_cfg(params):
+    cfg = params["eval_fidelity"]
+    if not isinstance(cfg, dict) or set(cfg) - {"n", "extractor", "kid_subsets", "kid_subset_size"} or not {"n", "extractor"} <= set(cfg):
+        raise ValueError(f"ddpm_run: eval_fidelity needs n and extractor (and optionally kid_subsets, kid_subset_size); got "
+                         f"{sorted(cfg) if isinstance(cfg, dict) else type(cfg).__name__}")
+    n, extractor = cfg["n"], cfg["extractor"]
+    if isinstance(n, bool) or not isinstance(n, (int, np.integer)) or not 2 <= n <= params["gen_total"]:
+        raise ValueError(f"ddpm_run: eval_fidelity n must be an int in [2, gen_total, the size of the generated set] (got {n!r})")
+    if not callable(extractor) and not isinstance(extractor, str):
+        raise ValueError(f"ddpm_run: eval_fidelity extractor must be a callable, the path of a TorchScript file or 'pixels' (got "
+                         f"{type(extractor).__name__})")
+    if isinstance(extractor, str) and extractor != "pixels" and not os.path.isfile(extractor):
+        raise ValueError(f"ddpm_run: eval_fidelity extractor {extractor!r} is neither 'pixels' nor an existing TorchScript file")
+    out = {"n": int(n), "extractor": extractor, "kid_subsets": cfg.get("kid_subsets", 100),
+           "kid_subset_size": cfg.get("kid_subset_size", min(1000, int(n)))}
+    for key, lo, hi in (("kid_subsets", 1, None), ("kid_subset_size", 2, int(n))):
+        val = out[key]
+        if isinstance(val, bool) or not isinstance(val, (int, np.integer)) or val < lo or (hi is not None and val > hi):
+            raise ValueError(f"ddpm_run: eval_fidelity {key} must be an int in [{lo}, {'...' if hi is None else 'n = ' + str(hi)}] (got {val!r})")
+        out[key] = int(val)
+    return out
+
+
+def _fidelity_pair(train, generated, cfg):
+    """fidelity.fidelity of generated uint8 images against as many of a DeviceDataset's first images, read as pixels."""
+    from .fidelity import fidelity
+    n = generated.shape[0]
+    return fidelity(generated.to(train.device), train.pixels(n), cfg["extractor"], kid_subsets=cfg["kid_subsets"],
+                    kid_subset_size=cfg["kid_subset_size"])
+
+
+def _eval_fidelity(params, args, generated, run_dir, name, v, dataset=None):
+    import json
+    cfg = _fidelity_cfg(params)
+    n = cfg["n"]
+    dataset = _training_store(name, args, dataset)
+    if not n <= len(dataset):
+        raise ValueError(f"ddpm_run: eval_fidelity n must lie in [2, {len(dataset)}] (the training set's size; got {n})")
+    res = _fidelity_pair(dataset, generated[:n], cfg)
+    with open(os.path.join(run_dir, f"fidelity_{name}_{v}.json"), "w") as fh:
+        json.dump(dict(res, n=n, kid_subsets=cfg["kid_subsets"], kid_subset_size=cfg["kid_subset_size"]), fh, indent=1)
+    print("fidelity: " + ", ".join(f"{k} {val:.6g}" for k, val in res.items()) + f" ({n} samples against {n} training images)")
+    return res
+
+
 def _eval_bpd(params, args, diffusion, model, run_dir, name, v, seed, dataset=None):
     N, K, sigma = int(params["eval_bpd"]), params.get("eval_bpd_t_samples"), params.get("eval_bpd_sigma", "beta")
     if dataset is None:
@@ -434,6 +487,24 @@ def spectrum_results(model_data, images, n, window="hann", remove_mean=True, **k
     set_seed(model_data["seed"])
     x, _ = diffusion.sample(model, n=int(n), image_channels=args.image_channels, **kw)
     return _spectrum_pair(train, x, window, remove_mean)
+
+
+def fidelity_results(model_data, images, n, extractor, **kw):
+    """Load the checkpoint as rotation_results does, seed, draw n samples (Diffusion.sample; **kw: steps, eta, sampler, ..., and
+    kid_subsets / kid_subset_size, which are taken out first) and score them against the first n of `images`: a DeviceDataset, or
+    (N, C, H, W) uint8 pixels or float32 values on the loader's scale.  Returns fidelity.fidelity's dict, as ddpm_run does for
+    params["eval_fidelity"]."""
+    kw = dict(kw)
+    cfg = {"n": n, "extractor": extractor}
+    cfg.update({k: kw.pop(k) for k in ("kid_subsets", "kid_subset_size") if k in kw})
+    if isinstance(n, bool) or not isinstance(n, (int, np.integer)) or not 2 <= n <= len(images):
+        raise ValueError(f"fidelity_results: n must be an int in [2, {len(images)}] (the number of images; got {n!r})")
+    cfg = _fidelity_cfg({"eval_fidelity": cfg, "gen_total": int(n)})
+    model, diffusion, args = _load(model_data)
+    train = images if isinstance(images, DeviceDataset) else DeviceDataset(images[:n], device=args.device)
+    set_seed(model_data["seed"])
+    x, _ = diffusion.sample(model, n=int(n), image_channels=args.image_channels, **kw)
+    return _fidelity_pair(train, x, cfg)
 
 
 def equivariance_results(model_data, images, **kw):

@@ -838,6 +838,46 @@ int afd_power_spectrum_f32(const float* images, long n, long C, long H, long W, 
                            const double* win_w_or_null, int remove_mean, const int* bins_or_null, long R, double* power_or_null,
                            double* radial_or_null, void* workspace, size_t workspace_bytes, afd_stream_t stream);
 
+/* ---- moments of a feature set and polynomial-kernel MMD sums, in fp64 (csrc/fidelity.hip) ----- fidelity.FeatureStats, kernel_distance
+ * The two contractions behind FID and KID.  Every fp32 value is widened to double while it is staged and
+ * everything after that is fp64 on the fp64 matrix pipe; there is no fp64 copy of an input in memory, and neither the per-row
+ * outer products nor a Gram matrix is ever stored.  Each call is two launches on `stream`: the first leaves per-workgroup partials
+ * in the workspace, the second folds them in a fixed order.  No atomics, no allocation, no memset (the workspace needs no initial
+ * contents), no synchronisation, so a call can be captured into a graph and repeats bit for bit.
+ *
+ * afd_feature_moments_f32: X is a contiguous (n, D) array of floats, any n >= 1 and D >= 1.
+ *     sum[c]      = sum_r X[r][c]                                                                          (D)
+ *     outer[i][j] = sum_r X[r][i] X[r][j]                                                                  (D, D)
+ * accumulate = 0 overwrites sum and outer, accumulate = 1 adds to what they hold, so a caller can feed batch after batch.  Only
+ * the 64 x 64 tiles on or above the diagonal are computed; an element and its mirror image are written from one value, so outer
+ * is symmetric bit for bit (with accumulate = 1 the elements on and above the diagonal are the ones read).  n is split into at
+ * most 64 slabs, a number that depends on (n, D) alone; a slab sums its rows in index order, and the slabs are added in slab
+ * order.  A NaN at X[r][c] makes sum[c], outer[c][:] and outer[:][c] NaN and nothing else.
+ * AFD_EINVAL (nothing launched) on a NULL X / sum / outer / workspace, n or D <= 0, n >= 2^31, D > 2^15, n D > 2^40, accumulate
+ * not 0 or 1, X not 4-byte aligned, sum / outer / workspace not 8-byte aligned, a workspace smaller than
+ * afd_feature_moments_workspace_bytes (0 for sizes the call rejects), or sum / outer / workspace overlapping X or each other.
+ *
+ * afd_poly_mmd_sums_f32: A (na, D) and B (nb, D) are contiguous arrays of floats, ia and ib (S, m) int64 row indices into A and
+ * B, k(x, y) = (gamma x.y + coef0)^degree with degree an int in [1, 8], the power taken by repeated multiplication.  For subset s,
+ * with a_i = A[ia[s][i]] and b_j = B[ib[s][j]],
+ *     sums[s][0] = sum_{i != j} k(a_i, a_j)     sums[s][1] = sum_{i != j} k(b_i, b_j)     sums[s][2] = sum_{i, j} k(a_i, b_j)
+ * Rows are gathered by index while they are staged.  The two symmetric problems compute the 64 x 64 tiles on or above the
+ * diagonal: a tile above it counts twice, a diagonal tile leaves i == j out.  A workgroup sums its tile in a fixed order, and the
+ * tiles of a sum are added in a fixed order.  Any m >= 2, S >= 1 and D >= 1; indices may repeat.  An index outside [0, na) /
+ * [0, nb) reads nothing outside the arrays: that row counts as NaN.  A NaN in a row reaches only the sums of the subsets that
+ * index the row, and only those the row takes part in.
+ * AFD_EINVAL (nothing launched) on a NULL A / B / ia / ib / sums / workspace, na, nb, D or S <= 0, m < 2, m > 2^16, degree outside
+ * [1, 8], D >= 2^31, na D or nb D > 2^40, more than 2^31 - 1 workgroups, A / B not 4-byte aligned, ia / ib / sums / workspace not
+ * 8-byte aligned, a workspace smaller than afd_poly_mmd_workspace_bytes (0 for sizes the call rejects), or sums / workspace
+ * overlapping an input or each other. */
+size_t afd_feature_moments_workspace_bytes(long n, long D);
+int afd_feature_moments_f32(const float* X, long n, long D, double* sum, double* outer, int accumulate, void* workspace,
+                            size_t workspace_bytes, afd_stream_t stream);
+size_t afd_poly_mmd_workspace_bytes(long S, long m, long D);
+int afd_poly_mmd_sums_f32(const float* A, long na, const float* B, long nb, long D, const int64_t* ia, const int64_t* ib, long S, long m,
+                          int degree, double gamma, double coef0, double* sums, void* workspace, size_t workspace_bytes,
+                          afd_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
