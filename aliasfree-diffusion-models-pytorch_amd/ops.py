@@ -2123,3 +2123,61 @@ def poly_mmd_sums(a, b, ia, ib, degree, gamma, coef0, check_range=True):
     lib().afd_poly_mmd_sums_f32(_p(a), na, _p(b), nb, D, _p(ia), _p(ib), S, m, int(degree), float(gamma), float(coef0), _p(sums), _p(ws),
                                 nbytes, _stream())
     return sums
+
+
+MANIFOLD_MAX_K = 16
+
+
+def _feature_set(what, name, v, D=None):
+    if not isinstance(v, torch.Tensor) or not v.is_cuda or v.dim() != 2 or v.numel() == 0 or v.dtype != torch.float32:
+        raise AfdError(f"afdm: {what}: {name} must be a non-empty (n, D) fp32 device tensor")
+    if D is not None and v.shape[1] != D:
+        raise AfdError(f"afdm: {what}: {name} must have the row size {D} (got {v.shape[1]})")
+    return _c(v.detach())
+
+
+def kth_neighbour(features, k):
+    """Per row of a feature set the k-th smallest squared L2 distance to another row, in fp64 (afd.h: afd_kth_neighbour_f32).
+    features (n, D) fp32 on the device (made contiguous if it is not), k an int in [1, 16].  -> radius2 (n,) fp64; rows are left
+    out by index, a NaN distance is no candidate, and a row with fewer than k candidates gets +inf."""
+    what = "kth_neighbour"
+    features = _feature_set(what, "features", features)
+    if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 1 <= k <= MANIFOLD_MAX_K:
+        raise AfdError(f"afdm: {what}: k must be an int in [1, {MANIFOLD_MAX_K}] (got {k!r})")
+    n, D = features.shape
+    nbytes = int(lib().afd_kth_neighbour_workspace_bytes(n, D, int(k)))
+    if nbytes <= 0:
+        raise AfdError(f"afdm: {what}: sizes out of range (n = {n}, D = {D})")
+    radius2 = torch.empty(n, device=features.device, dtype=torch.float64)
+    ws = torch.empty(nbytes // 8, device=features.device, dtype=torch.float64)
+    lib().afd_kth_neighbour_f32(_p(features), n, D, int(k), _p(radius2), _p(ws), nbytes, _stream())
+    return radius2
+
+
+def ball_membership(queries, store, radius2, exclude=None, want_count=True, want_nearest=True):
+    """For each query row the number of store rows whose ball holds it and its nearest store row, in fp64 (afd.h:
+    afd_ball_membership_f32).  queries (nq, D) and store (nr, D) fp32 on the device (made contiguous if they are not), radius2
+    (nr,) fp64: the squared radius of each store row's ball; exclude None or (nq,) int64 on the device: query q skips store row
+    exclude[q] (negative: nothing).  -> (count (nq,) int32, nearest (nq,) int64, nearest_d2 (nq,) fp64), None for what was not
+    asked for: count[q] is the number of j with d2(q, j) <= radius2[j], nearest[q] the j of smallest d2 (ties to the lower j; -1
+    and +inf with no candidate)."""
+    what = "ball_membership"
+    queries = _feature_set(what, "queries", queries)
+    store = _feature_set(what, "store", store, queries.shape[1])
+    (nq, D), nr = queries.shape, store.shape[0]
+    _dev_table(what, "radius2", radius2, torch.float64, (nr,))
+    if exclude is not None:
+        _dev_table(what, "exclude", exclude, torch.long, (nq,))
+    if not want_count and not want_nearest:
+        raise AfdError(f"afdm: {what}: nothing to compute (want_count and want_nearest are both False)")
+    nbytes = int(lib().afd_ball_membership_workspace_bytes(nq, nr, D))
+    if nbytes <= 0:
+        raise AfdError(f"afdm: {what}: sizes out of range (nq = {nq}, nr = {nr}, D = {D})")
+    dev = queries.device
+    count = torch.empty(nq, device=dev, dtype=torch.int32) if want_count else None
+    nearest = torch.empty(nq, device=dev, dtype=torch.long) if want_nearest else None
+    nearest_d2 = torch.empty(nq, device=dev, dtype=torch.float64) if want_nearest else None
+    ws = torch.empty(nbytes // 8, device=dev, dtype=torch.float64)
+    lib().afd_ball_membership_f32(_p(queries), nq, _p(store), nr, D, _p(radius2), _p(exclude), _p(count), _p(nearest), _p(nearest_d2),
+                                  _p(ws), nbytes, _stream())
+    return count, nearest, nearest_d2

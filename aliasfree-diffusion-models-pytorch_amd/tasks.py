@@ -87,6 +87,8 @@ def ddpm_run(params):
         _spectrum_cfg(params)
     if params.get("eval_fidelity") is not None:
         _fidelity_cfg(params)
+    if params.get("eval_manifold") is not None:
+        _manifold_cfg(params)
     cwd = os.getcwd()
     modelpath = os.path.join(cwd, f"models/DDPM_Uncondtional_{name}_{v}/ckpt_{name}_{v}.pt")
     f_settings = _f_settings(params)
@@ -133,6 +135,9 @@ def ddpm_run(params):
     # train
     set_seed(seed)
     dataloader, dataset = _loader(name, args, params)
+    if params.get("eval_manifold") is not None and not _manifold_cfg(params)["n"] <= len(dataset):
+        raise ValueError(f"ddpm_run: eval_manifold n must be at most {len(dataset)} (the training set's size; got "
+                         f"{_manifold_cfg(params)['n']})")
     model = UNet(c_in=args.image_channels, c_out=model_out_channels(args), image_size=args.image_size, f_settings=f_settings,
                  device=args.device, variant=v).to(args.device)
     diffusion = Diffusion(noise_steps=args.noise_steps, img_size=args.image_size, device=args.device, **diffusion_kwargs(args))
@@ -178,7 +183,8 @@ def ddpm_run(params):
     nearest_n = _nearest_cfg(params)["n"] if params.get("eval_nearest") is not None else 0
     spectrum_n = _spectrum_cfg(params)["n"] if params.get("eval_spectrum") is not None else 0
     fidelity_n = _fidelity_cfg(params)["n"] if params.get("eval_fidelity") is not None else 0
-    keep_n = max(nearest_n, spectrum_n, fidelity_n)
+    manifold_n = _manifold_cfg(params)["n"] if params.get("eval_manifold") is not None else 0
+    keep_n = max(nearest_n, spectrum_n, fidelity_n, manifold_n)
     generated = []                                             # the first images of the set that an evaluation asks for, uint8 as sampled
     for start in np.arange(0, params["gen_total"], params["gen_per_batch"]):
         fileno = np.arange(start, start + params["gen_per_batch"], 1)
@@ -218,6 +224,11 @@ def ddpm_run(params):
     # images through the extractor (fidelity.fidelity)
     if params.get("eval_fidelity") is not None:
         out["fidelity"] = _eval_fidelity(params, args, torch.cat(generated), run_dir, name, v, dev_set)
+    # optional precision / recall / density / coverage: params["eval_manifold"] = {"n": ..., "extractor": as for eval_fidelity,
+    # "k": ...} (k defaults to 3) scores the first n generated images against the first n training images through the extractor
+    # (manifold.manifold)
+    if params.get("eval_manifold") is not None:
+        out["manifold"] = _eval_manifold(params, args, torch.cat(generated), run_dir, name, v, dev_set)
     return out
 
 
@@ -389,6 +400,45 @@ def _eval_fidelity(params, args, generated, run_dir, name, v, dataset=None):
     return res
 
 
+def _manifold_cfg(params):
+    cfg = params["eval_manifold"]
+    if not isinstance(cfg, dict) or set(cfg) - {"n", "extractor", "k"} or not {"n", "extractor"} <= set(cfg):
+        raise ValueError(f"ddpm_run: eval_manifold needs n and extractor (and optionally k); got "
+                         f"{sorted(cfg) if isinstance(cfg, dict) else type(cfg).__name__}")
+    n, extractor, k = cfg["n"], cfg["extractor"], cfg.get("k", 3)
+    if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 1 <= k <= 16:
+        raise ValueError(f"ddpm_run: eval_manifold k must be an int in [1, 16] (got {k!r})")
+    if isinstance(n, bool) or not isinstance(n, (int, np.integer)) or not k + 1 <= n <= params["gen_total"]:
+        raise ValueError(f"ddpm_run: eval_manifold n must be an int in [k + 1 = {k + 1}, gen_total, the size of the generated set] "
+                         f"(got {n!r})")
+    if not callable(extractor) and not isinstance(extractor, str):
+        raise ValueError(f"ddpm_run: eval_manifold extractor must be a callable, the path of a TorchScript file or 'pixels' (got "
+                         f"{type(extractor).__name__})")
+    if isinstance(extractor, str) and extractor != "pixels" and not os.path.isfile(extractor):
+        raise ValueError(f"ddpm_run: eval_manifold extractor {extractor!r} is neither 'pixels' nor an existing TorchScript file")
+    return {"n": int(n), "extractor": extractor, "k": int(k)}
+
+
+def _manifold_pair(train, generated, cfg):
+    """manifold.manifold of generated uint8 images against as many of a DeviceDataset's first images, read as pixels."""
+    from .manifold import manifold
+    return manifold(generated.to(train.device), train.pixels(generated.shape[0]), cfg["extractor"], k=cfg["k"])
+
+
+def _eval_manifold(params, args, generated, run_dir, name, v, dataset=None):
+    import json
+    cfg = _manifold_cfg(params)
+    n = cfg["n"]
+    dataset = _training_store(name, args, dataset)
+    if not n <= len(dataset):
+        raise ValueError(f"ddpm_run: eval_manifold n must lie in [{cfg['k'] + 1}, {len(dataset)}] (the training set's size; got {n})")
+    res = _manifold_pair(dataset, generated[:n], cfg)
+    with open(os.path.join(run_dir, f"manifold_{name}_{v}.json"), "w") as fh:
+        json.dump(dict(res, n=n, k=cfg["k"]), fh, indent=1)
+    print("manifold: " + ", ".join(f"{key} {val:.6g}" for key, val in res.items()) + f" ({n} samples against {n} training images, k = {cfg['k']})")
+    return res
+
+
 def _eval_bpd(params, args, diffusion, model, run_dir, name, v, seed, dataset=None):
     N, K, sigma = int(params["eval_bpd"]), params.get("eval_bpd_t_samples"), params.get("eval_bpd_sigma", "beta")
     if dataset is None:
@@ -505,6 +555,20 @@ def fidelity_results(model_data, images, n, extractor, **kw):
     set_seed(model_data["seed"])
     x, _ = diffusion.sample(model, n=int(n), image_channels=args.image_channels, **kw)
     return _fidelity_pair(train, x, cfg)
+
+
+def manifold_results(model_data, images, n, extractor, k=3, **kw):
+    """Load the checkpoint as rotation_results does, seed, draw n samples (Diffusion.sample; **kw: steps, eta, sampler, ...) and
+    score them against the first n of `images`: a DeviceDataset, or (N, C, H, W) uint8 pixels or float32 values on the loader's
+    scale.  Returns manifold.manifold_scores' dict, as ddpm_run does for params["eval_manifold"]."""
+    if isinstance(n, bool) or not isinstance(n, (int, np.integer)) or not 2 <= n <= len(images):
+        raise ValueError(f"manifold_results: n must be an int in [2, {len(images)}] (the number of images; got {n!r})")
+    cfg = _manifold_cfg({"eval_manifold": {"n": n, "extractor": extractor, "k": k}, "gen_total": int(n)})
+    model, diffusion, args = _load(model_data)
+    train = images if isinstance(images, DeviceDataset) else DeviceDataset(images[:n], device=args.device)
+    set_seed(model_data["seed"])
+    x, _ = diffusion.sample(model, n=int(n), image_channels=args.image_channels, **kw)
+    return _manifold_pair(train, x, cfg)
 
 
 def equivariance_results(model_data, images, **kw):

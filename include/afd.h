@@ -878,6 +878,50 @@ int afd_poly_mmd_sums_f32(const float* A, long na, const float* B, long nb, long
                           int degree, double gamma, double coef0, double* sums, void* workspace, size_t workspace_bytes,
                           afd_stream_t stream);
 
+/* ---- k-th neighbour radii and ball membership of feature sets, in fp64 (csrc/manifold.hip) ---- manifold.manifold_scores
+ * The two contractions behind precision / recall / density / coverage.  Every fp32 value is widened to
+ * double while it is staged and everything after that is fp64 on the fp64 matrix pipe; there is no fp64 copy of an input in
+ * memory, and no distance matrix is ever stored.
+ *
+ * The distance.  d2(a, b) = max(0, (s_a + s_b) - 2 a.b), where a.b is one chain of mfma_f64_16x16x4_f64 over the D elements, 4 per
+ * instruction in ascending order from a zero accumulator, and s_a = a.a is the same chain.  Every product is exact, only the
+ * additions round.  So: d2 is a function of the two rows and D alone (not of n, a row's position, the tiling, or which of the two is
+ * the query), symmetric bit for bit and the same in both entry points; d2(a, a) == 0 exactly and d2 >= 0;
+ * |d2 - exact| <= 2 (D + 4) 2^-52 (|a|^2 + |b|^2); integer-valued rows whose sums stay below 2^53 give the exact integer.  A NaN in
+ * either row makes the distance NaN, and so does an infinity (inf - inf).
+ *
+ * afd_kth_neighbour_f32: X is a contiguous (n, D) array of floats, 1 <= k <= 16.  radius2[i] is the k-th smallest of d2(X_i, X_j)
+ * over j != i: rows are excluded by index, so an identical row elsewhere counts as a neighbour at 0.  A NaN distance is no
+ * candidate; with fewer than k candidates radius2[i] = +inf.
+ *
+ * afd_ball_membership_f32: Q (nq, D) and R (nr, D) are contiguous arrays of floats, radius2 nr doubles, exclude NULL or nq int64
+ * (query q skips store row exclude[q]; a negative value skips nothing).  For query q over the store rows j != exclude[q]:
+ *     count[q]      = the number of j with d2(Q_q, R_j) <= radius2[j]                                    (nq) int32
+ *     nearest[q]    = the j of smallest d2(Q_q, R_j), ties to the lower j;  nearest_d2[q] = that d2       (nq) int64, double
+ * A NaN distance or a NaN radius is in no ball and is never the nearest; a +inf radius holds every non-NaN distance.  With no
+ * candidate nearest = -1 and nearest_d2 = +inf.  nearest and nearest_d2 are given together or not at all; count may be NULL when
+ * they are given.
+ *
+ * Each call is a small pre-pass that leaves the rows' squared norms in the workspace, and two launches on `stream`: workgroup
+ * (stripe, segment) carries 64 rows (queries) past its segment of the other side and leaves their partial results in the
+ * workspace (the k smallest distances of the segment; the count and the nearest row there), and a second kernel folds the
+ * segments in index order.  The number of segments, at most 64, depends on the sizes alone, and the results do not depend on it.
+ * No atomics, no allocation, no memset (the workspace needs no initial contents), no synchronisation, so a call can be captured
+ * into a graph and repeats bit for bit.  Any pointer alignment of 4 bytes and any D take the same loads.
+ * afd_*_workspace_bytes: the bytes one call needs (at most 8 n (1 + 64 k), and 8 (nq + nr) + 20 x 64 nq; 0 for sizes the call
+ * rejects).
+ * AFD_EINVAL (nothing launched) on a NULL X / radius2 / Q / R / workspace, count, nearest and nearest_d2 all NULL or only one of
+ * nearest and nearest_d2 given, n, nq, nr or D <= 0, k outside [1, 16], n, nq or nr >= 2^31, D > 2^15, rows x D > 2^40, X / Q / R /
+ * count not 4-byte aligned, radius2 / exclude / nearest / nearest_d2 / workspace not 8-byte aligned, a workspace that is too
+ * small, or an output or the workspace overlapping an input or each other. */
+size_t afd_kth_neighbour_workspace_bytes(long n, long D, long k);
+int afd_kth_neighbour_f32(const float* X, long n, long D, long k, double* radius2, void* workspace, size_t workspace_bytes,
+                          afd_stream_t stream);
+size_t afd_ball_membership_workspace_bytes(long nq, long nr, long D);
+int afd_ball_membership_f32(const float* Q, long nq, const float* R, long nr, long D, const double* radius2,
+                            const int64_t* exclude_or_null, int* count_or_null, int64_t* nearest_or_null, double* nearest_d2_or_null,
+                            void* workspace, size_t workspace_bytes, afd_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
