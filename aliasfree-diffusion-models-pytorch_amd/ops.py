@@ -2181,3 +2181,43 @@ def ball_membership(queries, store, radius2, exclude=None, want_count=True, want
     lib().afd_ball_membership_f32(_p(queries), nq, _p(store), nr, D, _p(radius2), _p(exclude), _p(count), _p(nearest), _p(nearest_d2),
                                   _p(ws), nbytes, _stream())
     return count, nearest, nearest_d2
+
+
+QUALITY_MAX_SIDE = 64
+QUALITY_MAX_WINDOW = 15
+
+
+def pair_quality(a, b, win, c1, c2, region=None, want_map=False):
+    """PSNR and SSIM sums of image pairs in fp64, one launch (afd.h: afd_pair_quality_u8 / _f32).  a and b (n, C, H, W) uint8 or
+    fp32 on one device, of one shape and dtype (made contiguous if they are not), H and W at most 64; win: the K window weights,
+    a 1-D fp64 cpu tensor or a sequence of numbers, K odd, at most 15 and at most min(H, W); c1, c2: SSIM's two constants; region
+    None or a contiguous (1 | n, H, W) uint8 device tensor, non-zero = counted.  -> (out (n, C, 5) fp64: the sum of squared and
+    of absolute differences over the region, its pixels, the sum of SSIM over the windows centred in it, those windows; ssim_map
+    (n, C, H - K + 1, W - K + 1) fp64 with want_map, else None)."""
+    what = "pair_quality"
+    for name, v in (("a", a), ("b", b)):
+        if not isinstance(v, torch.Tensor) or not v.is_cuda or v.dim() != 4 or v.numel() == 0 or v.dtype not in (torch.uint8, torch.float32):
+            raise AfdError(f"afdm: {what}: {name} must be a non-empty (n, C, H, W) uint8 or fp32 device tensor")
+    if a.shape != b.shape or a.dtype != b.dtype or a.device != b.device:
+        raise AfdError(f"afdm: {what}: a and b must have one shape, dtype and device (got {tuple(a.shape)} {a.dtype} {a.device} and "
+                       f"{tuple(b.shape)} {b.dtype} {b.device})")
+    a, b = _c(a.detach()), _c(b.detach())
+    n, C, H, W = a.shape
+    if not (1 <= H <= QUALITY_MAX_SIDE and 1 <= W <= QUALITY_MAX_SIDE):
+        raise AfdError(f"afdm: {what}: H and W must lie in [1, {QUALITY_MAX_SIDE}] (got {H}, {W})")
+    w = np.ascontiguousarray(win.detach().cpu().numpy() if isinstance(win, torch.Tensor) else np.asarray(win), dtype=np.float64)
+    K = int(w.shape[0]) if w.ndim == 1 else 0
+    if K < 1 or K % 2 == 0 or K > QUALITY_MAX_WINDOW or K > min(H, W):
+        raise AfdError(f"afdm: {what}: win must hold K weights, K odd, at most {QUALITY_MAX_WINDOW} and at most min(H, W) = {min(H, W)} "
+                       f"(got shape {tuple(w.shape)})")
+    rows = 1
+    if region is not None:
+        if not isinstance(region, torch.Tensor) or region.device != a.device or region.dtype != torch.uint8 or region.dim() != 3 \
+                or tuple(region.shape[1:]) != (H, W) or region.shape[0] not in (1, n) or not region.is_contiguous():
+            raise AfdError(f"afdm: {what}: region must be None or a contiguous uint8 tensor of shape (1 | {n}, {H}, {W}) on the images' device")
+        rows = int(region.shape[0])
+    out = torch.empty(n, C, 5, device=a.device, dtype=torch.float64)
+    ssim_map = torch.empty(n, C, H - K + 1, W - K + 1, device=a.device, dtype=torch.float64) if want_map else None
+    fn = lib().afd_pair_quality_u8 if a.dtype == torch.uint8 else lib().afd_pair_quality_f32
+    fn(_p(a), _p(b), n * C, C, H, W, w.ctypes.data, K, float(c1), float(c2), _p(region), rows, _p(out), _p(ssim_map), _stream())
+    return out, ssim_map

@@ -89,6 +89,8 @@ def ddpm_run(params):
         _fidelity_cfg(params)
     if params.get("eval_manifold") is not None:
         _manifold_cfg(params)
+    if params.get("eval_restoration") is not None:
+        _restoration_cfg(params)
     cwd = os.getcwd()
     modelpath = os.path.join(cwd, f"models/DDPM_Uncondtional_{name}_{v}/ckpt_{name}_{v}.pt")
     f_settings = _f_settings(params)
@@ -138,6 +140,9 @@ def ddpm_run(params):
     if params.get("eval_manifold") is not None and not _manifold_cfg(params)["n"] <= len(dataset):
         raise ValueError(f"ddpm_run: eval_manifold n must be at most {len(dataset)} (the training set's size; got "
                          f"{_manifold_cfg(params)['n']})")
+    if params.get("eval_restoration") is not None and not _restoration_cfg(params)["n"] <= len(dataset):
+        raise ValueError(f"ddpm_run: eval_restoration n must lie in [1, {len(dataset)}] (the training set's size; got "
+                         f"{_restoration_cfg(params)['n']})")
     model = UNet(c_in=args.image_channels, c_out=model_out_channels(args), image_size=args.image_size, f_settings=f_settings,
                  device=args.device, variant=v).to(args.device)
     diffusion = Diffusion(noise_steps=args.noise_steps, img_size=args.image_size, device=args.device, **diffusion_kwargs(args))
@@ -229,6 +234,12 @@ def ddpm_run(params):
     # (manifold.manifold)
     if params.get("eval_manifold") is not None:
         out["manifold"] = _eval_manifold(params, args, torch.cat(generated), run_dir, name, v, dev_set)
+    # optional restoration scores: params["eval_restoration"] = {"n": ..., "mask": "center" | "half" | an (S, S) array of 0 / 1,
+    # "factor": ..., "tasks": ("inpaint", "superres"), "steps": ..., "eta": ..., "window": ..., "sigma": ...} inpaints and
+    # super-resolves the first n training images on the same model and scores the results against them in PSNR and SSIM
+    # (quality.image_quality)
+    if params.get("eval_restoration") is not None:
+        out["restoration"] = _eval_restoration(params, args, diffusion, gen_model, run_dir, name, v, seed, dev_set)
     return out
 
 
@@ -439,6 +450,123 @@ def _eval_manifold(params, args, generated, run_dir, name, v, dataset=None):
     return res
 
 
+RESTORATION_TASKS = ("inpaint", "superres")
+
+
+def _restoration_mask(mask, S):
+    """The (S, S) uint8 mask of `Diffusion.inpaint`, 1 = known: "center" (the hole is the central S/2 x S/2 square), "half" (the
+    hole is the right half), or an (S, S) array of 0 / 1 taken as it is."""
+    if isinstance(mask, str):
+        if mask not in ("center", "half"):
+            raise ValueError(f"restoration: mask must be 'center', 'half' or an ({S}, {S}) array of 0 / 1 (got {mask!r})")
+        m = np.ones((S, S), dtype=np.uint8)
+        if mask == "center":
+            m[S // 4:S // 4 + S // 2, S // 4:S // 4 + S // 2] = 0
+        else:
+            m[:, S // 2:] = 0
+        return m
+    m = mask.detach().cpu().numpy() if isinstance(mask, torch.Tensor) else np.asarray(mask)
+    if m.shape != (S, S) or m.dtype.kind not in "biuf" or not np.isin(m, (0, 1)).all():
+        raise ValueError(f"restoration: mask must be 'center', 'half' or an ({S}, {S}) array of 0 / 1 (got shape {m.shape}, {m.dtype})")
+    return m.astype(np.uint8)
+
+
+def _restoration_cfg(params):
+    from .quality import gaussian_window
+    cfg = params["eval_restoration"]
+    keys = {"n", "mask", "factor", "tasks", "steps", "eta", "window", "sigma"}
+    if not isinstance(cfg, dict) or set(cfg) - keys or "n" not in cfg:
+        raise ValueError(f"ddpm_run: eval_restoration needs n (and optionally {', '.join(sorted(keys - {'n'}))}); got "
+                         f"{sorted(cfg) if isinstance(cfg, dict) else type(cfg).__name__}")
+    out = {"n": cfg["n"], "mask": cfg.get("mask", "center"), "factor": cfg.get("factor", 4), "tasks": cfg.get("tasks", RESTORATION_TASKS),
+           "steps": cfg.get("steps"), "eta": cfg.get("eta", 0.0), "window": cfg.get("window", 11), "sigma": cfg.get("sigma", 1.5)}
+    n, S = out["n"], params.get("image_size")
+    if isinstance(n, bool) or not isinstance(n, (int, np.integer)) or n < 1:
+        raise ValueError(f"ddpm_run: eval_restoration n must be an int >= 1 (got {n!r})")
+    out["n"] = int(n)
+    tasks = (out["tasks"],) if isinstance(out["tasks"], str) else tuple(out["tasks"])
+    if not tasks or any(t not in RESTORATION_TASKS for t in tasks) or len(set(tasks)) != len(tasks):
+        raise ValueError(f"ddpm_run: eval_restoration tasks must be some of {RESTORATION_TASKS} (got {out['tasks']!r})")
+    out["tasks"] = tasks
+    factor = out["factor"]
+    if isinstance(factor, bool) or not isinstance(factor, (int, np.integer)) or factor < 2 or factor & (factor - 1):
+        raise ValueError(f"ddpm_run: eval_restoration factor must be a power of two >= 2 (got {factor!r})")
+    out["factor"] = int(factor)
+    try:
+        gaussian_window(out["window"], out["sigma"])
+    except ValueError as e:
+        raise ValueError(f"ddpm_run: eval_restoration {e}") from None
+    if S is not None:
+        if not 1 <= S <= 64 or out["window"] > S:
+            raise ValueError(f"ddpm_run: eval_restoration takes images of at most 64 x 64 and no smaller than its window of "
+                             f"{out['window']} taps (image_size is {S})")
+        if "superres" in tasks and 2 * out["factor"] > S:
+            raise ValueError(f"ddpm_run: eval_restoration factor must be at most image_size / 2 = {S // 2} (got {factor!r})")
+        if "inpaint" in tasks:
+            _restoration_mask(out["mask"], S)
+    return out
+
+
+def _spread(values):
+    """A per-image fp64 tensor as {"mean", "std" (population), "values"}: plain floats, ready for json."""
+    v = values.double().cpu()
+    return {"mean": float(v.mean()), "std": float(v.std(unbiased=False)), "values": v.tolist()}
+
+
+def _restoration_scores(diffusion, model, originals, cfg, seed, kw):
+    """Inpaints and / or super-resolves the uint8 images `originals` (n, C, S, S), on the sampler's device, from their own
+    degraded versions and scores the results against them; set_seed(seed) before each task."""
+    from . import ops
+    from .quality import gaussian_window, image_quality
+    n, C, S = originals.shape[0], originals.shape[1], originals.shape[2]
+    dev = originals.device
+    win = gaussian_window(cfg["window"], cfg["sigma"])
+    x0 = normalisation_table(C).to(dev)[torch.arange(C, device=dev).view(1, C, 1, 1), originals.long()]      # as the loader maps pixels
+    skw = dict(kw, steps=cfg["steps"], eta=cfg["eta"])
+    res = {"n": int(n), "window": int(cfg["window"]), "sigma": cfg["sigma"]}
+    if "inpaint" in cfg["tasks"]:
+        mask = _restoration_mask(cfg["mask"], S)
+        set_seed(seed)
+        filled = diffusion.inpaint(model, x0, torch.from_numpy(mask), **skw)[0]
+        whole = image_quality(filled, originals, window=win)
+        hole = image_quality(filled, originals, window=win, region=torch.from_numpy(1 - mask))
+        res["inpaint"] = {"mask": cfg["mask"] if isinstance(cfg["mask"], str) else "custom", "hole_pixels": int((1 - mask).sum()),
+                          "psnr": _spread(whole["psnr"]), "ssim": _spread(whole["ssim"]), "psnr_hole": _spread(hole["psnr"]),
+                          "ssim_hole": _spread(hole["ssim"])}
+    if "superres" in cfg["tasks"]:
+        factor = cfg["factor"]
+        taps, levels = diffusion._ilvr_operator("restoration", factor, None)
+        with torch.no_grad():
+            low = x0
+            for _ in range(levels):
+                low = ops.FiltDown2.apply(low, taps)
+        reference = diffusion.reference_from_lowres(low, factor)
+        set_seed(seed)
+        sample, _, sample_float = diffusion.ilvr(model, reference, factor=factor, return_float=True, **skw)
+        got, base = image_quality(sample, originals, window=win), image_quality(ops.quantize_u8(reference), originals, window=win)
+        kept = image_quality(ops.lowpass_project(sample_float, taps, levels), ops.lowpass_project(x0, taps, levels), data_range=2.0, window=win)
+        res["superres"] = {"factor": int(factor), "psnr": _spread(got["psnr"]), "ssim": _spread(got["ssim"]),
+                           "psnr_reference": _spread(base["psnr"]), "ssim_reference": _spread(base["ssim"]),
+                           "consistency_psnr": _spread(kept["psnr"])}
+    return res
+
+
+def _eval_restoration(params, args, diffusion, model, run_dir, name, v, seed, dataset=None):
+    import json
+    cfg = _restoration_cfg(params)
+    n = cfg["n"]
+    dataset = _training_store(name, args, dataset)
+    if not n <= len(dataset):
+        raise ValueError(f"ddpm_run: eval_restoration n must lie in [1, {len(dataset)}] (the training set's size; got {n})")
+    res = _restoration_scores(diffusion, model, dataset.pixels(n).to(args.device), cfg, seed, {})
+    with open(os.path.join(run_dir, f"restoration_{name}_{v}.json"), "w") as fh:
+        json.dump(res, fh, indent=1)
+    for task in cfg["tasks"]:
+        print(f"restoration {task}: " + ", ".join(f"{k} {val['mean']:.6g}" for k, val in res[task].items() if isinstance(val, dict))
+              + f" (means over {n} training images)")
+    return res
+
+
 def _eval_bpd(params, args, diffusion, model, run_dir, name, v, seed, dataset=None):
     N, K, sigma = int(params["eval_bpd"]), params.get("eval_bpd_t_samples"), params.get("eval_bpd_sigma", "beta")
     if dataset is None:
@@ -569,6 +697,36 @@ def manifold_results(model_data, images, n, extractor, k=3, **kw):
     set_seed(model_data["seed"])
     x, _ = diffusion.sample(model, n=int(n), image_channels=args.image_channels, **kw)
     return _manifold_pair(train, x, cfg)
+
+
+def restoration_results(model_data, images, n, mask="center", factor=4, tasks=RESTORATION_TASKS, window=11, sigma=1.5, **kw):
+    """Load the checkpoint as rotation_results does and score the model's restorations of the first n of `images` (a
+    DeviceDataset, or (N, C, H, W) uint8 pixels) against the images themselves, in PSNR and SSIM (quality.image_quality with a
+    Gaussian window of `window` taps and `sigma`); the seed is set before each task.  **kw: steps, eta, labels, cfg_scale, graph.
+    "inpaint": `Diffusion.inpaint` with `mask`, 1 = known: "center" (the hole is the central S/2 x S/2 square), "half" (the right
+    half) or an (S, S) array of 0 / 1; psnr and ssim over the whole image, psnr_hole and ssim_hole over the hole (region =
+    1 - mask; SSIM over the windows centred in it).
+    "superres": low = down2^L(images) with factor = 2^L, `Diffusion.ilvr` on `reference_from_lowres(low, factor)`; psnr and ssim
+    of the sample, psnr_reference and ssim_reference of the quantised reference alone (the baseline to read them against), and
+    consistency_psnr of ops.lowpass_project(sample) against ops.lowpass_project(image) in fp32 at data range 2: how far the sample
+    left the measurement.
+    Returns what ddpm_run writes for params["eval_restoration"]: {"n", "window", "sigma", task: {score: {"mean", "std" (population),
+    "values": one per image}, ...}}."""
+    if isinstance(n, bool) or not isinstance(n, (int, np.integer)) or not 1 <= n <= len(images):
+        raise ValueError(f"restoration_results: n must be an int in [1, {len(images)}] (the number of images; got {n!r})")
+    kw = dict(kw)
+    cfg = {"n": n, "mask": mask, "factor": factor, "tasks": tasks, "window": window, "sigma": sigma}
+    cfg.update({k: kw.pop(k) for k in ("steps", "eta") if k in kw})
+    if isinstance(images, DeviceDataset):
+        originals = images.pixels(int(n))
+    else:
+        originals = torch.from_numpy(images) if isinstance(images, np.ndarray) else images
+        if not isinstance(originals, torch.Tensor) or originals.dtype != torch.uint8 or originals.dim() != 4:
+            raise ValueError("restoration_results: images must be a DeviceDataset or (N, C, H, W) uint8 pixels")
+        originals = originals[:int(n)]
+    cfg = _restoration_cfg({"eval_restoration": cfg, "image_size": int(originals.shape[-1])})
+    model, diffusion, args = _load(model_data)
+    return _restoration_scores(diffusion, model, originals.to(args.device).contiguous(), cfg, model_data["seed"], kw)
 
 
 def equivariance_results(model_data, images, **kw):

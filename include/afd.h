@@ -922,6 +922,38 @@ int afd_ball_membership_f32(const float* Q, long nq, const float* R, long nr, lo
                             const int64_t* exclude_or_null, int* count_or_null, int64_t* nearest_or_null, double* nearest_d2_or_null,
                             void* workspace, size_t workspace_bytes, afd_stream_t stream);
 
+/* ---- PSNR and SSIM sums of image pairs, in fp64 (csrc/quality.hip) ------------------------------ quality.image_quality
+ * a and b are contiguous (rows, C, H, W) sets of floats or of uint8 pixels, planes = rows * C, 1 <= H, W <= 64.  Every value is
+ * widened exactly and everything after that is fp64.
+ * The region P of an image is the set of pixels where its H x W uint8 mask in `region` is non-zero, shared by the image's
+ * channels; region_rows is rows, or 1 when one mask serves all images; a NULL region is every pixel (region_rows is then 1 or
+ * rows all the same).  win is a HOST array of K doubles, K odd, 1 <= K <= 15, K <= min(H, W): window (i, j), 0 <= i <= H - K,
+ * 0 <= j <= W - K, covers rows i .. i + K - 1 and columns j .. j + K - 1 with the weights win[r] win[s] (the border is cropped).
+ * With the weighted sums m_a, m_b, m_aa, m_bb, m_ab of a, b, a a, b b, a b over a window,
+ *     v_aa = m_aa - m_a m_a,  v_bb = m_bb - m_b m_b,  v_ab = m_ab - m_a m_b
+ *     ssim = ((2 m_a m_b + c1) (2 v_ab + c2)) / ((m_a m_a + m_b m_b + c1) (v_aa + v_bb + c2))
+ * A weighted sum is sum_r win[r] (sum_s win[s] p[i + r][j + s]), s and r ascending, each step one fma from a zero accumulator;
+ * the products a a, b b, a b are exact in fp64 and take the same chain in the same operand order, and the rational is evaluated
+ * without contraction, so a == b gives ssim == 1.0 exactly in every window.
+ *     out[plane] = [ sum_{p in P} (a - b)^2,  sum_{p in P} |a - b|,  |P|,
+ *                    the sum of ssim over the windows whose centre pixel (i + (K - 1) / 2, j + (K - 1) / 2) is in P,
+ *                    the number of those windows ]                                                            (planes, 5)
+ *     ssim_map[plane][i][j] = ssim of window (i, j), whatever the region is (may be NULL)      (planes, H - K + 1, W - K + 1)
+ * A pixel outside P is not added to the first three (a NaN there stays out of them); otherwise a NaN or an infinity propagates
+ * to its own plane's outputs; nothing is clamped.  uint8 inputs give the exact integers in the first three.
+ * One launch on `stream`, one workgroup per plane: a thread adds its pixels and its windows in index order, a shuffle tree adds
+ * the lanes, the waves are added in order.  No atomics, no workspace, no allocation, no synchronisation, so a call can be
+ * captured into a graph and repeats bit for bit.
+ * AFD_EINVAL (nothing launched) on a NULL a / b / win / out, planes or C <= 0, planes not a multiple of C, planes >= 2^31, H or W
+ * outside [1, 64], K even, K < 1, K > 15 or K > min(H, W), region_rows neither 1 nor planes / C, out / ssim_map not 8-byte
+ * aligned, f32 a / b not 4-byte aligned, or out / ssim_map overlapping a, b, region or each other. */
+int afd_pair_quality_f32(const float* a, const float* b, long planes, int C, int H, int W, const double* win, int K, double c1,
+                         double c2, const uint8_t* region_or_null, long region_rows, double* out, double* ssim_map_or_null,
+                         afd_stream_t stream);
+int afd_pair_quality_u8(const uint8_t* a, const uint8_t* b, long planes, int C, int H, int W, const double* win, int K, double c1,
+                        double c2, const uint8_t* region_or_null, long region_rows, double* out, double* ssim_map_or_null,
+                        afd_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
