@@ -2,44 +2,20 @@
 // (mfma_f64_16x16x4_f64), each with its reduction fused behind it so that the contraction's output never reaches memory:
 //   afd_feature_moments_f32   sum_r x_r and sum_r x_r x_r^T of (n, D) fp32 features: the mean and covariance of a feature set
 //   afd_poly_mmd_sums_f32     per subset the three sums of a polynomial kernel over gathered rows: the unbiased MMD^2 of KID
-// Both work on 64 x 64 output tiles: a workgroup of four waves, each wave a 32 x 32 quadrant as 2 x 2 MFMA tiles.  The operands are
-// widened from fp32 to fp64 while they are staged into LDS as s[k][row], 32 k at a time; rows and k beyond the arrays are zeros in
-// the OPERANDS (a masked load), and the epilogues leave padded results out with a select, never a multiplication, so a NaN stays
-// where it belongs.  Partials go to the workspace and a second kernel folds them in a fixed order: no atomics, no memset, nothing
-// depends on the order in which workgroups run, so the same arguments give the same bits.
-#include "common.h"
+// Both work on the 64 x 64 output tiles of f64_tile.h.  The operands are widened from fp32 to fp64 while they are staged into LDS
+// as s[k][row], 32 k at a time; rows and k beyond the arrays are zeros in the OPERANDS (a masked load), and the epilogues leave
+// padded results out with a select, never a multiplication, so a NaN stays where it belongs.  Partials go to the workspace and a
+// second kernel folds them in a fixed order: no atomics, no memset, nothing depends on the order in which workgroups run, so the
+// same arguments give the same bits.
+#include "f64_tile.h"
 
 namespace afd {
 
-typedef double v4d __attribute__((ext_vector_type(4)));
-
-constexpr int kFdTile = 64;                        // output tile side
-constexpr int kFdThreads = 256;                    // 4 waves, a 32 x 32 quadrant each
-constexpr int kFdK = 32;                           // k staged per round
-constexpr int kFdPer = kFdTile * kFdK / kFdThreads;      // elements of one staged operand per thread
 constexpr int kMomPitch = 80;                      // moments: s[k][column]; the four k of a fragment lie 32 banks apart
 constexpr int kMmdPitch = 65;                      // MMD: written k-fastest (32 consecutive k of one row: 32 distinct bank pairs)
 constexpr long kMomTarget = 2048;                  // workgroups the moments aim for, whatever the device
 constexpr long kMomMaxSlabs = 64;
 constexpr long kMmdMaxM = 1L << 16;
-
-__device__ __forceinline__ v4d fd_mma(double a, double b, v4d c) { return __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, c, 0, 0, 0); }
-
-// Fragments of mfma_f64_16x16x4_f64: lane l holds A[row l & 15][k = l >> 4] and B[k = l >> 4][column l & 15]; result register r of
-// lane l is D[row (l >> 4) + 4 r][column l & 15].  sa / sb: the staged operands as s[k][row], the wave's quadrant starts at row ra
-// of sa and row cb of sb; acc[a][b] is the 16 x 16 tile at (ra + 16 a, cb + 16 b).
-template <int P>
-__device__ __forceinline__ void fd_round(const double* sa, const double* sb, int ra, int cb, int c16, int g4, v4d (&acc)[2][2]) {
-#pragma unroll
-  for (int kk = 0; kk < kFdK / 4; ++kk) {
-    const int o = (4 * kk + g4) * P + c16;
-    const double a0 = sa[o + ra], a1 = sa[o + ra + 16], b0 = sb[o + cb], b1 = sb[o + cb + 16];
-    acc[0][0] = fd_mma(a0, b0, acc[0][0]);
-    acc[0][1] = fd_mma(a0, b1, acc[0][1]);
-    acc[1][0] = fd_mma(a1, b0, acc[1][0]);
-    acc[1][1] = fd_mma(a1, b1, acc[1][1]);
-  }
-}
 
 // pair p of the upper triangle of a T x T grid, rows first: (0, 0), (0, 1), ..., (0, T - 1), (1, 1), ...
 __device__ __forceinline__ void fd_pair(long p, int T, int& ti, int& tj) {
@@ -57,32 +33,29 @@ __device__ __forceinline__ void fd_pair(long p, int T, int& ti, int& tj) {
 // Workgroup (pair, slab g) walks rows [g per, min(n, (g + 1) per)) of X and leaves the 64 x 64 tile (ti, tj), ti <= tj, of
 // sum_r x_r x_r^T in ws[(pair G + g)][64][64]; a diagonal workgroup also leaves the column sums of its 64 columns, summed row by
 // row in index order, in the sums part of the workspace, [(ti G + g)][64].
-__global__ __launch_bounds__(kFdThreads) void moments_k(const float* __restrict__ X, long n, int D, int T, long per, long G,
+__global__ __launch_bounds__(kTileThreads) void moments_k(const float* __restrict__ X, long n, int D, int T, long per, long G,
                                                         double* __restrict__ ws, double* __restrict__ ws_sum) {
-  __shared__ double sa[kFdK * kMomPitch], sb[kFdK * kMomPitch];
-  const int tid = threadIdx.x, lane = tid & 63, c16 = lane & 15, g4 = lane >> 4;
-  const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
+  __shared__ double sa[kTileK * kMomPitch], sb[kTileK * kMomPitch];
+  const int tid = threadIdx.x;
+  const TileLane q = tile_lane(tid);
   const long pair = blockIdx.x / G, g = blockIdx.x - pair * G;
   int ti, tj;
   fd_pair(pair, T, ti, tj);
   const bool diag = ti == tj;
-  const int I = ti * kFdTile, J = tj * kFdTile, ra = 32 * (w >> 1), cb = 32 * (w & 1);
+  const int I = ti * kTile, J = tj * kTile;
   const long r_begin = g * per, r_end = r_begin + per < n ? r_begin + per : n;
   v4d acc[2][2];
-#pragma unroll
-  for (int a = 0; a < 2; ++a)
-#pragma unroll
-    for (int b = 0; b < 2; ++b) acc[a][b] = v4d{0.0, 0.0, 0.0, 0.0};
+  tile_zero(acc);
   double colsum = 0.0;
   const double* sbp = diag ? sa : sb;
 
   // the thread's elements of a round are (k, c) = (e >> 6, e & 63), e = tid + 256 j; the next round's are loaded into registers
   // while the matrix pipe works on this one
-  float na_[kFdPer], nb_[kFdPer];
+  float na_[kTilePer], nb_[kTilePer];
   auto fetch = [&](long r0) {
 #pragma unroll
-    for (int j = 0; j < kFdPer; ++j) {
-      const int e = tid + kFdThreads * j, c = e & 63;
+    for (int j = 0; j < kTilePer; ++j) {
+      const int e = tid + kTileThreads * j, c = e & 63;
       const long r = r0 + (e >> 6);
       const bool rok = r < r_end;
       na_[j] = (rok && I + c < D) ? X[r * D + I + c] : 0.0f;
@@ -90,68 +63,63 @@ __global__ __launch_bounds__(kFdThreads) void moments_k(const float* __restrict_
     }
   };
   fetch(r_begin);
-  for (long r0 = r_begin; r0 < r_end; r0 += kFdK) {
+  for (long r0 = r_begin; r0 < r_end; r0 += kTileK) {
 #pragma unroll
-    for (int j = 0; j < kFdPer; ++j) {
-      const int e = tid + kFdThreads * j, k = e >> 6, c = e & 63;
+    for (int j = 0; j < kTilePer; ++j) {
+      const int e = tid + kTileThreads * j, k = e >> 6, c = e & 63;
       sa[k * kMomPitch + c] = (double)na_[j];
       if (!diag) sb[k * kMomPitch + c] = (double)nb_[j];
     }
     __syncthreads();
-    if (r0 + kFdK < r_end) fetch(r0 + kFdK);
-    fd_round<kMomPitch>(sa, sbp, ra, cb, c16, g4, acc);
-    if (diag && tid < kFdTile) {
+    if (r0 + kTileK < r_end) fetch(r0 + kTileK);
+    tile_round<kMomPitch>(sa, sbp, q, acc);
+    if (diag && tid < kTile) {
 #pragma unroll 8
-      for (int k = 0; k < kFdK; ++k) colsum += sa[k * kMomPitch + tid];
+      for (int k = 0; k < kTileK; ++k) colsum += sa[k * kMomPitch + tid];
     }
     __syncthreads();
   }
 
-  double* out = ws + (pair * G + g) * (long)(kFdTile * kFdTile);
-#pragma unroll
-  for (int a = 0; a < 2; ++a)
-#pragma unroll
-    for (int b = 0; b < 2; ++b)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) out[(ra + 16 * a + g4 + 4 * r) * kFdTile + cb + 16 * b + c16] = acc[a][b][r];
-  if (diag && tid < kFdTile) ws_sum[((long)ti * G + g) * kFdTile + tid] = colsum;
+  double* out = ws + (pair * G + g) * (long)(kTile * kTile);
+  tile_for_each(q, acc, [&](int row, int col, double v) { out[row * kTile + col] = v; });
+  if (diag && tid < kTile) ws_sum[((long)ti * G + g) * kTile + tid] = colsum;
 }
 
 // Workgroup `pair` folds the G slabs of its tile in slab order, adds what outer held (accumulate) and writes the element and its
 // mirror image from one value, so outer is symmetric bit for bit.  A diagonal tile is taken from its upper half alone.  Only
 // elements on or above the diagonal are ever read, and only by the thread that writes them.
-__global__ __launch_bounds__(kFdThreads) void moments_finish_k(const double* __restrict__ ws, const double* __restrict__ ws_sum, int D, int T, long G,
+__global__ __launch_bounds__(kTileThreads) void moments_finish_k(const double* __restrict__ ws, const double* __restrict__ ws_sum, int D, int T, long G,
                                                                int accumulate, double* __restrict__ sum, double* __restrict__ outer) {
   const int tid = threadIdx.x;
   const long pair = blockIdx.x;
   int ti, tj;
   fd_pair(pair, T, ti, tj);
-  const int I = ti * kFdTile, J = tj * kFdTile;
-  const double* p = ws + pair * G * (long)(kFdTile * kFdTile);
-  for (int e = tid; e < kFdTile * kFdTile; e += kFdThreads) {
+  const int I = ti * kTile, J = tj * kTile;
+  const double* p = ws + pair * G * (long)(kTile * kTile);
+  for (int e = tid; e < kTile * kTile; e += kTileThreads) {
     const int gi = I + (e >> 6), gj = J + (e & 63);
     if (gi >= D || gj >= D || gi > gj) continue;
     double v = p[e];
-    for (long g = 1; g < G; ++g) v += p[g * (kFdTile * kFdTile) + e];
+    for (long g = 1; g < G; ++g) v += p[g * (kTile * kTile) + e];
     if (accumulate) v = outer[(long)gi * D + gj] + v;
     outer[(long)gi * D + gj] = v;
     outer[(long)gj * D + gi] = v;
   }
-  if (ti == tj && tid < kFdTile && I + tid < D) {
-    const double* q = ws_sum + (long)ti * G * kFdTile + tid;
+  if (ti == tj && tid < kTile && I + tid < D) {
+    const double* q = ws_sum + (long)ti * G * kTile + tid;
     double v = q[0];
-    for (long g = 1; g < G; ++g) v += q[g * kFdTile];
+    for (long g = 1; g < G; ++g) v += q[g * kTile];
     sum[I + tid] = accumulate ? sum[I + tid] + v : v;
   }
 }
 
 static bool mom_sizes_ok(long n, long D) { return n > 0 && D > 0 && n < (1L << 31) && D <= (1L << 15) && D <= (1L << 40) / n; }
-static long mom_tiles(long D) { return (D + kFdTile - 1) / kFdTile; }
+static long mom_tiles(long D) { return (D + kTile - 1) / kTile; }
 static long mom_pairs(long D) { return mom_tiles(D) * (mom_tiles(D) + 1) / 2; }
 // the slabs of a call depend on (n, D) alone
 static long mom_slabs(long n, long D) {
   long G = kMomTarget / mom_pairs(D);
-  const long rounds = (n + kFdK - 1) / kFdK;
+  const long rounds = (n + kTileK - 1) / kTileK;
   G = G < 1 ? 1 : G;
   G = G > kMomMaxSlabs ? kMomMaxSlabs : G;
   return G > rounds ? rounds : G;
@@ -162,24 +130,24 @@ static long mom_slabs(long n, long D) {
 // A x B, MT = ceil(m / 64).  A workgroup gathers its 64 + 64 rows by index, runs the dot products over D, raises the accumulators
 // to the power and sums its tile: a symmetric problem's tile above the diagonal counts twice, a diagonal tile leaves i == j out.
 // An index outside its array reads nothing: that row is NaN.
-__global__ __launch_bounds__(kFdThreads) void mmd_k(const float* __restrict__ A, long na, const float* __restrict__ B, long nb, int D,
+__global__ __launch_bounds__(kTileThreads) void mmd_k(const float* __restrict__ A, long na, const float* __restrict__ B, long nb, int D,
                                                     const int64_t* __restrict__ ia, const int64_t* __restrict__ ib, int m, int MT, long per_subset,
                                                     int degree, double gamma, double coef0, double* __restrict__ ws) {
-  __shared__ double sa[kFdK * kMmdPitch], sb[kFdK * kMmdPitch];
-  __shared__ long rows_a[kFdTile], rows_b[kFdTile];
-  __shared__ double red[kFdThreads / kWave];
-  const int tid = threadIdx.x, lane = tid & 63, c16 = lane & 15, g4 = lane >> 4;
-  const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const long s = blockIdx.x / per_subset, q = blockIdx.x - s * per_subset;
+  __shared__ double sa[kTileK * kMmdPitch], sb[kTileK * kMmdPitch];
+  __shared__ long rows_a[kTile], rows_b[kTile];
+  __shared__ double red[kTileThreads / kWave];
+  const int tid = threadIdx.x, lane = tid & 63;
+  const TileLane q = tile_lane(tid);
+  const long s = blockIdx.x / per_subset, p = blockIdx.x - s * per_subset;
   const long TP = (long)MT * (MT + 1) / 2;
   int which, ti, tj;                                 // 0: A x A, 1: B x B, 2: A x B
-  if (q < 2 * TP) {
-    which = q < TP ? 0 : 1;
-    fd_pair(q - which * TP, MT, ti, tj);
+  if (p < 2 * TP) {
+    which = p < TP ? 0 : 1;
+    fd_pair(p - which * TP, MT, ti, tj);
   } else {
     which = 2;
-    ti = (int)((q - 2 * TP) / MT);
-    tj = (int)((q - 2 * TP) - (long)ti * MT);
+    ti = (int)((p - 2 * TP) / MT);
+    tj = (int)((p - 2 * TP) - (long)ti * MT);
   }
   const bool sym = which != 2, diag = sym && ti == tj;
   const float* src_a = which == 1 ? B : A;
@@ -187,16 +155,16 @@ __global__ __launch_bounds__(kFdThreads) void mmd_k(const float* __restrict__ A,
   const int64_t* ix_a = (which == 1 ? ib : ia) + s * m;
   const int64_t* ix_b = (which == 0 ? ia : ib) + s * m;
   const long lim_a = which == 1 ? nb : na, lim_b = which == 0 ? na : nb;
-  const int I = ti * kFdTile, J = tj * kFdTile, ra = 32 * (w >> 1), cb = 32 * (w & 1);
-  if (tid < kFdTile) {                               // -1: past the subset (zeros), -2: an index outside the array (NaN)
+  const int I = ti * kTile, J = tj * kTile;
+  if (tid < kTile) {                               // -1: past the subset (zeros), -2: an index outside the array (NaN)
     long v = -1;
     if (I + tid < m) {
       v = ix_a[I + tid];
       v = (v < 0 || v >= lim_a) ? -2 : v;
     }
     rows_a[tid] = v;
-  } else if (tid < 2 * kFdTile) {
-    const int t = tid - kFdTile;
+  } else if (tid < 2 * kTile) {
+    const int t = tid - kTile;
     long v = -1;
     if (J + t < m) {
       v = ix_b[J + t];
@@ -205,61 +173,49 @@ __global__ __launch_bounds__(kFdThreads) void mmd_k(const float* __restrict__ A,
     rows_b[t] = v;
   }
   __syncthreads();
-  long my_a[kFdPer], my_b[kFdPer];                   // thread's staged elements: k = tid & 31, rows (tid >> 5) + 8 j
+  long my_a[kTilePer], my_b[kTilePer];                   // thread's staged elements: k = tid & 31, rows (tid >> 5) + 8 j
 #pragma unroll
-  for (int j = 0; j < kFdPer; ++j) {
+  for (int j = 0; j < kTilePer; ++j) {
     my_a[j] = rows_a[(tid >> 5) + 8 * j];
     my_b[j] = rows_b[(tid >> 5) + 8 * j];
   }
   const int k = tid & 31;
   const float qnan = __builtin_nanf("");
   v4d acc[2][2];
-#pragma unroll
-  for (int a = 0; a < 2; ++a)
-#pragma unroll
-    for (int b = 0; b < 2; ++b) acc[a][b] = v4d{0.0, 0.0, 0.0, 0.0};
+  tile_zero(acc);
   const double* sbp = diag ? sa : sb;
 
   // the next round's elements are loaded into registers while the matrix pipe works on this one
-  float na_[kFdPer], nb_[kFdPer];
+  float na_[kTilePer], nb_[kTilePer];
   auto fetch = [&](int d0) {
     const bool dok = d0 + k < D;
 #pragma unroll
-    for (int j = 0; j < kFdPer; ++j) {
+    for (int j = 0; j < kTilePer; ++j) {
       na_[j] = my_a[j] == -2 ? qnan : (my_a[j] >= 0 && dok) ? src_a[my_a[j] * D + d0 + k] : 0.0f;
       if (!diag) nb_[j] = my_b[j] == -2 ? qnan : (my_b[j] >= 0 && dok) ? src_b[my_b[j] * D + d0 + k] : 0.0f;
     }
   };
   fetch(0);
-  for (int d0 = 0; d0 < D; d0 += kFdK) {
-#pragma unroll
-    for (int j = 0; j < kFdPer; ++j) {
-      const int row = (tid >> 5) + 8 * j;
-      sa[k * kMmdPitch + row] = (double)na_[j];
-      if (!diag) sb[k * kMmdPitch + row] = (double)nb_[j];
-    }
+  for (int d0 = 0; d0 < D; d0 += kTileK) {
+    tile_stage_kfast<kMmdPitch>(sa, tid, na_);
+    if (!diag) tile_stage_kfast<kMmdPitch>(sb, tid, nb_);
     __syncthreads();
-    if (d0 + kFdK < D) fetch(d0 + kFdK);
-    fd_round<kMmdPitch>(sa, sbp, ra, cb, c16, g4, acc);
+    if (d0 + kTileK < D) fetch(d0 + kTileK);
+    tile_round<kMmdPitch>(sa, sbp, q, acc);
     __syncthreads();
   }
 
-  double part = 0.0;                                 // the lane's elements in a fixed order
-#pragma unroll
-  for (int a = 0; a < 2; ++a)
-#pragma unroll
-    for (int b = 0; b < 2; ++b)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int i = I + ra + 16 * a + g4 + 4 * r, jj = J + cb + 16 * b + c16;
-        const double v = gamma * acc[a][b][r] + coef0;
-        double pw = v;
-        for (int t = 1; t < degree; ++t) pw *= v;
-        if (i < m && jj < m && !(diag && i == jj)) part += pw;
-      }
+  double part = 0.0;                                 // the lane's elements in a fixed order (tile_for_each's)
+  tile_for_each(q, acc, [&](int row, int col, double dot) {
+    const int i = I + row, jj = J + col;
+    const double v = gamma * dot + coef0;
+    double pw = v;
+    for (int t = 1; t < degree; ++t) pw *= v;
+    if (i < m && jj < m && !(diag && i == jj)) part += pw;
+  });
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) part += __shfl_xor(part, o, kWave);
-  if (lane == 0) red[w] = part;
+  if (lane == 0) red[q.w] = part;
   __syncthreads();
   if (tid == 0) {
     const double t = ((red[0] + red[1]) + red[2]) + red[3];
@@ -283,7 +239,7 @@ __global__ __launch_bounds__(kWave) void mmd_finish_k(const double* __restrict__
   if (lane == 0) sums[blockIdx.x] = v;
 }
 
-static long mmd_tiles(long m) { return (m + kFdTile - 1) / kFdTile; }
+static long mmd_tiles(long m) { return (m + kTile - 1) / kTile; }
 static long mmd_per_subset(long m) { return mmd_tiles(m) * (mmd_tiles(m) + 1) + mmd_tiles(m) * mmd_tiles(m); }
 static bool mmd_sizes_ok(long S, long m, long D) {
   return S > 0 && D > 0 && m >= 2 && m <= kMmdMaxM && D < (1L << 31) && S <= ((1L << 31) - 1) / mmd_per_subset(m);
@@ -297,7 +253,7 @@ extern "C" {
 size_t afd_feature_moments_workspace_bytes(long n, long D) {
   if (!mom_sizes_ok(n, D)) return 0;
   const size_t G = (size_t)mom_slabs(n, D);
-  return (G * (size_t)mom_pairs(D) * kFdTile * kFdTile + G * (size_t)mom_tiles(D) * kFdTile) * sizeof(double);
+  return (G * (size_t)mom_pairs(D) * kTile * kTile + G * (size_t)mom_tiles(D) * kTile) * sizeof(double);
 }
 
 int afd_feature_moments_f32(const float* X, long n, long D, double* sum, double* outer, int accumulate, void* workspace,
@@ -321,10 +277,10 @@ int afd_feature_moments_f32(const float* X, long n, long D, double* sum, double*
   const long T = mom_tiles(D), pairs = mom_pairs(D), slabs = mom_slabs(n, D);
   const long per = (n + slabs - 1) / slabs, G = (n + per - 1) / per;           // no slab is empty
   double* ws = static_cast<double*>(workspace);
-  double* ws_sum = ws + (size_t)slabs * (size_t)pairs * kFdTile * kFdTile;
+  double* ws_sum = ws + (size_t)slabs * (size_t)pairs * kTile * kTile;
   hipStream_t stream = as_stream(st);
-  hipLaunchKernelGGL(moments_k, dim3((unsigned)(pairs * G)), dim3(kFdThreads), 0, stream, X, n, (int)D, (int)T, per, G, ws, ws_sum);
-  hipLaunchKernelGGL(moments_finish_k, dim3((unsigned)pairs), dim3(kFdThreads), 0, stream, ws, ws_sum, (int)D, (int)T, G, accumulate, sum, outer);
+  hipLaunchKernelGGL(moments_k, dim3((unsigned)(pairs * G)), dim3(kTileThreads), 0, stream, X, n, (int)D, (int)T, per, G, ws, ws_sum);
+  hipLaunchKernelGGL(moments_finish_k, dim3((unsigned)pairs), dim3(kTileThreads), 0, stream, ws, ws_sum, (int)D, (int)T, G, accumulate, sum, outer);
   return check_launch(name);
 }
 
@@ -359,7 +315,7 @@ int afd_poly_mmd_sums_f32(const float* A, long na, const float* B, long nb, long
   const long MT = mmd_tiles(m), per_subset = mmd_per_subset(m);
   double* ws = static_cast<double*>(workspace);
   hipStream_t stream = as_stream(st);
-  hipLaunchKernelGGL(mmd_k, dim3((unsigned)(S * per_subset)), dim3(kFdThreads), 0, stream, A, na, B, nb, (int)D, ia, ib, (int)m, (int)MT, per_subset,
+  hipLaunchKernelGGL(mmd_k, dim3((unsigned)(S * per_subset)), dim3(kTileThreads), 0, stream, A, na, B, nb, (int)D, ia, ib, (int)m, (int)MT, per_subset,
                      degree, gamma, coef0, ws);
   hipLaunchKernelGGL(mmd_finish_k, dim3((unsigned)(3 * S)), dim3(kWave), 0, stream, ws, (int)MT, per_subset, sums);
   return check_launch(name);

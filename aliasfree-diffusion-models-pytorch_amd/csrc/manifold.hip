@@ -10,130 +10,93 @@
 // segment) of four waves carries a stripe of 64 rows past the 64-row tiles of its segment of the other side and leaves the stripe's
 // partial results in the workspace (a row's k smallest distances of the segment; its count and nearest row there), and a second
 // kernel folds the segments in index order.  The number of segments depends on the sizes alone.  No atomics, no memset, nothing
-// depends on the order in which workgroups run.  Operands are staged as in fidelity.hip: widened to fp64 into LDS as s[k][row], 32 k at a time, rows and k beyond
-// the arrays as zeros, the next round's floats loaded into registers while the matrix pipe works on this one.
-#include "common.h"
+// depends on the order in which workgroups run.  The distance tiles are the 64 x 64 tiles of f64_tile.h; operands are widened to fp64
+// into LDS as s[k][row], 32 k at a time, rows and k beyond the arrays as zeros, the next round's floats loaded into registers
+// while the matrix pipe works on this one.
+#include "f64_tile.h"
 
 namespace afd {
 
-typedef double v4d __attribute__((ext_vector_type(4)));
-
-constexpr int kMfTile = 64;                        // rows of a stripe, rows of a tile of the other side
-constexpr int kMfThreads = 256;                    // 4 waves, a 32 x 32 quadrant of the distance tile each
-constexpr int kMfK = 32;                           // k staged per round
-constexpr int kMfPer = kMfTile * kMfK / kMfThreads;      // elements of one staged operand per thread
+// (kTile: the rows of a stripe, and of a tile of the other side)
 constexpr int kMfPitch = 65;                       // s[k][row], written k-fastest; also the pitch of the distance tile
 constexpr int kMfMaxK = 16;
 constexpr int kMfListPitch = kMfMaxK + 1;
 constexpr long kMfTarget = 4096;                   // workgroups the second launch aims for, whatever the device
 constexpr long kMfMaxSegments = 64;                // (one lane per segment in the fold of the k-th neighbour)
-constexpr int kMfSmem = 2 * kMfK * kMfPitch;       // doubles: the two staged operands, and over them the 64 x 65 distance tile
-static_assert(kMfSmem >= kMfTile * kMfPitch, "the distance tile fits over the staged operands");
-
-__device__ __forceinline__ v4d mf_mma(double a, double b, v4d c) { return __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, c, 0, 0, 0); }
+constexpr int kMfSmem = 2 * kTileK * kMfPitch;     // doubles: the two staged operands, and over them the 64 x 65 distance tile
+static_assert(kMfSmem >= kTile * kMfPitch, "the distance tile fits over the staged operands");
 
 // The thread's elements of a round: k = tid & 31, rows (tid >> 5) + 8 j of the 64 from row0 (row0 < rows).  One uniform base and
 // 32-bit offsets per thread (64 rows of at most 2^15 floats).
-__device__ __forceinline__ void mf_fetch(const float* __restrict__ src, long rows, int D, long row0, int d0, int tid, float (&v)[kMfPer]) {
+__device__ __forceinline__ void mf_fetch(const float* __restrict__ src, long rows, int D, long row0, int d0, int tid, float (&v)[kTilePer]) {
   const int k = tid & 31, r = tid >> 5;
   const long left = rows - row0;
-  const int lim = d0 + k < D ? (left < kMfTile ? (int)left : kMfTile) : 0;      // the rows of the tile this thread may read
+  const int lim = d0 + k < D ? (left < kTile ? (int)left : kTile) : 0;      // the rows of the tile this thread may read
   const float* p = src + (row0 * D + d0);
   const int o = r * D + k, step = 8 * D;
 #pragma unroll
-  for (int j = 0; j < kMfPer; ++j) v[j] = r + 8 * j < lim ? p[o + j * step] : 0.0f;
-}
-
-__device__ __forceinline__ void mf_stage(double* s, int tid, const float (&v)[kMfPer]) {
-  const int k = tid & 31;
-#pragma unroll
-  for (int j = 0; j < kMfPer; ++j) s[k * kMfPitch + (tid >> 5) + 8 * j] = (double)v[j];
-}
-
-// Fragments of mfma_f64_16x16x4_f64: lane l holds A[row l & 15][k = l >> 4] and B[k = l >> 4][column l & 15]; result register r of
-// lane l is D[row (l >> 4) + 4 r][column l & 15].  acc[a][b] is the 16 x 16 tile at (ra + 16 a, cb + 16 b).
-__device__ __forceinline__ void mf_round(const double* sa, const double* sb, int ra, int cb, int c16, int g4, v4d (&acc)[2][2]) {
-#pragma unroll
-  for (int kk = 0; kk < kMfK / 4; ++kk) {
-    const int o = (4 * kk + g4) * kMfPitch + c16;
-    const double a0 = sa[o + ra], a1 = sa[o + ra + 16], b0 = sb[o + cb], b1 = sb[o + cb + 16];
-    acc[0][0] = mf_mma(a0, b0, acc[0][0]);
-    acc[0][1] = mf_mma(a0, b1, acc[0][1]);
-    acc[1][0] = mf_mma(a1, b0, acc[1][0]);
-    acc[1][1] = mf_mma(a1, b1, acc[1][1]);
-  }
+  for (int j = 0; j < kTilePer; ++j) v[j] = r + 8 * j < lim ? p[o + j * step] : 0.0f;
 }
 
 // ---- squared norms -----------------------------------------------------------------------------------------------------------------
 // Workgroup b < ta: rows [64 b, 64 b + 64) of A, else rows [64 (b - ta), ...) of B.  Wave w runs the chain of the cross term on
 // rows 16 w .. 16 w + 15 against themselves and keeps the diagonal: row i of the tile is in lane (i & 3) * 16 + i, register i >> 2.
-__global__ __launch_bounds__(kMfThreads) void mf_norms_k(const float* __restrict__ A, long na, const float* __restrict__ B, long nb, int D,
+__global__ __launch_bounds__(kTileThreads) void mf_norms_k(const float* __restrict__ A, long na, const float* __restrict__ B, long nb, int D,
                                                          long ta, double* __restrict__ norm_a, double* __restrict__ norm_b) {
-  __shared__ double s[kMfK * kMfPitch];
-  const int tid = threadIdx.x, lane = tid & 63, c16 = lane & 15, g4 = lane >> 4;
-  const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
+  __shared__ double s[kTileK * kMfPitch];
+  const int tid = threadIdx.x;
+  const TileLane q = tile_lane(tid);
   const bool second = (long)blockIdx.x >= ta;
   const float* src = second ? B : A;
-  const long rows = second ? nb : na, row0 = ((long)blockIdx.x - (second ? ta : 0)) * kMfTile;
+  const long rows = second ? nb : na, row0 = ((long)blockIdx.x - (second ? ta : 0)) * kTile;
   double* out = second ? norm_b : norm_a;
   v4d acc = v4d{0.0, 0.0, 0.0, 0.0};
-  float nx[kMfPer];
+  float nx[kTilePer];
   mf_fetch(src, rows, D, row0, 0, tid, nx);
-  for (int d0 = 0; d0 < D; d0 += kMfK) {
-    mf_stage(s, tid, nx);
+  for (int d0 = 0; d0 < D; d0 += kTileK) {
+    tile_stage_kfast<kMfPitch>(s, tid, nx);
     __syncthreads();
-    if (d0 + kMfK < D) mf_fetch(src, rows, D, row0, d0 + kMfK, tid, nx);
+    if (d0 + kTileK < D) mf_fetch(src, rows, D, row0, d0 + kTileK, tid, nx);
 #pragma unroll
-    for (int kk = 0; kk < kMfK / 4; ++kk) {
-      const double a = s[(4 * kk + g4) * kMfPitch + 16 * w + c16];
-      acc = mf_mma(a, a, acc);
+    for (int kk = 0; kk < kTileK / 4; ++kk) {
+      const double a = s[(4 * kk + q.g4) * kMfPitch + 16 * q.w + q.c16];
+      acc = mma_f64(a, a, acc);
     }
     __syncthreads();
   }
-  const int r = c16 >> 2;
+  const int r = q.c16 >> 2;
   const double v = r == 0 ? acc[0] : r == 1 ? acc[1] : r == 2 ? acc[2] : acc[3];
-  const long row = row0 + 16 * w + c16;
-  if (g4 == (c16 & 3) && row < rows) out[row] = v;
+  const long row = row0 + 16 * q.w + q.c16;
+  if (q.g4 == (q.c16 & 3) && row < rows) out[row] = v;
 }
 
 // The 64 x 64 tile of d2 between the stripe from row I of A and the rows from J of B, left in smem[row * 65 + column] (over the
 // staged operands).  nx_a / nx_b hold the first round's elements on entry and, on return, those of the tile from next_j (if next_j is
 // below j_end, the end of the workgroup's segment).  Ends behind a barrier: the tile is complete.
 __device__ __forceinline__ void mf_distance_tile(const float* __restrict__ A, long na, const float* __restrict__ B, long nb, int D, long I, long J,
-                                                 long next_j, long j_end, const double* sn_a, const double* sn_b, double* smem, float (&nx_a)[kMfPer],
-                                                 float (&nx_b)[kMfPer], int tid) {
+                                                 long next_j, long j_end, const double* sn_a, const double* sn_b, double* smem, float (&nx_a)[kTilePer],
+                                                 float (&nx_b)[kTilePer], int tid) {
   double* sa = smem;
-  double* sb = smem + kMfK * kMfPitch;
-  const int lane = tid & 63, c16 = lane & 15, g4 = lane >> 4;
-  const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int ra = 32 * (w >> 1), cb = 32 * (w & 1);
+  double* sb = smem + kTileK * kMfPitch;
+  const TileLane q = tile_lane(tid);
   v4d acc[2][2];
-#pragma unroll
-  for (int a = 0; a < 2; ++a)
-#pragma unroll
-    for (int b = 0; b < 2; ++b) acc[a][b] = v4d{0.0, 0.0, 0.0, 0.0};
-  for (int d0 = 0; d0 < D; d0 += kMfK) {
-    mf_stage(sa, tid, nx_a);
-    mf_stage(sb, tid, nx_b);
+  tile_zero(acc);
+  for (int d0 = 0; d0 < D; d0 += kTileK) {
+    tile_stage_kfast<kMfPitch>(sa, tid, nx_a);
+    tile_stage_kfast<kMfPitch>(sb, tid, nx_b);
     __syncthreads();
-    const bool more = d0 + kMfK < D;
+    const bool more = d0 + kTileK < D;
     if (more || next_j < j_end) {
-      mf_fetch(A, na, D, I, more ? d0 + kMfK : 0, tid, nx_a);
-      mf_fetch(B, nb, D, more ? J : next_j, more ? d0 + kMfK : 0, tid, nx_b);
+      mf_fetch(A, na, D, I, more ? d0 + kTileK : 0, tid, nx_a);
+      mf_fetch(B, nb, D, more ? J : next_j, more ? d0 + kTileK : 0, tid, nx_b);
     }
-    mf_round(sa, sb, ra, cb, c16, g4, acc);
+    tile_round<kMfPitch>(sa, sb, q, acc);
     __syncthreads();                               // every wave is done with the operands: the distance tile goes over them
   }
-#pragma unroll
-  for (int a = 0; a < 2; ++a)
-#pragma unroll
-    for (int b = 0; b < 2; ++b)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int row = ra + 16 * a + g4 + 4 * r, col = cb + 16 * b + c16;
-        const double d = (sn_a[row] + sn_b[col]) - 2.0 * acc[a][b][r];
-        smem[row * kMfPitch + col] = d < 0.0 ? 0.0 : d;      // (a select: a NaN stays a NaN)
-      }
+  tile_for_each(q, acc, [&](int row, int col, double dot) {
+    const double d = (sn_a[row] + sn_b[col]) - 2.0 * dot;
+    smem[row * kMfPitch + col] = d < 0.0 ? 0.0 : d;          // (a select: a NaN stays a NaN)
+  });
   __syncthreads();
 }
 
@@ -142,27 +105,27 @@ __device__ __forceinline__ void mf_distance_tile(const float* __restrict__ A, lo
 // holds the row's k smallest distances so far, ascending (+inf: an empty slot).  Per tile every thread tests 16 distances of one
 // row against the row's current k-th and leaves a bit mask; thread `row` then inserts the few that passed, in column order.  A
 // NaN compares false and is no candidate.  The lists go to the workspace as [segment][row][k].
-__global__ __launch_bounds__(kMfThreads, 2) void mf_kth_k(const float* __restrict__ X, long n, int D, int k, long seg,
+__global__ __launch_bounds__(kTileThreads, 2) void mf_kth_k(const float* __restrict__ X, long n, int D, int k, long seg,
                                                           const double* __restrict__ norms, double* __restrict__ parts) {
   __shared__ double smem[kMfSmem];
-  __shared__ double list[kMfTile * kMfListPitch];
-  __shared__ double sn_a[kMfTile], sn_b[kMfTile];
-  __shared__ unsigned mask[kMfThreads];
+  __shared__ double list[kTile * kMfListPitch];
+  __shared__ double sn_a[kTile], sn_b[kTile];
+  __shared__ unsigned mask[kTileThreads];
   const int tid = threadIdx.x, row = tid & 63, part = tid >> 6;
-  const long I = (long)blockIdx.x * kMfTile, gi = I + row;
+  const long I = (long)blockIdx.x * kTile, gi = I + row;
   const double inf = __builtin_inf();
-  if (tid < kMfTile) {
+  if (tid < kTile) {
 #pragma unroll
     for (int t = 0; t < kMfMaxK; ++t) list[tid * kMfListPitch + t] = inf;
     sn_a[tid] = I + tid < n ? norms[I + tid] : 0.0;
   }
-  float nx_a[kMfPer], nx_b[kMfPer];
+  float nx_a[kTilePer], nx_b[kTilePer];
   mf_fetch(X, n, D, I, 0, tid, nx_a);
   const long j_begin = (long)blockIdx.y * seg, j_end = j_begin + seg < n ? j_begin + seg : n;
   mf_fetch(X, n, D, j_begin, 0, tid, nx_b);
-  for (long J = j_begin; J < j_end; J += kMfTile) {
-    if (tid < kMfTile) sn_b[tid] = J + tid < n ? norms[J + tid] : 0.0;   // (read behind the barriers of the tile)
-    mf_distance_tile(X, n, X, n, D, I, J, J + kMfTile, j_end, sn_a, sn_b, smem, nx_a, nx_b, tid);
+  for (long J = j_begin; J < j_end; J += kTile) {
+    if (tid < kTile) sn_b[tid] = J + tid < n ? norms[J + tid] : 0.0;   // (read behind the barriers of the tile)
+    mf_distance_tile(X, n, X, n, D, I, J, J + kTile, j_end, sn_a, sn_b, smem, nx_a, nx_b, tid);
     const double thr = list[row * kMfListPitch + k - 1];
     unsigned m = 0;
 #pragma unroll
@@ -173,10 +136,10 @@ __global__ __launch_bounds__(kMfThreads, 2) void mf_kth_k(const float* __restric
     }
     mask[tid] = m;
     __syncthreads();
-    if (tid < kMfTile) {
+    if (tid < kTile) {
       double* mine = list + tid * kMfListPitch;
       for (int p = 0; p < 4; ++p) {
-        unsigned mm = mask[p * kMfTile + tid];
+        unsigned mm = mask[p * kTile + tid];
         while (mm) {
           const int c = __builtin_ctz(mm);
           mm &= mm - 1;
@@ -194,7 +157,7 @@ __global__ __launch_bounds__(kMfThreads, 2) void mf_kth_k(const float* __restric
     }
     __syncthreads();                               // the tile and the masks are free again, the lists are up to date
   }
-  if (tid < kMfTile && gi < n) {
+  if (tid < kTile && gi < n) {
     double* out = parts + ((long)blockIdx.y * n + gi) * k;
     for (int t = 0; t < k; ++t) out[t] = list[tid * kMfListPitch + t];
   }
@@ -202,9 +165,9 @@ __global__ __launch_bounds__(kMfThreads, 2) void mf_kth_k(const float* __restric
 
 // Wave i: the k-th smallest of row i's S ascending lists of k.  Lane s holds its position in list s; a round takes the smallest
 // head (the lowest lane among equal ones moves on), and round k's is the answer; +inf once the candidates have run out.
-__global__ __launch_bounds__(kMfThreads) void mf_kth_fold_k(const double* __restrict__ part, long n, int k, int S, double* __restrict__ radius2) {
+__global__ __launch_bounds__(kTileThreads) void mf_kth_fold_k(const double* __restrict__ part, long n, int k, int S, double* __restrict__ radius2) {
   const int lane = threadIdx.x & 63;
-  const long i = (long)blockIdx.x * (kMfThreads / kWave) + (threadIdx.x >> 6);
+  const long i = (long)blockIdx.x * (kTileThreads / kWave) + (threadIdx.x >> 6);
   if (i >= n) return;                                // (the whole wave)
   const double inf = __builtin_inf();
   const double* mine = part + ((long)(lane < S ? lane : 0) * n + i) * k;
@@ -229,29 +192,29 @@ __global__ __launch_bounds__(kMfThreads) void mf_kth_fold_k(const double* __rest
 // Workgroup (b, g): queries [64 b, 64 b + 64) against store rows [g seg, min(nr, (g + 1) seg)).  Thread (row, part) walks columns
 // 16 part .. 16 part + 15 of every tile in ascending store index and keeps its count and its nearest row (strictly smaller only:
 // the lower index stays); the four parts of a row are joined at the end by (distance, index) and left in the workspace.
-__global__ __launch_bounds__(kMfThreads, 2) void mf_ball_k(const float* __restrict__ Q, long nq, const float* __restrict__ R, long nr, int D,
+__global__ __launch_bounds__(kTileThreads, 2) void mf_ball_k(const float* __restrict__ Q, long nq, const float* __restrict__ R, long nr, int D,
                                                         const double* __restrict__ radius2, const int64_t* __restrict__ exclude,
                                                         const double* __restrict__ norm_q, const double* __restrict__ norm_r, long seg,
                                                         double* __restrict__ part_d, long* __restrict__ part_j, int* __restrict__ part_c) {
   __shared__ double smem[kMfSmem];
-  __shared__ double sn_a[kMfTile], sn_b[kMfTile], rad[kMfTile];
+  __shared__ double sn_a[kTile], sn_b[kTile], rad[kTile];
   const int tid = threadIdx.x, row = tid & 63, part = tid >> 6;
-  const long I = (long)blockIdx.x * kMfTile, gi = I + row;
+  const long I = (long)blockIdx.x * kTile, gi = I + row;
   const long ex = (exclude && gi < nq) ? exclude[gi] : -1;
-  if (tid < kMfTile) sn_a[tid] = I + tid < nq ? norm_q[I + tid] : 0.0;
+  if (tid < kTile) sn_a[tid] = I + tid < nq ? norm_q[I + tid] : 0.0;
   int cnt = 0;
   long best_j = -1;
   double best = __builtin_inf();
-  float nx_a[kMfPer], nx_b[kMfPer];
+  float nx_a[kTilePer], nx_b[kTilePer];
   mf_fetch(Q, nq, D, I, 0, tid, nx_a);
   const long j_begin = (long)blockIdx.y * seg, j_end = j_begin + seg < nr ? j_begin + seg : nr;
   mf_fetch(R, nr, D, j_begin, 0, tid, nx_b);
-  for (long J = j_begin; J < j_end; J += kMfTile) {
-    if (tid < kMfTile) {                             // (read behind the barriers of the tile)
+  for (long J = j_begin; J < j_end; J += kTile) {
+    if (tid < kTile) {                             // (read behind the barriers of the tile)
       sn_b[tid] = J + tid < nr ? norm_r[J + tid] : 0.0;
       rad[tid] = J + tid < nr ? radius2[J + tid] : 0.0;
     }
-    mf_distance_tile(Q, nq, R, nr, D, I, J, J + kMfTile, j_end, sn_a, sn_b, smem, nx_a, nx_b, tid);
+    mf_distance_tile(Q, nq, R, nr, D, I, J, J + kTile, j_end, sn_a, sn_b, smem, nx_a, nx_b, tid);
 #pragma unroll
     for (int c = 0; c < 16; ++c) {
       const int col = 16 * part + c;
@@ -268,17 +231,17 @@ __global__ __launch_bounds__(kMfThreads, 2) void mf_ball_k(const float* __restri
     __syncthreads();                               // the tile is free again
   }
   double* jd = smem;                                 // the parts' results: [part][row]
-  long* jj = reinterpret_cast<long*>(smem + kMfThreads);
-  int* jc = reinterpret_cast<int*>(smem + 2 * kMfThreads);
+  long* jj = reinterpret_cast<long*>(smem + kTileThreads);
+  int* jc = reinterpret_cast<int*>(smem + 2 * kTileThreads);
   jd[tid] = best;
   jj[tid] = best_j;
   jc[tid] = cnt;
   __syncthreads();
-  if (tid < kMfTile && gi < nq) {
+  if (tid < kTile && gi < nq) {
     for (int p = 1; p < 4; ++p) {
-      const double d = jd[p * kMfTile + tid];
-      const long j = jj[p * kMfTile + tid];
-      cnt += jc[p * kMfTile + tid];
+      const double d = jd[p * kTile + tid];
+      const long j = jj[p * kTile + tid];
+      cnt += jc[p * kTile + tid];
       if (j >= 0 && (best_j < 0 || d < best || (d == best && j < best_j))) {
         best = d;
         best_j = j;
@@ -293,10 +256,10 @@ __global__ __launch_bounds__(kMfThreads, 2) void mf_ball_k(const float* __restri
 
 // Thread q folds query q's S partial results in segment order: the segments ascend in store index, so on equal distances the
 // lower index stays.
-__global__ __launch_bounds__(kMfThreads) void mf_ball_fold_k(const double* __restrict__ part_d, const long* __restrict__ part_j,
+__global__ __launch_bounds__(kTileThreads) void mf_ball_fold_k(const double* __restrict__ part_d, const long* __restrict__ part_j,
                                                              const int* __restrict__ part_c, long nq, int S, int* __restrict__ count,
                                                              int64_t* __restrict__ nearest, double* __restrict__ nearest_d2) {
-  const long q = (long)blockIdx.x * kMfThreads + threadIdx.x;
+  const long q = (long)blockIdx.x * kTileThreads + threadIdx.x;
   if (q >= nq) return;
   int cnt = 0;
   long best_j = -1;
@@ -318,7 +281,7 @@ __global__ __launch_bounds__(kMfThreads) void mf_ball_fold_k(const double* __res
 }
 
 static bool mf_rows_ok(long n, long D) { return n > 0 && D > 0 && n < (1L << 31) && D <= (1L << 15) && D <= (1L << 40) / n; }
-static long mf_stripes(long n) { return (n + kMfTile - 1) / kMfTile; }
+static long mf_stripes(long n) { return (n + kTile - 1) / kTile; }
 // the store's tiles are cut into segments of `per` tiles each, a number that depends on the two sizes alone; no segment is empty
 static long mf_tiles_per_segment(long nq, long nr) {
   const long stripes = mf_stripes(nq), tiles = mf_stripes(nr);
@@ -359,11 +322,11 @@ int afd_kth_neighbour_f32(const float* X, long n, long D, long k, double* radius
   AFD_REQUIRE(!overlaps(workspace, (long)need, radius2, rb), "%s: radius2 and workspace must not overlap each other", name);
   double* norms = static_cast<double*>(workspace);
   double* part = norms + n;
-  const long T = mf_stripes(n), S = mf_segments(n, n), seg = mf_tiles_per_segment(n, n) * kMfTile;
+  const long T = mf_stripes(n), S = mf_segments(n, n), seg = mf_tiles_per_segment(n, n) * kTile;
   hipStream_t stream = as_stream(st);
-  hipLaunchKernelGGL(mf_norms_k, dim3((unsigned)T), dim3(kMfThreads), 0, stream, X, n, X, 0L, (int)D, T, norms, norms);
-  hipLaunchKernelGGL(mf_kth_k, dim3((unsigned)T, (unsigned)S), dim3(kMfThreads), 0, stream, X, n, (int)D, (int)k, seg, norms, part);
-  hipLaunchKernelGGL(mf_kth_fold_k, dim3((unsigned)((n + 3) / 4)), dim3(kMfThreads), 0, stream, part, n, (int)k, (int)S, radius2);
+  hipLaunchKernelGGL(mf_norms_k, dim3((unsigned)T), dim3(kTileThreads), 0, stream, X, n, X, 0L, (int)D, T, norms, norms);
+  hipLaunchKernelGGL(mf_kth_k, dim3((unsigned)T, (unsigned)S), dim3(kTileThreads), 0, stream, X, n, (int)D, (int)k, seg, norms, part);
+  hipLaunchKernelGGL(mf_kth_fold_k, dim3((unsigned)((n + 3) / 4)), dim3(kTileThreads), 0, stream, part, n, (int)k, (int)S, radius2);
   return check_launch(name);
 }
 
@@ -400,17 +363,17 @@ int afd_ball_membership_f32(const float* Q, long nq, const float* R, long nr, lo
     for (int j = i + 1; j < 4; ++j)
       AFD_REQUIRE(!out[i].p || !overlaps(out[i].p, out[i].bytes, out[j].p, out[j].bytes),
                   "%s: count, nearest, nearest_d2 and workspace must not overlap each other", name);
-  const long TQ = mf_stripes(nq), TR = mf_stripes(nr), S = mf_segments(nq, nr), seg = mf_tiles_per_segment(nq, nr) * kMfTile;
+  const long TQ = mf_stripes(nq), TR = mf_stripes(nr), S = mf_segments(nq, nr), seg = mf_tiles_per_segment(nq, nr) * kTile;
   double* norm_q = static_cast<double*>(workspace);
   double* norm_r = norm_q + nq;
   double* part_d = norm_r + nr;
   long* part_j = reinterpret_cast<long*>(part_d + S * nq);
   int* part_c = reinterpret_cast<int*>(part_j + S * nq);
   hipStream_t stream = as_stream(st);
-  hipLaunchKernelGGL(mf_norms_k, dim3((unsigned)(TQ + TR)), dim3(kMfThreads), 0, stream, Q, nq, R, nr, (int)D, TQ, norm_q, norm_r);
-  hipLaunchKernelGGL(mf_ball_k, dim3((unsigned)TQ, (unsigned)S), dim3(kMfThreads), 0, stream, Q, nq, R, nr, (int)D, radius2, exclude, norm_q, norm_r,
+  hipLaunchKernelGGL(mf_norms_k, dim3((unsigned)(TQ + TR)), dim3(kTileThreads), 0, stream, Q, nq, R, nr, (int)D, TQ, norm_q, norm_r);
+  hipLaunchKernelGGL(mf_ball_k, dim3((unsigned)TQ, (unsigned)S), dim3(kTileThreads), 0, stream, Q, nq, R, nr, (int)D, radius2, exclude, norm_q, norm_r,
                      seg, part_d, part_j, part_c);
-  hipLaunchKernelGGL(mf_ball_fold_k, dim3((unsigned)((nq + kMfThreads - 1) / kMfThreads)), dim3(kMfThreads), 0, stream, part_d, part_j, part_c, nq,
+  hipLaunchKernelGGL(mf_ball_fold_k, dim3((unsigned)((nq + kTileThreads - 1) / kTileThreads)), dim3(kTileThreads), 0, stream, part_d, part_j, part_c, nq,
                      (int)S, count, nearest, nearest_d2);
   return check_launch(name);
 }

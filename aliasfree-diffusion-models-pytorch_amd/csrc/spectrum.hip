@@ -11,11 +11,9 @@
 // Workgroup (g, c) walks channel c of the images of slice g, keeps sum |F|^2 in registers and leaves one (H, Wh) partial in the
 // workspace; spectrum_finish_k folds the partials in a fixed tree, divides by n once and reduces the radial sums in a fixed order.
 // No atomics, no memset, nothing depends on the order in which workgroups run: the same arguments give the same bits.
-#include "common.h"
+#include "f64_tile.h"                              // v4d, mma_f64 and the fragment layout; the tiles here are a shape of their own
 
 namespace afd {
-
-typedef double v4d __attribute__((ext_vector_type(4)));
 
 constexpr int kSpMax = 64;                         // largest H and W
 constexpr int kSpThreads = 256;                    // 4 waves; the 4 x 3 tiles of a 64 x 33 result are 3 per wave
@@ -39,10 +37,6 @@ __device__ __forceinline__ void unit_root(int m, int N, double& c, double& s) {
   s = q == 0 ? sr : q == 1 ? cr : q == 2 ? -sr : -cr;
 }
 
-__device__ __forceinline__ v4d mma(double a, double b, v4d c) { return __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, c, 0, 0, 0); }
-
-// Fragments of mfma_f64_16x16x4_f64: lane l holds A[row l & 15][k = l >> 4] and B[k = l >> 4][column l & 15]; result register r of
-// lane l is D[row (l >> 4) + 4 r][column l & 15].
 template <bool U8>
 __global__ __launch_bounds__(kSpThreads, 3) void spectrum_k(const void* __restrict__ images, const float* __restrict__ table, long n, int C, int H,
                                                          int W, const double* __restrict__ win_h, const double* __restrict__ win_w,
@@ -119,8 +113,8 @@ __global__ __launch_bounds__(kSpThreads, 3) void spectrum_k(const void* __restri
           const int k = 4 * kk + g4;
           const double a = (rok && k < W) ? buf[row * kXPitch + k] : 0.0;
           const double br = vok ? cw[idx] : 0.0, bi = vok ? -sw[idx] : 0.0;
-          yr[i] = mma(a, br, yr[i]);
-          yi[i] = mma(a, bi, yi[i]);
+          yr[i] = mma_f64(a, br, yr[i]);
+          yi[i] = mma_f64(a, bi, yi[i]);
           idx += step;
           idx -= idx >= W ? W : 0;
         }
@@ -154,10 +148,10 @@ __global__ __launch_bounds__(kSpThreads, 3) void spectrum_k(const void* __restri
         for (int kk = 0; kk < K2; ++kk) {
           const int o = (4 * kk + g4) * kYPitch + vc;
           const double cc = ch[idx], ss = sh[idx], br = buf[o], bi = buf[kYImag + o];
-          fr = mma(cc, br, fr);
-          fi = mma(cc, bi, fi);
-          fr = mma(ss, bi, fr);
-          fi = mma(-ss, br, fi);
+          fr = mma_f64(cc, br, fr);
+          fi = mma_f64(cc, bi, fi);
+          fr = mma_f64(ss, bi, fr);
+          fi = mma_f64(-ss, br, fi);
           idx += step;
           idx -= idx >= H ? H : 0;
         }

@@ -2008,6 +2008,15 @@ def nn_search(data, queries, k=1, exclude=None):
     return dist, idx
 
 
+def _workspace(what, nbytes, sizes, device):
+    """-> (the fp64 workspace of an evaluation call, its bytes); nbytes: what the call's afd_*_workspace_bytes gave (0: sizes, the
+    text that names them, are out of range)."""
+    nbytes = int(nbytes)
+    if nbytes <= 0:
+        raise AfdError(f"afdm: {what}: sizes out of range ({sizes})")
+    return torch.empty(nbytes // 8, device=device, dtype=torch.float64), nbytes
+
+
 SPECTRUM_MAX_SIDE = 64
 
 
@@ -2042,18 +2051,23 @@ def power_spectrum(images, table=None, win_h=None, win_w=None, remove_mean=True,
         _dev_table(what, "bins", bins, torch.int32, (H, Wh))
         if isinstance(R, bool) or not isinstance(R, int) or R < 1:
             raise AfdError(f"afdm: {what}: R must be an int >= 1 (got {R!r})")
-    nbytes = int(lib().afd_spectrum_workspace_bytes(n, C, H, W))
-    if nbytes <= 0:
-        raise AfdError(f"afdm: {what}: sizes out of range (n = {n}, C = {C}, H = {H}, W = {W})")
+    ws, nbytes = _workspace(what, lib().afd_spectrum_workspace_bytes(n, C, H, W), f"n = {n}, C = {C}, H = {H}, W = {W}", images.device)
     power = torch.empty(C, H, Wh, device=images.device, dtype=torch.float64) if want_power else None
     radial = torch.empty(C, R, device=images.device, dtype=torch.float64) if bins is not None else None
-    ws = torch.empty(nbytes // 8, device=images.device, dtype=torch.float64)
     tail = (n, C, H, W, _p(win_h), _p(win_w), int(bool(remove_mean)), _p(bins), R or 0, _p(power), _p(radial), _p(ws), nbytes, _stream())
     if u8:
         lib().afd_power_spectrum_u8(_p(images), _p(table), *tail)
     else:
         lib().afd_power_spectrum_f32(_p(images), *tail)
     return power, radial
+
+
+def _feature_set(what, name, v, D=None):
+    if not isinstance(v, torch.Tensor) or not v.is_cuda or v.dim() != 2 or v.numel() == 0 or v.dtype != torch.float32:
+        raise AfdError(f"afdm: {what}: {name} must be a non-empty (n, D) fp32 device tensor")
+    if D is not None and v.shape[1] != D:
+        raise AfdError(f"afdm: {what}: {name} must have the row size {D} (got {v.shape[1]})")
+    return _c(v.detach())
 
 
 MMD_MAX_DEGREE = 8
@@ -2065,10 +2079,7 @@ def feature_moments(features, sum=None, outer=None):
     (made contiguous if it is not); sum (D,) and outer (D, D): contiguous fp64 device tensors to ADD to, given together, or None
     for fresh ones.  -> (sum, outer): sum[c] = sum_r x[r][c], outer[i][j] = sum_r x[r][i] x[r][j], outer symmetric bit for bit."""
     what = "feature_moments"
-    if not isinstance(features, torch.Tensor) or not features.is_cuda or features.dim() != 2 or features.numel() == 0 \
-            or features.dtype != torch.float32:
-        raise AfdError(f"afdm: {what}: features must be a non-empty (n, D) fp32 device tensor")
-    features = _c(features.detach())
+    features = _feature_set(what, "features", features)
     n, D = features.shape
     if (sum is None) != (outer is None):
         raise AfdError(f"afdm: {what}: sum and outer go together")
@@ -2079,10 +2090,7 @@ def feature_moments(features, sum=None, outer=None):
     else:
         sum = torch.empty(D, device=features.device, dtype=torch.float64)
         outer = torch.empty(D, D, device=features.device, dtype=torch.float64)
-    nbytes = int(lib().afd_feature_moments_workspace_bytes(n, D))
-    if nbytes <= 0:
-        raise AfdError(f"afdm: {what}: sizes out of range (n = {n}, D = {D})")
-    ws = torch.empty(nbytes // 8, device=features.device, dtype=torch.float64)
+    ws, nbytes = _workspace(what, lib().afd_feature_moments_workspace_bytes(n, D), f"n = {n}, D = {D}", features.device)
     lib().afd_feature_moments_f32(_p(features), n, D, _p(sum), _p(outer), int(accumulate), _p(ws), nbytes, _stream())
     return sum, outer
 
@@ -2094,12 +2102,9 @@ def poly_mmd_sums(a, b, ia, ib, degree, gamma, coef0, check_range=True):
     the same within b's, and over all (i, j) between them.  check_range: the indices are checked against na and nb first (one
     synchronising read); without it an index out of range makes its row NaN."""
     what = "poly_mmd_sums"
-    for name, v in (("a", a), ("b", b)):
-        if not isinstance(v, torch.Tensor) or not v.is_cuda or v.dim() != 2 or v.numel() == 0 or v.dtype != torch.float32:
-            raise AfdError(f"afdm: {what}: {name} must be a non-empty (n, D) fp32 device tensor")
+    a, b = _feature_set(what, "a", a), _feature_set(what, "b", b)
     if a.shape[1] != b.shape[1]:
         raise AfdError(f"afdm: {what}: a and b must have one row size (got {a.shape[1]} and {b.shape[1]})")
-    a, b = _c(a.detach()), _c(b.detach())
     (na, D), nb = a.shape, b.shape[0]
     for name, v in (("ia", ia), ("ib", ib)):
         if not isinstance(v, torch.Tensor) or not v.is_cuda or v.dtype != torch.long or v.dim() != 2 or not v.is_contiguous():
@@ -2115,25 +2120,14 @@ def poly_mmd_sums(a, b, ia, ib, degree, gamma, coef0, check_range=True):
         if lo[0] < 0 or hi[0] >= na or lo[1] < 0 or hi[1] >= nb:
             raise AfdError(f"afdm: {what}: an index lies outside its array (ia in [{lo[0]}, {hi[0]}] for {na} rows, ib in [{lo[1]}, {hi[1]}] "
                            f"for {nb} rows)")
-    nbytes = int(lib().afd_poly_mmd_workspace_bytes(S, m, D))
-    if nbytes <= 0:
-        raise AfdError(f"afdm: {what}: sizes out of range (S = {S}, m = {m}, D = {D})")
+    ws, nbytes = _workspace(what, lib().afd_poly_mmd_workspace_bytes(S, m, D), f"S = {S}, m = {m}, D = {D}", a.device)
     sums = torch.empty(S, 3, device=a.device, dtype=torch.float64)
-    ws = torch.empty(nbytes // 8, device=a.device, dtype=torch.float64)
     lib().afd_poly_mmd_sums_f32(_p(a), na, _p(b), nb, D, _p(ia), _p(ib), S, m, int(degree), float(gamma), float(coef0), _p(sums), _p(ws),
                                 nbytes, _stream())
     return sums
 
 
 MANIFOLD_MAX_K = 16
-
-
-def _feature_set(what, name, v, D=None):
-    if not isinstance(v, torch.Tensor) or not v.is_cuda or v.dim() != 2 or v.numel() == 0 or v.dtype != torch.float32:
-        raise AfdError(f"afdm: {what}: {name} must be a non-empty (n, D) fp32 device tensor")
-    if D is not None and v.shape[1] != D:
-        raise AfdError(f"afdm: {what}: {name} must have the row size {D} (got {v.shape[1]})")
-    return _c(v.detach())
 
 
 def kth_neighbour(features, k):
@@ -2145,11 +2139,8 @@ def kth_neighbour(features, k):
     if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 1 <= k <= MANIFOLD_MAX_K:
         raise AfdError(f"afdm: {what}: k must be an int in [1, {MANIFOLD_MAX_K}] (got {k!r})")
     n, D = features.shape
-    nbytes = int(lib().afd_kth_neighbour_workspace_bytes(n, D, int(k)))
-    if nbytes <= 0:
-        raise AfdError(f"afdm: {what}: sizes out of range (n = {n}, D = {D})")
+    ws, nbytes = _workspace(what, lib().afd_kth_neighbour_workspace_bytes(n, D, int(k)), f"n = {n}, D = {D}", features.device)
     radius2 = torch.empty(n, device=features.device, dtype=torch.float64)
-    ws = torch.empty(nbytes // 8, device=features.device, dtype=torch.float64)
     lib().afd_kth_neighbour_f32(_p(features), n, D, int(k), _p(radius2), _p(ws), nbytes, _stream())
     return radius2
 
@@ -2170,14 +2161,11 @@ def ball_membership(queries, store, radius2, exclude=None, want_count=True, want
         _dev_table(what, "exclude", exclude, torch.long, (nq,))
     if not want_count and not want_nearest:
         raise AfdError(f"afdm: {what}: nothing to compute (want_count and want_nearest are both False)")
-    nbytes = int(lib().afd_ball_membership_workspace_bytes(nq, nr, D))
-    if nbytes <= 0:
-        raise AfdError(f"afdm: {what}: sizes out of range (nq = {nq}, nr = {nr}, D = {D})")
     dev = queries.device
+    ws, nbytes = _workspace(what, lib().afd_ball_membership_workspace_bytes(nq, nr, D), f"nq = {nq}, nr = {nr}, D = {D}", dev)
     count = torch.empty(nq, device=dev, dtype=torch.int32) if want_count else None
     nearest = torch.empty(nq, device=dev, dtype=torch.long) if want_nearest else None
     nearest_d2 = torch.empty(nq, device=dev, dtype=torch.float64) if want_nearest else None
-    ws = torch.empty(nbytes // 8, device=dev, dtype=torch.float64)
     lib().afd_ball_membership_f32(_p(queries), nq, _p(store), nr, D, _p(radius2), _p(exclude), _p(count), _p(nearest), _p(nearest_d2),
                                   _p(ws), nbytes, _stream())
     return count, nearest, nearest_d2

@@ -4,8 +4,10 @@ same `params` keys, run-directory layout, settings text and file names; the plot
 cells of the reference are not reproduced (out of scope: visualisation)."""
 import csv
 import gc
+import json
 import logging
 import os
+from collections import namedtuple
 
 import numpy as np
 import torch
@@ -81,16 +83,7 @@ def ddpm_run(params):
     data_keys = [k for k in DATA_KEYS if params.get(k) is not None]
     if params.get("distill") is not None:
         _distill_cfg(params)                                   # a malformed key fails here, not after the training
-    if params.get("eval_nearest") is not None:
-        _nearest_cfg(params)
-    if params.get("eval_spectrum") is not None:
-        _spectrum_cfg(params)
-    if params.get("eval_fidelity") is not None:
-        _fidelity_cfg(params)
-    if params.get("eval_manifold") is not None:
-        _manifold_cfg(params)
-    if params.get("eval_restoration") is not None:
-        _restoration_cfg(params)
+    evals = _eval_cfgs(params)                                 # (and so does a malformed evaluation key: EVALS)
     cwd = os.getcwd()
     modelpath = os.path.join(cwd, f"models/DDPM_Uncondtional_{name}_{v}/ckpt_{name}_{v}.pt")
     f_settings = _f_settings(params)
@@ -137,12 +130,9 @@ def ddpm_run(params):
     # train
     set_seed(seed)
     dataloader, dataset = _loader(name, args, params)
-    if params.get("eval_manifold") is not None and not _manifold_cfg(params)["n"] <= len(dataset):
-        raise ValueError(f"ddpm_run: eval_manifold n must be at most {len(dataset)} (the training set's size; got "
-                         f"{_manifold_cfg(params)['n']})")
-    if params.get("eval_restoration") is not None and not _restoration_cfg(params)["n"] <= len(dataset):
-        raise ValueError(f"ddpm_run: eval_restoration n must lie in [1, {len(dataset)}] (the training set's size; got "
-                         f"{_restoration_cfg(params)['n']})")
+    for e, cfg in evals.items():                               # an n beyond the training set fails here, not after the training
+        if e.parse is not None:
+            _check_n(f"{e.key} n", cfg["n"], e.n_min(cfg), dataset)
     model = UNet(c_in=args.image_channels, c_out=model_out_channels(args), image_size=args.image_size, f_settings=f_settings,
                  device=args.device, variant=v).to(args.device)
     diffusion = Diffusion(noise_steps=args.noise_steps, img_size=args.image_size, device=args.device, **diffusion_kwargs(args))
@@ -185,11 +175,7 @@ def ddpm_run(params):
     distill = None
     if params.get("distill") is not None:
         distill, gen_model, gen_kw = _distill(params, args, diffusion, gen_model, modelpath, name, seed, dataloader)
-    nearest_n = _nearest_cfg(params)["n"] if params.get("eval_nearest") is not None else 0
-    spectrum_n = _spectrum_cfg(params)["n"] if params.get("eval_spectrum") is not None else 0
-    fidelity_n = _fidelity_cfg(params)["n"] if params.get("eval_fidelity") is not None else 0
-    manifold_n = _manifold_cfg(params)["n"] if params.get("eval_manifold") is not None else 0
-    keep_n = max(nearest_n, spectrum_n, fidelity_n, manifold_n)
+    keep_n = max([cfg["n"] for e, cfg in evals.items() if e.samples], default=0)
     generated = []                                             # the first images of the set that an evaluation asks for, uint8 as sampled
     for start in np.arange(0, params["gen_total"], params["gen_per_batch"]):
         fileno = np.arange(start, start + params["gen_per_batch"], 1)
@@ -205,41 +191,10 @@ def ddpm_run(params):
         out["ema_modelpath"] = ema_path(modelpath)
     if distill is not None:
         out["distill"] = distill
-    # optional likelihood: params["eval_bpd"] = N scores the first N training images, in dataset order, on the model the
-    # FID/KID image set came from (Diffusion.calc_bpd; "eval_bpd_t_samples": K timesteps per image, "eval_bpd_sigma": "beta", "posterior" or,
-    # with "variance": "learned", "learned")
     dev_set = dataset if isinstance(dataset, DeviceDataset) else None      # (the host path loads its data set again, as before)
-    if params.get("eval_bpd"):
-        out["bpd"] = _eval_bpd(params, args, diffusion, gen_model, run_dir, name, v, seed, dev_set)
-    # optional equivariance scores: params["eval_equivariance"] = the keyword arguments of Diffusion.equivariance (t, transforms,
-    # margin, peak, batch, ...) plus "N" (default 16), the number of training images scored, in dataset order, on the same model
-    if params.get("eval_equivariance"):
-        out["equivariance"] = _eval_equivariance(params, args, diffusion, gen_model, run_dir, name, v, seed, dev_set)
-    # optional nearest training images: params["eval_nearest"] = {"n": ..., "k": ...} (k defaults to 5) searches the training set
-    # for the k nearest neighbours of the first n generated images, and of the first n training images (leave-one-out) as the
-    # baseline the distances are read against (DeviceDataset.nearest)
-    if params.get("eval_nearest") is not None:
-        out["nearest"] = _eval_nearest(params, args, torch.cat(generated), run_dir, name, v, dev_set)
-    # optional power spectra: params["eval_spectrum"] = {"n": ..., "window": "hann" | None} sets the mean power spectrum of the first
-    # n generated images against that of the first n training images (spectrum.power_spectrum / compare_spectra)
-    if params.get("eval_spectrum") is not None:
-        out["spectrum"] = _eval_spectrum(params, args, torch.cat(generated), run_dir, name, v, dev_set)
-    # optional FID / KID / Inception Score: params["eval_fidelity"] = {"n": ..., "extractor": a callable, the path of a TorchScript
-    # file or "pixels", "kid_subsets": ..., "kid_subset_size": ...} scores the first n generated images against the first n training
-    # images through the extractor (fidelity.fidelity)
-    if params.get("eval_fidelity") is not None:
-        out["fidelity"] = _eval_fidelity(params, args, torch.cat(generated), run_dir, name, v, dev_set)
-    # optional precision / recall / density / coverage: params["eval_manifold"] = {"n": ..., "extractor": as for eval_fidelity,
-    # "k": ...} (k defaults to 3) scores the first n generated images against the first n training images through the extractor
-    # (manifold.manifold)
-    if params.get("eval_manifold") is not None:
-        out["manifold"] = _eval_manifold(params, args, torch.cat(generated), run_dir, name, v, dev_set)
-    # optional restoration scores: params["eval_restoration"] = {"n": ..., "mask": "center" | "half" | an (S, S) array of 0 / 1,
-    # "factor": ..., "tasks": ("inpaint", "superres"), "steps": ..., "eta": ..., "window": ..., "sigma": ...} inpaints and
-    # super-resolves the first n training images on the same model and scores the results against them in PSNR and SSIM
-    # (quality.image_quality)
-    if params.get("eval_restoration") is not None:
-        out["restoration"] = _eval_restoration(params, args, diffusion, gen_model, run_dir, name, v, seed, dev_set)
+    ctx = EvalContext(params, args, diffusion, gen_model, run_dir, name, v, seed, dev_set, torch.cat(generated) if generated else None)
+    for e, cfg in evals.items():
+        out[e.out] = e.run(ctx, cfg)
     return out
 
 
@@ -269,6 +224,35 @@ def _distill(params, args, diffusion, model, modelpath, name, seed, device_loade
     return {"rounds": rounds, "modelpath": path}, student, {"steps": rounds[-1]["chain"], "eta": 0.0}
 
 
+def _int_in(val, lo, hi, message):
+    """val as a plain int if it is an int (numpy's count, a bool does not) with lo <= val <= hi (hi None: no upper end); else
+    ValueError(message)."""
+    if isinstance(val, bool) or not isinstance(val, (int, np.integer)) or val < lo or (hi is not None and val > hi):
+        raise ValueError(message)
+    return int(val)
+
+
+def _extractor_cfg(what, extractor):
+    if not callable(extractor) and not isinstance(extractor, str):
+        raise ValueError(f"ddpm_run: {what} extractor must be a callable, the path of a TorchScript file or 'pixels' (got "
+                         f"{type(extractor).__name__})")
+    if isinstance(extractor, str) and extractor != "pixels" and not os.path.isfile(extractor):
+        raise ValueError(f"ddpm_run: {what} extractor {extractor!r} is neither 'pixels' nor an existing TorchScript file")
+
+
+def _check_n(what, n, lo, dataset):
+    """An evaluation's number of training images against the training set's size."""
+    if not lo <= n <= len(dataset):
+        raise ValueError(f"ddpm_run: {what} must lie in [{lo}, {len(dataset)}] (the training set's size; got {n})")
+
+
+def _write_json(ctx, stem, table, line):
+    """An evaluation's json beside the run's other files, and its one printed line."""
+    with open(os.path.join(ctx.run_dir, f"{stem}_{ctx.name}_{ctx.v}.json"), "w") as fh:
+        json.dump(table, fh, indent=1)
+    print(line)
+
+
 def _nearest_cfg(params):
     cfg = params["eval_nearest"]
     if not isinstance(cfg, dict) or set(cfg) - {"n", "k"} or "n" not in cfg:
@@ -276,10 +260,7 @@ def _nearest_cfg(params):
                          f"{sorted(cfg) if isinstance(cfg, dict) else type(cfg).__name__}")
     cfg = {"n": cfg["n"], "k": cfg.get("k", 5)}
     for key, hi, why in (("n", params["gen_total"], "gen_total, the size of the generated set"), ("k", 16, "16")):
-        val = cfg[key]
-        if isinstance(val, bool) or not isinstance(val, (int, np.integer)) or not 1 <= val <= hi:
-            raise ValueError(f"ddpm_run: eval_nearest {key} must be an int in [1, {why}] (got {val!r})")
-        cfg[key] = int(val)
+        cfg[key] = _int_in(cfg[key], 1, hi, f"ddpm_run: eval_nearest {key} must be an int in [1, {why}] (got {cfg[key]!r})")
     return cfg
 
 
@@ -292,13 +273,11 @@ def _training_store(name, args, dataset=None):
             DeviceDataset.from_folder(args.dataset_path, args.image_size, device=args.device))
 
 
-def _eval_nearest(params, args, generated, run_dir, name, v, dataset=None):
+def _eval_nearest(ctx, cfg):
     from .imageio_utils import save_images
-    cfg = _nearest_cfg(params)
-    n, k = cfg["n"], cfg["k"]
-    dataset = _training_store(name, args, dataset)
-    if not n <= len(dataset):
-        raise ValueError(f"ddpm_run: eval_nearest n must lie in [1, {len(dataset)}] (the training set's size; got {n})")
+    n, k, generated, run_dir, name, v = cfg["n"], cfg["k"], ctx.generated, ctx.run_dir, ctx.name, ctx.v
+    dataset = _training_store(name, ctx.args, ctx.dataset)
+    _check_n("eval_nearest n", n, 1, dataset)
     C = dataset.images.shape[1]
     queries = generated[:n].to(dataset.device)
     if dataset.images.dtype != torch.uint8:                    # a float store: the samples on its scale, as the loader maps pixels
@@ -328,14 +307,14 @@ def _spectrum_cfg(params):
     if not isinstance(cfg, dict) or set(cfg) - {"n", "window"} or "n" not in cfg:
         raise ValueError(f"ddpm_run: eval_spectrum needs n (and optionally window); got "
                          f"{sorted(cfg) if isinstance(cfg, dict) else type(cfg).__name__}")
-    n, window = cfg["n"], cfg.get("window", "hann")
-    if isinstance(n, bool) or not isinstance(n, (int, np.integer)) or not 1 <= n <= params["gen_total"]:
-        raise ValueError(f"ddpm_run: eval_spectrum n must be an int in [1, gen_total, the size of the generated set] (got {n!r})")
+    window = cfg.get("window", "hann")
+    n = _int_in(cfg["n"], 1, params["gen_total"],
+                f"ddpm_run: eval_spectrum n must be an int in [1, gen_total, the size of the generated set] (got {cfg['n']!r})")
     if window is not None and window != "hann":
         raise ValueError(f"ddpm_run: eval_spectrum window must be 'hann' or None (got {window!r})")
     if params.get("image_size") is not None and not 1 <= params["image_size"] <= 64:
         raise ValueError(f"ddpm_run: eval_spectrum takes images of at most 64 x 64 (image_size is {params['image_size']})")
-    return {"n": int(n), "window": window}
+    return {"n": n, "window": window}
 
 
 def _spectrum_pair(train, generated, window, remove_mean=True):
@@ -353,14 +332,12 @@ def _spectrum_pair(train, generated, window, remove_mean=True):
             "hf_ratio": np.float64(hf_ratio)}
 
 
-def _eval_spectrum(params, args, generated, run_dir, name, v, dataset=None):
-    cfg = _spectrum_cfg(params)
+def _eval_spectrum(ctx, cfg):
     n = cfg["n"]
-    dataset = _training_store(name, args, dataset)
-    if not n <= len(dataset):
-        raise ValueError(f"ddpm_run: eval_spectrum n must lie in [1, {len(dataset)}] (the training set's size; got {n})")
-    res = _spectrum_pair(dataset, generated[:n], cfg["window"])
-    np.savez(os.path.join(run_dir, f"spectrum_{name}_{v}.npz"), **res)
+    dataset = _training_store(ctx.name, ctx.args, ctx.dataset)
+    _check_n("eval_spectrum n", n, 1, dataset)
+    res = _spectrum_pair(dataset, ctx.generated[:n], cfg["window"])
+    np.savez(os.path.join(ctx.run_dir, f"spectrum_{ctx.name}_{ctx.v}.npz"), **res)
     print(f"spectrum: log-spectral distance {res['lsd']:.4f} dB, high-frequency energy ratio {res['hf_ratio']:.4f} "
           f"({n} samples against {n} training images)")
     return res
@@ -371,21 +348,13 @@ def _fidelity_cfg(params):
     if not isinstance(cfg, dict) or set(cfg) - {"n", "extractor", "kid_subsets", "kid_subset_size"} or not {"n", "extractor"} <= set(cfg):
         raise ValueError(f"ddpm_run: eval_fidelity needs n and extractor (and optionally kid_subsets, kid_subset_size); got "
                          f"{sorted(cfg) if isinstance(cfg, dict) else type(cfg).__name__}")
-    n, extractor = cfg["n"], cfg["extractor"]
-    if isinstance(n, bool) or not isinstance(n, (int, np.integer)) or not 2 <= n <= params["gen_total"]:
-        raise ValueError(f"ddpm_run: eval_fidelity n must be an int in [2, gen_total, the size of the generated set] (got {n!r})")
-    if not callable(extractor) and not isinstance(extractor, str):
-        raise ValueError(f"ddpm_run: eval_fidelity extractor must be a callable, the path of a TorchScript file or 'pixels' (got "
-                         f"{type(extractor).__name__})")
-    if isinstance(extractor, str) and extractor != "pixels" and not os.path.isfile(extractor):
-        raise ValueError(f"ddpm_run: eval_fidelity extractor {extractor!r} is neither 'pixels' nor an existing TorchScript file")
-    out = {"n": int(n), "extractor": extractor, "kid_subsets": cfg.get("kid_subsets", 100),
-           "kid_subset_size": cfg.get("kid_subset_size", min(1000, int(n)))}
-    for key, lo, hi in (("kid_subsets", 1, None), ("kid_subset_size", 2, int(n))):
-        val = out[key]
-        if isinstance(val, bool) or not isinstance(val, (int, np.integer)) or val < lo or (hi is not None and val > hi):
-            raise ValueError(f"ddpm_run: eval_fidelity {key} must be an int in [{lo}, {'...' if hi is None else 'n = ' + str(hi)}] (got {val!r})")
-        out[key] = int(val)
+    n = _int_in(cfg["n"], 2, params["gen_total"],
+                f"ddpm_run: eval_fidelity n must be an int in [2, gen_total, the size of the generated set] (got {cfg['n']!r})")
+    _extractor_cfg("eval_fidelity", cfg["extractor"])
+    out = {"n": n, "extractor": cfg["extractor"], "kid_subsets": cfg.get("kid_subsets", 100), "kid_subset_size": cfg.get("kid_subset_size", min(1000, n))}
+    for key, lo, hi in (("kid_subsets", 1, None), ("kid_subset_size", 2, n)):
+        out[key] = _int_in(out[key], lo, hi, f"ddpm_run: eval_fidelity {key} must be an int in [{lo}, {'...' if hi is None else 'n = ' + str(hi)}] "
+                                             f"(got {out[key]!r})")
     return out
 
 
@@ -397,17 +366,13 @@ def _fidelity_pair(train, generated, cfg):
                     kid_subset_size=cfg["kid_subset_size"])
 
 
-def _eval_fidelity(params, args, generated, run_dir, name, v, dataset=None):
-    import json
-    cfg = _fidelity_cfg(params)
+def _eval_fidelity(ctx, cfg):
     n = cfg["n"]
-    dataset = _training_store(name, args, dataset)
-    if not n <= len(dataset):
-        raise ValueError(f"ddpm_run: eval_fidelity n must lie in [2, {len(dataset)}] (the training set's size; got {n})")
-    res = _fidelity_pair(dataset, generated[:n], cfg)
-    with open(os.path.join(run_dir, f"fidelity_{name}_{v}.json"), "w") as fh:
-        json.dump(dict(res, n=n, kid_subsets=cfg["kid_subsets"], kid_subset_size=cfg["kid_subset_size"]), fh, indent=1)
-    print("fidelity: " + ", ".join(f"{k} {val:.6g}" for k, val in res.items()) + f" ({n} samples against {n} training images)")
+    dataset = _training_store(ctx.name, ctx.args, ctx.dataset)
+    _check_n("eval_fidelity n", n, 2, dataset)
+    res = _fidelity_pair(dataset, ctx.generated[:n], cfg)
+    _write_json(ctx, "fidelity", dict(res, n=n, kid_subsets=cfg["kid_subsets"], kid_subset_size=cfg["kid_subset_size"]),
+                "fidelity: " + ", ".join(f"{k} {val:.6g}" for k, val in res.items()) + f" ({n} samples against {n} training images)")
     return res
 
 
@@ -416,18 +381,11 @@ def _manifold_cfg(params):
     if not isinstance(cfg, dict) or set(cfg) - {"n", "extractor", "k"} or not {"n", "extractor"} <= set(cfg):
         raise ValueError(f"ddpm_run: eval_manifold needs n and extractor (and optionally k); got "
                          f"{sorted(cfg) if isinstance(cfg, dict) else type(cfg).__name__}")
-    n, extractor, k = cfg["n"], cfg["extractor"], cfg.get("k", 3)
-    if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 1 <= k <= 16:
-        raise ValueError(f"ddpm_run: eval_manifold k must be an int in [1, 16] (got {k!r})")
-    if isinstance(n, bool) or not isinstance(n, (int, np.integer)) or not k + 1 <= n <= params["gen_total"]:
-        raise ValueError(f"ddpm_run: eval_manifold n must be an int in [k + 1 = {k + 1}, gen_total, the size of the generated set] "
-                         f"(got {n!r})")
-    if not callable(extractor) and not isinstance(extractor, str):
-        raise ValueError(f"ddpm_run: eval_manifold extractor must be a callable, the path of a TorchScript file or 'pixels' (got "
-                         f"{type(extractor).__name__})")
-    if isinstance(extractor, str) and extractor != "pixels" and not os.path.isfile(extractor):
-        raise ValueError(f"ddpm_run: eval_manifold extractor {extractor!r} is neither 'pixels' nor an existing TorchScript file")
-    return {"n": int(n), "extractor": extractor, "k": int(k)}
+    k = _int_in(cfg.get("k", 3), 1, 16, f"ddpm_run: eval_manifold k must be an int in [1, 16] (got {cfg.get('k', 3)!r})")
+    n = _int_in(cfg["n"], k + 1, params["gen_total"], f"ddpm_run: eval_manifold n must be an int in [k + 1 = {k + 1}, gen_total, the size of the "
+                                                      f"generated set] (got {cfg['n']!r})")
+    _extractor_cfg("eval_manifold", cfg["extractor"])
+    return {"n": n, "extractor": cfg["extractor"], "k": k}
 
 
 def _manifold_pair(train, generated, cfg):
@@ -436,17 +394,13 @@ def _manifold_pair(train, generated, cfg):
     return manifold(generated.to(train.device), train.pixels(generated.shape[0]), cfg["extractor"], k=cfg["k"])
 
 
-def _eval_manifold(params, args, generated, run_dir, name, v, dataset=None):
-    import json
-    cfg = _manifold_cfg(params)
+def _eval_manifold(ctx, cfg):
     n = cfg["n"]
-    dataset = _training_store(name, args, dataset)
-    if not n <= len(dataset):
-        raise ValueError(f"ddpm_run: eval_manifold n must lie in [{cfg['k'] + 1}, {len(dataset)}] (the training set's size; got {n})")
-    res = _manifold_pair(dataset, generated[:n], cfg)
-    with open(os.path.join(run_dir, f"manifold_{name}_{v}.json"), "w") as fh:
-        json.dump(dict(res, n=n, k=cfg["k"]), fh, indent=1)
-    print("manifold: " + ", ".join(f"{key} {val:.6g}" for key, val in res.items()) + f" ({n} samples against {n} training images, k = {cfg['k']})")
+    dataset = _training_store(ctx.name, ctx.args, ctx.dataset)
+    _check_n("eval_manifold n", n, cfg["k"] + 1, dataset)
+    res = _manifold_pair(dataset, ctx.generated[:n], cfg)
+    _write_json(ctx, "manifold", dict(res, n=n, k=cfg["k"]), "manifold: " + ", ".join(f"{key} {val:.6g}" for key, val in res.items())
+                + f" ({n} samples against {n} training images, k = {cfg['k']})")
     return res
 
 
@@ -480,18 +434,16 @@ def _restoration_cfg(params):
                          f"{sorted(cfg) if isinstance(cfg, dict) else type(cfg).__name__}")
     out = {"n": cfg["n"], "mask": cfg.get("mask", "center"), "factor": cfg.get("factor", 4), "tasks": cfg.get("tasks", RESTORATION_TASKS),
            "steps": cfg.get("steps"), "eta": cfg.get("eta", 0.0), "window": cfg.get("window", 11), "sigma": cfg.get("sigma", 1.5)}
-    n, S = out["n"], params.get("image_size")
-    if isinstance(n, bool) or not isinstance(n, (int, np.integer)) or n < 1:
-        raise ValueError(f"ddpm_run: eval_restoration n must be an int >= 1 (got {n!r})")
-    out["n"] = int(n)
+    S = params.get("image_size")
+    out["n"] = _int_in(out["n"], 1, None, f"ddpm_run: eval_restoration n must be an int >= 1 (got {out['n']!r})")
     tasks = (out["tasks"],) if isinstance(out["tasks"], str) else tuple(out["tasks"])
     if not tasks or any(t not in RESTORATION_TASKS for t in tasks) or len(set(tasks)) != len(tasks):
         raise ValueError(f"ddpm_run: eval_restoration tasks must be some of {RESTORATION_TASKS} (got {out['tasks']!r})")
     out["tasks"] = tasks
-    factor = out["factor"]
-    if isinstance(factor, bool) or not isinstance(factor, (int, np.integer)) or factor < 2 or factor & (factor - 1):
-        raise ValueError(f"ddpm_run: eval_restoration factor must be a power of two >= 2 (got {factor!r})")
-    out["factor"] = int(factor)
+    factor, bad_factor = out["factor"], f"ddpm_run: eval_restoration factor must be a power of two >= 2 (got {out['factor']!r})"
+    out["factor"] = _int_in(factor, 2, None, bad_factor)
+    if factor & (factor - 1):
+        raise ValueError(bad_factor)
     try:
         gaussian_window(out["window"], out["sigma"])
     except ValueError as e:
@@ -551,31 +503,25 @@ def _restoration_scores(diffusion, model, originals, cfg, seed, kw):
     return res
 
 
-def _eval_restoration(params, args, diffusion, model, run_dir, name, v, seed, dataset=None):
-    import json
-    cfg = _restoration_cfg(params)
+def _eval_restoration(ctx, cfg):
     n = cfg["n"]
-    dataset = _training_store(name, args, dataset)
-    if not n <= len(dataset):
-        raise ValueError(f"ddpm_run: eval_restoration n must lie in [1, {len(dataset)}] (the training set's size; got {n})")
-    res = _restoration_scores(diffusion, model, dataset.pixels(n).to(args.device), cfg, seed, {})
-    with open(os.path.join(run_dir, f"restoration_{name}_{v}.json"), "w") as fh:
-        json.dump(res, fh, indent=1)
-    for task in cfg["tasks"]:
-        print(f"restoration {task}: " + ", ".join(f"{k} {val['mean']:.6g}" for k, val in res[task].items() if isinstance(val, dict))
-              + f" (means over {n} training images)")
+    dataset = _training_store(ctx.name, ctx.args, ctx.dataset)
+    _check_n("eval_restoration n", n, 1, dataset)
+    res = _restoration_scores(ctx.diffusion, ctx.gen_model, dataset.pixels(n).to(ctx.args.device), cfg, ctx.seed, {})
+    _write_json(ctx, "restoration", res, "\n".join(
+        f"restoration {task}: " + ", ".join(f"{k} {val['mean']:.6g}" for k, val in res[task].items() if isinstance(val, dict))
+        + f" (means over {n} training images)" for task in cfg["tasks"]))
     return res
 
 
-def _eval_bpd(params, args, diffusion, model, run_dir, name, v, seed, dataset=None):
+def _eval_bpd(ctx, cfg=None):
+    params, diffusion, run_dir, name, v = ctx.params, ctx.diffusion, ctx.run_dir, ctx.name, ctx.v
     N, K, sigma = int(params["eval_bpd"]), params.get("eval_bpd_t_samples"), params.get("eval_bpd_sigma", "beta")
-    if dataset is None:
-        dataset = _loader(name, args)[1]
-    if not 1 <= N <= len(dataset):
-        raise ValueError(f"ddpm_run: eval_bpd must lie in [1, {len(dataset)}] (the training set's size; got {N})")
+    dataset = ctx.dataset if ctx.dataset is not None else _loader(name, ctx.args)[1]
+    _check_n("eval_bpd", N, 1, dataset)
     images = _first_images(dataset, N)
-    set_seed(seed)
-    r = diffusion.calc_bpd(model, images, sigma=sigma, t_samples=K)
+    set_seed(ctx.seed)
+    r = diffusion.calc_bpd(ctx.gen_model, images, sigma=sigma, t_samples=K)
     bpd = r["bpd"].numpy()
     se = float(bpd.std(ddof=1) / np.sqrt(N)) if N > 1 else float("nan")
     lines = [f"bpd: {bpd.mean():.6f}", f"bpd_stderr: {se:.6f}"]
@@ -587,26 +533,66 @@ def _eval_bpd(params, args, diffusion, model, run_dir, name, v, seed, dataset=No
     return float(bpd.mean())
 
 
-def _eval_equivariance(params, args, diffusion, model, run_dir, name, v, seed, dataset=None):
-    import json
-    kw = dict(params["eval_equivariance"])
+def _eval_equivariance(ctx, cfg=None):
+    kw = dict(ctx.params["eval_equivariance"])
     N = int(kw.pop("N", 16))
-    if dataset is None:
-        dataset = _loader(name, args)[1]
-    if not 1 <= N <= len(dataset):
-        raise ValueError(f"ddpm_run: eval_equivariance N must lie in [1, {len(dataset)}] (the training set's size; got {N})")
+    dataset = ctx.dataset if ctx.dataset is not None else _loader(ctx.name, ctx.args)[1]
+    _check_n("eval_equivariance N", N, 1, dataset)
     images = _first_images(dataset, N).float()
-    set_seed(seed)
-    r = diffusion.equivariance(model, images, **kw)
+    set_seed(ctx.seed)
+    r = ctx.diffusion.equivariance(ctx.gen_model, images, **kw)
     t = kw["t"]
     table = {"t": [int(t)] if isinstance(t, (int, np.integer)) else [int(a) for a in t],
              "transforms": [list(sp) for sp in kw["transforms"]], "N": N, "margin": float(kw.get("margin", 4.0)),
              "peak": float(kw.get("peak", 2.0)), "count": r["count"].tolist(), "eq_db": r["eq_db"].tolist(),
              "snr_db": r["snr_db"].tolist()}
-    with open(os.path.join(run_dir, f"equivariance_{name}_{v}.json"), "w") as fh:
-        json.dump(table, fh, indent=1)
-    print(json.dumps(table))
+    _write_json(ctx, "equivariance", table, json.dumps(table))
     return table
+
+
+# What a runner gets: the run's params and args, the sampler and the model the image set came from, where and under which names
+# the run writes, the run's DeviceDataset (None on the host loaders: a runner loads the data set again, as before) and the first
+# generated images that the evaluations asked to keep, uint8 as sampled (None if none did).
+EvalContext = namedtuple("EvalContext", "params args diffusion gen_model run_dir name v seed dataset generated")
+
+# One optional evaluation of ddpm_run: params[key] asks for it, parse(params) -> its config (None: the key is no dict and counts
+# when it is truthy), samples: the first cfg["n"] generated images are kept for it, n_min(cfg): the smallest n it takes,
+# run(ctx, cfg) -> out[out].  All of them score the model the FID/KID image set came from.
+Eval = namedtuple("Eval", "key out parse samples n_min run")
+
+EVALS = (                                                      # in the order they run and appear in ddpm_run's result
+    # likelihood: params["eval_bpd"] = N scores the first N training images, in dataset order (Diffusion.calc_bpd;
+    # "eval_bpd_t_samples": K timesteps per image, "eval_bpd_sigma": "beta", "posterior" or, with "variance": "learned", "learned")
+    Eval("eval_bpd", "bpd", None, False, None, _eval_bpd),
+    # equivariance scores: params["eval_equivariance"] = the keyword arguments of Diffusion.equivariance (t, transforms, margin,
+    # peak, batch, ...) plus "N" (default 16), the number of training images scored, in dataset order
+    Eval("eval_equivariance", "equivariance", None, False, None, _eval_equivariance),
+    # nearest training images: params["eval_nearest"] = {"n": ..., "k": ...} (k defaults to 5) searches the training set for the
+    # k nearest neighbours of the first n generated images, and of the first n training images (leave-one-out) as the baseline
+    # the distances are read against (DeviceDataset.nearest)
+    Eval("eval_nearest", "nearest", _nearest_cfg, True, lambda cfg: 1, _eval_nearest),
+    # power spectra: params["eval_spectrum"] = {"n": ..., "window": "hann" | None} sets the mean power spectrum of the first n
+    # generated images against that of the first n training images (spectrum.power_spectrum / compare_spectra)
+    Eval("eval_spectrum", "spectrum", _spectrum_cfg, True, lambda cfg: 1, _eval_spectrum),
+    # FID / KID / Inception Score: params["eval_fidelity"] = {"n": ..., "extractor": a callable, the path of a TorchScript file or
+    # "pixels", "kid_subsets": ..., "kid_subset_size": ...} scores the first n generated images against the first n training
+    # images through the extractor (fidelity.fidelity)
+    Eval("eval_fidelity", "fidelity", _fidelity_cfg, True, lambda cfg: 2, _eval_fidelity),
+    # precision / recall / density / coverage: params["eval_manifold"] = {"n": ..., "extractor": as for eval_fidelity, "k": ...}
+    # (k defaults to 3) scores the first n generated images against the first n training images through the extractor
+    # (manifold.manifold)
+    Eval("eval_manifold", "manifold", _manifold_cfg, True, lambda cfg: cfg["k"] + 1, _eval_manifold),
+    # restoration scores: params["eval_restoration"] = {"n": ..., "mask": "center" | "half" | an (S, S) array of 0 / 1, "factor":
+    # ..., "tasks": ("inpaint", "superres"), "steps": ..., "eta": ..., "window": ..., "sigma": ...} inpaints and super-resolves the
+    # first n training images and scores the results against them in PSNR and SSIM (quality.image_quality)
+    Eval("eval_restoration", "restoration", _restoration_cfg, False, lambda cfg: 1, _eval_restoration),
+)
+
+
+def _eval_cfgs(params):
+    """{entry of EVALS: its parsed config} of the evaluations that params asks for, in table order."""
+    asked = [e for e in EVALS if (params.get(e.key) if e.parse is None else params.get(e.key) is not None)]
+    return {e: e.parse(params) if e.parse is not None else None for e in asked}
 
 
 def _load(model_data):
@@ -653,17 +639,24 @@ def bpd_results(model_data, images, **kw):
     return diffusion.calc_bpd(model, images, **kw)
 
 
+def _sample_against(who, model_data, images, n, lo, kw, parse=lambda n: None):
+    """What spectrum_results, fidelity_results and manifold_results share: check n, parse the caller's options (they fail before
+    the checkpoint is loaded), load, wrap the images, seed and draw n samples.  -> (the training store, the samples, parse(n))."""
+    n = _int_in(n, lo, len(images), f"{who}: n must be an int in [{lo}, {len(images)}] (the number of images; got {n!r})")
+    cfg = parse(n)
+    model, diffusion, args = _load(model_data)
+    train = images if isinstance(images, DeviceDataset) else DeviceDataset(images[:n], device=args.device)
+    set_seed(model_data["seed"])
+    x, _ = diffusion.sample(model, n=n, image_channels=args.image_channels, **kw)
+    return train, x, cfg
+
+
 def spectrum_results(model_data, images, n, window="hann", remove_mean=True, **kw):
     """Load the checkpoint as rotation_results does, seed, draw n samples (Diffusion.sample; **kw: steps, eta, sampler, ...) and set
     their mean power spectrum against that of the first n of `images`: a DeviceDataset, or (N, C, H, W) uint8 pixels or float32
     values on the loader's scale.  Returns the arrays ddpm_run writes for params["eval_spectrum"]: power_train, power_gen,
     radial_train, radial_gen, counts, db, lsd, hf_ratio."""
-    if isinstance(n, bool) or not isinstance(n, (int, np.integer)) or not 1 <= n <= len(images):
-        raise ValueError(f"spectrum_results: n must be an int in [1, {len(images)}] (the number of images; got {n!r})")
-    model, diffusion, args = _load(model_data)
-    train = images if isinstance(images, DeviceDataset) else DeviceDataset(images[:n], device=args.device)
-    set_seed(model_data["seed"])
-    x, _ = diffusion.sample(model, n=int(n), image_channels=args.image_channels, **kw)
+    train, x, _ = _sample_against("spectrum_results", model_data, images, n, 1, kw)
     return _spectrum_pair(train, x, window, remove_mean)
 
 
@@ -673,15 +666,9 @@ def fidelity_results(model_data, images, n, extractor, **kw):
     (N, C, H, W) uint8 pixels or float32 values on the loader's scale.  Returns fidelity.fidelity's dict, as ddpm_run does for
     params["eval_fidelity"]."""
     kw = dict(kw)
-    cfg = {"n": n, "extractor": extractor}
-    cfg.update({k: kw.pop(k) for k in ("kid_subsets", "kid_subset_size") if k in kw})
-    if isinstance(n, bool) or not isinstance(n, (int, np.integer)) or not 2 <= n <= len(images):
-        raise ValueError(f"fidelity_results: n must be an int in [2, {len(images)}] (the number of images; got {n!r})")
-    cfg = _fidelity_cfg({"eval_fidelity": cfg, "gen_total": int(n)})
-    model, diffusion, args = _load(model_data)
-    train = images if isinstance(images, DeviceDataset) else DeviceDataset(images[:n], device=args.device)
-    set_seed(model_data["seed"])
-    x, _ = diffusion.sample(model, n=int(n), image_channels=args.image_channels, **kw)
+    opt = {k: kw.pop(k) for k in ("kid_subsets", "kid_subset_size") if k in kw}
+    train, x, cfg = _sample_against("fidelity_results", model_data, images, n, 2, kw,
+                                    lambda n: _fidelity_cfg({"eval_fidelity": dict(opt, n=n, extractor=extractor), "gen_total": n}))
     return _fidelity_pair(train, x, cfg)
 
 
@@ -689,13 +676,8 @@ def manifold_results(model_data, images, n, extractor, k=3, **kw):
     """Load the checkpoint as rotation_results does, seed, draw n samples (Diffusion.sample; **kw: steps, eta, sampler, ...) and
     score them against the first n of `images`: a DeviceDataset, or (N, C, H, W) uint8 pixels or float32 values on the loader's
     scale.  Returns manifold.manifold_scores' dict, as ddpm_run does for params["eval_manifold"]."""
-    if isinstance(n, bool) or not isinstance(n, (int, np.integer)) or not 2 <= n <= len(images):
-        raise ValueError(f"manifold_results: n must be an int in [2, {len(images)}] (the number of images; got {n!r})")
-    cfg = _manifold_cfg({"eval_manifold": {"n": n, "extractor": extractor, "k": k}, "gen_total": int(n)})
-    model, diffusion, args = _load(model_data)
-    train = images if isinstance(images, DeviceDataset) else DeviceDataset(images[:n], device=args.device)
-    set_seed(model_data["seed"])
-    x, _ = diffusion.sample(model, n=int(n), image_channels=args.image_channels, **kw)
+    train, x, cfg = _sample_against("manifold_results", model_data, images, n, 2, kw,
+                                    lambda n: _manifold_cfg({"eval_manifold": {"n": n, "extractor": extractor, "k": k}, "gen_total": n}))
     return _manifold_pair(train, x, cfg)
 
 
@@ -712,18 +694,17 @@ def restoration_results(model_data, images, n, mask="center", factor=4, tasks=RE
     left the measurement.
     Returns what ddpm_run writes for params["eval_restoration"]: {"n", "window", "sigma", task: {score: {"mean", "std" (population),
     "values": one per image}, ...}}."""
-    if isinstance(n, bool) or not isinstance(n, (int, np.integer)) or not 1 <= n <= len(images):
-        raise ValueError(f"restoration_results: n must be an int in [1, {len(images)}] (the number of images; got {n!r})")
+    n = _int_in(n, 1, len(images), f"restoration_results: n must be an int in [1, {len(images)}] (the number of images; got {n!r})")
     kw = dict(kw)
     cfg = {"n": n, "mask": mask, "factor": factor, "tasks": tasks, "window": window, "sigma": sigma}
     cfg.update({k: kw.pop(k) for k in ("steps", "eta") if k in kw})
     if isinstance(images, DeviceDataset):
-        originals = images.pixels(int(n))
+        originals = images.pixels(n)
     else:
         originals = torch.from_numpy(images) if isinstance(images, np.ndarray) else images
         if not isinstance(originals, torch.Tensor) or originals.dtype != torch.uint8 or originals.dim() != 4:
             raise ValueError("restoration_results: images must be a DeviceDataset or (N, C, H, W) uint8 pixels")
-        originals = originals[:int(n)]
+        originals = originals[:n]
     cfg = _restoration_cfg({"eval_restoration": cfg, "image_size": int(originals.shape[-1])})
     model, diffusion, args = _load(model_data)
     return _restoration_scores(diffusion, model, originals.to(args.device).contiguous(), cfg, model_data["seed"], kw)
