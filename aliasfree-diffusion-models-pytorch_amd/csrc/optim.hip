@@ -14,26 +14,35 @@ static inline int gs_grid(long total, int block = 256) {
 }
 
 // ---- AdamW (torch.optim.AdamW semantics, decoupled weight decay) ---------------------------
-__global__ void adamw_tick_k(float* state, float b1, float b2) {
-  // state = {step, 1 - b1^step, 1 - b2^step, unused}; double keeps the powers exact enough for 1e6 steps
+// state = {step, 1 - b1^step, 1 - b2^step, unused}; double keeps the powers exact enough for 1e6 steps
+__device__ __forceinline__ void adam_advance(float* state, float b1, float b2) {
   const double step = (double)state[0] + 1.0;
   state[0] = (float)step;
   state[1] = (float)(1.0 - pow((double)b1, step));
   state[2] = (float)(1.0 - pow((double)b2, step));
 }
-__global__ void adamw_step_k(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
-                             long n, const float* __restrict__ state, float lr, float b1, float b2, float eps, float wd, float gscale) {
-  const float bc1 = state[1], bc2 = state[2];
-  const float step_size = lr / bc1, inv_sqrt_bc2 = 1.0f / sqrtf(bc2), decay = 1.0f - lr * wd;
-  AFD_GRID_STRIDE(i, n) {
-    const float gi = g[i] * gscale;
-    const float pi = p[i] * decay;
-    const float mi = m[i] + (gi - m[i]) * (1.0f - b1);            // lerp, as torch does
-    const float vi = v[i] * b2 + gi * gi * (1.0f - b2);
-    const float denom = sqrtf(vi) * inv_sqrt_bc2 + eps;
-    p[i] = pi - step_size * (mi / denom);
-    m[i] = mi; v[i] = vi;
-  }
+// the EMA's call counter: ema_state = {calls, copy}; copy = calls < start, then ++calls (the order of EMA.step_ema).
+// Device-resident so that a replayed step crosses `start` where the eager one would.
+__device__ __forceinline__ void ema_count(int* ema_state, int start) {
+  const int calls = ema_state[0];
+  ema_state[1] = calls < start ? 1 : 0;
+  ema_state[0] = calls + 1;
+}
+__global__ void adamw_tick_k(float* state, float b1, float b2, int* ema_state, int start) {
+  adam_advance(state, b1, b2);
+  if (ema_state) ema_count(ema_state, start);
+}
+// one AdamW element: one rounding per operation, in the order written (m is a lerp, as torch does); adamw_k below is its only
+// caller, and tests/test_gpu_optim.py restates it in numpy fp32 and compares the bits
+__device__ __forceinline__ void adamw_elem(float& p, float g, float& m, float& v, float gscale, float decay, float b1, float b2,
+                                           float step_size, float inv_sqrt_bc2, float eps) {
+  const float gi = g * gscale;
+  const float pi = p * decay;
+  const float mi = m + (gi - m) * (1.0f - b1);
+  const float vi = v * b2 + gi * gi * (1.0f - b2);
+  const float denom = sqrtf(vi) * inv_sqrt_bc2 + eps;
+  p = pi - step_size * (mi / denom);
+  m = mi; v = vi;
 }
 
 // ---- EMA of the weights (training.EMA, modules/ddpm_utils.py:26-51) -------------------------------------------------------
@@ -67,71 +76,6 @@ __device__ __forceinline__ void ema_range(float* __restrict__ ema, const float* 
 template <bool VEC>
 __global__ void ema_step_k(float* __restrict__ ema, const float* __restrict__ p, long n, int copy, float beta, float omb) {
   ema_range<VEC>(ema, p, 0, n, copy, beta, omb);
-}
-
-// adamw_tick_k's arithmetic, plus the EMA's call counter: ema_state = {calls, copy}; copy = calls < start, then ++calls
-// (the order of EMA.step_ema).  Device-resident so that a replayed step crosses `start` where the eager one would.
-__global__ void adamw_ema_tick_k(float* state, float b1, float b2, int* ema_state, int start) {
-  const double step = (double)state[0] + 1.0;
-  state[0] = (float)step;
-  state[1] = (float)(1.0 - pow((double)b1, step));
-  state[2] = (float)(1.0 - pow((double)b2, step));
-  const int calls = ema_state[0];
-  ema_state[1] = calls < start ? 1 : 0;
-  ema_state[0] = calls + 1;
-}
-
-// one AdamW element, the expressions and order of adamw_step_k
-__device__ __forceinline__ void adamw_elem(float& p, float g, float& m, float& v, float gscale, float decay, float b1, float b2,
-                                           float step_size, float inv_sqrt_bc2, float eps) {
-  const float gi = g * gscale;
-  const float pi = p * decay;
-  const float mi = m + (gi - m) * (1.0f - b1);
-  const float vi = v * b2 + gi * gi * (1.0f - b2);
-  const float denom = sqrtf(vi) * inv_sqrt_bc2 + eps;
-  p = pi - step_size * (mi / denom);
-  m = mi; v = vi;
-}
-
-// AdamW over [0, n_active) with the EMA rule applied to the NEW p, then the EMA rule alone over [n_active, n_ema) (FlatParams'
-// tail: parameters the optimiser never touches, which the reference's EMA still walks).  One pass: p, g, m, v, ema streamed once.
-template <bool VEC>
-__global__ void adamw_ema_step_k(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
-                                 long n_active, const float* __restrict__ state, float lr, float b1, float b2, float eps, float wd,
-                                 float gscale, float* __restrict__ ema, long n_ema, const int* __restrict__ ema_state, float beta,
-                                 float omb) {
-  const float bc1 = state[1], bc2 = state[2];
-  const float step_size = lr / bc1, inv_sqrt_bc2 = 1.0f / sqrtf(bc2), decay = 1.0f - lr * wd;
-  const int copy = ema_state[1];
-  const long tid = blockIdx.x * (long)blockDim.x + threadIdx.x, stride = (long)gridDim.x * blockDim.x;
-  long s = 0;
-  if (VEC) {
-    const long n4 = n_active >> 2;
-    for (long k = tid; k < n4; k += stride) {
-      float4 pv = reinterpret_cast<const float4*>(p)[k];
-      const float4 gv = reinterpret_cast<const float4*>(g)[k];
-      float4 mv = reinterpret_cast<const float4*>(m)[k], vv = reinterpret_cast<const float4*>(v)[k];
-      float4 ev = reinterpret_cast<const float4*>(ema)[k];
-      adamw_elem(pv.x, gv.x, mv.x, vv.x, gscale, decay, b1, b2, step_size, inv_sqrt_bc2, eps);
-      adamw_elem(pv.y, gv.y, mv.y, vv.y, gscale, decay, b1, b2, step_size, inv_sqrt_bc2, eps);
-      adamw_elem(pv.z, gv.z, mv.z, vv.z, gscale, decay, b1, b2, step_size, inv_sqrt_bc2, eps);
-      adamw_elem(pv.w, gv.w, mv.w, vv.w, gscale, decay, b1, b2, step_size, inv_sqrt_bc2, eps);
-      ev.x = ema_rule(ev.x, pv.x, copy, beta, omb); ev.y = ema_rule(ev.y, pv.y, copy, beta, omb);
-      ev.z = ema_rule(ev.z, pv.z, copy, beta, omb); ev.w = ema_rule(ev.w, pv.w, copy, beta, omb);
-      reinterpret_cast<float4*>(p)[k] = pv;
-      reinterpret_cast<float4*>(m)[k] = mv;
-      reinterpret_cast<float4*>(v)[k] = vv;
-      reinterpret_cast<float4*>(ema)[k] = ev;
-    }
-    s = 4 * n4;
-  }
-  for (long i = s + tid; i < n_active; i += stride) {
-    float pi = p[i], mi = m[i], vi = v[i];
-    adamw_elem(pi, g[i], mi, vi, gscale, decay, b1, b2, step_size, inv_sqrt_bc2, eps);
-    p[i] = pi; m[i] = mi; v[i] = vi;
-    ema[i] = ema_rule(ema[i], pi, copy, beta, omb);
-  }
-  ema_range<VEC>(ema, p, n_active, n_ema, copy, beta, omb);
 }
 
 // ---- gradient-norm clipping and the learning-rate schedule, on the device (training.FusedAdamW(max_grad_norm=, lr_schedule=)) ----
@@ -188,9 +132,9 @@ __device__ __forceinline__ double lr_factor(const afd_opt_ctl& c, double k) {
   return c.min_ratio + (1.0 - c.min_ratio) * base;
 }
 
-// One workgroup: the partials in index order -> norm -> clip coefficient; unless the step is skipped, adamw_tick_k (or
-// adamw_ema_tick_k) and the learning rate of this update.  The partials go through LDS so that thread 0's chain of fp64 adds
-// does not wait on one global load each.
+// One workgroup: the partials in index order -> norm -> clip coefficient; unless the step is skipped, adamw_tick_k's two
+// advances and the learning rate of this update.  The partials go through LDS so that thread 0's chain of fp64 adds does not
+// wait on one global load each.
 __global__ void adamw_ctl_tick_k(float* state, float b1, float b2, int* ema_state, int start, const double* __restrict__ partials,
                                  int n_partials, afd_opt_ctl cfg, double* ctl) {
   __shared__ double sp[kCtlMaxPartials];
@@ -213,15 +157,8 @@ __global__ void adamw_ctl_tick_k(float* state, float b1, float b2, int* ema_stat
     ctl[kCtlNSkipped] += 1.0;
     return;
   }
-  const double step = (double)state[0] + 1.0;   // adamw_tick_k
-  state[0] = (float)step;
-  state[1] = (float)(1.0 - pow((double)b1, step));
-  state[2] = (float)(1.0 - pow((double)b2, step));
-  if (ema_state) {                              // adamw_ema_tick_k
-    const int calls = ema_state[0];
-    ema_state[1] = calls < start ? 1 : 0;
-    ema_state[0] = calls + 1;
-  }
+  adam_advance(state, b1, b2);
+  if (ema_state) ema_count(ema_state, start);
   const double k = (double)state[0] - 1.0, factor = lr_factor(cfg, k);
   ctl[kCtlLr] = (double)(float)(cfg.base_lr * factor);
   ctl[kCtlCoef] = coef;
@@ -230,15 +167,21 @@ __global__ void adamw_ctl_tick_k(float* state, float b1, float b2, int* ema_stat
   ctl[kCtlFactor] = factor;
 }
 
-// adamw_step_k (EMA = false) / adamw_ema_step_k (EMA = true) with lr and the clip coefficient read from ctl; every thread
-// returns before its first access when ctl says skip.
-template <bool VEC, bool EMA>
-__global__ void adamw_ctl_step_k(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
-                                 long n_active, const float* __restrict__ state, const double* __restrict__ ctl, float b1, float b2,
-                                 float eps, float wd, float grad_scale, float* __restrict__ ema, long n_ema,
-                                 const int* __restrict__ ema_state, float beta, float omb) {
-  if (ctl[kCtlSkip] != 0.0) return;
-  const float lr = (float)ctl[kCtlLr], gscale = grad_scale * (float)ctl[kCtlCoef];
+// ---- the AdamW step, every form of it ---------------------------------------------------------------------------------------
+// AdamW over [0, n_active).  CTL: lr and the clip coefficient come from ctl, and every thread returns before its first access
+// when ctl says skip; otherwise lr and gscale are the arguments.  EMA: the EMA rule on the NEW p in the same pass, then the rule
+// alone over [n_active, n_ema) (FlatParams' tail: parameters the optimiser never touches, which the reference's EMA still
+// walks).  VEC: every pointer 16-byte aligned -> float4 accesses.  p, g, m, v (and ema) are streamed once.
+template <bool VEC, bool EMA, bool CTL>
+__global__ void adamw_k(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
+                        long n_active, const float* __restrict__ state, float lr, const double* __restrict__ ctl, float b1, float b2,
+                        float eps, float wd, float gscale, float* __restrict__ ema, long n_ema, const int* __restrict__ ema_state,
+                        float beta, float omb) {
+  if (CTL) {
+    if (ctl[kCtlSkip] != 0.0) return;
+    lr = (float)ctl[kCtlLr];
+    gscale = gscale * (float)ctl[kCtlCoef];
+  }
   const float bc1 = state[1], bc2 = state[2];
   const float step_size = lr / bc1, inv_sqrt_bc2 = 1.0f / sqrtf(bc2), decay = 1.0f - lr * wd;
   const int copy = EMA ? ema_state[1] : 0;
@@ -278,21 +221,42 @@ __global__ void adamw_ctl_step_k(float* __restrict__ p, const float* __restrict_
 }  // namespace afd
 using namespace afd;
 
+static inline bool beta_ok(float beta, float omb) { return beta >= 0.0f && beta <= 1.0f && omb >= 0.0f && omb <= 1.0f; }
+
+// The one launcher of adamw_k.  `who` is the entry point, for the messages; ctl and ema select the form (NULL: lr by value, no
+// EMA), and the float4 instance runs when every pointer the kernel walks is 16-byte aligned.
+static int launch_adamw(const char* who, float* p, const float* g, float* m, float* v, long n_active, const float* state, float lr,
+                        const double* ctl, float b1, float b2, float eps, float wd, float gscale, float* ema, long n_ema,
+                        const int* ema_state, float beta, float omb, afd_stream_t st) {
+  AFD_REQUIRE(p && g && m && v && state, "%s: a pointer is NULL", who);
+  AFD_REQUIRE(!ema || ema_state, "%s: ema is given but ema_state is NULL", who);
+  AFD_REQUIRE(!ema || (n_active > 0 && n_ema > 0), "%s: n_active and n_ema must be positive (got %ld, %ld)", who, n_active, n_ema);
+  AFD_REQUIRE(n_active > 0, "%s: n_active must be positive (got %ld)", who, n_active);
+  AFD_REQUIRE(!ema || n_active <= n_ema, "%s: n_active > n_ema (%ld > %ld)", who, n_active, n_ema);
+  AFD_REQUIRE(!ema || beta_ok(beta, omb), "%s: beta and 1 - beta must lie in [0, 1] (got %g, %g)", who, (double)beta, (double)omb);
+  using kernel_t = decltype(&adamw_k<false, false, false>);
+  static const kernel_t kernels[2][2][2] = {      // [VEC][EMA][CTL]
+      {{adamw_k<false, false, false>, adamw_k<false, false, true>}, {adamw_k<false, true, false>, adamw_k<false, true, true>}},
+      {{adamw_k<true, false, false>, adamw_k<true, false, true>}, {adamw_k<true, true, false>, adamw_k<true, true, true>}}};
+  const bool vec = aligned16(p) && aligned16(g) && aligned16(m) && aligned16(v) && (!ema || aligned16(ema));
+  const long items = ema ? n_ema : n_active;
+  hipLaunchKernelGGL(kernels[vec][ema != nullptr][ctl != nullptr], dim3(gs_grid(vec ? (items + 3) / 4 : items)), dim3(256), 0,
+                     as_stream(st), p, g, m, v, n_active, state, lr, ctl, b1, b2, eps, wd, gscale, ema, n_ema, ema_state, beta, omb);
+  return check_launch(who);
+}
+
 extern "C" {
 
 int afd_adamw_tick(float* state, float b1, float b2, afd_stream_t st) {
   AFD_REQUIRE(state, "afd_adamw_tick: state is NULL");
-  hipLaunchKernelGGL(adamw_tick_k, dim3(1), dim3(1), 0, as_stream(st), state, b1, b2);
+  hipLaunchKernelGGL(adamw_tick_k, dim3(1), dim3(1), 0, as_stream(st), state, b1, b2, (int*)nullptr, 0);
   return check_launch("afd_adamw_tick");
 }
 int afd_adamw_step(float* p, const float* g, float* m, float* v, long n, const float* state,
                    float lr, float b1, float b2, float eps, float wd, float gscale, afd_stream_t st) {
-  AFD_REQUIRE(p && g && m && v && state && n > 0, "afd_adamw_step: bad argument");
-  hipLaunchKernelGGL(adamw_step_k, dim3(gs_grid(n)), dim3(256), 0, as_stream(st), p, g, m, v, n, state, lr, b1, b2, eps, wd, gscale);
-  return check_launch("afd_adamw_step");
+  return launch_adamw("afd_adamw_step", p, g, m, v, n, state, lr, nullptr, b1, b2, eps, wd, gscale, nullptr, 0, nullptr, 0.0f, 0.0f, st);
 }
 
-static inline bool beta_ok(float beta, float omb) { return beta >= 0.0f && beta <= 1.0f && omb >= 0.0f && omb <= 1.0f; }
 int afd_ema_step(float* ema, const float* p, long n, int copy, float beta, float one_minus_beta, afd_stream_t st) {
   AFD_REQUIRE(ema && p, "afd_ema_step: ema or p is NULL");
   AFD_REQUIRE(n > 0, "afd_ema_step: n must be positive (got %ld)", n);
@@ -308,24 +272,15 @@ int afd_ema_step(float* ema, const float* p, long n, int copy, float beta, float
 int afd_adamw_ema_tick(float* adam_state, float b1, float b2, int* ema_state, int start, afd_stream_t st) {
   AFD_REQUIRE(adam_state && ema_state, "afd_adamw_ema_tick: adam_state or ema_state is NULL");
   AFD_REQUIRE(start >= 0, "afd_adamw_ema_tick: start must be >= 0 (got %d)", start);
-  hipLaunchKernelGGL(adamw_ema_tick_k, dim3(1), dim3(1), 0, as_stream(st), adam_state, b1, b2, ema_state, start);
+  hipLaunchKernelGGL(adamw_tick_k, dim3(1), dim3(1), 0, as_stream(st), adam_state, b1, b2, ema_state, start);
   return check_launch("afd_adamw_ema_tick");
 }
 int afd_adamw_ema_step(float* p, const float* g, float* m, float* v, long n_active, const float* adam_state, float lr, float b1,
                        float b2, float eps, float wd, float gscale, float* ema, long n_ema, const int* ema_state, float beta,
                        float one_minus_beta, afd_stream_t st) {
-  AFD_REQUIRE(p && g && m && v && adam_state && ema && ema_state, "afd_adamw_ema_step: a pointer is NULL");
-  AFD_REQUIRE(n_active > 0 && n_ema > 0, "afd_adamw_ema_step: n_active and n_ema must be positive (got %ld, %ld)", n_active, n_ema);
-  AFD_REQUIRE(n_active <= n_ema, "afd_adamw_ema_step: n_active > n_ema (%ld > %ld)", n_active, n_ema);
-  AFD_REQUIRE(beta_ok(beta, one_minus_beta), "afd_adamw_ema_step: beta and 1 - beta must lie in [0, 1] (got %g, %g)",
-              (double)beta, (double)one_minus_beta);
-  if (aligned16(p) && aligned16(g) && aligned16(m) && aligned16(v) && aligned16(ema))
-    hipLaunchKernelGGL(adamw_ema_step_k<true>, dim3(gs_grid((n_ema + 3) / 4)), dim3(256), 0, as_stream(st), p, g, m, v, n_active,
-                       adam_state, lr, b1, b2, eps, wd, gscale, ema, n_ema, ema_state, beta, one_minus_beta);
-  else
-    hipLaunchKernelGGL(adamw_ema_step_k<false>, dim3(gs_grid(n_ema)), dim3(256), 0, as_stream(st), p, g, m, v, n_active,
-                       adam_state, lr, b1, b2, eps, wd, gscale, ema, n_ema, ema_state, beta, one_minus_beta);
-  return check_launch("afd_adamw_ema_step");
+  AFD_REQUIRE(ema && ema_state, "afd_adamw_ema_step: a pointer is NULL");
+  return launch_adamw("afd_adamw_ema_step", p, g, m, v, n_active, adam_state, lr, nullptr, b1, b2, eps, wd, gscale, ema, n_ema,
+                      ema_state, beta, one_minus_beta, st);
 }
 
 int afd_grad_sqnorm_n_partials(void) { return kGradNormPartials; }
@@ -364,28 +319,11 @@ int afd_adamw_ctl_tick(float* adam_state, float b1, float b2, int* ema_state, in
 int afd_adamw_ctl_step(float* p, const float* g, float* m, float* v, long n_active, const float* adam_state, const double* ctl,
                        float b1, float b2, float eps, float wd, float grad_scale, float* ema, long n_ema, const int* ema_state,
                        float beta, float one_minus_beta, afd_stream_t st) {
-  AFD_REQUIRE(p && g && m && v && adam_state && ctl, "afd_adamw_ctl_step: a pointer is NULL");
-  AFD_REQUIRE(n_active > 0, "afd_adamw_ctl_step: n_active must be positive (got %ld)", n_active);
-  if (!ema) {
-    if (aligned16(p) && aligned16(g) && aligned16(m) && aligned16(v))
-      hipLaunchKernelGGL((adamw_ctl_step_k<true, false>), dim3(gs_grid((n_active + 3) / 4)), dim3(256), 0, as_stream(st), p, g, m, v,
-                         n_active, adam_state, ctl, b1, b2, eps, wd, grad_scale, (float*)nullptr, 0L, (const int*)nullptr, 0.0f, 0.0f);
-    else
-      hipLaunchKernelGGL((adamw_ctl_step_k<false, false>), dim3(gs_grid(n_active)), dim3(256), 0, as_stream(st), p, g, m, v, n_active,
-                         adam_state, ctl, b1, b2, eps, wd, grad_scale, (float*)nullptr, 0L, (const int*)nullptr, 0.0f, 0.0f);
-    return check_launch("afd_adamw_ctl_step");
-  }
-  AFD_REQUIRE(ema_state, "afd_adamw_ctl_step: ema is given but ema_state is NULL");
-  AFD_REQUIRE(n_ema > 0 && n_active <= n_ema, "afd_adamw_ctl_step: 0 < n_active <= n_ema is required (got %ld, %ld)", n_active, n_ema);
-  AFD_REQUIRE(beta_ok(beta, one_minus_beta), "afd_adamw_ctl_step: beta and 1 - beta must lie in [0, 1] (got %g, %g)", (double)beta,
-              (double)one_minus_beta);
-  if (aligned16(p) && aligned16(g) && aligned16(m) && aligned16(v) && aligned16(ema))
-    hipLaunchKernelGGL((adamw_ctl_step_k<true, true>), dim3(gs_grid((n_ema + 3) / 4)), dim3(256), 0, as_stream(st), p, g, m, v, n_active,
-                       adam_state, ctl, b1, b2, eps, wd, grad_scale, ema, n_ema, ema_state, beta, one_minus_beta);
-  else
-    hipLaunchKernelGGL((adamw_ctl_step_k<false, true>), dim3(gs_grid(n_ema)), dim3(256), 0, as_stream(st), p, g, m, v, n_active,
-                       adam_state, ctl, b1, b2, eps, wd, grad_scale, ema, n_ema, ema_state, beta, one_minus_beta);
-  return check_launch("afd_adamw_ctl_step");
+  AFD_REQUIRE(ctl, "afd_adamw_ctl_step: a pointer is NULL");
+  AFD_REQUIRE(!ema || n_ema <= 0 || n_active <= n_ema, "afd_adamw_ctl_step: 0 < n_active <= n_ema is required (got %ld, %ld)", n_active,
+              n_ema);                              // (this entry point's wording of the launcher's range check)
+  return launch_adamw("afd_adamw_ctl_step", p, g, m, v, n_active, adam_state, 0.0f, ctl, b1, b2, eps, wd, grad_scale, ema, n_ema,
+                      ema_state, beta, one_minus_beta, st);
 }
 
 }  // extern "C"

@@ -289,36 +289,34 @@ class FusedAdamW:
 
     def step(self, grad_scale=1.0, ema=None):
         """ema: an _EMAHome (TrainStep(ema=...)): the same two launches, in their fused EMA form (afd.h)."""
-        L, s = lib(), ops._stream()
+        L, s, fp = lib(), ops._stream(), self.fp
+        state, (b1, b2) = self.state.data_ptr(), self.betas
+        bufs = (fp.flat.data_ptr(), fp.grad.data_ptr(), self.m.data_ptr(), self.v.data_ptr(), fp.n_active, state)
+        hyper = (b1, b2, self.eps, self.weight_decay, grad_scale)
+        if ema is not None:
+            es, start = ema.state.data_ptr(), ema.start
+            ema_args = (ema.flat.data_ptr(), ema.flat.numel(), es, ema.beta, ema.one_minus_beta)
+        else:
+            es, start, ema_args = None, 0, (None, 0, None, 0.0, 0.0)
         if self._ctl_on:
-            cfg, fp = self._cfg(), self.fp
             parts, n_parts = None, 0
             if self._need_norm:
                 parts, n_parts = self.partials.data_ptr(), self.partials.numel()
                 L.afd_grad_sqnorm_partials(fp.grad.data_ptr(), fp.n_active, grad_scale, parts, n_parts, s)
-            es = ema.state.data_ptr() if ema is not None else None
-            L.afd_adamw_ctl_tick(self.state.data_ptr(), self.betas[0], self.betas[1], es, ema.start if ema is not None else 0,
-                                 parts, n_parts, ctypes.byref(cfg), self.ctl.data_ptr(), s)
-            L.afd_adamw_ctl_step(fp.flat.data_ptr(), fp.grad.data_ptr(), self.m.data_ptr(), self.v.data_ptr(), fp.n_active,
-                                 self.state.data_ptr(), self.ctl.data_ptr(), self.betas[0], self.betas[1], self.eps,
-                                 self.weight_decay, grad_scale, ema.flat.data_ptr() if ema is not None else None,
-                                 ema.flat.numel() if ema is not None else 0, es, ema.beta if ema is not None else 0.0,
-                                 ema.one_minus_beta if ema is not None else 0.0, s)
-            ops.bump_param_epoch()
-            return
-        if ema is not None:
-            L.afd_adamw_ema_tick(self.state.data_ptr(), self.betas[0], self.betas[1], ema.state.data_ptr(), ema.start, s)
-            L.afd_adamw_ema_step(self.fp.flat.data_ptr(), self.fp.grad.data_ptr(), self.m.data_ptr(), self.v.data_ptr(),
-                                 self.fp.n_active, self.state.data_ptr(), self.lr, self.betas[0], self.betas[1], self.eps,
-                                 self.weight_decay, grad_scale, ema.flat.data_ptr(), ema.flat.numel(), ema.state.data_ptr(),
-                                 ema.beta, ema.one_minus_beta, s)
-            ops.bump_param_epoch()                      # (both the model's and the EMA model's parameters moved)
-            return
-        L.afd_adamw_tick(self.state.data_ptr(), self.betas[0], self.betas[1], s)
-        L.afd_adamw_step(self.fp.flat.data_ptr(), self.fp.grad.data_ptr(), self.m.data_ptr(), self.v.data_ptr(),
-                         self.fp.n_active, self.state.data_ptr(), self.lr, self.betas[0], self.betas[1], self.eps,
-                         self.weight_decay, grad_scale, s)
-        ops.bump_param_epoch()                          # the parameters moved under raw pointers: cached transforms are stale
+            ctl = self.ctl.data_ptr()
+            L.afd_adamw_ctl_tick(state, b1, b2, es, start, parts, n_parts, ctypes.byref(self._cfg()), ctl, s)
+            L.afd_adamw_ctl_step(*bufs, ctl, *hyper, *ema_args, s)
+        elif ema is not None:
+            L.afd_adamw_ema_tick(state, b1, b2, es, start, s)
+            L.afd_adamw_ema_step(*bufs, self.lr, *hyper, *ema_args, s)
+        else:
+            L.afd_adamw_tick(state, b1, b2, s)
+            L.afd_adamw_step(*bufs, self.lr, *hyper, s)
+        ops.bump_param_epoch()      # the parameters (and the EMA model's) moved under raw pointers: cached transforms are stale
+
+    def state_buffers(self):
+        """Every device buffer a step changes (what TrainStep's capture warm-up saves and puts back)."""
+        return (self.fp.flat, self.m, self.v, self.state) + ((self.ctl,) if self.ctl is not None else ())
 
 
 def _named_shapes(module):
@@ -355,6 +353,10 @@ class _EMAHome:
         self.state = torch.zeros(2, device=fp.flat.device, dtype=torch.int32)
         self.start, self.beta, self.one_minus_beta = 0, 0.0, 1.0       # set by TrainStep when it drives the EMA
 
+    def state_buffers(self):
+        """FusedAdamW.state_buffers' counterpart: the EMA buffer and its call counter."""
+        return self.flat, self.state
+
 
 class EMA:
     """Exponential moving average of a model's weights: modules/ddpm_utils.py:26-51, same interface and call counting --
@@ -373,20 +375,19 @@ class EMA:
     on reset and left alone on blend, as load_state_dict does."""
 
     def __init__(self, beta):
-        try:
-            ok = 0.0 <= float(beta) <= 1.0
-        except (TypeError, ValueError):
-            ok = False
-        if not ok:
-            raise ValueError(f"EMA: beta must lie in [0, 1] (got {beta!r})")
         self.beta = beta
+        self._betas()
         self.step = 0
         self._home = None
         self._driver = None          # the TrainStep whose AdamW launch advances this EMA
 
     def _betas(self):
-        b = float(self.beta)
-        if not 0.0 <= b <= 1.0:
+        try:
+            b = float(self.beta)
+            ok = 0.0 <= b <= 1.0
+        except (TypeError, ValueError):
+            ok = False
+        if not ok:
             raise ValueError(f"EMA: beta must lie in [0, 1] (got {self.beta!r})")
         return b, float(1.0 - b)     # 1 - beta in double, as Python evaluates `(1 - self.beta)`
 
@@ -992,9 +993,8 @@ class TrainStep:
             # the first batch, so everything they change is put back afterwards -- parameters, AdamW moments and step
             # counter, the clip / schedule control buffer, the EMA buffer and its counter, the device generator -- and under data parallel they stop before the
             # exchange: the first graph call is then exactly one step, like the eager one (and like the reference's).
-            fp, opt, h = self.opt.fp, self.opt, self._ema_home
-            bufs = (fp.flat, opt.m, opt.v, opt.state) + ((h.flat, h.state) if h is not None else ())
-            bufs += (opt.ctl,) if opt.ctl is not None else ()
+            bufs = self.opt.state_buffers()
+            bufs += self._ema_home.state_buffers() if self._ema_home is not None else ()
             bufs += self.t_sampler.buffers() if self.t_sampler is not None else ()
             keep = [b.clone() for b in bufs]
             rng = torch.cuda.get_rng_state(images.device)

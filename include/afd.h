@@ -532,7 +532,14 @@ int afd_eq_terms(const double* coef, long n_src, const int64_t* img, const doubl
  * mse: loss_out[0] = mean((pred-target)^2) (deterministic two-stage reduction; workspace >= 4096 floats);
  * mse_bwd: dpred = 2*(pred-target)/n * dloss[0].
  * adamw: torch.optim.AdamW(lr, betas, eps, weight_decay) over flat fp32 buffers; `state` is
- * device float[4] {step, bias_corr1, bias_corr2, _} advanced by afd_adamw_tick (graph-replay safe). */
+ * device float[4] {step, bias_corr1, bias_corr2, _} advanced by afd_adamw_tick (graph-replay safe).
+ * The AdamW element, per fp32 value, one rounding per operation in this order (no fused multiply-add), with
+ * decay = 1 - lr * weight_decay, step_size = lr / bias_corr1, inv_sqrt_bc2 = 1 / sqrt(bias_corr2) formed once in fp32:
+ *     gi = g * grad_scale;  pi = p * decay;  m = m + (gi - m) * (1 - beta1);  v = v * beta2 + gi * gi * (1 - beta2);
+ *     p = pi - step_size * (m / (sqrt(v) * inv_sqrt_bc2 + eps))
+ * ONE kernel applies it, in every form below: afd_adamw_step (lr by value), afd_adamw_ema_step (lr by value, the EMA rule on
+ * the new p in the same pass) and afd_adamw_ctl_step (lr and the clip coefficient read from `ctl` on the device, with or
+ * without the EMA).  The forms differ in nothing else: the same inputs give the same bits through each. */
 int afd_mse_fwd(const float* pred, const float* target, float* loss_out, float* workspace, long n, afd_stream_t stream);
 int afd_mse_bwd(const float* pred, const float* target, const float* dloss, float* dpred, long n, afd_stream_t stream);
 
@@ -689,7 +696,7 @@ int afd_adamw_step(float* p, const float* g, float* m, float* v, long n, const f
  * afd_ema_step: the rule alone over n elements (ema and p must not overlap).
  * afd_adamw_ema_tick: exactly afd_adamw_tick on adam_state, plus the EMA call counter ema_state = device int[2] {calls, copy}:
  *   copy = (calls < start), then ++calls -- EMA.step_ema's order, kept on the device so a replayed step crosses `start` correctly.
- * afd_adamw_ema_step: for i < n_active, p, m and v exactly as afd_adamw_step (same expressions, same order), then the rule on the
+ * afd_adamw_ema_step: afd_adamw_step's form with the EMA: for i < n_active the AdamW element (above), then the rule on the
  *   NEW p with copy = ema_state[1]; for n_active <= i < n_ema the rule alone on the unchanged p (parameters the optimiser never
  *   touches, which the reference's EMA still walks).  Requires 0 < n_active <= n_ema.
  * 16-byte accesses when every pointer is 16-byte aligned, element-wise otherwise; the results do not depend on which. */
@@ -727,9 +734,9 @@ int afd_adamw_ema_step(float* p, const float* g, float* m, float* v, long n_acti
  *   is device state).  Rejected before any device is touched: NULL adam_state / cfg / ctl, base_lr not finite or < 0, warmup < 0,
  *   unknown kind, total < warmup for a non-constant kind, min_ratio outside [0, 1], NaN max_norm, n_partials outside [1, 1024]
  *   when partials is given, ema_start < 0 when ema_state is given.
- * afd_adamw_ctl_step: afd_adamw_step (ema == NULL; n_ema, ema_state, beta, one_minus_beta ignored) or afd_adamw_ema_step with
- *   lr = (float)ctl.lr and grad_scale * (float)ctl.coef read from the device, the same expressions in the same order otherwise:
- *   with ctl.lr = lr, ctl.coef = 1, ctl.skip = 0 the results are bit-identical to those entry points.  With ctl.skip != 0 every
+ * afd_adamw_ctl_step: the form of afd_adamw_step (ema == NULL; n_ema, ema_state, beta, one_minus_beta ignored) or of
+ *   afd_adamw_ema_step that takes lr = (float)ctl.lr and grad_scale * (float)ctl.coef (an fp32 product) from the device: with
+ *   ctl.lr = lr, ctl.coef = 1, ctl.skip = 0 the results are bit-identical to those entry points.  With ctl.skip != 0 every
  *   thread returns at once: p, m, v and ema are not written. */
 #define AFD_LR_CONSTANT 0
 #define AFD_LR_LINEAR 1

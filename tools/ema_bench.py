@@ -8,8 +8,8 @@ TrainStep(ema=...), eager and "lanes".
 A worker measures ONE configuration in its own process and prints one JSON line: step_ms, the median over W windows of 10
 train steps (after 10 warm-up steps; timesteps from the CPU generator, noise from the device), and the parameter counts.
 The driver runs every worker under `timeout -k 10`, stops at the first failure, then runs --profile-run once under
-`rocprofv3 --kernel-trace --stats` (a process of its own): eager steps without and with the EMA, so that adamw_step_k and
-adamw_ema_step_k are timed in the same process.  Bytes moved per parameter: 28 for AdamW (p, m, v read and written, g read),
+`rocprofv3 --kernel-trace --stats` (a process of its own): eager steps without and with the EMA, so that both instances of
+adamw_k<VEC, EMA, CTL> are timed in the same process.  Bytes moved per parameter: 28 for AdamW (p, m, v read and written, g read),
 36 for the fused form (and the EMA read and written)."""
 import copy
 import csv
@@ -17,6 +17,7 @@ import glob
 import json
 import math
 import os
+import re
 import subprocess
 import sys
 import tempfile
@@ -128,12 +129,10 @@ def driver():
     print("|---|---|---|---|---|")
     for s in _kernel_stats(pdir):
         name = s.get("Name", s.get("KernelName", ""))
-        if "adamw_step_k" in name:
-            nbytes = 28 * n_act
-        elif "adamw_ema_step_k" in name:
-            nbytes = 28 * n_act + 8 * n_all
-        else:
+        m = re.search(r"adamw_k<[^,>]+,\s*([^,>]+),", name)         # adamw_k<VEC, EMA, CTL>
+        if m is None:
             continue
+        nbytes = 28 * n_act + (8 * n_all if m.group(1).strip() in ("true", "(bool)1", "1") else 0)
         mean_ns = float(s["AverageNs"])
         prof[name] = {"calls": int(s["Calls"]), "mean_us": mean_ns / 1e3, "GB_s": nbytes / mean_ns}
         print(f"| {name[:48]} | {s['Calls']} | {mean_ns / 1e3:.2f} | {nbytes / n_act:.1f} | {nbytes / mean_ns:.0f} |")
