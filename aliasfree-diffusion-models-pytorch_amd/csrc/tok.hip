@@ -19,50 +19,17 @@
 //
 // Weights sit in LDS for the life of the workgroup: [n][C + 4] per C x C matrix.  C = 128 (3 x 67.6 KB > 160 KB) runs the
 // three products of a chain as phases over TWO slots: the third matrix replaces the first behind a barrier.
-#include "common.h"
+//
+// This file holds the fp32 forms (v_mfma_f32_32x32x2_f32) and the four entry points.  At C = 64 and C = 128 the entry points
+// send the (site, kernel) pairs where it measured faster to the f16x2 forms of tok_h2.hip (use_h2 below).
+#include "tok_common.h"
+#include "tok_h2.h"
 #include <algorithm>
 #include <cstdint>
 #include <mutex>
 #include <set>
 
 namespace afd {
-
-using f32x16 = __attribute__((ext_vector_type(16))) float;
-
-template <int NB> struct TT { f32x16 b[NB]; };
-
-__device__ __forceinline__ constexpr int tch(int j, int r) { return 32 * j + (r & 3) + 8 * (r >> 2); }   // + 4 * half
-
-struct Pix { unsigned b, p, f; bool live; };
-__device__ __forceinline__ Pix pix_of(int tile, int l31, unsigned total, unsigned P) {
-  Pix q;
-  q.f = (unsigned)tile * 32u + (unsigned)l31;
-  q.live = q.f < total;
-  const unsigned fc = q.live ? q.f : 0u;
-  q.b = fc / P;
-  q.p = fc - q.b * P;
-  return q;
-}
-// element offset of (pixel, channel 4*half) in a tensor with Cx channels
-__device__ __forceinline__ unsigned tbase(const Pix& q, unsigned Cx, unsigned P, int half) {
-  return q.b * Cx * P + q.p + 4u * (unsigned)half * P;
-}
-
-template <int NB>
-__device__ __forceinline__ void t_load(TT<NB>& z, const float* __restrict__ src, unsigned base, unsigned P, bool live) {
-#pragma unroll
-  for (int j = 0; j < NB; ++j)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) z.b[j][r] = live ? src[base + (unsigned)tch(j, r) * P] : 0.f;
-}
-template <int NB>
-__device__ __forceinline__ void t_store(const TT<NB>& z, float* __restrict__ dst, unsigned base, unsigned P, bool live) {
-  if (!live) return;
-#pragma unroll
-  for (int j = 0; j < NB; ++j)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) dst[base + (unsigned)tch(j, r) * P] = z.b[j][r];
-}
 
 // one 32-channel output block: acc (+)= W[nb*32 .. +32][:] . z     (Ws: LDS [n][32 KB + 4])
 template <int KB>
@@ -80,12 +47,6 @@ __device__ __forceinline__ f32x16 t_block(const float* __restrict__ Ws, int nb, 
       acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.w, z.b[j][4 * q + 3], acc, 0, 0, 0);
     }
   return acc;
-}
-__device__ __forceinline__ f32x16 zero16() {
-  f32x16 a;
-#pragma unroll
-  for (int r = 0; r < 16; ++r) a[r] = 0.f;
-  return a;
 }
 
 // weights -> LDS.  forward: Ws[n][k] = w[(n0 + n) * ldw + k0 + k];  transposed (dgrad): Ws[n][k] = w[(k0 + k) * ldw + n0 + n]
@@ -106,61 +67,6 @@ __device__ __forceinline__ void stage_w(float* __restrict__ Ws, const float* __r
       Ws[n * WS + k] = w[(long)(k0 + k) * ldw + n0 + n];
     }
   }
-}
-
-// LayerNorm over the C channels of each pixel, T layout.  gs / bs: gamma / beta in LDS.
-template <int KB>
-__device__ __forceinline__ void t_ln_fwd(const TT<KB>& x, const float* __restrict__ gs, const float* __restrict__ bs, int half,
-                                         float eps, TT<KB>& y, float& mean, float& rstd) {
-  constexpr float invC = 1.0f / (32 * KB);
-  float s = 0.f;
-#pragma unroll
-  for (int j = 0; j < KB; ++j)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) s += x.b[j][r];
-  s += __shfl_xor(s, 32, 64);
-  mean = s * invC;
-  float q = 0.f;
-#pragma unroll
-  for (int j = 0; j < KB; ++j)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) { const float d = x.b[j][r] - mean; q = fmaf(d, d, q); }
-  q += __shfl_xor(q, 32, 64);
-  rstd = 1.0f / sqrtf(q * invC + eps);
-#pragma unroll
-  for (int j = 0; j < KB; ++j)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const int c = tch(j, r) + 4 * half;
-      y.b[j][r] = (x.b[j][r] - mean) * rstd * gs[c] + bs[c];
-    }
-}
-// dx = rstd * (g*dy - mean_c(g*dy) - xhat * mean_c(g*dy*xhat)) + add      (x: the LayerNorm input, in place in `dy`)
-template <int KB>
-__device__ __forceinline__ void t_ln_bwd(TT<KB>& dy, const TT<KB>& x, const float* __restrict__ gs, int half, float mean,
-                                         float rstd, const TT<KB>& add) {
-  constexpr float invC = 1.0f / (32 * KB);
-  float s1 = 0.f, s2 = 0.f;
-#pragma unroll
-  for (int j = 0; j < KB; ++j)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const float gv = gs[tch(j, r) + 4 * half] * dy.b[j][r];
-      const float xh = (x.b[j][r] - mean) * rstd;
-      dy.b[j][r] = gv;
-      s1 += gv;
-      s2 = fmaf(gv, xh, s2);
-    }
-  s1 += __shfl_xor(s1, 32, 64);
-  s2 += __shfl_xor(s2, 32, 64);
-  const float m1 = s1 * invC, m2 = s2 * invC;
-#pragma unroll
-  for (int j = 0; j < KB; ++j)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const float xh = (x.b[j][r] - mean) * rstd;
-      dy.b[j][r] = rstd * (dy.b[j][r] - m1 - xh * m2) + add.b[j][r];
-    }
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -819,7 +725,24 @@ static size_t chain_lds(int C, int nvec) {
 // kernels that need more than 64 KB of dynamic LDS opt in once per (device, kernel): common.h lds_opt_in
 template <class K> static int set_lds(K kern, size_t lds) { return lds_opt_in(kern, lds); }
 static int g_tok_max_wg = 0;       // test hook (afd_debug_tok_grid): cap on the workgroups of a launch, 0 = by the rule
-static int g_tok_path = 0;         // test hook (afd_debug_tok_path): 0 = by the rule, 1 = never the wide forms, 2 = wide wherever they exist
+static int g_tok_path = 0;         // test hook (afd_debug_tok_path): 0 = by the rule, 1 = never the wide forms, 2 = wide wherever they exist,
+                                   // 3 = the fp32 forms by their own rule (never f16x2), 4 = f16x2 wherever it exists,
+                                   // 5 / 6 = as 4 with 2 / 4 waves per workgroup at C = 64
+// f16x2 forms (tok_h2.hip) exist for C in {64, 128}; `kern`: 0 head fwd, 1 tail fwd, 2 tail bwd, 3 head bwd.  The rule is
+// what tools/tok_bench.py measured at B = 256 (us, fp32 form -> f16x2):
+//   C = 64, 16x16 (2048 tiles)  30.3 -> 18.4 | 36.6 -> 23.5 | 41.1 -> 23.4 | 41.5 -> 22.3     all four
+//   C = 64, 8x8 (512 tiles)     10.9 -> 11.6 | 12.1 -> 13.9 | 15.8 -> 11.7 | 11.0 -> 10.8     tail backward (head backward: a tie)
+//   C = 128, 8x8 (512 tiles)    30.5 -> 27.4 | 34.5 -> 34.4 | 53.4 -> 29.6 | 35.1 -> 28.0     all but the tail forward (a tie)
+//   C = 128, 4x4 (128 tiles)    14.0 -> 24.2 | 17.0 -> 31.0 | 20.1 -> 25.9 | 16.7 -> 22.1     none
+// One wave carries a whole tile there, so a layer with fewer tiles than SIMDs pays a tile's full vector work (splits, GELU,
+// LayerNorm) on one wave at one wave per SIMD; the wide fp32 forms spread it over C / 32 waves and keep the small maps.
+static bool use_h2(int C, long ntile, int kern) {
+  if (C != 64 && C != 128) return false;
+  if (g_tok_path >= 4) return true;
+  if (g_tok_path != 0) return false;
+  if (C == 64) return ntile >= 1024 || (kern == 2 && ntile >= 512);
+  return kern != 1 && ntile >= 512;
+}
 // wide forms: C = 128 always, C = 64 for layers of fewer than 1024 pixel tiles (they exist for C in {64, 128})
 static bool use_wide(int C, long ntile) {
   if (C != 64 && C != 128) return false;
@@ -841,7 +764,12 @@ extern "C" {
 
 int afd_tok_supported(int C) { return tok_ok(C) ? 1 : 0; }
 int afd_debug_tok_grid(int max_workgroups) { g_tok_max_wg = max_workgroups; return AFD_OK; }
-int afd_debug_tok_path(int mode) { g_tok_path = mode; return AFD_OK; }
+int afd_debug_tok_path(int mode) {
+  AFD_REQUIRE(mode >= 0 && mode <= 6, "afd_debug_tok_path: mode %d not in 0..6", mode);
+  g_tok_path = mode;
+  tok_h2_debug_tpw(mode == 5 ? 2 : (mode == 6 ? 4 : 0));
+  return AFD_OK;
+}
 
 int afd_tok_head_fwd(const float* x, const float* gamma, const float* beta, const float* w, const float* bias, float* h_out,
                      float* stats_out, float* qkv, int B, int C, int P, float eps, afd_stream_t st) {
@@ -850,6 +778,7 @@ int afd_tok_head_fwd(const float* x, const float* gamma, const float* beta, cons
   AFD_REQUIRE((long)B * P * 3 * C < (1L << 31), "afd_tok_head_fwd: tensor too large for 32-bit offsets");
   const int N = 3 * C;
   const long ntile = ((long)B * P + 31) / 32, wg_tiles = (ntile + 3) / 4;
+  if (use_h2(C, ntile, 0)) return tok_h2_head_fwd(x, gamma, beta, w, bias, h_out, stats_out, qkv, B, C, P, eps, g_tok_max_wg, as_stream(st));
   // wide head: one wave per (tile, 32-channel block), 3C/32 redundant LayerNorms per tile -- pays only while the layer has too
   // few tiles to fill the chip otherwise (measured at B = 256: 128 -> 384 @ 4x4 15.8 -> 13.8 us, @ 8x8 30.8 -> 39 us; three
   // blocks per wave: 44.6 us)
@@ -890,6 +819,8 @@ int afd_tok_tail_fwd(const float* att, const float* x, const float* wo, const fl
   AFD_REQUIRE(!train || (stats_out && f_out && u_out && g_out), "afd_tok_tail_fwd: a_out given but a saved-tensor pointer is NULL");
   const long ntile = ((long)B * P + 31) / 32;
   hipStream_t s = as_stream(st);
+  if (use_h2(C, ntile, 1))
+    return tok_h2_tail_fwd(att, x, wo, bo, gamma, beta, w1, b1, w2, b2, a_out, stats_out, f_out, u_out, g_out, out, B, C, P, eps, g_tok_max_wg, s);
   if (use_wide(C, ntile) && aligned16(wo) && aligned16(w1) && aligned16(w2)) {
     const dim3 wgrid((unsigned)((ntile + Wide<64>::TPW - 1) / Wide<64>::TPW)), wgrid128((unsigned)ntile);
 #define AFD_TAILW(C_, T_, G_) hipLaunchKernelGGL((tok_tail_fwd_wide<C_, T_>), G_, dim3(256), 0, s, att, x, wo, bo, gamma, beta, w1, b1, w2, b2, \
@@ -922,6 +853,7 @@ int afd_tok_tail_bwd(const float* d_out, const float* u, const float* a, const f
   AFD_REQUIRE((long)B * P * C < (1L << 31), "afd_tok_tail_bwd: tensor too large for 32-bit offsets");
   const long ntile = ((long)B * P + 31) / 32;
   hipStream_t s = as_stream(st);
+  if (use_h2(C, ntile, 2)) return tok_h2_tail_bwd(d_out, u, a, stats, gamma, w2, w1, wo, du_out, df_out, da_out, datt_out, B, C, P, g_tok_max_wg, s);
   if (use_wide(C, ntile)) {
     if (C == 64) hipLaunchKernelGGL(tok_tail_bwd_wide<64>, dim3((unsigned)((ntile + 1) / 2)), dim3(256), 0, s, d_out, u, a, stats, gamma, w2, w1, wo, du_out, df_out, da_out, datt_out, B, P);
     else         hipLaunchKernelGGL(tok_tail_bwd_wide<128>, dim3((unsigned)ntile), dim3(256), 0, s, d_out, u, a, stats, gamma, w2, w1, wo, du_out, df_out, da_out, datt_out, B, P);
@@ -943,6 +875,7 @@ int afd_tok_head_bwd(const float* dqkv, const float* x, const float* stats, cons
   AFD_REQUIRE((long)B * P * 3 * C < (1L << 31), "afd_tok_head_bwd: tensor too large for 32-bit offsets");
   const long ntile = ((long)B * P + 31) / 32;
   hipStream_t s = as_stream(st);
+  if (use_h2(C, ntile, 3)) return tok_h2_head_bwd(dqkv, x, stats, gamma, w_in, d_res, dh_out, dx_out, B, C, P, g_tok_max_wg, s);
   if (use_wide(C, ntile)) {
     if (C == 64) hipLaunchKernelGGL(tok_head_bwd_wide<64>, dim3((unsigned)((ntile + 1) / 2)), dim3(256), 0, s, dqkv, x, stats, gamma, w_in, d_res, dh_out, dx_out, B, P);
     else         hipLaunchKernelGGL(tok_head_bwd_wide<128>, dim3((unsigned)ntile), dim3(256), 0, s, dqkv, x, stats, gamma, w_in, d_res, dh_out, dx_out, B, P);

@@ -288,7 +288,11 @@ int afd_attn_bwd(const float* qkv, const float* o, const float* d_o, const float
 int afd_tok_supported(int C);
 /* test hook: cap the workgroups per launch of the four kernels below (forces several passes per workgroup); 0 = default */
 int afd_debug_tok_grid(int max_workgroups);
-/* test hook: 0 = kernel form by the rule, 1 = never the wide (one wave per 32-channel block) forms, 2 = wide wherever they exist */
+/* test hook: 0 = kernel form by the rule, 1 = never the wide (one wave per 32-channel block) forms, 2 = wide wherever they exist
+ * (1 and 2: fp32 forms only);
+ * 3 = the fp32 forms by their own rule, never the f16x2 forms (csrc/tok_h2.hip: C in {64, 128}, every product as two fp16
+ *     pieces on the fp16 matrix pipe);  4 = the f16x2 forms wherever they exist;
+ * 5 / 6 = as 4, with 2 / 4 waves (= pixel tiles) per workgroup at C = 64 (tuning) */
 int afd_debug_tok_path(int mode);
 int afd_tok_head_fwd(const float* x, const float* gamma, const float* beta, const float* w_in, const float* b_in,
                      float* h_out, float* stats_out, float* qkv, int B, int C, int P, float eps, afd_stream_t stream);
