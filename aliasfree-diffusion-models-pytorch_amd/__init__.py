@@ -22,8 +22,9 @@ from .training import (argument, set_seed, setup_logging, train, TrainStep, Fuse
                        GradAllReduce, EMA, LRSchedule, clip_coefficient, DistillStep, progressive_distill,
                        LossSecondMomentSampler)
 
-from .tasks import (bpd_results, ddpm_run, equivariance_results, fidelity_results, ilvr_results, inpaint_results,  # noqa: F401
-                    manifold_results, restoration_results, rotation_results, shift_results, spectrum_results)
+from .tasks import (bpd_results, ddpm_run, edit_results, equivariance_results, fidelity_results, ilvr_results,  # noqa: F401
+                    inpaint_results, manifold_results, reconstruct_results, restoration_results, rotation_results, shift_results,
+                    spectrum_results)
 from .data import (get_data, get_data_MNIST, save_gen_images, make_collage, DeviceDataset, DeviceLoader,  # noqa: F401
                    get_data_device, get_data_MNIST_device)
 

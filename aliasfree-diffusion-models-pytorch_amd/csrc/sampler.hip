@@ -1,5 +1,5 @@
-// sampler.hip -- the samplers: noising, the sampler steps (DDPM, DDIM, DPM-Solver++(2M); plain, guided and masked), renoise and
-// quantisation.  (Losses, learned variances and the likelihood bound are objective.hip, the optimizer is optim.hip.)
+// sampler.hip -- the samplers: noising, the sampler steps (DDPM, DDIM, DPM-Solver++(2M); plain, guided and masked), the ascending
+// DDIM step of the inversion, renoise and quantisation.  (Losses, learned variances and the likelihood bound are objective.hip, the optimizer is optim.hip.)
 //
 // noise_images / denoise_step / quantize restate the reference's fp32 expression ORDER with one
 // IEEE rounding per torch op (no FMA contraction, correctly rounded sqrt and divide), so given the
@@ -71,6 +71,38 @@ struct Ddim {
   }
   __device__ __forceinline__ int t_prev() const { return tp; }
   __device__ __forceinline__ bool gen_takes_noise() const { return eta != 0.0f && tp > 0; }
+};
+
+// The ascending DDIM step (inversion), one move s -> u of a chain walked upwards, 0 <= s < u.  a_s = alpha_hat[s],
+// a_u = alpha_hat[u]; fp32, one rounding per operation, in this order:
+//   x0  = (x - sqrt(1 - a_s) * e) / sqrt(a_s)
+//   out = (sqrt(a_u) * x0) + (sqrt(1 - a_u) * e)
+// the algebraic inverse of Ddim's eta = 0 step u -> s for the e that step used (there dir = sqrt(1 - a_s) and no noise term).
+// It takes no noise and has no masked form: t_prev() and gen_takes_noise() are here because step_k names them.
+struct DdimInvert {
+  struct Args {
+    const float* alpha_hat;
+    int s, u;
+    const int64_t *s_dev, *u_dev;
+  };
+  float sq1m_as, sq_as, sq_au, sq1m_au;
+  __device__ __forceinline__ static DdimInvert make(const Args& a) {
+    const int s = a.s_dev ? (int)a.s_dev[0] : a.s, u = a.u_dev ? (int)a.u_dev[0] : a.u;
+    const float a_s = a.alpha_hat[s], a_u = a.alpha_hat[u];
+    DdimInvert k;
+    k.sq1m_as = sqrtf(1.0f - a_s);
+    k.sq_as = sqrtf(a_s);
+    k.sq_au = sqrtf(a_u);
+    k.sq1m_au = sqrtf(1.0f - a_u);
+    return k;
+  }
+  __device__ __forceinline__ float update(float x, float e, float, bool) const {
+    const float pe = sq1m_as * e;
+    const float x0 = (x - pe) / sq_as;
+    return noised(sq_au, sq1m_au, x0, e);
+  }
+  __device__ __forceinline__ int t_prev() const { return 0; }
+  __device__ __forceinline__ bool gen_takes_noise() const { return false; }
 };
 
 // masked step (inpainting, RePaint): the rule's update for the generated region, x0 noised to t_prev for the known one:
@@ -399,6 +431,44 @@ int afd_ddim_step_masked_cfg_dev(const float* x, const float* eps2, const float*
                                  float* x_out, float* x_out2, long n, afd_stream_t st) {
   return ddim_step({"afd_ddim_step_masked_cfg_dev", true, true, true}, x, eps2, noise, x0, mask, alpha_hat, 0, 0, t_dev, t_prev_dev, eta,
                    cfg_scale, x_out, x_out2, n, st);
+}
+
+// The ascending DDIM step: 0 <= s < u where the host knows them.  x_out is normally apart from x (the refinement re-reads the
+// base state) and may be x itself; eps is read by other elements while x_out / x_out2 are written, so they share no memory.
+static int ddim_invert_step(const StepForm& f, const float* x, const float* eps, const float* alpha_hat, int s, int u,
+                            const int64_t* s_dev, const int64_t* u_dev, float scale, float* x_out, float* x_out2, long n,
+                            afd_stream_t st) {
+  if (int rc = check_step_buffers(f, alpha_hat && (!f.dev || (s_dev && u_dev)), f.dev ? "alpha_hat, s_dev, u_dev" : "alpha_hat", x, eps,
+                                  nullptr, nullptr, x_out, x_out2, n))
+    return rc;
+  AFD_REQUIRE(f.dev || (s >= 0 && s < u), "%s: need 0 <= s < u (got s = %d, u = %d)", f.name, s, u);
+  const long fb = n * (long)sizeof(float), eb = (f.cfg ? 2 : 1) * fb;
+  AFD_REQUIRE(!overlaps(eps, eb, x_out, fb) && !overlaps(eps, eb, x_out2, fb), "%s: x_out and x_out2 must not overlap %s", f.name,
+              f.cfg ? "eps2" : "eps");
+  AFD_REQUIRE((x_out == x || !overlaps(x, fb, x_out, fb)) && (x_out2 == x || !overlaps(x, fb, x_out2, fb)),
+              "%s: x_out and x_out2 must each be x itself or apart from it", f.name);
+  auto launch = f.cfg ? launch_step<DdimInvert, true, false> : launch_step<DdimInvert, false, false>;      // (no masked kernels)
+  launch(x, eps, nullptr, DdimInvert::Args{alpha_hat, s, u, s_dev, u_dev}, scale, nullptr, nullptr, x_out, x_out2, n, as_stream(st));
+  return check_launch(f.name);
+}
+int afd_ddim_invert_step(const float* x, const float* eps, const float* alpha_hat, int s, int u, float* x_out, long n, afd_stream_t st) {
+  return ddim_invert_step({"afd_ddim_invert_step", false, false, false}, x, eps, alpha_hat, s, u, nullptr, nullptr, 0.0f, x_out, nullptr, n,
+                          st);
+}
+int afd_ddim_invert_step_dev(const float* x, const float* eps, const float* alpha_hat, const int64_t* s_dev, const int64_t* u_dev,
+                             float* x_out, long n, afd_stream_t st) {
+  return ddim_invert_step({"afd_ddim_invert_step_dev", true, false, false}, x, eps, alpha_hat, 0, 0, s_dev, u_dev, 0.0f, x_out, nullptr, n,
+                          st);
+}
+int afd_ddim_invert_step_cfg(const float* x, const float* eps2, const float* alpha_hat, int s, int u, float cfg_scale, float* x_out,
+                             float* x_out2, long n, afd_stream_t st) {
+  return ddim_invert_step({"afd_ddim_invert_step_cfg", false, true, false}, x, eps2, alpha_hat, s, u, nullptr, nullptr, cfg_scale, x_out,
+                          x_out2, n, st);
+}
+int afd_ddim_invert_step_cfg_dev(const float* x, const float* eps2, const float* alpha_hat, const int64_t* s_dev, const int64_t* u_dev,
+                                 float cfg_scale, float* x_out, float* x_out2, long n, afd_stream_t st) {
+  return ddim_invert_step({"afd_ddim_invert_step_cfg_dev", true, true, false}, x, eps2, alpha_hat, 0, 0, s_dev, u_dev, cfg_scale, x_out,
+                          x_out2, n, st);
 }
 
 // ---- renoise (the inpainting sampler's up-move) -----------------------------------------------------------------------------------

@@ -57,8 +57,8 @@ class Diffusion:
         log sigma^2 = ((v + 1) / 2) log beta_t + (1 - (v + 1) / 2) log beta~_t per pixel (`lvar_coefficients`).  The DDPM chain
         (`sample`, `revert`, `sample_sharded`, `ilvr`, guided or not, eager or graph=True) then draws with that variance,
         `calc_bpd(sigma="learned")` scores it and `TrainStep` trains it with the hybrid loss.  Everything that goes through
-        `predict_eps` -- DDIM (also under `ilvr`), DPM-Solver++(2M), `inpaint`, `equivariance`, the sweeps, `sample_shift` and
-        `sample_concurrent` --
+        `predict_eps` -- DDIM (also under `ilvr`), DPM-Solver++(2M), `inpaint`, `invert`, `decode`, `sdedit`, `interpolate`,
+        `equivariance`, the sweeps, `sample_shift` and `sample_concurrent` --
         reads the prediction half alone and keeps its own variance."""
         if not isinstance(variance, str) or variance not in self.VARIANCES:
             raise ValueError(f"Diffusion: unknown variance {variance!r} ('fixed' or 'learned')")
@@ -414,13 +414,15 @@ class Diffusion:
         full chain (t_prev = t - 1) this is the DDPM sampler's i % 100 == 0."""
         return t_prev // 100 < t // 100
 
-    def _ddim_loop(self, model, n, image_channels, pairs, eta, noise_source="reference", graph=None, labels=None, cfg_scale=0.0):
+    def _ddim_loop(self, model, n, image_channels, pairs, eta, noise_source="reference", graph=None, labels=None, cfg_scale=0.0,
+                   start=None):
         """`_loop` over the DDIM steps `pairs` (see `sample`).  x_T is drawn as in `_loop`; with eta > 0 every step but the
         last draws the noise of n images (`_step_noise`), with eta == 0 none is drawn.  graph: capture one step (forward,
-        noise, the update with t and t_prev read on the device) and replay it for every step but the last, which runs eagerly."""
+        noise, the update with t and t_prev read on the device) and replay it for every step but the last, which runs eagerly.
+        start: the (n, C, S, S) state at level pairs[0][0] to start from instead of drawn noise (`decode`); it is not written."""
         snaps = []
         with self._model_scope(model):
-            x = self._initial_noise(n, image_channels, noise_source)
+            x = self._initial_noise(n, image_channels, noise_source) if start is None else start.to(self.device).contiguous().clone()
             y, s = self._guided(labels, cfg_scale)
             xs = torch.cat([x, x]) if s > 0 else x
             rows = xs.shape[0]
@@ -707,11 +709,7 @@ class Diffusion:
 
     def _inpaint_inputs(self, images, mask):
         """-> (images, mask) on the device: fp32 (n, C, img_size, img_size) and a contiguous uint8 mask of the same shape."""
-        if not isinstance(images, torch.Tensor) or images.dtype != torch.float32:
-            raise ValueError("Diffusion.inpaint: images must be an fp32 tensor")
-        if images.dim() != 4 or images.shape[0] < 1 or tuple(images.shape[2:]) != (self.img_size, self.img_size):
-            raise ValueError(f"Diffusion.inpaint: images must have shape (n, C, {self.img_size}, {self.img_size}) "
-                             f"(got {tuple(images.shape)})")
+        self._check_images("inpaint", images)
         m = torch.as_tensor(mask)
         if m.dtype.is_complex:
             raise ValueError("Diffusion.inpaint: mask must hold 0 or 1")
@@ -832,11 +830,7 @@ class Diffusion:
         return ops.Taps(k), int(factor).bit_length() - 1
 
     def _ilvr_reference(self, reference):
-        if not isinstance(reference, torch.Tensor) or reference.dtype != torch.float32:
-            raise ValueError("Diffusion.ilvr: reference must be an fp32 tensor")
-        if reference.dim() != 4 or reference.shape[0] < 1 or tuple(reference.shape[2:]) != (self.img_size, self.img_size):
-            raise ValueError(f"Diffusion.ilvr: reference must have shape (n, C, {self.img_size}, {self.img_size}) "
-                             f"(got {tuple(reference.shape)})")
+        self._check_images("ilvr", reference, "reference")
         return reference.to(self.device).contiguous()
 
     def reference_from_lowres(self, low, factor, taps=None):
@@ -945,6 +939,172 @@ class Diffusion:
             x = xs[:n].clone()
         snaps.append(x)
         return x, snaps
+
+    # Real images: DDIM inversion with fixed-point refinement, decoding, SDEdit, interpolation ----------------
+    def ddim_timesteps_from(self, t0, steps):
+        """The S = `steps` timesteps of a DDIM chain that starts at t0 instead of T - 1, strictly decreasing:
+        tau_k = 1 + (k (t0 - 1)) // (S - 1) for k = 0 .. S-1, in descending order (S = 1: [t0]); needs 1 <= S <= t0 <= T - 1.
+        ddim_timesteps_from(T - 1, S) == ddim_timesteps(S)."""
+        T = self.noise_steps
+        for name, v in (("t0", t0), ("steps", steps)):
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+                raise ValueError(f"Diffusion.ddim_timesteps_from: {name} must be an int (got {type(v).__name__})")
+        t0, S = int(t0), int(steps)
+        if not 1 <= S <= t0 <= T - 1:
+            raise ValueError(f"Diffusion.ddim_timesteps_from: needs 1 <= steps <= t0 <= {T - 1} (got steps = {S}, t0 = {t0})")
+        if S == 1:
+            return [t0]
+        return [1 + (k * (t0 - 1)) // (S - 1) for k in reversed(range(S))]
+
+    def _invert_moves(self, steps):
+        """The moves (s, u) of `invert` over `steps` (what `sample(steps=)` accepts): the sampler's pairs (t, t_prev) reversed and
+        swapped, so the chain climbs the levels [0] + reversed(taus) and ends at taus[0]."""
+        return [(tp, t) for t, tp in reversed(self._ddim_pairs(steps, 0.0))]
+
+    def _check_images(self, where, images, name="images"):
+        """ValueError unless `images` is an fp32 (n, C, img_size, img_size) tensor with n >= 1; nothing is moved."""
+        if not isinstance(images, torch.Tensor) or images.dtype != torch.float32:
+            raise ValueError(f"Diffusion.{where}: {name} must be an fp32 tensor")
+        if images.dim() != 4 or images.shape[0] < 1 or tuple(images.shape[2:]) != (self.img_size, self.img_size):
+            raise ValueError(f"Diffusion.{where}: {name} must have shape (n, C, {self.img_size}, {self.img_size}) "
+                             f"(got {tuple(images.shape)})")
+
+    def _check_guidance(self, where, model, n, labels, cfg_scale):
+        """-> the labels on the device (or None), as `sample` checks them; cfg_scale without labels is refused."""
+        if labels is not None:
+            return self._check_labels(model, n, None, labels, where)
+        if cfg_scale:
+            raise ValueError(f"Diffusion.{where}: cfg_scale needs class labels")
+        return None
+
+    def invert(self, model, images, steps, refine=0, labels=None, cfg_scale=0.0, graph=None):
+        """DDIM inversion: the latents at level taus[0] whose deterministic DDIM chain (`decode` with eta = 0 over the same
+        `steps`, labels and cfg_scale) regenerates `images`.  images: fp32 (n, C, img_size, img_size) in [-1, 1]; steps: what
+        `sample(steps=)` accepts, an int S (`ddim_timesteps`) or an explicit strictly decreasing sequence.  The chain is walked
+        upwards over the levels [0] + reversed(taus) (`_invert_moves`).  A move s -> u evaluates the model at timestep u (always
+        >= 1: `sample_timesteps` never draws 0, so the network is untrained there) and iterates
+            z_0 = x_s,   z_{k+1} = step(x_s, eps_theta(z_k, u), s, u)  for k = 0 .. refine,   x_u = z_{refine + 1}
+        with step = ops.ddim_invert_step: each iteration is one iteration of the fixed-point equation whose solution is the exact
+        inverse of the sampler's step u -> s.  refine = 0 is plain DDIM inversion, one forward per level; each further iteration
+        costs one more forward, (refine + 1) S in all.  With guidance the 2n rows [z ; z] go through one forward and the guided
+        step writes both halves.  Nothing is drawn: no generator's state changes.  graph=True captures one iteration (forward
+        and the step with s and u read on the device) and replays it.  Returns fp32 (n, C, img_size, img_size) on the device."""
+        logging.info(f"Inverting {images.shape[0] if isinstance(images, torch.Tensor) else '?'} images....")
+        self._check_images("invert", images)
+        moves = self._invert_moves(steps)
+        if isinstance(refine, bool) or not isinstance(refine, (int, np.integer)) or refine < 0:
+            raise ValueError(f"Diffusion.invert: refine must be an int >= 0 (got {refine!r})")
+        n = images.shape[0]
+        labels = self._check_guidance("invert", model, n, labels, cfg_scale)
+        self.check_model(model, images.shape[1], "Diffusion.invert")
+        return self._invert_loop(model, images, moves, int(refine), graph, labels, float(cfg_scale))
+
+    def _invert_loop(self, model, images, moves, refine, graph, labels, cfg_scale):
+        """`invert`'s trajectory over `moves`, [(s, u)] ascending from 0.  base holds x_s and is only read within a level; the
+        iterate lives in zs, n rows or the 2n rows [z ; z] of the guided forward, which every step writes (both halves)."""
+        with self._model_scope(model):
+            base = images.to(self.device).contiguous().clone()
+            n = base.shape[0]
+            y, s = self._guided(labels, cfg_scale)
+            zs = torch.cat([base, base]) if s > 0 else base.clone()
+            rows = zs.shape[0]
+
+            def iterate(t_rows, lo, hi):
+                eps = self.predict_eps(model, zs, t_rows, y)
+                dev = "_dev" if isinstance(lo, torch.Tensor) else ""
+                if s > 0:
+                    getattr(ops, "ddim_invert_step_cfg" + dev)(base, eps, self.alpha_hat, lo, hi, s, zs[:n], zs[n:])
+                else:
+                    getattr(ops, "ddim_invert_step" + dev)(base, eps, self.alpha_hat, lo, hi, zs)
+
+            replay = None
+            if graph and len(moves) * (refine + 1) > 1:
+                t_dev = torch.full((rows,), moves[0][1], device=base.device, dtype=torch.long)
+                lo_dev = torch.full((1,), moves[0][0], device=base.device, dtype=torch.long)
+                g = self._capture(lambda: iterate(t_dev, lo_dev, t_dev), zs)
+
+                def replay(lo, hi):
+                    lo_dev.fill_(lo)
+                    t_dev.fill_(hi)
+                    g.replay()
+            for lo, hi in moves:
+                for _ in range(refine + 1):
+                    if replay is not None:
+                        replay(lo, hi)
+                    else:
+                        iterate(self._t_full(rows, hi, base.device), lo, hi)
+                base.copy_(zs[:n])
+        return base
+
+    def decode(self, model, latents, steps, eta=0.0, labels=None, cfg_scale=0.0, noise_source="reference", graph=None,
+               return_float=False):
+        """The DDIM chain of `sample` started from `latents`, the state at level taus[0], instead of drawn noise.  latents: fp32
+        (n, C, img_size, img_size), e.g. what `invert` returns for the same `steps`; it is not written.  steps / eta / labels /
+        cfg_scale / noise_source / graph / return_float and the snapshots: as for `sample` with steps= (DDIM only: there is no
+        sampler argument).  With eta > 0 the step noise comes from the generator path `sample` uses; with eta = 0 nothing is
+        drawn.  For latents drawn as `sample` draws x_T the result is `sample`'s, bit for bit.  Returns what `sample` returns."""
+        logging.info(f"Decoding {latents.shape[0] if isinstance(latents, torch.Tensor) else '?'} latents....")
+        self._check_images("decode", latents, "latents")
+        if steps is None:
+            raise ValueError("Diffusion.decode: steps is required (an int or an explicit sequence of timesteps: DDIM only)")
+        pairs = self._check_ddim("decode", steps, eta)
+        n, c = latents.shape[0], latents.shape[1]
+        labels = self._check_guidance("decode", model, n, labels, cfg_scale)
+        x, snaps = self._ddim_loop(model, n, c, pairs, float(eta), noise_source, graph, labels, float(cfg_scale), start=latents)
+        return self._finish(x, snaps, return_float)
+
+    def sdedit(self, model, images, t0, steps, eta=0.0, labels=None, cfg_scale=0.0, noise_source="reference", graph=None,
+               return_float=False):
+        """SDEdit (Meng et al. 2022): noise `images` to level t0 and denoise them from there, so the coarse content survives and
+        the detail is drawn anew; the larger t0, the freer the edit.  images: fp32 (n, C, img_size, img_size) in [-1, 1], e.g. a
+        stroke painting or a composite; t0: an int in [1, T - 1].  z is drawn as `sample` draws x_T (`_initial_noise`),
+        x = ops.noise_images(images, z, t0, alpha_hat), then `decode` over ddim_timesteps_from(t0, S) for an int `steps` = S, or
+        over an explicit sequence whose first element must be t0.  Everything else as `decode`.  Returns what `sample` returns."""
+        logging.info(f"Editing {images.shape[0] if isinstance(images, torch.Tensor) else '?'} images....")
+        self._check_images("sdedit", images)
+        T = self.noise_steps
+        if isinstance(t0, bool) or not isinstance(t0, (int, np.integer)) or not 1 <= t0 <= T - 1:
+            raise ValueError(f"Diffusion.sdedit: t0 must be an int in [1, {T - 1}] (got {t0!r})")
+        if steps is None:
+            raise ValueError("Diffusion.sdedit: steps is required (an int or an explicit sequence of timesteps starting at t0)")
+        if isinstance(steps, (int, np.integer)) and not isinstance(steps, bool):
+            steps = self.ddim_timesteps_from(int(t0), steps)
+        pairs = self._check_ddim("sdedit", steps, eta)
+        if pairs[0][0] != t0:
+            raise ValueError(f"Diffusion.sdedit: an explicit steps sequence must start at t0 = {t0} (got {list(steps)!r})")
+        n, c = images.shape[0], images.shape[1]
+        self._check_guidance("sdedit", model, n, labels, cfg_scale)
+        z = self._initial_noise(n, c, noise_source)
+        x = ops.noise_images(images.to(self.device), z, self._t_full(n, int(t0), z.device), self.alpha_hat)
+        return self.decode(model, x, [t for t, _ in pairs], eta, labels, cfg_scale, noise_source, graph, return_float)
+
+    def interpolate(self, model, a, b, weights, steps, refine=0, labels=None, cfg_scale=0.0, graph=None, return_float=False):
+        """Interpolate between the images a and b through their latents: `invert` torch.cat([a, b]) as one batch of 2n rows (labels
+        repeated), ops.slerp(lat[:n], lat[n:], weights) -> (n, W, ...), and `decode` the n W rows as one batch with eta = 0 (the
+        labels repeated per weight).  Rows are ordered (pair, weight): row i W + k is pair i at weights[k]; weight 0 reconstructs
+        a, weight 1 b.  The batching is part of the contract: the result equals those three public calls made by hand, bit for
+        bit.  a, b: fp32 (n, C, img_size, img_size) in [-1, 1]; weights: a non-empty 1-D sequence of finite numbers; steps /
+        refine / labels / cfg_scale / graph: as for `invert` and `decode`.  Returns what `sample` returns."""
+        self._check_images("interpolate", a, "a")
+        self._check_images("interpolate", b, "b")
+        if a.shape != b.shape:
+            raise ValueError(f"Diffusion.interpolate: a and b must have one shape (got {tuple(a.shape)} and {tuple(b.shape)})")
+        try:
+            w = np.asarray(weights.detach().cpu() if isinstance(weights, torch.Tensor) else weights, dtype=np.float64)
+        except (TypeError, ValueError):
+            w = None
+        if w is None or w.ndim != 1 or w.size < 1 or not np.isfinite(w).all():
+            raise ValueError("Diffusion.interpolate: weights must be a non-empty 1-D sequence of finite numbers")
+        self._invert_moves(steps)
+        if isinstance(refine, bool) or not isinstance(refine, (int, np.integer)) or refine < 0:
+            raise ValueError(f"Diffusion.interpolate: refine must be an int >= 0 (got {refine!r})")
+        n = a.shape[0]
+        y = self._check_guidance("interpolate", model, n, labels, cfg_scale)
+        lat = self.invert(model, torch.cat([a.to(self.device), b.to(self.device)]), steps, refine,
+                          None if y is None else torch.cat([y, y]), cfg_scale, graph)
+        mid = ops.slerp(lat[:n], lat[n:], weights)
+        return self.decode(model, mid.reshape((n * w.size,) + tuple(lat.shape[1:])), steps, 0.0,
+                           None if y is None else y.repeat_interleave(w.size), cfg_scale, graph=graph, return_float=return_float)
 
     @staticmethod
     def _capture(one_step, xs):

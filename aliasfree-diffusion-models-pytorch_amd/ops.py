@@ -1209,6 +1209,84 @@ def ddim_step_cfg_dev(x, eps2, noise, alpha_hat, t_dev, t_prev_dev, eta, cfg_sca
                  dev=True)
 
 
+def _ddim_invert(what, x, eps, alpha_hat, s, u, out, cfg_scale=None, out2=None, dev=False):
+    """One ascending DDIM step s -> u: checks the arguments and calls afd_ddim_invert_step[_cfg][_dev], whose arguments run
+    x, eps, alpha_hat, s, u, [cfg_scale], x_out, [x_out2], n, stream.  dev: s and u are int64 device tensors."""
+    guided = cfg_scale is not None
+    out = torch.empty_like(x) if out is None else out
+    n = _step_args(what, x, eps, None, alpha_hat, out, out2, guided)
+    if dev:
+        for v in (s, u):
+            if not isinstance(v, torch.Tensor) or not v.is_cuda or v.dtype != torch.long or v.numel() < 1:
+                raise AfdError(f"afdm: {what}: s_dev / u_dev must be int64 device tensors (element 0 is read)")
+        index = [_p(s), _p(u)]
+    else:
+        s, u = int(s), int(u)
+        if not 0 <= s < u < alpha_hat.numel():
+            raise AfdError(f"afdm: {what} needs 0 <= s < u < {alpha_hat.numel()} (got s = {s}, u = {u})")
+        index = [s, u]
+    name = "afd_ddim_invert_step" + "_cfg" * guided + "_dev" * dev
+    args = [_p(x), _p(eps), _p(alpha_hat)] + index + ([float(cfg_scale)] if guided else []) + [_p(out)] + ([_p(out2)] if guided else [])
+    getattr(lib(), name)(*args, n, _stream())
+    return out
+
+
+def ddim_invert_step(x, eps, alpha_hat, s, u, out=None):
+    """The ascending DDIM step s -> u, 0 <= s < u (include/afd.h: afd_ddim_invert_step gives the exact expression): the inverse of
+    `ddim_step(., eps, None, alpha_hat, u, s, 0.0)` for the same eps.  `out` defaults to a new tensor (the refinement of
+    `Diffusion.invert` re-reads x) and may be x (in place); it must not overlap eps."""
+    return _ddim_invert("DDIM invert step", x, eps, alpha_hat, s, u, out)
+
+
+def ddim_invert_step_dev(x, eps, alpha_hat, s_dev, u_dev, out):
+    """ddim_invert_step with s = s_dev[0] and u = u_dev[0] read on the device (graph-replayable)."""
+    return _ddim_invert("DDIM invert step", x, eps, alpha_hat, s_dev, u_dev, out, dev=True)
+
+
+def ddim_invert_step_cfg(x, eps2, alpha_hat, s, u, cfg_scale, out=None, out2=None):
+    """Classifier-free guided ascending step: e = torch.lerp(eps2[n:], eps2[:n], cfg_scale), then exactly
+    `ddim_invert_step(x, e, ...)`, in one launch.  `out2` (optional) receives the same values as `out`."""
+    return _ddim_invert("guided DDIM invert step", x, eps2, alpha_hat, s, u, out, cfg_scale=cfg_scale, out2=out2)
+
+
+def ddim_invert_step_cfg_dev(x, eps2, alpha_hat, s_dev, u_dev, cfg_scale, out, out2=None):
+    """ddim_invert_step_cfg with the levels read on the device (graph-replayable)."""
+    return _ddim_invert("guided DDIM invert step", x, eps2, alpha_hat, s_dev, u_dev, out, cfg_scale=cfg_scale, out2=out2, dev=True)
+
+
+SLERP_MAX_ROW = 3 * 64 * 64
+
+
+def slerp(a, b, weights):
+    """Spherical interpolation of the rows of a towards those of b (include/afd.h: afd_slerp_rows gives the exact expression; rows
+    that are parallel, antiparallel or zero are interpolated linearly).  a, b: contiguous fp32 (n, ...) device tensors of one
+    shape, at most 3 * 64 * 64 values per row; weights: a 1-D sequence or tensor of W finite numbers (0 gives a, 1 gives b, bit
+    for bit).  One launch for all rows and weights.  Returns (n, W, ...): row (i, k) is pair i at weights[k]."""
+    for v in (a, b):
+        if not isinstance(v, torch.Tensor):
+            raise AfdError("afdm: slerp: a and b must be tensors")
+    _chk(a, b)
+    if a.dim() < 2 or a.shape != b.shape or a.shape[0] < 1:
+        raise AfdError(f"afdm: slerp: a and b must be (n, ...) tensors of one shape, n >= 1 (got {tuple(a.shape)} and {tuple(b.shape)})")
+    if not a.is_contiguous() or not b.is_contiguous():
+        raise AfdError("afdm: slerp: a and b must be contiguous")
+    n, row = a.shape[0], a.numel() // a.shape[0]
+    if not 1 <= row <= SLERP_MAX_ROW:
+        raise AfdError(f"afdm: slerp: a row must hold between 1 and {SLERP_MAX_ROW} values (got {row})")
+    if isinstance(weights, torch.Tensor) and (weights.dtype.is_complex or weights.dtype == torch.bool):
+        raise AfdError(f"afdm: slerp: weights must be real numbers (got {weights.dtype})")
+    try:
+        w = torch.as_tensor(weights).detach().to(device="cpu", dtype=torch.float64)
+    except (TypeError, ValueError, RuntimeError):
+        raise AfdError("afdm: slerp: weights must be a 1-D sequence or tensor of numbers") from None
+    if w.dim() != 1 or w.numel() < 1 or not bool(torch.isfinite(w).all()):
+        raise AfdError(f"afdm: slerp: weights must be a non-empty 1-D sequence of finite numbers (got shape {tuple(w.shape)})")
+    w = w.to(device=a.device, dtype=torch.float32)
+    out = torch.empty((n, w.numel()) + tuple(a.shape[1:]), device=a.device, dtype=torch.float32)
+    lib().afd_slerp_rows(_p(a), _p(b), _p(w), _p(out), n, w.numel(), row, _stream())
+    return out
+
+
 def _dpmpp_args(what, x, eps, x0_prev, coef, out, x0_out, out2=None, guided=False):
     n = _step_args(what, x, eps, x0_prev, coef, out, out2, guided)
     _chk(x0_out)

@@ -710,6 +710,41 @@ def restoration_results(model_data, images, n, mask="center", factor=4, tasks=RE
     return _restoration_scores(diffusion, model, originals.to(args.device).contiguous(), cfg, model_data["seed"], kw)
 
 
+def reconstruct_results(model_data, images, n, steps=50, refine=0, **kw):
+    """Load the checkpoint as rotation_results does, seed, invert the first n of `images` (a DeviceDataset, or (N, C, H, W) uint8
+    pixels, as restoration_results takes them) with `Diffusion.invert(steps, refine)` and decode the latents again with
+    `Diffusion.decode(steps)`, eta = 0.  **kw: labels, cfg_scale, graph, given to both.  Returns {"n", "steps", "refine", "psnr" and
+    "ssim" of the reconstructions against the images ({"mean", "std" (population), "values": one per image}; quality.image_quality),
+    "latent_std": each latent's standard deviation (1 for a latent that looks like the noise the sampler starts from)}."""
+    from .quality import image_quality
+    n = _int_in(n, 1, len(images), f"reconstruct_results: n must be an int in [1, {len(images)}] (the number of images; got {n!r})")
+    if isinstance(images, DeviceDataset):
+        originals = images.pixels(n)
+    else:
+        originals = torch.from_numpy(images) if isinstance(images, np.ndarray) else images
+        if not isinstance(originals, torch.Tensor) or originals.dtype != torch.uint8 or originals.dim() != 4:
+            raise ValueError("reconstruct_results: images must be a DeviceDataset or (N, C, H, W) uint8 pixels")
+        originals = originals[:n]
+    model, diffusion, args = _load(model_data)
+    set_seed(model_data["seed"])
+    originals = originals.to(args.device).contiguous()
+    C = originals.shape[1]
+    x0 = normalisation_table(C).to(args.device)[torch.arange(C, device=args.device).view(1, C, 1, 1), originals.long()]      # as the loader maps pixels
+    latents = diffusion.invert(model, x0, steps, refine=refine, **kw)
+    score = image_quality(diffusion.decode(model, latents, steps, **kw)[0], originals)
+    return {"n": n, "steps": int(steps) if isinstance(steps, (int, np.integer)) else [int(t) for t in steps], "refine": int(refine),
+            "psnr": _spread(score["psnr"]), "ssim": _spread(score["ssim"]),
+            "latent_std": latents.flatten(1).double().std(dim=1, unbiased=False).tolist()}
+
+
+def edit_results(model_data, images, t0, **kw):
+    """Load the checkpoint as rotation_results does, seed, and edit `images` from noise level t0 (Diffusion.sdedit; **kw: steps,
+    eta, labels, cfg_scale, noise_source, graph, return_float)."""
+    model, diffusion, _ = _load(model_data)
+    set_seed(model_data["seed"])
+    return diffusion.sdedit(model, images, t0, **kw)
+
+
 def equivariance_results(model_data, images, **kw):
     """Load the checkpoint as rotation_results does, seed, and score the model's equivariance on `images`
     (Diffusion.equivariance; **kw: t, transforms, margin, peak, labels, batch, noise_source, noise_fn).  Returns its dict."""

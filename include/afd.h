@@ -406,6 +406,26 @@ int afd_ddim_step_cfg(const float* x, const float* eps2, const float* noise, con
 int afd_ddim_step_cfg_dev(const float* x, const float* eps2, const float* noise, const float* alpha_hat, const int64_t* t_dev,
                           const int64_t* t_prev_dev, float eta, float cfg_scale, float* x_out, float* x_out2, long n,
                           afd_stream_t stream);
+/* The ascending DDIM step (DDIM inversion): one move s -> u of a chain walked upwards, 0 <= s < u; level 0 is the image, read
+ * as alpha_hat[0] exactly as afd_ddim_step's last step t_prev = 0 reads it.  a_s = alpha_hat[s], a_u = alpha_hat[u].  fp32 with
+ * one IEEE rounding per operation (no FMA contraction, correctly rounded / and sqrt), evaluated in exactly this order:
+ *   x0  = (x - sqrt(1 - a_s) * eps) / sqrt(a_s)
+ *   out = (sqrt(a_u) * x0) + (sqrt(1 - a_u) * eps)
+ * the algebraic inverse of afd_ddim_step's eta = 0 step u -> s for the eps that step used.  No noise, no masked form.
+ * Requires 0 <= s < u (host forms; u is not checked against the table's length) and n > 0.  x_out is normally apart from x (a
+ * fixed-point refinement re-reads the base state) and may be x itself; x_out and x_out2 must not overlap eps.  n: elements of x. */
+int afd_ddim_invert_step(const float* x, const float* eps, const float* alpha_hat, int s, int u, float* x_out, long n,
+                         afd_stream_t stream);
+/* same with s = s_dev[0] and u = u_dev[0] read on the device (graph-replayable; the indices are not checked) */
+int afd_ddim_invert_step_dev(const float* x, const float* eps, const float* alpha_hat, const int64_t* s_dev, const int64_t* u_dev,
+                             float* x_out, long n, afd_stream_t stream);
+/* classifier-free guided form: eps2 as for afd_ddim_step_cfg (conditional element j at j, unconditional at n + j),
+ * eps = torch.lerp(e_u, e_c, cfg_scale) with the same scalar formula, then exactly the afd_ddim_invert_step expression.
+ * x_out2 is NULL or a second destination of the same n values; neither output may overlap any of eps2's 2n values. */
+int afd_ddim_invert_step_cfg(const float* x, const float* eps2, const float* alpha_hat, int s, int u, float cfg_scale, float* x_out,
+                             float* x_out2, long n, afd_stream_t stream);
+int afd_ddim_invert_step_cfg_dev(const float* x, const float* eps2, const float* alpha_hat, const int64_t* s_dev,
+                                 const int64_t* u_dev, float cfg_scale, float* x_out, float* x_out2, long n, afd_stream_t stream);
 /* DPM-Solver++(2M) (Lu et al. 2022): one multistep update t -> t_prev of the probability-flow ODE, for a model trained on the
  * eps-objective.  coef: 5 fp32 values in device memory, [alpha_t, sigma_t, A, B0, B1] of this step (Diffusion.dpmpp_coefficients
  * builds the table on the host).  fp32 with one IEEE rounding per operation (no FMA contraction, correctly rounded /), in
@@ -964,6 +984,20 @@ int afd_pair_quality_f32(const float* a, const float* b, long planes, int C, int
 int afd_pair_quality_u8(const uint8_t* a, const uint8_t* b, long planes, int C, int H, int W, const double* win, int K, double c1,
                         double c2, const uint8_t* region_or_null, long region_rows, double* out, double* ssim_map_or_null,
                         afd_stream_t stream);
+
+/* ---- spherical interpolation of latent rows (csrc/slerp.hip) --------------------------------------- Diffusion.interpolate
+ * a, b: (pairs, row) fp32; w: W fp32 weights in device memory; out: (pairs, W, row) fp32; row <= 3 * 64 * 64.  Per pair, in fp64:
+ *   d = sum_i a_i b_i,  na = sum_i a_i^2,  nb = sum_i b_i^2
+ *   c = clamp(d / sqrt(na nb), -1, 1),  omega = acos(c),  so = sin(omega)
+ *   na == 0, nb == 0 or so < 1e-6 (parallel and antiparallel rows):  ca = 1 - w,  cb = w                  (lerp: the definition)
+ *   otherwise:                                ca = sin((1 - w) omega) / so,  cb = sin(w omega) / so
+ *   out_i = (float)(ca * a_i + cb * b_i)      (the products and the sum in fp64 without contraction, then one rounding)
+ * With finite inputs w = 0 returns a and w = 1 returns b bit for bit.  One launch on `stream`, one workgroup per (pair, weight).
+ * The sums run in an order that depends on `row` alone (element i belongs to thread (i / 4) % 256, ascending within a thread;
+ * a shuffle tree over the lanes; the four waves in order), whatever the alignment: no atomics, the same bits from call to call.
+ * AFD_EINVAL (nothing launched) on a NULL pointer, pairs, W or row <= 0, row > 12288, pairs * W >= 2^31, a pointer that is not
+ * 4-byte aligned, or out overlapping a, b or w. */
+int afd_slerp_rows(const float* a, const float* b, const float* w, float* out, long pairs, long W, long row, afd_stream_t stream);
 
 #ifdef __cplusplus
 }
