@@ -655,10 +655,12 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkv_mfma(const float* __restr
 // transposition and dQ cost the MFMAs and accumulator registers of d = 8; S and dP take six bf16 MFMAs each (28 per tile).
 // A wave owns ONE key tile and the workgroup walks the keys 128 at a time: with two tiles per wave the images come to 103 KB
 // of LDS and one workgroup per CU, measured 106 us at sa1's shape against 92 us for this form (70 KB, two per CU).
-// dQ = sum_key dS (K - c) with c one constant per (batch, head) and head dim -- the mean of the head's first 256 keys, taken
-// once by the workgroup: every row of dS sums to zero, so the result is the same, but a component of K that is large and
-// nearly constant over the keys (a shifted feature) no longer multiplies the rounding errors of dS: on the +30 row-shift
-// case of tests/test_gpu_attn_d16.py the error of that dQ component falls from 3.5e-4 to 3e-6 (round-2 kernels: 5.5e-5).
+// Both head dims: dQ = sum_key dS (K - c) with c one constant per (batch, head) and head dim -- the mean of the head's first
+// 256 keys, taken once by the workgroup: every row of dS sums to zero, so the result is the same, but a component of K that is
+// large and nearly constant over the keys (a shifted feature) no longer multiplies the rounding errors of dS: on the +30
+// row-shift case of tests/test_gpu_attn_d16.py the error of that dQ component falls from 3.5e-4 to 3e-6 (round-2 kernels:
+// 5.5e-5).  d = 8 ran without it until tests/test_gpu_attn_d8.py put the same case to it: dqkv 3.5e-5 against the round-2
+// kernels' 7.7e-6.
 // ------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void attn_delta_k(const float* __restrict__ o, const float* __restrict__ d_o, float* __restrict__ delta,
                                                     int heads, int D, int L, long total) {
@@ -719,7 +721,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_fused(const float* __restrict
   __shared__ __attribute__((aligned(16))) float Ds[kTK];
   __shared__ float DQ[4][D][kTK];                                      // the waves' dQ partials of one stage
   __shared__ float wmax[4][4];
-  __shared__ float Kc[D == 16 ? D : 1];                                // d = 16: the constant taken off K in the dQ operand
+  __shared__ float Kc[D];                                              // the constant taken off K in the dQ operand
   const int b = blockIdx.y, h = blockIdx.x, C = heads * D;
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, half = lane >> 5, l31 = lane & 31;
   const float* qp = qkv + ((long)b * 3 * C + h * D) * L;
@@ -749,18 +751,19 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_fused(const float* __restrict
   const int sbase = ((((rr >> 5) * 2 + (sr >> 3)) * 2 + sh) * ROWS) * 8 + (sr & 7);       // + m * 8, m = the rows of d
   auto row1 = [](int d) { return D == 8 ? d : a_row16(d); };          // piece 1 of head dim d; piece 2: + D
 
-  if (D == 16) {                                                       // c = mean of the head's first 256 keys (DQ is free until the first stage ends)
+  {                                                                    // c = mean of the head's first 256 keys (DQ is free until the first stage ends)
+    constexpr int CH = 256 / D;                                        // a thread sums every CH-th key of one head dim
     float* part = &DQ[0][0][0];
-    const int d = threadIdx.x >> 4, ch = threadIdx.x & 15;
+    const int d = threadIdx.x / CH, ch = threadIdx.x % CH;
     float t = 0.f;
 #pragma unroll
-    for (int i = 0; i < 16; ++i) t += kp[(long)d * L + i * 16 + ch];
+    for (int i = 0; i < 256 / CH; ++i) t += kp[(long)d * L + i * CH + ch];
     part[ch * D + d] = t;
     __syncthreads();
     if (threadIdx.x < D) {
       float m = 0.f;
 #pragma unroll
-      for (int c = 0; c < 16; ++c) m += part[c * D + threadIdx.x];
+      for (int c = 0; c < CH; ++c) m += part[c * D + threadIdx.x];
       Kc[threadIdx.x] = m * (1.0f / 256.0f);
     }
     __syncthreads();
@@ -781,7 +784,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_fused(const float* __restrict
         xk[j][d] = kp[(long)d * L + key0 + j * 32 + l31];
         xs[d] = xk[j][d] * (scale * kLog2e);
         xv[d] = vp[(long)d * L + key0 + j * 32 + l31];
-        if (D == 16) xk[j][d] -= Kc[d];                                 // the dQ operand is K - c (header comment)
+        xk[j][d] -= Kc[d];                                              // the dQ operand is K - c (header comment)
         n1 += fabsf(xv[d]); kmax = fmaxf(kmax, fabsf(xk[j][d]));
       }
       v1 = fmaxf(v1, n1);
