@@ -940,6 +940,107 @@ class Diffusion:
         snaps.append(x)
         return x, snaps
 
+    # Diffusion posterior sampling (DPS, Chung et al. 2023) for noisy linear measurements ---------------------
+    def x0_coefficients(self, t):
+        """(a, b), two (B,) fp64 host tensors with x0_hat = a x_t + b out for `self.prediction` at the timesteps t: (1 / sqrt(ah),
+        -sqrt(1 - ah) / sqrt(ah)) for "eps", (sqrt(ah), -sqrt(1 - ah)) for "v" and (0, 1) for "x0", ah the fp32 alpha_hat[t]
+        widened to fp64.  The kernels round each once to fp32 (afd.h: afd_dps_residual)."""
+        ah = self.alpha_hat.detach().cpu().double()[torch.as_tensor(t).cpu().long()]
+        sa, sb = torch.sqrt(ah), torch.sqrt(1.0 - ah)
+        if self.prediction == "v":
+            return sa, -sb
+        if self.prediction == "x0":
+            return torch.zeros_like(ah), torch.ones_like(ah)
+        return 1.0 / sa, -sb / sa
+
+    def _output_and_vjp(self, model, x_t, t, y, seed_fn):
+        """-> (out, v): the network's output at x_t, detached, and its vector-Jacobian product v = (d out / d x_t)^T g with the seed
+        g = seed_fn(out).  One forward and one backward under enable_grad (the samplers' scope runs under no_grad), x_t a fresh
+        leaf.  While it runs every parameter of the model is frozen (requires_grad False), so the ops that look at
+        needs_input_grad compute no weight gradient, and no parameter's .grad is written; the flags come back as they were found,
+        also after an exception.  Works for any differentiable nn.Module."""
+        frozen = [p for p in model.parameters() if p.requires_grad]
+        for p in frozen:
+            p.requires_grad_(False)
+        try:
+            with torch.enable_grad():
+                x = x_t.detach().requires_grad_(True)
+                out = self._raw_output(model, x, t, y)
+                found = out.detach()
+                with torch.autograd.set_multithreading_enabled(False):          # backward on the calling thread, as TrainStep runs it
+                    (v,) = torch.autograd.grad(out, x, seed_fn(found))
+        finally:
+            for p in frozen:
+                p.requires_grad_(True)
+        return found, v.contiguous()
+
+    def posterior_sample(self, model, measurement, operator, zeta=1.0, steps=None, eta=0.0, labels=None, noise_source="reference",
+                         return_float=False):
+        """Restore images from a noisy linear measurement y = A x + sigma n without retraining (diffusion posterior sampling,
+        Chung et al. 2023): after every step of the chain the state moves down the gradient, with respect to x_t, of
+        |y - A x0_hat(x_t)|, with the step zeta / |y - A x0_hat| per row,
+            x <- update(x, out) - zeta grad_{x_t} |y - A x0_hat(x_t)|,     x0_hat = a_t x_t + b_t out(x_t)   (`x0_coefficients`).
+        measurement: fp32 (n, C, h, w); operator: a `posterior.LinearOperator`, whose stride gives the image size
+        (h s, w s) = (img_size, img_size).  zeta: a finite number >= 0, the guidance's weight (0: the plain sampler's images,
+        at the same cost).
+        steps=None runs the DDPM chain, an int or an explicit sequence DDIM with `eta`, as `sample` does; x_T, the steps' noise,
+        the snapshots and the result are drawn, taken and returned as `sample` draws, takes and returns them.
+        Per step: one forward and one backward of the network (`_output_and_vjp`; the parameters are frozen meanwhile), the fused
+        residual kernel as the backward's seed (ops.dps_residual), the sampler's own update, and one elementwise correction
+        (ops.dps_correct), on the last step too; nothing is read back from the device.
+        labels: class labels for a conditional model.  Classifier-free guidance is not offered (it would need the
+        vector-Jacobian product of a 2n-row combination), nor variance="learned", graph capture or a rotation."""
+        where = "posterior_sample"
+        from .posterior import LinearOperator
+        if not isinstance(operator, LinearOperator):
+            raise ValueError(f"Diffusion.{where}: operator must be a posterior.LinearOperator (got {type(operator).__name__})")
+        if isinstance(zeta, bool) or not isinstance(zeta, (int, float, np.integer, np.floating)) or not (zeta >= 0 and math.isfinite(zeta)):
+            raise ValueError(f"Diffusion.{where}: zeta must be a finite number >= 0 (got {zeta!r})")
+        if self.variance == "learned":
+            raise ValueError(f"Diffusion.{where}: variance='learned' is not supported (the guidance differentiates the prediction "
+                             f"alone and the chain keeps the fixed variance)")
+        if not isinstance(measurement, torch.Tensor) or measurement.dtype != torch.float32 or measurement.dim() != 4 \
+                or measurement.shape[0] < 1:
+            raise ValueError(f"Diffusion.{where}: measurement must be an fp32 (n, C, h, w) tensor with n >= 1")
+        s, S = operator.stride, self.img_size
+        if not 1 <= S <= 64 or S % s or tuple(measurement.shape[2:]) != (S // s, S // s):
+            raise ValueError(f"Diffusion.{where}: at stride {s} and img_size {S} (at most 64, a multiple of the stride) the measurement "
+                             f"must have shape (n, C, {S // s}, {S // s}) (got {tuple(measurement.shape)})")
+        n, C = int(measurement.shape[0]), int(measurement.shape[1])
+        try:
+            operator._mask_for(C, S // s, S // s)
+        except ValueError as e:
+            raise ValueError(f"Diffusion.{where}: {e}") from None
+        logging.info(f"Restoring {n} images from their measurements....")
+        pairs = self._check_ddim(where, steps, eta)
+        if labels is not None:
+            labels = self._check_labels(model, n, None, labels, where)
+        self.check_model(model, C, f"Diffusion.{where}")
+        moves = [(t, t - 1) for t in range(self.noise_steps - 1, 0, -1)] if pairs is None else pairs
+        ddim_eta = None if pairs is None else float(eta)
+        takes_noise = ddim_eta is None or ddim_eta > 0
+        zeta = float(zeta)
+        snaps = []
+        with self._model_scope(model):
+            x = self._initial_noise(n, C, noise_source)
+            y = measurement.to(self.device).contiguous()
+            taps, mask = operator._taps, operator._device_mask(x.device)
+            g = torch.empty_like(x)
+            sums = torch.empty(n, C, device=x.device, dtype=torch.float64)
+            for t, tp in moves:
+                t_rows = self._t_full(n, t, x.device)
+                seed = lambda out: ops.dps_residual(x, out, t_rows, self.alpha_hat, self.prediction, y, taps, s, mask, g, sums)[0]
+                out, v = self._output_and_vjp(model, x, t_rows, labels, seed)
+                eps = out if self.prediction == "eps" else ops.pred_to_eps(out, x, t_rows, self.alpha_hat, self.prediction, eps_out=out)
+                z = self._step_noise(x, noise_source) if takes_noise and tp > 0 else None
+                self._update(x, n, eps, z, t, tp if ddim_eta is not None else None, eta=ddim_eta)
+                ops.dps_correct(x, g, v, sums, t_rows, self.alpha_hat, self.prediction, zeta)
+                if self.ddim_snapshot(t, tp):
+                    snaps.append(x.clone())
+            x = x.clone()
+        snaps.append(x)
+        return self._finish(x, snaps, return_float)
+
     # Real images: DDIM inversion with fixed-point refinement, decoding, SDEdit, interpolation (DESIGN.md section 6v) ----------------
     def ddim_timesteps_from(self, t0, steps):
         """The S = `steps` timesteps of a DDIM chain that starts at t0 instead of T - 1, strictly decreasing:

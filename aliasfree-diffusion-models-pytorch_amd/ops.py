@@ -2287,3 +2287,105 @@ def pair_quality(a, b, win, c1, c2, region=None, want_map=False):
     fn = lib().afd_pair_quality_u8 if a.dtype == torch.uint8 else lib().afd_pair_quality_f32
     fn(_p(a), _p(b), n * C, C, H, W, w.ctypes.data, K, float(c1), float(c2), _p(region), rows, _p(out), _p(ssim_map), _stream())
     return out, ssim_map
+
+
+# ---- diffusion posterior sampling: the linear operator A x = m . S_s(k * x) and the step's two launches (afd.h) ----
+LINOP_MAX_SIDE = 64
+LINOP_MAX_KERNEL = 15
+LINOP_STRIDES = (1, 2, 4)
+
+
+def _linop_args(what, kernel, stride, mask, C, h, w, device):
+    """-> (the host taps, K, the mask's channels) after checking an operator against a (.., C, h, w) measurement plane.  kernel: a
+    (K, K) float32 host array (numpy, or a cpu tensor), K odd and at most 15; stride 1, 2 or 4; mask None or a contiguous
+    (1 | C, h, w) fp32 tensor on `device`."""
+    taps = np.ascontiguousarray(kernel.detach().cpu().numpy() if isinstance(kernel, torch.Tensor) else np.asarray(kernel), dtype=np.float32)
+    K = int(taps.shape[0]) if taps.ndim == 2 and taps.shape[0] == taps.shape[1] else 0
+    if K < 1 or K % 2 == 0 or K > LINOP_MAX_KERNEL:
+        raise AfdError(f"afdm: {what}: kernel must be (K, K) with K odd and at most {LINOP_MAX_KERNEL} (got shape {tuple(taps.shape)})")
+    if stride not in LINOP_STRIDES:
+        raise AfdError(f"afdm: {what}: stride must be 1, 2 or 4 (got {stride!r})")
+    if not (1 <= h * stride <= LINOP_MAX_SIDE and 1 <= w * stride <= LINOP_MAX_SIDE):
+        raise AfdError(f"afdm: {what}: H and W must lie in [1, {LINOP_MAX_SIDE}] (got {h * stride}, {w * stride})")
+    mc = 0
+    if mask is not None:
+        if not isinstance(mask, torch.Tensor) or mask.device != device or mask.dtype != torch.float32 or mask.dim() != 3 \
+                or mask.shape[0] not in (1, C) or tuple(mask.shape[1:]) != (h, w) or not mask.is_contiguous():
+            raise AfdError(f"afdm: {what}: mask must be None or a contiguous fp32 tensor of shape (1 | {C}, {h}, {w}) on the images' device")
+        mc = int(mask.shape[0])
+    return taps, K, mc
+
+
+def _linop_images(what, name, v):
+    if not isinstance(v, torch.Tensor) or not v.is_cuda or v.dtype != torch.float32 or v.dim() != 4 or v.numel() == 0:
+        raise AfdError(f"afdm: {what}: {name} must be a non-empty (n, C, H, W) fp32 device tensor")
+    return _c(v.detach())
+
+
+def linop_apply(x, kernel, stride=1, mask=None):
+    """y (n, C, H / s, W / s) = m . S_s(k * x), one launch (afd.h: afd_linop_apply)."""
+    what = "linop_apply"
+    x = _linop_images(what, "x", x)
+    B, C, H, W = x.shape
+    if H % stride or W % stride:
+        raise AfdError(f"afdm: {what}: H and W must be multiples of the stride {stride} (got {H}, {W})")
+    h, w = H // stride, W // stride
+    taps, K, mc = _linop_args(what, kernel, stride, mask, C, h, w, x.device)
+    y = torch.empty(B, C, h, w, device=x.device, dtype=torch.float32)
+    lib().afd_linop_apply(_p(x), _p(y), taps.ctypes.data, K, stride, _p(mask), mc, B, C, H, W, _stream())
+    return y
+
+
+def linop_adjoint(r, kernel, stride=1, mask=None):
+    """g (n, C, h s, w s) = A^T r, the transposed strided correlation of m . r, one launch (afd.h: afd_linop_adjoint)."""
+    what = "linop_adjoint"
+    r = _linop_images(what, "r", r)
+    B, C, h, w = r.shape
+    taps, K, mc = _linop_args(what, kernel, stride, mask, C, h, w, r.device)
+    g = torch.empty(B, C, h * stride, w * stride, device=r.device, dtype=torch.float32)
+    lib().afd_linop_adjoint(_p(r), _p(g), taps.ctypes.data, K, stride, _p(mask), mc, B, C, h * stride, w * stride, _stream())
+    return g
+
+
+def dps_residual(x_t, out, t, alpha_hat, kind, y, kernel, stride=1, mask=None, g=None, sums=None):
+    """The step side of diffusion posterior sampling in one launch (afd.h: afd_dps_residual): x0_hat = a_t x_t + b_t out with
+    (a_t, b_t) of `kind` at alpha_hat[t[row]], r = A x0_hat - y, sums[row, c] = the plane's sum of r^2 in fp64, g = A^T r.
+    x_t, out (n, C, H, W) and y (n, C, H / s, W / s) fp32 on one device, contiguous; t (n,) int64 on the device.
+    -> (g (n, C, H, W) fp32, sums (n, C) fp64)."""
+    what = "dps_residual"
+    code, B, _ = _objective_args(what, kind, t, alpha_hat, x_t, out)
+    if x_t.dim() != 4:
+        raise AfdError(f"afdm: {what}: x_t and out must be (n, C, H, W)")
+    _, C, H, W = x_t.shape
+    if H % stride or W % stride:
+        raise AfdError(f"afdm: {what}: H and W must be multiples of the stride {stride} (got {H}, {W})")
+    h, w = H // stride, W // stride
+    taps, K, mc = _linop_args(what, kernel, stride, mask, C, h, w, x_t.device)
+    _chk(y)
+    if tuple(y.shape) != (B, C, h, w) or not y.is_contiguous() or y.device != x_t.device:
+        raise AfdError(f"afdm: {what}: y must be a contiguous ({B}, {C}, {h}, {w}) tensor on the images' device (got {tuple(y.shape)})")
+    g = torch.empty_like(x_t) if g is None else g
+    sums = torch.empty(B, C, device=x_t.device, dtype=torch.float64) if sums is None else sums
+    if g.dtype != torch.float32 or tuple(g.shape) != tuple(x_t.shape) or not g.is_contiguous() or g.device != x_t.device \
+            or sums.dtype != torch.float64 or tuple(sums.shape) != (B, C) or not sums.is_contiguous() or sums.device != x_t.device:
+        raise AfdError(f"afdm: {what}: g must be a contiguous fp32 tensor of x_t's shape and sums a contiguous ({B}, {C}) fp64 one")
+    lib().afd_dps_residual(_p(x_t), _p(out), _p(t), _p(alpha_hat), code, _p(y), taps.ctypes.data, K, stride, _p(mask), mc, _p(g),
+                           _p(sums), B, C, H, W, _stream())
+    return g, sums
+
+
+def dps_correct(x, g, v, sums, t, alpha_hat, kind, zeta):
+    """x[row] -= c_row (a_t g + b_t v) in place, c_row = zeta / sqrt(sum_c sums[row, c]) decided on the device (0 where that sum
+    is 0: the row is not touched), one launch (afd.h: afd_dps_correct).  x, g, v: contiguous (n, C, ...) fp32; sums (n, C) fp64;
+    t (n,) int64 on the device.  -> x."""
+    what = "dps_correct"
+    code, B, chw = _objective_args(what, kind, t, alpha_hat, x, g, v)
+    if x.dim() < 2 or not isinstance(sums, torch.Tensor) or sums.dtype != torch.float64 or sums.device != x.device \
+            or tuple(sums.shape) != (B, x.shape[1]) or not sums.is_contiguous():
+        raise AfdError(f"afdm: {what}: sums must be a contiguous (n, C) fp64 tensor on x's device")
+    zeta = float(zeta)
+    if not (zeta >= 0 and np.isfinite(zeta)):
+        raise AfdError(f"afdm: {what}: zeta must be finite and >= 0 (got {zeta})")
+    C = int(x.shape[1])
+    lib().afd_dps_correct(_p(x), _p(g), _p(v), _p(sums), _p(t), _p(alpha_hat), code, zeta, B, C, chw // C, _stream())
+    return x

@@ -737,6 +737,49 @@ def reconstruct_results(model_data, images, n, steps=50, refine=0, **kw):
             "latent_std": latents.flatten(1).double().std(dim=1, unbiased=False).tolist()}
 
 
+def posterior_results(model_data, images, operator, sigma=0.05, zeta=1.0, n=4, steps=100, eta=1.0, **kw):
+    """Load the checkpoint as rotation_results does, measure the first n of `images` (a DeviceDataset, or (N, C, H, W) uint8 pixels,
+    as restoration_results takes them) with `operator.measure(x0, sigma)` (a posterior.LinearOperator; the seed is set first) and
+    restore them with `Diffusion.posterior_sample(zeta, steps, eta)` (steps=None: the DDPM chain, eta is then unused); the seed is
+    set again before each restoration.  **kw: labels, noise_source.  Returns {"n", "steps", "eta", "sigma", "zeta", "psnr" and "ssim" of the restorations against the images
+    ({"mean", "std" (population), "values": one per image}; quality.image_quality), "consistency": |A x - y| / |y| per image, x the
+    unquantised restoration, and "baseline": the same three scores at zeta = 0, the unguided sampler from the same noise, which
+    the scores are to be read against}."""
+    from .posterior import LinearOperator
+    from .quality import image_quality
+    if not isinstance(operator, LinearOperator):
+        raise ValueError(f"posterior_results: operator must be a posterior.LinearOperator (got {type(operator).__name__})")
+    n = _int_in(n, 1, len(images), f"posterior_results: n must be an int in [1, {len(images)}] (the number of images; got {n!r})")
+    if isinstance(images, DeviceDataset):
+        originals = images.pixels(n)
+    else:
+        originals = torch.from_numpy(images) if isinstance(images, np.ndarray) else images
+        if not isinstance(originals, torch.Tensor) or originals.dtype != torch.uint8 or originals.dim() != 4:
+            raise ValueError("posterior_results: images must be a DeviceDataset or (N, C, H, W) uint8 pixels")
+        originals = originals[:n]
+    model, diffusion, args = _load(model_data)
+    originals = originals.to(args.device).contiguous()
+    C = originals.shape[1]
+    x0 = normalisation_table(C).to(args.device)[torch.arange(C, device=args.device).view(1, C, 1, 1), originals.long()]      # as the loader maps pixels
+    set_seed(model_data["seed"])
+    y = operator.measure(x0, sigma)
+    y_norm = y.double().flatten(1).norm(dim=1)
+
+    def restore(z):
+        set_seed(model_data["seed"])
+        xq, _, x = diffusion.posterior_sample(model, y, operator, zeta=z, steps=steps, eta=eta if steps is not None else 0.0,
+                                                 return_float=True, **kw)
+        score = image_quality(xq, originals)
+        gap = (operator.apply(x) - y).double().flatten(1).norm(dim=1) / y_norm
+        return {"psnr": _spread(score["psnr"]), "ssim": _spread(score["ssim"]), "consistency": _spread(gap)}
+
+    res = {"n": n, "steps": None if steps is None else (int(steps) if isinstance(steps, (int, np.integer)) else [int(t) for t in steps]),
+           "eta": float(eta), "sigma": float(sigma), "zeta": float(zeta)}
+    res.update(restore(zeta))
+    res["baseline"] = restore(0.0)
+    return res
+
+
 def edit_results(model_data, images, t0, **kw):
     """Load the checkpoint as rotation_results does, seed, and edit `images` from noise level t0 (Diffusion.sdedit; **kw: steps,
     eta, labels, cfg_scale, noise_source, graph, return_float)."""

@@ -999,6 +999,41 @@ int afd_pair_quality_u8(const uint8_t* a, const uint8_t* b, long planes, int C, 
  * 4-byte aligned, or out overlapping a, b or w. */
 int afd_slerp_rows(const float* a, const float* b, const float* w, float* out, long pairs, long W, long row, afd_stream_t stream);
 
+/* ---- diffusion posterior sampling for linear operators (csrc/posterior.hip) ------ posterior.LinearOperator / Diffusion.posterior_sample
+ * The operator, per (row, channel) plane of a contiguous (B, C, H, W) fp32 tensor, 1 <= H, W <= 64:
+ *   A x = m . S_s(k * x)
+ * k * x: the correlation with `kernel`, a HOST float[K * K] (K odd, 1 <= K <= 15; NULL with K == 1 is the delta), zero padding K / 2;
+ * S_s: every stride-th row and column, stride 1, 2 or 4 dividing H and W, so the measurement plane is h x w = H / s x W / s;
+ * m: `mask`, (mask_channels, h, w) device floats with mask_channels 1 (one mask for every channel) or C, or NULL with
+ * mask_channels 0.  That is F.conv2d(x, k, padding = K / 2, stride = s, groups = C) times m; DESIGN.md section 6w.
+ *   afd_linop_apply:   y (B, C, h, w) = A x
+ *   afd_linop_adjoint: g (B, C, H, W) = A^T r, the transposed strided correlation of m . r -- the exact adjoint
+ *   afd_dps_residual:  the step side of DPS in one launch, per plane from LDS.  With a = alpha_hat[t_rows[row]] widened to fp64,
+ *       (a_t, b_t) = (1 / sqrt(a), -sqrt(1 - a) / sqrt(a))   AFD_PRED_EPS
+ *                    (sqrt(a),     -sqrt(1 - a))             AFD_PRED_V
+ *                    (0,           1)                        AFD_PRED_X0        each rounded once to fp32,
+ *     x0_hat = (a_t x_t) + (b_t out),   r = A x0_hat - y,   sums[row][c] = sum r^2 of the plane in fp64,   g = A^T r.
+ *     x0_hat and r stay in LDS.  t_rows: B int64 timesteps on the device (read unchecked), the tensor the model received.
+ *   afd_dps_correct:   x[row] -= c_row ((a_t g) + (b_t v)),  c_row = (float)(zeta / sqrt(sum_c sums[row][c])), the sum in fp64 for
+ *     c = 0 .. C - 1; a row whose sum is 0 (and every row when zeta == 0) is not touched.  With v the network's vector-Jacobian
+ *     product of g, a_t g + b_t v = |r| grad_{x_t} |y - A x0_hat|: DPS's step zeta / |r| (Chung et al. 2023), decided on the device.
+ * Tap sums run a outer, b inner, ascending, one fmaf per tap from a zero accumulator; a plane's sum of squares adds a thread's
+ * elements in index order, then a shuffle tree over the lanes, then the four waves in order.  One launch each on `stream`, one
+ * workgroup per plane (afd_dps_correct: elementwise); no atomics, no workspace, no synchronisation: the same bits from call to call.
+ * AFD_EINVAL (nothing launched) on a NULL pointer (but `mask`, and `kernel` with K == 1), B or C <= 0, B C >= 2^31, K even or outside
+ * [1, 15], a stride other than 1, 2, 4 or not dividing H and W, H or W outside [1, 64], mask_channels not 1 or C with a mask or
+ * not 0 without, an unknown prediction, a zeta that is negative or not finite, sums not 8-byte aligned, or an output overlapping
+ * an input. */
+int afd_linop_apply(const float* x, float* y, const float* kernel /* HOST float[K*K] */, int K, int stride, const float* mask_or_null,
+                    int mask_channels, long B, int C, int H, int W, afd_stream_t stream);
+int afd_linop_adjoint(const float* r, float* g, const float* kernel /* HOST float[K*K] */, int K, int stride, const float* mask_or_null,
+                      int mask_channels, long B, int C, int H, int W, afd_stream_t stream);
+int afd_dps_residual(const float* x_t, const float* out, const int64_t* t_rows, const float* alpha_hat, int prediction, const float* y,
+                     const float* kernel /* HOST float[K*K] */, int K, int stride, const float* mask_or_null, int mask_channels,
+                     float* g, double* sums, long B, int C, int H, int W, afd_stream_t stream);
+int afd_dps_correct(float* x, const float* g, const float* v, const double* sums, const int64_t* t_rows, const float* alpha_hat,
+                    int prediction, double zeta, long B, int C, long HW, afd_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
