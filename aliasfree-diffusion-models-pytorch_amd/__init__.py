@@ -17,6 +17,7 @@ from .fidelity import (FeatureStats, extract_features, feature_stats, fidelity, 
 from .manifold import ball_membership, manifold, manifold_scores, neighbour_radii  # noqa: F401
 from .quality import gaussian_window, image_quality, pair_sums, psnr, ssim  # noqa: F401
 from .posterior import LinearOperator, gaussian_kernel  # noqa: F401
+from .likelihood import ode_likelihood_reference  # noqa: F401
 from .unet import UNet  # noqa: F401
 from .diffusion import Diffusion  # noqa: F401
 from .training import (argument, set_seed, setup_logging, train, TrainStep, FusedAdamW, FlatParams,  # noqa: F401
@@ -24,8 +25,8 @@ from .training import (argument, set_seed, setup_logging, train, TrainStep, Fuse
                        LossSecondMomentSampler)
 
 from .tasks import (bpd_results, ddpm_run, edit_results, equivariance_results, fidelity_results, ilvr_results,  # noqa: F401
-                    inpaint_results, manifold_results, posterior_results, reconstruct_results, restoration_results, rotation_results,
-                    shift_results, spectrum_results)
+                    inpaint_results, likelihood_results, manifold_results, posterior_results, reconstruct_results, restoration_results,
+                    rotation_results, shift_results, spectrum_results)
 from .data import (get_data, get_data_MNIST, save_gen_images, make_collage, DeviceDataset, DeviceLoader,  # noqa: F401
                    get_data_device, get_data_MNIST_device)
 

@@ -2389,3 +2389,43 @@ def dps_correct(x, g, v, sums, t, alpha_hat, kind, zeta):
     C = int(x.shape[1])
     lib().afd_dps_correct(_p(x), _p(g), _p(v), _p(sums), _p(t), _p(alpha_hat), code, zeta, B, C, chw // C, _stream())
     return x
+
+
+# ---- likelihoods from the probability-flow ODE: the trace reduction and Heun's corrector (afd.h) ----
+def ode_trace_rows(v, w, cvv, cvw, acc):
+    """acc[r] += cvv * sum_j v[r, j]^2 + cvw * sum_j v[r, j] w[r, j] in fp64, one launch, the same bits from call to call (afd.h:
+    afd_ode_trace_rows gives the order).  v, w: contiguous fp32 (rows, ...) device tensors of one shape, w None when cvw == 0;
+    acc: a contiguous fp64 (rows,) tensor on the same device, updated in place.  -> acc."""
+    what = "ode_trace_rows"
+    _chk(v, w)
+    if not isinstance(v, torch.Tensor) or v.dim() < 1 or v.numel() == 0 or not v.is_contiguous():
+        raise AfdError(f"afdm: {what}: v must be a non-empty contiguous (rows, ...) tensor")
+    if w is not None and (tuple(w.shape) != tuple(v.shape) or not w.is_contiguous() or w.device != v.device):
+        raise AfdError(f"afdm: {what}: w must be None or a contiguous tensor of v's shape {tuple(v.shape)} on v's device")
+    rows = int(v.shape[0])
+    if not isinstance(acc, torch.Tensor) or acc.dtype != torch.float64 or acc.device != v.device or tuple(acc.shape) != (rows,) \
+            or not acc.is_contiguous():
+        raise AfdError(f"afdm: {what}: acc must be a contiguous ({rows},) fp64 tensor on v's device")
+    cvv, cvw = float(cvv), float(cvw)
+    if not (np.isfinite(cvv) and np.isfinite(cvw)):
+        raise AfdError(f"afdm: {what}: cvv and cvw must be finite (got {cvv}, {cvw})")
+    if w is None and cvw != 0.0:
+        raise AfdError(f"afdm: {what}: w may be None only when cvw == 0 (got {cvw})")
+    lib().afd_ode_trace_rows(_p(v), _p(w), cvv, cvw, _p(acc), rows, v.numel() // rows, _stream())
+    return acc
+
+
+def ode_heun_step(x, eps_s, eps_u, alpha_hat, s, u, out=None):
+    """The corrector of Heun's rule for the move s -> u, 1 <= s < u, of the probability-flow ODE (afd.h: afd_ode_heun_step gives the
+    exact expression): x_u = sqrt(a_u) (x / sqrt(a_s) + h (eps_s + eps_u) / 2).  `out` defaults to a new tensor and may be x (in
+    place); it must not overlap eps_s or eps_u."""
+    what = "ODE Heun step"
+    out = torch.empty_like(x) if out is None else out
+    n = _step_args(what, x, eps_s, eps_u, alpha_hat, out)
+    s, u = int(s), int(u)
+    if not 1 <= s < u < alpha_hat.numel():
+        raise AfdError(f"afdm: {what} needs 1 <= s < u < {alpha_hat.numel()} (got s = {s}, u = {u})")
+    if len({t.device for t in (x, eps_s, eps_u, alpha_hat, out)}) != 1:
+        raise AfdError(f"afdm: {what}: every tensor must be on one device")
+    lib().afd_ode_heun_step(_p(x), _p(eps_s), _p(eps_u), _p(alpha_hat), s, u, _p(out), n, _stream())
+    return out

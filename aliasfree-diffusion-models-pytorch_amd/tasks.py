@@ -737,6 +737,35 @@ def reconstruct_results(model_data, images, n, steps=50, refine=0, **kw):
             "latent_std": latents.flatten(1).double().std(dim=1, unbiased=False).tolist()}
 
 
+def likelihood_results(model_data, images, n=4, steps=100, **kw):
+    """Load the checkpoint as rotation_results does and score the first n of `images` (a DeviceDataset, or (N, C, H, W) uint8 pixels,
+    as restoration_results takes them) in bits per dimension two ways: the model's own log-density from the probability-flow ODE
+    (`Diffusion.ode_likelihood(steps)`; **kw: method, probes, probe, labels, dequantize, noise_source) and, beside it, `calc_bpd`'s
+    variational bound of the same images (labels and noise_source are passed on).  The seed is set before each.  Returns {"n",
+    "steps", "method", "probes", "probe", "bpd": {"mean", "std" (population), "values": one per image}, "logp", "trace_sem" (the
+    same three of the log-density in nats and of the trace's standard error), "bound_bpd": calc_bpd's, the same three}."""
+    n = _int_in(n, 1, len(images), f"likelihood_results: n must be an int in [1, {len(images)}] (the number of images; got {n!r})")
+    if isinstance(images, DeviceDataset):
+        originals = images.pixels(n)
+    else:
+        originals = torch.from_numpy(images) if isinstance(images, np.ndarray) else images
+        if not isinstance(originals, torch.Tensor) or originals.dtype != torch.uint8 or originals.dim() != 4:
+            raise ValueError("likelihood_results: images must be a DeviceDataset or (N, C, H, W) uint8 pixels")
+        originals = originals[:n]
+    model, diffusion, args = _load(model_data)
+    originals = originals.to(args.device).contiguous()
+    C = originals.shape[1]
+    x0 = normalisation_table(C).to(args.device)[torch.arange(C, device=args.device).view(1, C, 1, 1), originals.long()]      # as the loader maps pixels
+    set_seed(model_data["seed"])
+    ode = diffusion.ode_likelihood(model, x0, steps=steps, **kw)
+    set_seed(model_data["seed"])
+    bound = diffusion.calc_bpd(model, originals, **{k: kw[k] for k in ("labels", "noise_source") if k in kw})
+    return {"n": n, "steps": int(steps) if isinstance(steps, (int, np.integer)) else [int(t) for t in steps],
+            "method": kw.get("method", "heun"), "probes": int(kw.get("probes", 1)), "probe": kw.get("probe", "rademacher"),
+            "bpd": _spread(ode["bpd"]), "logp": _spread(ode["logp"]), "trace_sem": _spread(ode["trace_sem"]),
+            "bound_bpd": _spread(bound["bpd"])}
+
+
 def posterior_results(model_data, images, operator, sigma=0.05, zeta=1.0, n=4, steps=100, eta=1.0, **kw):
     """Load the checkpoint as rotation_results does, measure the first n of `images` (a DeviceDataset, or (N, C, H, W) uint8 pixels,
     as restoration_results takes them) with `operator.measure(x0, sigma)` (a posterior.LinearOperator; the seed is set first) and

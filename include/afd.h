@@ -1034,6 +1034,33 @@ int afd_dps_residual(const float* x_t, const float* out, const int64_t* t_rows, 
 int afd_dps_correct(float* x, const float* g, const float* v, const double* sums, const int64_t* t_rows, const float* alpha_hat,
                     int prediction, double zeta, long B, int C, long HW, afd_stream_t stream);
 
+/* ---- likelihoods from the probability-flow ODE (csrc/likelihood.hip) ------------------------------ Diffusion.ode_likelihood
+ * afd_ode_trace_rows: for every row r of the contiguous fp32 (rows, per) arrays v and w, in fp64,
+ *     acc[r] = acc[r] + ((cvv * sum_j v[r][j]^2) + (cvw * sum_j v[r][j] w[r][j]))          (w NULL: acc[r] + (cvv * sum_j v[r][j]^2))
+ *   acc: `rows` doubles on the device, read and written.  With v a probe and w = J_out^T v this adds one evaluation of the
+ *   Hutchinson estimate weight * (c1 |v|^2 + c2 v.w) of the divergence (cvv = weight c1, cvw = weight c2, folded on the host in
+ *   fp64); with v = x_U, w = NULL and cvv = -0.5 it adds the prior's -|x_U|^2 / 2.  w may be NULL only when cvw == 0.
+ *   One 256-thread workgroup per row.  Each fp32 value is widened and the products are formed in fp64 (exact); element j belongs
+ *   to thread (j / 4) % 256, a thread adds its elements in ascending j, a shuffle tree adds the 64 lanes, the four waves are added
+ *   in order, and one thread does the read-modify-write of acc[r].  16-byte loads when per % 4 == 0 and v, w are 16-byte aligned,
+ *   scalar loads otherwise, the same sums either way.  No atomics, no workspace: the same bits from call to call.
+ *   AFD_EINVAL (nothing launched) on NULL v or acc, NULL w with cvw != 0, rows <= 0, per <= 0, rows >= 2^31 or rows * per > 2^40, a
+ *   coefficient that is not finite, v / w not 4-byte or acc not 8-byte aligned, or acc overlapping v or w.
+ * afd_ode_heun_step: the corrector of Heun's rule for the move s -> u of the ODE dy / dsig = eps, y = x / sqrt(a), sig =
+ *   sqrt((1 - a) / a), a_s = alpha_hat[s], a_u = alpha_hat[u].  h = (float)(sqrt((1 - a_u) / a_u) - sqrt((1 - a_s) / a_s)) with the
+ *   fp32 table values widened and the whole expression in fp64, rounded once.  Then fp32 with one IEEE rounding per operation (no FMA
+ *   contraction, correctly rounded / and sqrt), evaluated in exactly this order:
+ *     y   = x / sqrt(a_s)
+ *     d   = (0.5 * h) * (eps_s + eps_u)                 (0.5 * h is exact)
+ *     out = sqrt(a_u) * (y + d)
+ *   eps_s: eps at (x_s, s); eps_u: eps at (the Euler predictor afd_ddim_invert_step(x_s, eps_s, s, u), u).  Requires 1 <= s < u (u is
+ *   not checked against the table's length: level 0 is left by an Euler move, the network is never evaluated there) and n > 0,
+ *   the elements of x.  x_out may be x itself (otherwise apart from it) and must not overlap eps_s or eps_u. */
+int afd_ode_trace_rows(const float* v, const float* w_or_null, double cvv, double cvw, double* acc, long rows, long per,
+                       afd_stream_t stream);
+int afd_ode_heun_step(const float* x, const float* eps_s, const float* eps_u, const float* alpha_hat, int s, int u, float* x_out, long n,
+                      afd_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
