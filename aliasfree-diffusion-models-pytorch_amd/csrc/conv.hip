@@ -808,7 +808,7 @@ bool pw_launch(const float* in, const float* w, const float* bias, const float* 
 void pw_set_mode(int m);
 // wino.hip: Winograd F(2x2,3x3) forward / dgrad
 int wino_plan(int B, int K, int N, int H, int W);
-bool wino_conv(const float* x, const float* w, const float* bias, const float* res, float* y, float* U, int B, int K, int N, int H,
+int wino_conv(const float* x, const float* w, const float* bias, const float* res, float* y, float* U, int B, int K, int N, int H,
                int W, int act, bool dgrad, bool weights_ready, hipStream_t s);
 void wino_set_mode(int m);
 void wino_weights_launch(const float* w, float* Uf, float* Ud, int Cin, int Cout, int kinds, hipStream_t s);
@@ -818,6 +818,7 @@ void direct_form_set(int m);
 bool direct_form_is_bf3();
 void h2_sk_set_mode(int m);
 void h2_lds_set(int m);
+void h2_skw_set(int m);
 void wino_weights_batched_launch(const afd_wino_desc* descs, const int* wg_desc, int n_wg, hipStream_t s);
 void wino_set_grid(int g);
 int wgrad_wino_plan(int B, int Cin, int Cout, int H, int W, int* bn, int* bk, int* cps, int* nchunks);
@@ -956,6 +957,8 @@ int afd_debug_conv_path(int mode) {
   if (mode >= 48 && mode <= 49) { wgrad_plan_target_set(mode == 48 ? 256 : 160); return AFD_OK; }   // 3x3 matrix-core weight gradient, workgroups per launch: 48 = one per CU (fastest alone; default), 49 = 160 (fastest beside the dependent chain of a train step: TrainStep asks for it)
   if (mode >= 59 && mode <= 63) { h2_lds_set(mode == 59 ? 4 : (mode == 60 ? 1 : (mode == 61 ? 0 : mode - 60))); return AFD_OK; }   // f16x2 tile kernel: 60 = both operands from LDS, weights by LDS-DMA (default), 61 = the register-fed kernel (before round 3's last third), 62 / 63 / 59 = LDS-fed wherever covered, the (128 px, 64 ch) / (256 px, 32 ch) / (128 px, 32 ch) workgroup first (tests)
   if (mode == 73) { h2_sk_set_mode(2); return AFD_OK; }                          // ... 73 = wherever the shape is covered (tests)
+  if (mode >= 71 && mode <= 72) { h2_skw_set(mode - 70); return AFD_OK; }          // slice-walking form of the split-K kernel (conv_h2_skw, 4x4 maps): 71 = wherever the split-K kernel runs and two or more slices per wave are possible (tests), 72 = never (conv_h2_sk everywhere); 74 returns it to the rule
+  if (mode == 74) h2_skw_set(0);
   if (mode >= 74 && mode <= 75) { h2_sk_set_mode(mode - 74); return AFD_OK; }    // f16x2 split-K kernel for the 4x4 / thin 8x8 maps: 74 = by rule (default), 75 = off (round 1's fp32 Winograd split-K kernel)
   if (mode >= 78 && mode <= 79) { wgrad_arith_set(mode - 78); return AFD_OK; }   // arithmetic of the matrix-core 3x3 weight gradient: 78 = f16x2 (default), 79 = bf16x3 (round 2)
   if (mode >= 76 && mode <= 77) { direct_form_set(mode - 76); return AFD_OK; }   // arithmetic of the direct 3x3 forward / dgrad: 76 = f16x2 (default), 77 = bf16x3 (round 2)
@@ -1050,7 +1053,9 @@ int afd_conv3x3_wino_fwd(const float* x, const float* w, const float* bias, cons
   AFD_REQUIRE(x && w && y && workspace && B > 0 && Cin > 0 && Cout > 0 && H > 0 && W > 0, "afd_conv3x3_wino_fwd: bad argument");
   AFD_REQUIRE(act == 0 || act == 1, "afd_conv3x3_wino_fwd: act must be 0 or 1");
   if (weights_ready && check_kinds("afd_conv3x3_wino_fwd", kinds, B, Cin, Cout, H, W, 0) != AFD_OK) return AFD_EINVAL;
-  AFD_REQUIRE(wino_conv(x, w, bias, res, y, static_cast<float*>(workspace), B, Cin, Cout, H, W, act, false, weights_ready != 0, as_stream(st)),
+  const int rc = wino_conv(x, w, bias, res, y, static_cast<float*>(workspace), B, Cin, Cout, H, W, act, false, weights_ready != 0, as_stream(st));
+  if (rc > 0) return rc;                                                  // (a launcher's own code: AFD_ELAUNCH from a failed LDS opt-in)
+  AFD_REQUIRE(rc == 0,
               "afd_conv3x3_wino_fwd: shape (%d,%d->%d,%dx%d) is not covered (afd_conv3x3_wino_workspace_bytes returns 0 for it)", B, Cin, Cout, H, W);
   return check_launch("afd_conv3x3_wino_fwd");
 }
@@ -1059,7 +1064,9 @@ int afd_conv3x3_wino_dgrad(const float* dy, const float* w, float* dx, const flo
                            void* workspace, int weights_ready, int kinds, afd_stream_t st) {
   AFD_REQUIRE(dy && w && dx && workspace && B > 0 && Cin > 0 && Cout > 0 && H > 0 && W > 0, "afd_conv3x3_wino_dgrad: bad argument");
   if (weights_ready && check_kinds("afd_conv3x3_wino_dgrad", kinds, B, Cin, Cout, H, W, 1) != AFD_OK) return AFD_EINVAL;
-  AFD_REQUIRE(wino_conv(dy, w, nullptr, add_to_dx, dx, static_cast<float*>(workspace), B, Cout, Cin, H, W, 0, true, weights_ready != 0, as_stream(st)),
+  const int rc = wino_conv(dy, w, nullptr, add_to_dx, dx, static_cast<float*>(workspace), B, Cout, Cin, H, W, 0, true, weights_ready != 0, as_stream(st));
+  if (rc > 0) return rc;
+  AFD_REQUIRE(rc == 0,
               "afd_conv3x3_wino_dgrad: shape (%d,%d->%d,%dx%d) is not covered", B, Cin, Cout, H, W);
   return check_launch("afd_conv3x3_wino_dgrad");
 }

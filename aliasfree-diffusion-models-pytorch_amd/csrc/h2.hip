@@ -718,6 +718,213 @@ __global__ __launch_bounds__(256, 2) void conv_h2_sk(const float* __restrict__ x
   }
 }
 
+// ---- the slice-walking form of the split-K kernel (4 x 4 maps) ---------------------------------------------------------------
+// conv_h2_sk above fetches a chunk's 36 weight fragments from L2 for ONE 32-pixel slice: at 256 -> 256 @ 4 x 4, B = 256 the 1024
+// workgroups read the 4.7 MB weight image 128 times (302 MB through L2 for a 6 us layer of matrix work).  Here a wave is still one
+// K-slice of one block of 32 output channels, but it walks SW consecutive slices (1, 2 or 4): a tap's four fragments are fetched
+// once and multiplied into all SW slices, whose images of the chunk sit side by side in the wave's own LDS area (10 KB each).
+// Per slice nothing changes -- its own running scale, its own accumulators, the same three multiplies per (tap, block) in the
+// same order, the KSP partial sums unscaled and added in wave order -- so every output element is the sum conv_h2_sk forms, bit
+// for bit (tests/test_gpu_h2_skw.py).  The order of the requests hides the latencies:
+//   * A fragments: three taps in registers; when a tap is done with all SW slices its registers take the tap three further on
+//     (the next filter row's, in the last row the next chunk's), 4 SW units of six multiplies ahead of its use;
+//   * the next chunk's x of all SW slices is requested behind the first of those and has taps 1 .. 3 to land in;
+//   * B fragments are read from LDS two (tap, slice, block) units ahead of their multiplies, the order pinned by sched_barrier.
+// Staging: a lane owns (image, row, 8-channel group, half) of a slice and loads four channels x one row of four pixels as four
+// dwordx4 -- 4 loads per slice and chunk where the dword plan above has 40 -- and each pixel's four channels are half a record
+// (ds_write_b64).  Halo and padding records are zeroed once, behind the first requests.  At the end the wave's LDS area takes
+// its partial sums (16-byte units), and ALL four waves share the epilogue (conv_h2_sk leaves it to the waves of K-slice 0).
+// Measured per layer at B = 256 (tools/h2sk_bench.py): two workgroups per CU beat one with twice the
+// reuse, and the SW = 1 form beats conv_h2_sk too -- the staging and the shared epilogue are a good part of the gain.
+// Registers (gfx950, no scratch): SW = 1 / 2 / 4 = 163 / 210 / 246 VGPRs + 0 / 0 / 80 AGPRs; LDS 40 / 80 / 160 KB.
+using h4 = __attribute__((ext_vector_type(4))) _Float16;
+
+template <int KSP, int SW>
+__global__ __launch_bounds__(256, SW == 4 ? 1 : 2) void conv_h2_skw(const float* __restrict__ x, const h8* __restrict__ Wp,
+                                                      const float* __restrict__ bias, const float* __restrict__ res,
+                                                      float* __restrict__ y, int B, int K, int N, int act, int nslices) {
+  using G = SkGeo<4>;
+  constexpr int S = 4, PSP = 4 / KSP, NPP = G::NPP, HW = S * S;
+  constexpr int IMGREC = 2 * G::KG * NPP;                             // records of one slice image [piece 2][kg 4][NPP]
+  constexpr int UT = 2 * SW, U = 9 * UT;                              // (slice, pixel block) units per tap / per chunk
+  extern __shared__ __attribute__((aligned(16))) uint8_t smem_raw[];
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, kgl = lane >> 4, l15 = lane & 15;
+  const int kw = wv % KSP, pw = wv / KSP;
+  h8* Xw = reinterpret_cast<h8*>(smem_raw) + (size_t)wv * SW * IMGREC;           // this wave's SW slice images
+  const int sl0 = (blockIdx.x * PSP + pw) * SW, n0 = blockIdx.y * 32;  // slices sl0 .. sl0 + SW - 1 = images 2 sl0 .. 2 (sl0 + SW) - 1
+
+  // ---- staging plan: lane = (image si of the slice, 8-channel group skg, half sh, row sr)
+  const int sr = lane & 3, sh = (lane >> 2) & 1, skg = (lane >> 3) & 3, si = lane >> 5;
+  const int s_src = ((si * K + 8 * skg + 4 * sh) * S + sr) * S;       // element offset of (channel 8 skg + 4 sh, row sr) from the slice's first image
+  const int s_dst = skg * NPP + si * G::IMG + (sr + 1) * G::Wp + 1;   // record of (row sr, column 0)
+  f32x4 xr[SW][4];
+  auto fetch = [&](int k0) {
+#pragma unroll
+    for (int j = 0; j < SW; ++j) {
+      const int b0 = 2 * (sl0 + j);
+      const float* p = x + ((long)b0 * K + k0) * HW + s_src;
+#pragma unroll
+      for (int c4 = 0; c4 < 4; ++c4)
+        xr[j][c4] = b0 + si < B ? *reinterpret_cast<const f32x4*>(p + c4 * HW) : f32x4{0.f, 0.f, 0.f, 0.f};
+    }
+  };
+
+  int bbase[2];
+#pragma unroll
+  for (int ps = 0; ps < 2; ++ps) {
+    const int q = ps * 16 + l15;
+    const int i = q / (G::R * S), rem = q - i * (G::R * S), r = rem / S, c = rem - r * S;
+    bbase[ps] = kgl * NPP + i * G::IMG + r * G::Wp + c;
+  }
+  f32x4 acc[SW][2][2];
+  float sx[SW];
+#pragma unroll
+  for (int j = 0; j < SW; ++j) {
+    sx[j] = __uint_as_float(kH2ScaleCapBits);
+#pragma unroll
+    for (int ns = 0; ns < 2; ++ns)
+#pragma unroll
+      for (int ps = 0; ps < 2; ++ps) acc[j][ns][ps] = f32x4{0.f, 0.f, 0.f, 0.f};
+  }
+
+  const int KS = K >> 5;
+  const long pstride = (long)9 * (K >> 3) * N;
+  const h8* wl = Wp + (long)kgl * N + n0 + l15;
+  // A fragments: three taps in registers.  A tap's four fragments serve all SW slices, then its registers take the tap three
+  // further on (the next filter row's, or the next chunk's): requested two taps = 4 SW units ahead of their use
+  h8 ac[3][2][2];
+  auto a_tap = [&](h8 (&a)[2][2], int ks, int tap) {
+    const long r = ((long)tap * (K >> 3) + 4 * ks) * N;
+#pragma unroll
+    for (int ns = 0; ns < 2; ++ns) { a[ns][0] = wl[r + 16 * ns]; a[ns][1] = wl[pstride + r + 16 * ns]; }
+  };
+  auto b_read = [&](h8 (&b)[2], int u) {                              // unit u of a chunk = (tap, slice, pixel block)
+    const int tap = u / UT, j = (u % UT) / 2, ps = u & 1;
+    const int o = j * IMGREC + bbase[ps] + (tap / 3) * G::Wp + (tap % 3);
+    b[0] = Xw[o]; b[1] = Xw[G::KG * NPP + o];
+  };
+  if (kw < KS) {
+    fetch(32 * kw);
+#pragma unroll
+    for (int t = 0; t < 3; ++t) a_tap(ac[t], kw, t);
+  }
+  __builtin_amdgcn_sched_barrier(0);                                  // (the first requests are in flight while the images are zeroed)
+#pragma unroll
+  for (int r = 0; r < SW * IMGREC / 64; ++r) Xw[r * 64 + lane] = h8{0, 0, 0, 0, 0, 0, 0, 0};
+  asm volatile("" ::: "memory");
+  for (int ks = kw; ks < KS; ks += KSP) {
+    const bool more = ks + KSP < KS;
+    // ---- the chunk's SW slices: magnitude -> the slice's scale (this wave's alone), split, store
+#pragma unroll
+    for (int j = 0; j < SW; ++j) {
+      float m = 0.f;
+#pragma unroll
+      for (int c4 = 0; c4 < 4; ++c4)
+#pragma unroll
+        for (int e = 0; e < 4; ++e) m = fmaxf(m, fabsf(xr[j][c4][e]));
+      const float sn = fminf(sx[j], h2_scale_for(wave_amax(m)));
+      if (sn != sx[j]) {
+        const float f = sn * h2_inv_pow2(sx[j]);
+#pragma unroll
+        for (int ns = 0; ns < 2; ++ns)
+#pragma unroll
+          for (int ps = 0; ps < 2; ++ps) acc[j][ns][ps] *= f;
+        sx[j] = sn;
+      }
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {                                   // pixel (sr, e): channels 8 skg + 4 sh .. + 3 = half a record
+        h4 p0, p1;
+#pragma unroll
+        for (int c4 = 0; c4 < 4; ++c4) { _Float16 a, b; h2_split(xr[j][c4][e], sx[j], a, b); p0[c4] = a; p1[c4] = b; }
+        h4* d = reinterpret_cast<h4*>(Xw + j * IMGREC + s_dst + e) + sh;
+        d[0] = p0;
+        d[2 * G::KG * NPP] = p1;
+      }
+    }
+    asm volatile("" ::: "memory");
+    h8 bq[3][2];
+    b_read(bq[0], 0);
+    b_read(bq[1], 1);
+#pragma unroll
+    for (int ty = 0; ty < 3; ++ty) {
+#pragma unroll
+      for (int tx = 0; tx < 3; ++tx) {
+        const int tap = ty * 3 + tx;
+#pragma unroll
+        for (int j = 0; j < SW; ++j) {
+#pragma unroll
+          for (int ps = 0; ps < 2; ++ps) {
+            const int u = tap * UT + 2 * j + ps;
+            if (u + 2 < U) b_read(bq[(u + 2) % 3], u + 2);
+            __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+            for (int ns = 0; ns < 2; ++ns) {
+              acc[j][ns][ps] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ac[tx][ns][0], bq[u % 3][0], acc[j][ns][ps], 0, 0, 0);
+              acc[j][ns][ps] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ac[tx][ns][1], bq[u % 3][0], acc[j][ns][ps], 0, 0, 0);
+              acc[j][ns][ps] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ac[tx][ns][0], bq[u % 3][1], acc[j][ns][ps], 0, 0, 0);
+            }
+            __builtin_amdgcn_sched_barrier(0);
+          }
+        }
+        // the tap is done with its fragments
+        if (ty < 2) a_tap(ac[tx], ks, tap + 3);
+        else if (more) a_tap(ac[tx], ks + KSP, tx);
+        if (tap == 0 && more) fetch(32 * (ks + KSP));                 // behind row 1's first tap: taps 1 .. 3 to land in
+        __builtin_amdgcn_sched_barrier(0);
+      }
+    }
+    asm volatile("" ::: "memory");
+  }
+  // ---- the K-slices' partial sums: unscaled (each wave had its own scale per slice), added in wave order.  The wave's image area
+  // is free (it alone read it): [slice][4][64] x 4 floats
+  {
+    f32x4* redw = reinterpret_cast<f32x4*>(Xw);
+#pragma unroll
+    for (int j = 0; j < SW; ++j) {
+      const float isx = h2_inv_pow2(sx[j]);
+#pragma unroll
+      for (int ns = 0; ns < 2; ++ns)
+#pragma unroll
+        for (int ps = 0; ps < 2; ++ps)
+          redw[(j * 4 + ns * 2 + ps) * 64 + lane] = acc[j][ns][ps] * isx;
+    }
+  }
+  __syncthreads();
+  // every wave takes its share of the workgroup's PSP x SW x 4 (pixel group, slice, 16-pixel block, 16-channel half) items
+  const float* isw = reinterpret_cast<const float*>(reinterpret_cast<const uint8_t*>(Wp) + h2_scale_offset_bytes(K, N));
+  constexpr int RW = SW * IMGREC;                                     // 16-byte units between the areas of two waves
+  constexpr int IPW = PSP * SW;                                       // items per wave
+#pragma unroll
+  for (int t = 0; t < IPW; ++t) {
+    const int q = wv * IPW + t, ns = q & 1, ps = (q >> 1) & 1, j = (q >> 2) % SW, pq = (q >> 2) / SW;
+    const int sl = (blockIdx.x * PSP + pq) * SW + j;
+    if (sl >= nslices) continue;
+    const f32x4* red = reinterpret_cast<const f32x4*>(smem_raw) + (size_t)pq * KSP * RW;
+    const int px = ps * 16 + l15;
+    const int i = px / (G::R * S), rem = px - i * (G::R * S), r = rem / S, c = rem - r * S;
+    const int b = 2 * sl + i;
+    if (b >= B) continue;
+    {
+      const int nn = n0 + 16 * ns + 4 * kgl;
+      const long o = ((long)b * N + nn) * HW + r * S + c;
+      f32x4 pr[KSP];
+#pragma unroll
+      for (int g = 0; g < KSP; ++g) pr[g] = red[g * RW + (j * 4 + ns * 2 + ps) * 64 + lane];
+#pragma unroll
+      for (int rg = 0; rg < 4; ++rg) {
+        float v = 0.f;
+#pragma unroll
+        for (int g = 0; g < KSP; ++g) v += pr[g][rg];
+        v *= isw[nn + rg];
+        if (bias) v += bias[nn + rg];
+        if (act == 1) v = gelu_erf(v);
+        if (res) v += res[o + (long)rg * HW];
+        y[o + (long)rg * HW] = v;
+      }
+    }
+  }
+}
+
 // ---- host side -------------------------------------------------------------------------------------------------------------
 // channel blocks per workgroup: as bf3.hip (as many as divide N while the launch keeps two workgroups per CU)
 static int h2_nblk(long tiles, int N, int S) {
@@ -750,6 +957,34 @@ static void h2_sk_launch_t(const float* x, const void* Wp, const float* bias, co
   const int nslices = (int)(((long)B * S * S + 31) / 32), psp = 4 / KSP;
   hipLaunchKernelGGL((conv_h2_sk<S, KSP>), dim3((unsigned)((nslices + psp - 1) / psp), (unsigned)(N / 32)), dim3(256), lds, s, x,
                      static_cast<const h8*>(Wp), bias, res, y, B, K, N, act, nslices);
+}
+// the slice-walking form: SW slices per wave, > 64 KB of dynamic LDS (SW x 10 KB per wave)
+template <int KSP, int SW>
+static int h2_skw_launch_t(const float* x, const void* Wp, const float* bias, const float* res, float* y, int B, int K, int N, int act,
+                           hipStream_t s) {
+  using G = SkGeo<4>;
+  const size_t lds = (size_t)4 * SW * 2 * G::KG * G::NPP * 16;
+  if (int rc = lds_opt_in(conv_h2_skw<KSP, SW>, lds)) return rc;
+  const int nslices = (int)(((long)B * 16 + 31) / 32), per = (4 / KSP) * SW;
+  hipLaunchKernelGGL((conv_h2_skw<KSP, SW>), dim3((unsigned)((nslices + per - 1) / per), (unsigned)(N / 32)), dim3(256), lds, s, x,
+                     static_cast<const h8*>(Wp), bias, res, y, B, K, N, act, nslices);
+  return AFD_OK;
+}
+// slices per wave of a split-K launch; 0 = conv_h2_sk.  By rule, on the shapes where the per-layer A/B (tools/h2sk_bench.py,
+// B = 256) showed conv_h2_skw faster -- the 4 x 4 maps with K >= 128 -- the largest of {4, 2, 1} that keeps TWO workgroups per CU:
+// measured, the second workgroup's multiplies behind this one's staging and epilogue are worth more than half the weight
+// fetches again (256 -> 256: SW = 1 / 2 / 4 = 18.6 / 15.1 / 18.5 us against conv_h2_sk's 23.0; 128 -> 128: 7.0 / 7.8 / 11.9
+// against 9.3)
+static int g_h2_skw = 0;                                              // afd_debug_conv_path 71 / 72: wherever SW >= 2 is possible (tests) / never; 74 = by rule (default)
+void h2_skw_set(int m) { g_h2_skw = m; }
+static int h2_skw_width(const float* x, int B, int K, int N, int S) {
+  if (S != 4 || g_h2_skw == 2 || !aligned16(x)) return 0;             // (the staging loads are dwordx4)
+  const long nslices = ((long)B * 16 + 31) / 32, psp = K >= 128 ? 1 : 2;
+  if (g_h2_skw == 1) return nslices > 2 * psp ? 4 : 2;
+  if (K < 128) return 0;
+  for (int sw = 4; sw >= 1; sw >>= 1)
+    if (((nslices + sw - 1) / sw) * (N / 32) >= 512) return sw;
+  return 0;
 }
 // does the split-K small-map kernel take the layer?  4 x 4 and 8 x 8 maps, 32-channel blocks, at least two chunks of K, and a
 // launch that the tile kernel above cannot fill (its rule: >= 512 workgroups) but this one can (>= 128)
@@ -788,22 +1023,26 @@ static int h2l_launch(const float* x, const void* Wp, const float* bias, const f
   return h2l_launch_t<S, 128, 1>(x, Wp, bias, res, y, B, K, N, act, s);
 }
 
-// x (B,K,S,S), Wp = the f16x2 weight image for (K -> N) -> y (B,N,S,S)
-void h2_conv(const float* x, const void* Wp, const float* bias, const float* res, float* y, int B, int K, int N, int S, int act,
-             hipStream_t s, bool small) {
+// x (B,K,S,S), Wp = the f16x2 weight image for (K -> N) -> y (B,N,S,S).  Returns AFD_OK or the code of a failed LDS opt-in
+// (nothing launched then)
+int h2_conv(const float* x, const void* Wp, const float* bias, const float* res, float* y, int B, int K, int N, int S, int act,
+            hipStream_t s, bool small) {
   if (small) {
+    const int sw = h2_skw_width(x, B, K, N, S);
+    if (sw == 4) return K >= 128 ? h2_skw_launch_t<4, 4>(x, Wp, bias, res, y, B, K, N, act, s) : h2_skw_launch_t<2, 4>(x, Wp, bias, res, y, B, K, N, act, s);
+    if (sw == 2) return K >= 128 ? h2_skw_launch_t<4, 2>(x, Wp, bias, res, y, B, K, N, act, s) : h2_skw_launch_t<2, 2>(x, Wp, bias, res, y, B, K, N, act, s);
+    if (sw == 1) return h2_skw_launch_t<4, 1>(x, Wp, bias, res, y, B, K, N, act, s);
     if (S == 4) { if (K >= 128) h2_sk_launch_t<4, 4>(x, Wp, bias, res, y, B, K, N, act, s); else h2_sk_launch_t<4, 2>(x, Wp, bias, res, y, B, K, N, act, s); }
     else { if (K >= 128) h2_sk_launch_t<8, 4>(x, Wp, bias, res, y, B, K, N, act, s); else h2_sk_launch_t<8, 2>(x, Wp, bias, res, y, B, K, N, act, s); }
-    return;
+    return AFD_OK;
   }
   // by rule (measured per layer shape at B = 256, tools/abl_conv_bench.py 61 62): the LDS-fed kernel wins where a workgroup has ONE block
   // of 32 output channels on the 32 x 32 maps (every wave of the register-fed kernel then re-reads the same weight fragments:
   // 27.6 -> 25.3 and 47.3 -> 41.7 us), the register-fed one elsewhere (64 -> 64 @ 32 x 32: 63.5 against 67.9; 128 -> 128 @ 16 x 16: 48 against 63)
   if (g_h2_lds > 1 || (g_h2_lds == 1 && S == 32 && N % 64 != 0)) {
-    if (S == 32) h2l_launch<32>(x, Wp, bias, res, y, B, K, N, act, s);
-    else if (S == 16) h2l_launch<16>(x, Wp, bias, res, y, B, K, N, act, s);
-    else h2l_launch<8>(x, Wp, bias, res, y, B, K, N, act, s);
-    return;
+    if (S == 32) return h2l_launch<32>(x, Wp, bias, res, y, B, K, N, act, s);
+    if (S == 16) return h2l_launch<16>(x, Wp, bias, res, y, B, K, N, act, s);
+    return h2l_launch<8>(x, Wp, bias, res, y, B, K, N, act, s);
   }
   const int nblk = h2_nblk(((long)B * S * S + 127) / 128, N, S);
 #define AFD_H2(S_)                                                                      \
@@ -812,6 +1051,7 @@ void h2_conv(const float* x, const void* Wp, const float* bias, const float* res
   else h2_launch_t<S_, 1>(x, Wp, bias, res, y, B, K, N, act, s)
   if (S == 32) { AFD_H2(32); } else if (S == 16) { AFD_H2(16); } else { AFD_H2(8); }
 #undef AFD_H2
+  return AFD_OK;
 }
 
 }  // namespace afd

@@ -572,12 +572,14 @@ void bf3_weights_launch(const float* w, void* Wf, void* Wd, int Cin, int Cout, h
 void bf3_conv(const float* x, const void* Wp, const float* bias, const float* res, float* y, int B, int K, int N, int S, int act,
               hipStream_t s);
 void h2_weights_launch(const float* w, void* Wf, void* Wd, int Cin, int Cout, hipStream_t s);
-void h2_conv(const float* x, const void* Wp, const float* bias, const float* res, float* y, int B, int K, int N, int S, int act,
-             hipStream_t s, bool small);
+int h2_conv(const float* x, const void* Wp, const float* bias, const float* res, float* y, int B, int K, int N, int S, int act,
+            hipStream_t s, bool small);
 int direct_plan(int B, int K, int N, int H, int W);
 
-// conv (dgrad = false: x (B,K,H,W), w (N,K,3,3)) or its input gradient (dgrad = true: x = dY (B,K=Cout,H,W), w (K,N,3,3))
-bool wino_conv(const float* x, const float* w, const float* bias, const float* res, float* y, float* U, int B, int K, int N, int H,
+// conv (dgrad = false: x (B,K,H,W), w (N,K,3,3)) or its input gradient (dgrad = true: x = dY (B,K=Cout,H,W), w (K,N,3,3)).
+// Returns -1 where the shape is not covered, else AFD_OK or the code of a launcher that could not launch (the f16x2 direct form's
+// LDS opt-in)
+int wino_conv(const float* x, const float* w, const float* bias, const float* res, float* y, float* U, int B, int K, int N, int H,
                int W, int act, bool dgrad, bool weights_ready, hipStream_t s) {
   const int Cin = dgrad ? N : K, Cout = dgrad ? K : N;
   if (U && bf3_ok(B, K, N, H, W)) {                 // the workspace then holds the direct form's weight image of this pass
@@ -586,18 +588,18 @@ bool wino_conv(const float* x, const float* w, const float* bias, const float* r
       bf3_conv(x, U, bias, res, y, B, K, N, W, act, s);
     } else {
       if (!weights_ready) h2_weights_launch(w, dgrad ? nullptr : U, dgrad ? U : nullptr, Cin, Cout, s);
-      h2_conv(x, U, bias, res, y, B, K, N, W, act, s, direct_plan(B, K, N, H, W) == 2);
+      return h2_conv(x, U, bias, res, y, B, K, N, W, act, s, direct_plan(B, K, N, H, W) == 2);
     }
-    return true;
+    return AFD_OK;
   }
   const int plan = wino_plan(B, K, N, H, W);
-  if (!plan || !U) return false;
+  if (!plan || !U) return -1;
   const int bn = plan >> 8, nt = plan & 255;
   if (plan == 1) {
     if (!weights_ready)
       hipLaunchKernelGGL(wino_weights, dim3((unsigned)((K * N / 64 + 3) / 4)), dim3(256), 0, s, w, dgrad ? nullptr : U, dgrad ? U : nullptr, Cin, Cout);
     if (W == 4) wino_sk_launch<4>(x, U, bias, res, y, B, K, N, act, s); else wino_sk_launch<8>(x, U, bias, res, y, B, K, N, act, s);
-    return true;
+    return AFD_OK;
   }
   if (!weights_ready)
     hipLaunchKernelGGL(wino_weights, dim3((unsigned)((K * N / 64 + 3) / 4)), dim3(256), 0, s, w, dgrad ? nullptr : U, dgrad ? U : nullptr, Cin, Cout);
@@ -608,7 +610,7 @@ bool wino_conv(const float* x, const float* w, const float* bias, const float* r
   else wino_launch_t<GEO_, 32, 32>(x, U, bias, res, y, B, K, N, act, s)
   if (W == 64) { AFD_WINO(64); } else if (W == 32) { AFD_WINO(32); } else if (W == 16) { AFD_WINO(16); } else if (W == 8) { AFD_WINO(8); } else { AFD_WINO(4); }
 #undef AFD_WINO
-  return true;
+  return AFD_OK;
 }
 
 

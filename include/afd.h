@@ -197,7 +197,13 @@ int afd_conv_wgrad_partials(const float* x, const float* dy, float* dw, float* d
  * same w and the same pass, so the transform launch is skipped (sampling: w is constant over the 999 steps).
  * afd_debug_conv_path: 64 / 65 = Winograd chosen by the measured rule (default) / never; 66..69 = whenever covered,
  * with workgroups of 64x64 / 32x64 / 64x32 / 32x32 (output channels x tiles); 70 = the small-map (4x4, 8x8)
- * in-workgroup split-K kernel wherever it is covered. */
+ * in-workgroup split-K kernel wherever it is covered.
+ * 74 / 75 / 73 = the f16x2 split-K kernel of the 4x4 and thin 8x8 maps (conv_h2_sk) by rule (default) / never / wherever the
+ * shape is covered.  71 / 72 = its slice-walking form on the 4x4 maps (conv_h2_skw: a wave keeps the weight fragments of a tap
+ * for 1, 2 or 4 consecutive 32-pixel slices; the same bits as conv_h2_sk): 71 = wherever the split-K kernel runs, with two or
+ * four slices per wave (tests, small shapes), 72 = never (conv_h2_sk everywhere: the A/B baseline); by default the measured rule
+ * chooses (K >= 128 and at least two workgroups per CU), and 74 returns 71 / 72 to it.  A failed opt-in to the form's dynamic LDS
+ * (up to 160 KB) makes afd_conv3x3_wino_fwd / _dgrad return AFD_ELAUNCH with nothing launched. */
 size_t afd_conv3x3_wino_workspace_bytes(int B, int Cin, int Cout, int H, int W, int dgrad);
 /* the transformed weights of both passes (either pointer may be NULL) in ONE launch: the dgrad image is the forward
  * image with permuted transform indices.  Buffers of 16*Cin*Cout floats each; afterwards call the entry points below
