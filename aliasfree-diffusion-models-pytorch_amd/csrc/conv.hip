@@ -1112,18 +1112,22 @@ static int conv_wgrad_impl(const float* x, const float* dy, float* dw, float* db
   const int T = ksize * ksize;
   const TileGeom g = make_geom(H, W, 64, ksize == 3 ? 1 : 0);
   int rc = AFD_OK;
+  // the f16x2 / bf16x3 forms (3x3 and 1x1) and the Winograd form stage x and dY with 16-byte loads: a pointer that is not
+  // 16-byte aligned (a contiguous view at an odd offset) takes the forms with scalar loads below.  dw and dbias may sit at
+  // any 4-byte offset in every form: the slabs go to the workspace, and every fold into dw / dbias is scalar (fold.hip).
+  const bool vec = aligned16(x) && aligned16(dy);
   if (ksize == 3 && !dbias && workspace) {                               // bf16x3 form on the matrix pipe, else Winograd F(3x3, 2x2): 16 multiplies per tile instead of 36
     float* part = static_cast<float*>(workspace);
-    int slabs = wgrad_arith_is_bf3() ? wgrad_bf3(x, dy, part, B, Cin, Cout, H, W, s) : wgrad_h2(x, dy, part, B, Cin, Cout, H, W, s);
+    int slabs = !vec ? 0 : (wgrad_arith_is_bf3() ? wgrad_bf3(x, dy, part, B, Cin, Cout, H, W, s) : wgrad_h2(x, dy, part, B, Cin, Cout, H, W, s));
     if (!slabs) slabs = wgrad_cin3(x, dy, part, B, Cin, Cout, H, W, s);
-    if (!slabs) slabs = wgrad_wino(x, dy, part, B, Cin, Cout, H, W, s);
+    if (!slabs && vec) slabs = wgrad_wino(x, dy, part, B, Cin, Cout, H, W, s);
     if (slabs) {
       const long n = (long)Cout * Cin * 9;
       rc = launch_wgrad_reduce(part, dw, n, slabs, nullptr, nullptr, 0, accumulate, 9, s, sink);
       return rc != AFD_OK ? rc : check_launch(who);
     }
   }
-  if (ksize == 1 && workspace) {                                         // bf16x3 form straight from global memory (HBM-bound)
+  if (ksize == 1 && workspace && vec) {                                  // bf16x3 form straight from global memory (HBM-bound)
     int a, b, c, d;
     const int slabs = pw_wgrad_bf3_plan(B, Cin, Cout, H * W, &a, &b, &c, &d);
     if (slabs) {

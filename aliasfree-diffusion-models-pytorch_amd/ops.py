@@ -196,6 +196,7 @@ class _GradMode:
     folds = []            # per side stream: [packed afd_fold_desc bytes, ...] of producers already launched there
     fold_writes = []      # params whose .grad is complete once the queued folds have been launched
     flushes = 0           # flushes since the last fold launch
+    lane_of = {}          # data pointer of a .grad -> index of the side stream that writes it (for the life of the scope)
     fold_every = 2        # launch the queued folds every this many flushes (and at the join, and when a bucket completes)
 
 
@@ -236,22 +237,67 @@ def defer_to_side_stream(fn, *keep, writes=()):
         flush_wgrads()
 
 
-def flush_wgrads(final=False):
-    """Launch the queued parameter-gradient kernels on the side stream (one fork for the whole batch), then the queued
-    folds if it is time: every `fold_every` flushes, at the join (final) and whenever they would complete a bucket."""
+FOLD_MAX = 56                # descriptors per afd_fold_batched launch (kFoldMax of csrc/fold.hip)
+
+
+def fold_batches(descs, limit=FOLD_MAX):
+    """Partition packed afd_fold_desc bytes into the batches that may each travel in ONE afd_fold_batched launch: the order
+    is kept, a batch holds at most `limit` descriptors, and no two descriptors of a batch have the same `dst`.  A fold
+    reads dst, adds and writes it back without atomics (fold_batched_k), so two folds into one gradient -- a parameter used
+    twice in one backward -- must be two launches on one stream.  A descriptor whose dst is already in the open batch closes
+    it and starts the next.  Without repeats this is what fold_launch does by itself: cuts of `limit`, one batch for <= limit."""
+    assert len(descs) % 56 == 0 and limit > 0
+    out, cur, seen = [], [], set()
+    for o in range(0, len(descs), 56):
+        d = descs[o:o + 56]
+        dst = d[8:16]
+        if dst in seen or len(cur) == limit:
+            out.append(b"".join(cur))
+            cur, seen = [], set()
+        cur.append(d)
+        seen.add(dst)
+    if cur:
+        out.append(b"".join(cur))
+    return out
+
+
+def deal_lane(keys, lane_of, turn, n_lanes):
+    """Side stream of one queued producer.  `keys`: the gradients it writes (data pointers); `lane_of`: pointer -> lane of
+    everything queued before it in this scope (updated here).  The first writer of a gradient takes the round-robin lane
+    `turn % n_lanes`; every later writer of the same gradient follows it, so all read-modify-writes of one .grad are on one
+    in-order stream, in queue order.  -> (lane, conflict): conflict = the gradients it writes already live on DIFFERENT
+    lanes (say a weight shared with one module and a bias shared with another); the caller must then order the lanes
+    against each other before it launches this producer."""
+    known = [lane_of[k] for k in keys if k in lane_of]
+    lane = known[0] if known else turn % n_lanes
+    conflict = any(l != lane for l in known)
+    for k in keys:
+        lane_of[k] = lane
+    return lane, conflict
+
+
+def _grad_keys(params):
+    return [q.grad.data_ptr() for q in params if q is not None and q.grad is not None]
+
+
+def _launch_folds():
+    """Launch every queued fold, per side stream, in as many launches as fold_batches asks for."""
     G = _GradMode
-    sides, q = G.sides, G.pending
-    if not q and not (final and any(G.folds)):
-        return
+    for k, side in enumerate(G.sides):
+        if G.folds[k]:
+            for batch in fold_batches(b"".join(G.folds[k])):
+                fold_now(batch, side.cuda_stream)
+            G.folds[k] = []
+    done = G.fold_writes
+    G.fold_writes, G.flushes = [], 0
+    return done
+
+
+def _launch_lanes(lanes, done):
+    """Launch dealt producers, lane by lane (one fork per side stream); queue or launch the folds they return."""
+    G = _GradMode
     cur = torch.cuda.current_stream()
-    lanes = [[] for _ in sides]
-    for item in q:
-        lanes[G.turn % len(sides)].append(item)
-        G.turn += 1
-    if len(G.folds) != len(sides):
-        G.folds = [[] for _ in sides]
-    done = []
-    for k, (side, items) in enumerate(zip(sides, lanes)):
+    for k, (side, items) in enumerate(zip(G.sides, lanes)):
         if not items:
             continue
         side.wait_stream(cur)                                                 # fork: every queued dY (and the zeroed .grad) exists
@@ -260,28 +306,68 @@ def flush_wgrads(final=False):
             for fn, keep, ws in items:
                 descs = fn(h) if fn is not None else keep[0]
                 if descs and G.fold_every == 0:                               # (A/B hook: one fold launch per producer, as in round 2)
-                    fold_now(descs, h)
+                    for batch in fold_batches(descs):
+                        fold_now(batch, h)
                     done.extend(ws)
                 elif descs:
                     G.folds[k].append(descs)
                     G.fold_writes.extend(ws)
                 else:
                     done.extend(ws)
+
+
+def flush_wgrads(final=False):
+    """Launch the queued parameter-gradient kernels on the side stream (one fork for the whole batch), then the queued
+    folds if it is time: every `fold_every` flushes, at the join (final) and whenever they would complete a bucket."""
+    G = _GradMode
+    sides, q = G.sides, G.pending
+    if not q and not (final and any(G.folds)):
+        return
+    if len(G.folds) != len(sides):
+        G.folds = [[] for _ in sides]
+    done = []
+    lanes = [[] for _ in sides]
+    for item in q:
+        lane, conflict = deal_lane(_grad_keys(item[2]), G.lane_of, G.turn, len(sides))
+        G.turn += 1
+        if conflict:
+            # its gradients were written on different lanes: finish what is dealt and folded so far, then order every
+            # side stream behind every other one -- whatever comes later, on any lane, follows all earlier writes
+            _launch_lanes(lanes, done)
+            done.extend(_launch_folds())
+            lanes = [[] for _ in sides]
+            for a in sides:
+                for b in sides:
+                    if a is not b:
+                        a.wait_stream(b)
+        lanes[lane].append(item)
+    _launch_lanes(lanes, done)
     G.launched.extend(q)
     G.pending = []
     G.flushes += 1
     if any(G.folds) and (final or G.flushes >= max(1, G.fold_every) or (G.fold_hint is not None and G.fold_hint(G.fold_writes + done))):
-        for k, side in enumerate(sides):
-            if G.folds[k]:
-                fold_now(b"".join(G.folds[k]), side.cuda_stream)
-                G.folds[k] = []
-        done.extend(G.fold_writes)
-        G.fold_writes, G.flushes = [], 0
+        done.extend(_launch_folds())
     if G.on_write is not None and done:
         _wrote(*done)
 
 
 class inplace_param_grads:
+    """Scope in which the parameter-gradient kernels ADD into the preallocated `.grad` tensors (see _GradMode), optionally
+    queued for one or more side streams and finished by batched folds.
+
+    A parameter used twice in one backward (tied weights, a module called twice) is safe: every queued producer and fold
+    that writes one `.grad` runs on the side stream its first writer was dealt to, in queue order (deal_lane), and two folds
+    into one `.grad` never share a launch (fold_batches).  A model without repeated parameters sees the same streams,
+    the same launch order and the same number of launches as before.  Not ordered against the queued work: a producer
+    that must run on the main stream because the same launch produces a gradient the chain consumes (SiluLinear with a
+    time embedding that needs a gradient, EmbedAdd) -- tie such a parameter only with other main-stream uses.
+
+    `on_write` / `fold_hint` (the data-parallel readiness hook) know nothing of repeated parameters: a tied parameter is
+    reported after EACH of its uses, so a bucket that holds it may be reported before its last contribution is enqueued.
+
+    A parameter without a preallocated contiguous fp32 `.grad`, or a plain tensor in a parameter's place, takes the
+    out-of-place path inside the scope: its gradient is returned to autograd."""
+
     def __init__(self, side_stream=None, batch=8, on_write=None, fold_hint=None, fold_every=None):
         self.side_stream, self.batch, self.on_write, self.fold_hint = side_stream, batch, on_write, fold_hint
         self.fold_every = int(os.environ.get("AFD_FOLD_EVERY", 2)) if fold_every is None else fold_every
@@ -293,7 +379,7 @@ class inplace_param_grads:
         self.streams = [] if ss is None else (list(ss) if isinstance(ss, (list, tuple)) else [ss])
         G.inplace, G.batch, G.on_write, G.fold_hint, G.fold_every = True, self.batch, self.on_write, self.fold_hint, max(0, self.fold_every)
         G.sides, G.side, G.turn = self.streams, (self.streams[0] if self.streams else None), 0
-        G.folds, G.fold_writes, G.flushes = [[] for _ in self.streams], [], 0
+        G.folds, G.fold_writes, G.flushes, G.lane_of = [[] for _ in self.streams], [], 0, {}
 
     def __exit__(self, exc_type, *a):
         G = _GradMode
@@ -304,6 +390,7 @@ class inplace_param_grads:
             for st in self.streams:
                 torch.cuda.current_stream().wait_stream(st)                  # join: every dW is in .grad
             G.launched = []                                                  # buffers may be freed now (main-stream order)
+        G.lane_of = {}
         G.inplace, G.side, G.sides, G.on_write, G.fold_hint, G.fold_every = self.prev
 
 
@@ -610,7 +697,8 @@ class Conv(_Fn):
             nbytes = L.afd_conv_wgrad_workspace_bytes(B, Cin, Cout, H, W, ks)
             ws = torch.empty(max(nbytes // 4, 1), device=x.device, dtype=torch.float32)
             wp, bp = ctx.w_param, ctx.b_param
-            if _direct(wp, bp) and wp.grad.numel() == w.numel():
+            # (a plain tensor as weight, or as the bias of a Parameter weight, has no .grad to add into: out of place)
+            if wp is not None and (bp is not None or not ctx.has_bias) and _direct(wp, bp) and wp.grad.numel() == w.numel():
                 side = _GradMode.side
                 if side is None:
                     L.afd_conv_wgrad(_p(x), _p(dy), _p(wp.grad), _p(bp.grad) if bp is not None else None,
@@ -993,7 +1081,7 @@ class EmbedAdd(_Fn):
 
 
 class SiluLinear(_Fn):
-    """emb_layer = nn.Sequential(nn.SiLU(), nn.Linear(emb_dim, C))   (ddpm_utils.py:208-214)."""
+    """emb_layer = nn.Sequential(nn.SiLU(), nn.Linear(emb_dim, C))   (ddpm_utils.py:208-214).  bias may be None."""
 
     @staticmethod
     def forward(ctx, temb, w, bias):
@@ -1005,29 +1093,37 @@ class SiluLinear(_Fn):
         lib().afd_silu_linear_fwd(_p(temb), _p(w), _p(bias), _p(out), B, K, N, _stream())
         ctx.save_for_backward(temb, w)
         ctx.params = (w if isinstance(w, torch.nn.Parameter) else None, bias if isinstance(bias, torch.nn.Parameter) else None)
+        ctx.has_bias = bias is not None
         return out
 
     @staticmethod
     def backward(ctx, dout):
         temb, w = ctx.saved_tensors
-        B, K = temb.shape
-        N = w.shape[0]
         dout = _c(dout)
         dtemb = torch.zeros_like(temb) if ctx.needs_input_grad[0] else None
-        wp, bp = ctx.params
-        if _direct(wp, bp):
-            if dtemb is None and _GradMode.side is not None:      # parameter gradients only: off the critical path
-                pw, pb = _p(wp.grad), _p(bp.grad)
-                defer_to_side_stream(lambda st, temb=temb, w=w, dout=dout: lib().afd_silu_linear_bwd(
-                    _p(temb), _p(w), _p(dout), pw, pb, None, B, K, N, 1, st), temb, w, dout, writes=(wp, bp))
-                return None, None, None
-            lib().afd_silu_linear_bwd(_p(temb), _p(w), _p(dout), _p(wp.grad), _p(bp.grad), _p(dtemb), B, K, N, 1, _stream())
+        return (dtemb,) + _silu_linear_param_grads(temb, w, dout, dtemb, ctx.params, ctx.has_bias)
+
+
+def _silu_linear_param_grads(temb, w, dout, dtemb, params, has_bias):
+    """dW / dbias of SiluLinear (and dtemb += ..., when given, in the same call).  In-place mode with Parameters that own a
+    .grad: accumulated there, on the side stream when nothing the chain consumes comes out of the launch -> (None, None);
+    otherwise (out of place, a plain tensor in a Parameter's place, no .grad): fresh (dw, db) for autograd."""
+    B, K = temb.shape
+    N = w.shape[0]
+    wp, bp = params
+    if wp is not None and (bp is not None or not has_bias) and _direct(wp, bp):
+        pw, pb = _p(wp.grad), (_p(bp.grad) if bp is not None else None)
+        if dtemb is None and _GradMode.side is not None:          # parameter gradients only: off the critical path
+            defer_to_side_stream(lambda st, temb=temb, w=w, dout=dout: lib().afd_silu_linear_bwd(
+                _p(temb), _p(w), _p(dout), pw, pb, None, B, K, N, 1, st), temb, w, dout, writes=(wp, bp))
+        else:
+            lib().afd_silu_linear_bwd(_p(temb), _p(w), _p(dout), pw, pb, _p(dtemb), B, K, N, 1, _stream())
             _wrote(wp, bp)
-            return dtemb, None, None
-        dw = torch.empty_like(w)
-        db = torch.empty(N, device=w.device, dtype=torch.float32)
-        lib().afd_silu_linear_bwd(_p(temb), _p(w), _p(dout), _p(dw), _p(db), _p(dtemb), B, K, N, 0, _stream())
-        return dtemb, dw, db
+        return None, None
+    dw = torch.empty_like(w)
+    db = torch.empty(N, device=w.device, dtype=torch.float32) if has_bias else None
+    lib().afd_silu_linear_bwd(_p(temb), _p(w), _p(dout), _p(dw), _p(db), _p(dtemb), B, K, N, 0, _stream())
+    return dw, db
 
 
 def silu_linear_batched(temb, layers):
@@ -1073,28 +1169,13 @@ class SiluLinearPre(_Fn):
     def forward(ctx, out, temb, w, bias):
         ctx.save_for_backward(temb, w)
         ctx.params = (w if isinstance(w, torch.nn.Parameter) else None, bias if isinstance(bias, torch.nn.Parameter) else None)
+        ctx.has_bias = bias is not None
         return out.view_as(out)
 
     @staticmethod
     def backward(ctx, dout):
         temb, w = ctx.saved_tensors
-        B, K = temb.shape
-        N = w.shape[0]
-        dout = _c(dout)
-        wp, bp = ctx.params
-        if _direct(wp, bp):
-            if _GradMode.side is not None:                         # parameter gradients only: off the critical path
-                pw, pb = _p(wp.grad), _p(bp.grad)
-                defer_to_side_stream(lambda st, temb=temb, w=w, dout=dout: lib().afd_silu_linear_bwd(
-                    _p(temb), _p(w), _p(dout), pw, pb, None, B, K, N, 1, st), temb, w, dout, writes=(wp, bp))
-            else:
-                lib().afd_silu_linear_bwd(_p(temb), _p(w), _p(dout), _p(wp.grad), _p(bp.grad), None, B, K, N, 1, _stream())
-                _wrote(wp, bp)
-            return None, None, None, None
-        dw = torch.empty_like(w)
-        db = torch.empty(N, device=w.device, dtype=torch.float32)
-        lib().afd_silu_linear_bwd(_p(temb), _p(w), _p(dout), _p(dw), _p(db), None, B, K, N, 0, _stream())
-        return None, None, dw, db
+        return (None, None) + _silu_linear_param_grads(temb, w, _c(dout), None, ctx.params, ctx.has_bias)
 
 
 # ---------------------------------------------------------------------------------------------

@@ -157,7 +157,18 @@ size_t afd_conv_wgrad_workspace_bytes(int B, int Cin, int Cout, int H, int W, in
  * 1 = Winograd F(3x3,2x2) on the fp32 MFMA, 2 = pixel-reduction GEMM on the bf16 MFMA with exact three-piece splits
  * (fp32 accuracy), 3 = the first layer's vector-FMA form (3 input channels: memory-bound), 4 = the pixel-reduction GEMM on
  * the fp16 MFMA with two-piece splits under online power-of-two scales (fp32-class accuracy, half the products of 2; the
- * default since round 3).  For reporting (bench.py prices each launch against the peak of the instruction it issues). */
+ * default since round 3).  For reporting (bench.py prices each launch against the peak of the instruction it issues).
+ * The answer goes by the shape alone.  Two things send a call to form 0 whatever it says: a 3x3 call WITH dbias (forms 1-4
+ * have no bias row), and an x or dy that is not 16-byte aligned (forms 1, 2 and 4 stage both with 16-byte loads).
+ *
+ * Alignment and accumulate (every wgrad entry point): x, dy and the workspace are fp32 tensors at any 4-byte offset, the
+ * fast forms want x and dy 16-byte aligned and fall back otherwise.  dw and dbias may sit at ANY 4-byte offset (a training
+ * step hands in views of one flat gradient buffer with no padding between tensors): every form writes its slabs to the
+ * workspace, and the one access to dw / dbias is the scalar read-add-write of the final fold.  accumulate = 1: dw[i] =
+ * dw[i] + t[i], ONE fp32 add of the finished sum t onto what dw held -- bit for bit what `dw_old + afd_conv_wgrad(...,
+ * accumulate = 0)` gives.  That add is not atomic: two calls that accumulate into one dw (a parameter used twice in one
+ * backward) must be ordered on one stream, and two fold descriptors with one dst must not share an afd_fold_batched call
+ * (ops.deal_lane / ops.fold_batches see to both). */
 int afd_conv_wgrad_form(int B, int Cin, int Cout, int H, int W, int ksize);
 int afd_conv_wgrad(const float* x, const float* dy, float* dw, float* dbias /* or NULL */,
                    int B, int Cin, int Cout, int H, int W, int ksize, int accumulate,
@@ -169,7 +180,10 @@ int afd_conv_wgrad(const float* x, const float* dy, float* dw, float* dbias /* o
  * atomics (identity map: inner = n, rstride = 1; [tap][plane] slabs -> OIHW: inner = n / 9, rstride = 9).
  * afd_fold_batched folds any number of them in ceil(n / 56) launches (descs: HOST array; the descriptors travel as
  * kernel arguments, so the call is legal under stream capture and needs no device table).  The result of a fold does
- * not depend on what it is batched with.
+ * not depend on what it is batched with -- PROVIDED no two descriptors of a call share a dst: a fold reads dst, adds and
+ * writes back without atomics, one workgroup per 32 or 128 elements, so two folds into one dst in one launch race.  dst may
+ * sit at any 4-byte offset (scalar accesses); part is read with 16-byte loads where n % 128 == 0, inner % 4 == 0,
+ * stride % 4 == 0 and part is 16-byte aligned, with scalar loads otherwise (the launcher tests all four).
  * afd_conv_wgrad_partials = afd_conv_wgrad without its final fold: launches the slab producer and writes the fold
  * descriptor(s) (weights, then bias) to folds_out[0..*n_folds) (HOST, room for 2) for a later afd_fold_batched ON THE
  * SAME STREAM; the workspace must stay alive until that fold has run.  Shapes whose kernel has no slab stage are
@@ -329,7 +343,10 @@ int afd_add(const float* a, const float* b, float* y, long n, afd_stream_t strea
 /* ---- F9: time embedding ------------------------------------- ddpm_models.py:261-269,272-273
  * temb[b, k] = sin(t[b]*inv_freq[k]), temb[b, half+k] = cos(...); t int64, inv_freq (half,) fp32
  * (computed once on the host exactly as the reference does).
- * silu_linear: out[b, n] = sum_k silu(temb[b,k]) * w[n,k] + bias[n]      ddpm_utils.py:208-214 */
+ * silu_linear: out[b, n] = sum_k silu(temb[b,k]) * w[n,k] + bias[n]      ddpm_utils.py:208-214
+ * bias / dbias may be NULL.  bwd, accumulate = 1: dw[n,k] = dw[n,k] + t and dbias[n] = dbias[n] + t, one fp32 add of the
+ * finished batch sum t each (= old + what accumulate = 0 writes), not atomic: calls that accumulate into one dw run in
+ * order on one stream.  Every pointer may sit at any 4-byte offset (scalar accesses only); afd_embed_add_bwd likewise. */
 int afd_pos_encoding(const int64_t* t, const float* inv_freq, float* temb, int B, int half, afd_stream_t stream);
 int afd_silu_linear_fwd(const float* temb, const float* w, const float* bias, float* out,
                         int B, int K, int N, afd_stream_t stream);
