@@ -18,6 +18,7 @@ from .manifold import ball_membership, manifold, manifold_scores, neighbour_radi
 from .quality import gaussian_window, image_quality, pair_sums, psnr, ssim  # noqa: F401
 from .posterior import LinearOperator, gaussian_kernel  # noqa: F401
 from .likelihood import ode_likelihood_reference  # noqa: F401
+from .unipc import unipc_reference  # noqa: F401
 from .unet import UNet  # noqa: F401
 from .diffusion import Diffusion  # noqa: F401
 from .training import (argument, set_seed, setup_logging, train, TrainStep, FusedAdamW, FlatParams,  # noqa: F401

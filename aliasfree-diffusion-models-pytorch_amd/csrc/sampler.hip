@@ -1,4 +1,4 @@
-// sampler.hip -- the samplers: noising, the sampler steps (DDPM, DDIM, DPM-Solver++(2M); plain, guided and masked), the ascending
+// sampler.hip -- the samplers: noising, the sampler steps (DDPM, DDIM, DPM-Solver++(2M), UniPC; plain, guided and masked), the ascending
 // DDIM step of the inversion, renoise and quantisation.  (Losses, learned variances and the likelihood bound are objective.hip, the optimizer is optim.hip.)
 //
 // noise_images / denoise_step / quantize restate the reference's fp32 expression ORDER with one
@@ -160,7 +160,7 @@ __global__ __launch_bounds__(256) void step_k(const float* x, const float* __res
   }
 }
 
-// Launch geometry of the streaming step kernels (these, renoise, DPM++): 16-byte accesses when vec_ok; memory-bound, so at most
+// Launch geometry of the streaming step kernels (these, renoise, DPM++, UniPC): 16-byte accesses when vec_ok; memory-bound, so at most
 // 2048 workgroups and the loop takes the rest.
 static inline long step_grid(long work) { return std::min<long>(2048, std::max<long>(1, (work + 255) / 256)); }
 
@@ -294,6 +294,78 @@ static void launch_dpmpp_step(const float* x, const float* eps, const float* x0_
   const long work = vec ? n / 4 : n;
   launch_vec(vec, dpmpp_step_k<kCfg, true>, dpmpp_step_k<kCfg, false>, step_grid(work), st, x, eps, x0_prev, coef, s, x_out, x_out2,
              x0_out, work);
+}
+
+// ---- UniPC (Zhao et al. 2023), orders 1-3: the corrector of the last move and the predictor of the next, one launch -------------
+// coef (device, 12 floats, one row of Diffusion.unipc_coefficients) = [alpha, sigma, Ac, c0, c1, c2, c3, Ap, p0, p1, p2, slot];
+// fp32, one rounding per operation, in this order:
+//   m  = (x - (sigma * e)) / alpha
+//   xc = ((((Ac * xc) + (c0 * m)) + (c1 * h1)) + (c2 * h2)) + (c3 * h3)
+//   xn = (((Ap * xc) + (p0 * m)) + (p1 * h1)) + (p2 * h2)
+// hist is a ring of three n-element planes: h_j is plane (slot - j) mod 3 and m goes to plane `slot`, which is h3's (each element
+// reads its h3 before it writes m).  slot is read on the device and clamped into {0, 1, 2}.  Every term is always evaluated:
+// the table's zero weights meet a zeroed or finite history.  xc is updated in place; xn goes to x_out (may alias x) and to the
+// optional x_out2.  With CFG, e is cfg_lerp of the two halves of eps2 first.  VEC: n % 4 == 0, every pointer 16-byte aligned
+// (then the planes are too); n counts float4s.
+struct UniCoef {
+  float alpha, sigma, Ac, c0, c1, c2, c3, Ap, p0, p1, p2;
+};
+__device__ __forceinline__ float unipc_update(const UniCoef& k, float x, float e, float h1, float h2, float h3, float& xc, float& m) {
+  const float pe = k.sigma * e;
+  m = (x - pe) / k.alpha;
+  float c = (k.Ac * xc) + (k.c0 * m);
+  c = c + (k.c1 * h1);
+  c = c + (k.c2 * h2);
+  c = c + (k.c3 * h3);
+  xc = c;
+  float p = (k.Ap * c) + (k.p0 * m);
+  p = p + (k.p1 * h1);
+  return p + (k.p2 * h2);
+}
+template <bool kCfg, bool VEC>
+__global__ __launch_bounds__(256) void unipc_step_k(const float* x, const float* __restrict__ eps, float* __restrict__ xc, float* hist,
+                                                    const float* __restrict__ coef, float s, float* x_out, float* x_out2, long n) {
+  const UniCoef k{coef[0], coef[1], coef[2], coef[3], coef[4], coef[5], coef[6], coef[7], coef[8], coef[9], coef[10]};
+  const float sf = coef[11];
+  const int slot = sf >= 1.5f ? 2 : (sf >= 0.5f ? 1 : 0);          // clamped; anything else (a NaN too) reads as 0
+  const long plane = VEC ? 4 * n : n;                           // floats per plane of the ring
+  const float* h1 = hist + ((slot + 2) % 3) * plane;
+  const float* h2 = hist + ((slot + 1) % 3) * plane;
+  float* h3 = hist + slot * plane;                              // read as h3, then written with m
+  const Guidance g = guidance(s);
+  AFD_GRID_STRIDE(i, n) {
+    if (VEC) {
+      const float4 xv = reinterpret_cast<const float4*>(x)[i], c = reinterpret_cast<const float4*>(eps)[i];
+      const float4 u = kCfg ? reinterpret_cast<const float4*>(eps)[n + i] : c;
+      const float4 a1 = reinterpret_cast<const float4*>(h1)[i], a2 = reinterpret_cast<const float4*>(h2)[i];
+      const float4 a3 = reinterpret_cast<const float4*>(h3)[i];
+      float4 cv = reinterpret_cast<const float4*>(xc)[i], r, m;
+      r.x = unipc_update(k, xv.x, guided_eps<kCfg>(g, c.x, u.x), a1.x, a2.x, a3.x, cv.x, m.x);
+      r.y = unipc_update(k, xv.y, guided_eps<kCfg>(g, c.y, u.y), a1.y, a2.y, a3.y, cv.y, m.y);
+      r.z = unipc_update(k, xv.z, guided_eps<kCfg>(g, c.z, u.z), a1.z, a2.z, a3.z, cv.z, m.z);
+      r.w = unipc_update(k, xv.w, guided_eps<kCfg>(g, c.w, u.w), a1.w, a2.w, a3.w, cv.w, m.w);
+      reinterpret_cast<float4*>(x_out)[i] = r;
+      if (x_out2) reinterpret_cast<float4*>(x_out2)[i] = r;
+      reinterpret_cast<float4*>(xc)[i] = cv;
+      reinterpret_cast<float4*>(h3)[i] = m;
+    } else {
+      const float e = guided_eps<kCfg>(g, eps[i], kCfg ? eps[n + i] : 0.0f);
+      float cv = xc[i], m;
+      const float r = unipc_update(k, x[i], e, h1[i], h2[i], h3[i], cv, m);
+      x_out[i] = r;
+      if (x_out2) x_out2[i] = r;
+      xc[i] = cv;
+      h3[i] = m;
+    }
+  }
+}
+template <bool kCfg>
+static void launch_unipc_step(const float* x, const float* eps, float* xc, float* hist, const float* coef, float s, float* x_out,
+                              float* x_out2, long n, hipStream_t st) {
+  const bool vec = vec_ok(n, {x, eps, xc, hist, x_out, x_out2});
+  const long work = vec ? n / 4 : n;
+  launch_vec(vec, unipc_step_k<kCfg, true>, unipc_step_k<kCfg, false>, step_grid(work), st, x, eps, xc, hist, coef, s, x_out, x_out2,
+             work);
 }
 
 // ((clamp(x,-1,1) + 1) / 2 * 255).type(uint8): truncation toward zero
@@ -509,6 +581,36 @@ int afd_dpmpp_step_cfg(const float* x, const float* eps2, const float* x0_prev, 
               "afd_dpmpp_step_cfg: x0_out must not overlap x, eps2, x_out or x_out2, and must be x0_prev itself or apart from it");
   launch_dpmpp_step<true>(x, eps2, x0_prev, coef, cfg_scale, x_out, x_out2, x0_out, n, as_stream(st));
   return check_launch("afd_dpmpp_step_cfg");
+}
+// ---- UniPC ---------------------------------------------------------------------------------------------------------------------
+// xc (n values) and hist (3n) are read and written per element while x and eps are read and the outputs written by other
+// elements: the two share no memory with each other, with x, with eps or with the outputs.
+static inline bool unipc_apart(const float* x, const float* eps, long eps_n, const float* xc, const float* hist, const float* x_out,
+                               const float* x_out2, long n) {
+  const long fb = n * (long)sizeof(float);
+  auto apart = [&](const float* q, long qb) {
+    return !overlaps(q, qb, x, fb) && !overlaps(q, qb, eps, eps_n * (long)sizeof(float)) && !overlaps(q, qb, x_out, fb) &&
+           !overlaps(q, qb, x_out2, fb);
+  };
+  if (!apart(xc, fb) || !apart(hist, 3 * fb)) return false;
+  return !overlaps(xc, fb, hist, 3 * fb);
+}
+int afd_unipc_step(const float* x, const float* eps, float* xc, float* hist, const float* coef, float* x_out, long n, afd_stream_t st) {
+  AFD_REQUIRE(x && eps && xc && hist && coef && x_out, "afd_unipc_step: x, eps, xc, hist, coef and x_out must not be NULL");
+  AFD_REQUIRE(n > 0, "afd_unipc_step: n must be positive (got %ld)", n);
+  AFD_REQUIRE(unipc_apart(x, eps, n, xc, hist, x_out, nullptr, n),
+              "afd_unipc_step: xc and hist must not overlap each other, x, eps or x_out");
+  launch_unipc_step<false>(x, eps, xc, hist, coef, 0.0f, x_out, nullptr, n, as_stream(st));
+  return check_launch("afd_unipc_step");
+}
+int afd_unipc_step_cfg(const float* x, const float* eps2, float* xc, float* hist, const float* coef, float cfg_scale, float* x_out,
+                       float* x_out2, long n, afd_stream_t st) {
+  AFD_REQUIRE(x && eps2 && xc && hist && coef && x_out, "afd_unipc_step_cfg: x, eps2, xc, hist, coef and x_out must not be NULL");
+  AFD_REQUIRE(n > 0, "afd_unipc_step_cfg: n must be positive (got %ld)", n);
+  AFD_REQUIRE(unipc_apart(x, eps2, 2 * n, xc, hist, x_out, x_out2, n),
+              "afd_unipc_step_cfg: xc and hist must not overlap each other, x, eps2, x_out or x_out2");
+  launch_unipc_step<true>(x, eps2, xc, hist, coef, cfg_scale, x_out, x_out2, n, as_stream(st));
+  return check_launch("afd_unipc_step_cfg");
 }
 int afd_quantize_u8(const float* x, uint8_t* out, long n, afd_stream_t st) {
   AFD_REQUIRE(x && out && n > 0, "afd_quantize_u8: bad argument");

@@ -14,7 +14,7 @@ import numpy as np
 import torch
 import torch.distributed as dist
 
-from . import ops
+from . import ops, unipc
 from .filters import circularLowpassKernel
 
 
@@ -564,6 +564,102 @@ class Diffusion:
         snaps.append(x)
         return x, snaps
 
+    # UniPC (Zhao et al. 2023): a multistep predictor-corrector of order up to 3, one forward per step (unipc.py) -------------
+    UNIPC_SAMPLERS = {"unipc": 2, "unipc_1": 1, "unipc_2": 2, "unipc_3": 3}
+
+    @staticmethod
+    def unipc_order(k, S, P):
+        """The order of step k of an S-step UniPC chain of order P: min(P, k + 1) and, when S < 15, also min(., S - k)
+        (`dpmpp_order`'s convention; P = 2 gives `dpmpp_order`)."""
+        return unipc.unipc_order(k, S, P)
+
+    def unipc_coefficients(self, pairs, order, dtype=torch.float32):
+        """(S, 12) host table of the UniPC chain `pairs` at order P = `order` (1 .. 3), computed in fp64 and rounded once to
+        `dtype` (torch.float64: the unrounded table).  Row k = [alpha, sigma, Ac, c0, c1, c2, c3, Ap, p0, p1, p2, slot] of
+        evaluation k at level lev[k] (lev = taus + [0]; alpha, sigma, lam as in `dpmpp_coefficients`): with
+        m_k = (x~_k - sigma e) / alpha,
+            x_k      = Ac x_{k-1} + c0 m_k + c1 m_{k-1} + c2 m_{k-2} + c3 m_{k-3}     (the corrector, order[k-1])
+            x~_{k+1} = Ap x_k     + p0 m_k + p1 m_{k-1} + p2 m_{k-2}                  (the predictor, order[k])
+        the rho / D_i form of unipc.py folded per evaluation: for a move s -> u of width h with B = expm1(-h), A = sigma_u / sigma_s,
+        the earlier evaluation i weighs -alpha_u B rho_i / r_i, the corrector's new one -alpha_u B rho_p, and the base takes
+        -alpha_u B minus all of those, so each move's weights sum to -alpha_u B.  Row 0: Ac = 1 and c* = 0 (no corrector: the
+        corrected state starts as x_T); unused history weights are 0.  slot = k mod 3, the ring position that receives m_k."""
+        P = int(order)
+        if not 1 <= P <= unipc.MAX_ORDER:
+            raise ValueError(f"Diffusion.unipc_coefficients: order must be 1, 2 or 3 (got {order!r})")
+        _, alpha, sigma, lam = unipc.schedule_levels(self.alpha_hat, pairs)
+        S = len(pairs)
+
+        def weights(s, u, earlier, corrector):
+            """-> (A, w_new, w_base, [w_1 ..]) of the move s -> u with the earlier evaluations at the positions `earlier`; w_new
+            (the corrector's weight of the new evaluation) is 0 for a predictor."""
+            h = lam[u] - lam[s]
+            aB = alpha[u] * math.expm1(-h)
+            rs = [(lam[q] - lam[s]) / h for q in earlier]
+            rho = unipc.unipc_rho(rs, h, corrector)
+            w = [-aB * w_i / r for w_i, r in zip(rho, rs)]
+            w_new = -aB * rho[-1] if corrector else 0.0
+            return sigma[u] / sigma[s], w_new, -aB - sum(w) - w_new, w
+
+        rows = []
+        for k in range(S):
+            c = [1.0, 0.0, 0.0, 0.0, 0.0]
+            if k >= 1:
+                p = self.unipc_order(k - 1, S, P)
+                A, w_new, w_base, w = weights(k - 1, k, [k - 1 - i for i in range(1, p)], True)
+                c = [A, w_new, w_base] + w + [0.0] * (3 - p)
+            p = self.unipc_order(k, S, P)
+            A, _, w_base, w = weights(k, k + 1, [k - i for i in range(1, p)], False)
+            rows.append([alpha[k], sigma[k]] + c + [A, w_base] + w + [0.0] * (3 - p) + [float(k % 3)])
+        table = np.array(rows, dtype=np.float64)
+        return torch.tensor(table if dtype == torch.float64 else table.astype(np.float32))
+
+    def _unipc_loop(self, model, n, image_channels, pairs, order, noise_source="reference", graph=None, labels=None, cfg_scale=0.0):
+        """`_dpmpp_loop` for UniPC of order `order`: x_T drawn as in `_loop`, no noise after it, one forward per step (2n rows
+        when guided) and one update launch that corrects the last state with the new evaluation and predicts the next.  The
+        solver's state is xc (n rows: the corrected state, starts as x_T) and hist (a ring of the last three m), both updated in
+        place by the kernel; xs holds the predicted state the network sees.  graph: capture one step (forward and update,
+        reading the step's row from a static device buffer) and replay it for every step but the last, which runs eagerly."""
+        snaps = []
+        with self._model_scope(model):
+            x = self._initial_noise(n, image_channels, noise_source)
+            table = self.unipc_coefficients(pairs, order).to(x.device)   # once per trajectory
+            y, s = self._guided(labels, cfg_scale)
+            xs = torch.cat([x, x]) if s > 0 else x
+            rows = xs.shape[0]
+            xc = x.clone()
+            hist = torch.zeros((3,) + tuple(x.shape), device=x.device, dtype=x.dtype)
+
+            def step(t_rows, coef):
+                eps = self.predict_eps(model, xs, t_rows, y)
+                if s > 0:
+                    ops.unipc_step_cfg(xs[:n], eps, xc, hist, coef, s, xs[:n], xs[n:])
+                else:
+                    ops.unipc_step(xs, eps, xc, hist, coef, xs)           # in place (elementwise)
+
+            replay = None
+            if graph and len(pairs) > 1:
+                t_dev = torch.full((rows,), pairs[0][0], device=x.device, dtype=torch.long)
+                coef = table[0].clone()
+                g = self._capture(lambda: step(t_dev, coef), xs)
+                xc.copy_(xs[:n])                                          # undo the warm-up's state as well (xs is x_T again)
+                hist.zero_()
+
+                def replay(k):
+                    t_dev.fill_(pairs[k][0])
+                    coef.copy_(table[k])
+                    g.replay()
+            for k, (t, tp) in enumerate(pairs):
+                if replay is not None and tp > 0:
+                    replay(k)
+                else:
+                    step(self._t_full(rows, t, x.device), table[k])
+                if self.ddim_snapshot(t, tp):
+                    snaps.append(xs[:n].clone())
+            x = xs[:n].clone()
+        snaps.append(x)
+        return x, snaps
+
     def _hint(self, model):
         """Tell the model the range of the timesteps this process will pass (all of them in [0, noise_steps)): lets the
         UNet tabulate its time embeddings once per trajectory (unet.UNet._timestep_tables); cleared again when the loop
@@ -629,18 +725,19 @@ class Diffusion:
 
     def _check_sampler(self, where, sampler, steps, eta, theta=None):
         """-> (solver, pairs): ("ddim", the `_check_ddim` pairs or None) for sampler None / "ddim", ("dpmpp_2m", the DPM++
-        pairs) for "dpmpp_2m"."""
+        pairs) for "dpmpp_2m", (the name, the same pairs) for a key of `UNIPC_SAMPLERS`."""
         if sampler is None or (isinstance(sampler, str) and sampler == "ddim"):
             return "ddim", self._check_ddim(where, steps, eta, theta)
-        if not (isinstance(sampler, str) and sampler == "dpmpp_2m"):
-            raise ValueError(f"Diffusion.{where}: unknown sampler {sampler!r} (None, 'ddim' or 'dpmpp_2m')")
+        if not (isinstance(sampler, str) and (sampler == "dpmpp_2m" or sampler in self.UNIPC_SAMPLERS)):
+            raise ValueError(f"Diffusion.{where}: unknown sampler {sampler!r} (None, 'ddim', 'dpmpp_2m', 'unipc', 'unipc_1', "
+                             f"'unipc_2' or 'unipc_3')")
         if theta is not None:
-            raise NotImplementedError(f"Diffusion.{where}: sampler='dpmpp_2m' together with a rotation (theta) is not supported")
+            raise NotImplementedError(f"Diffusion.{where}: sampler={sampler!r} together with a rotation (theta) is not supported")
         if steps is None:
-            raise ValueError(f"Diffusion.{where}: sampler='dpmpp_2m' needs steps (an int or an explicit sequence of timesteps)")
+            raise ValueError(f"Diffusion.{where}: sampler={sampler!r} needs steps (an int or an explicit sequence of timesteps)")
         if eta != 0:
-            raise ValueError(f"Diffusion.{where}: sampler='dpmpp_2m' is deterministic: eta must be 0 (got {eta})")
-        return "dpmpp_2m", self.dpmpp_pairs(steps)
+            raise ValueError(f"Diffusion.{where}: sampler={sampler!r} is deterministic: eta must be 0 (got {eta})")
+        return sampler, self.dpmpp_pairs(steps)
 
     def sample(self, model, n, image_channels, theta=None, noise_source="reference", return_float=False, graph=None,
                labels=None, cfg_scale=0.0, steps=None, eta=0.0, sampler=None):
@@ -654,7 +751,10 @@ class Diffusion:
         crosses a multiple of 100 (`ddim_snapshot`), plus the final x.  Not supported together with theta.
         sampler: None or "ddim" (the samplers above); "dpmpp_2m" runs DPM-Solver++(2M) over `steps` (an int S, spaced
         uniformly in log-SNR by `logsnr_timesteps`, or an explicit sequence), S forwards, deterministic (eta must be 0; no
-        noise is drawn after x_T).  Guidance, graph= and the snapshots work as for DDIM."""
+        noise is drawn after x_T).  Guidance, graph= and the snapshots work as for DDIM.  "unipc_1" / "unipc_2" / "unipc_3"
+        ("unipc" = "unipc_2") run UniPC of that order under the same rules: a predictor-corrector that still costs one forward
+        per step.  Order 3 pays from about S = 16 on; below that its extrapolation over log-SNR steps near 1 is worse than
+        "unipc_2" or "dpmpp_2m" (DESIGN.md section 6z)."""
         logging.info(f"Sampling {n} new images....")
         if theta is not None:
             logging.info(f"Theta {theta} provided. Rotation will be applied.")
@@ -665,6 +765,9 @@ class Diffusion:
             raise ValueError("Diffusion.sample: cfg_scale needs class labels")
         if solver == "dpmpp_2m":
             x, snaps = self._dpmpp_loop(model, n, image_channels, pairs, noise_source, graph, labels, float(cfg_scale))
+        elif solver in self.UNIPC_SAMPLERS:
+            x, snaps = self._unipc_loop(model, n, image_channels, pairs, self.UNIPC_SAMPLERS[solver], noise_source, graph, labels,
+                                        float(cfg_scale))
         elif pairs is None:
             x, snaps = self._loop(model, n, image_channels, theta, noise_source, graph, labels=labels, cfg_scale=float(cfg_scale))
         else:
@@ -1880,6 +1983,8 @@ class Diffusion:
         solver, pairs = self._check_sampler("revert", sampler, steps, eta)
         if solver == "dpmpp_2m":
             _, snaps = self._dpmpp_loop(model, n, image_channels, pairs, noise_source, graph)
+        elif solver in self.UNIPC_SAMPLERS:
+            _, snaps = self._unipc_loop(model, n, image_channels, pairs, self.UNIPC_SAMPLERS[solver], noise_source, graph)
         elif pairs is None:
             _, snaps = self._loop(model, n, image_channels, None, noise_source, graph)
         else:

@@ -1399,6 +1399,36 @@ def dpmpp_step_cfg(x, eps2, x0_prev, coef, cfg_scale, out=None, out2=None, x0_ou
     return out, x0_out
 
 
+def _unipc_args(what, x, eps, xc, hist, coef, out, out2=None, guided=False):
+    n = _step_args(what, x, eps, xc, coef, out, out2, guided)
+    _chk(hist)
+    if coef.numel() != 12:
+        raise AfdError(f"afdm: {what} needs coef of 12 values [alpha, sigma, Ac, c0..c3, Ap, p0..p2, slot] (got {coef.numel()})")
+    if not hist.is_contiguous() or hist.numel() != 3 * n:
+        raise AfdError(f"afdm: {what}: hist must be contiguous and hold 3 x {n} elements")
+    return n
+
+
+def unipc_step(x, eps, xc, hist, coef, out=None):
+    """One UniPC evaluation: the corrector of the last move and the predictor of the next (include/afd.h: afd_unipc_step gives the
+    exact expression).  coef: the evaluation's row of `Diffusion.unipc_coefficients`, 12 fp32 values on the device (read there:
+    graph-replayable).  xc (the corrected state, n elements) and hist (the ring of the last three m, 3n elements) are the
+    solver's state, updated in place.  `out` may be x.  Returns out, the predicted state of the next level."""
+    out = torch.empty_like(x) if out is None else out
+    n = _unipc_args("UniPC step", x, eps, xc, hist, coef, out)
+    lib().afd_unipc_step(_p(x), _p(eps), _p(xc), _p(hist), _p(coef), _p(out), n, _stream())
+    return out
+
+
+def unipc_step_cfg(x, eps2, xc, hist, coef, cfg_scale, out=None, out2=None):
+    """Classifier-free guided UniPC evaluation: e = torch.lerp(eps2[n:], eps2[:n], cfg_scale), then exactly
+    `unipc_step(x, e, ...)`, in one launch.  `out2` (optional) receives the same values as `out`.  Returns out."""
+    out = torch.empty_like(x) if out is None else out
+    n = _unipc_args("guided UniPC step", x, eps2, xc, hist, coef, out, out2, guided=True)
+    lib().afd_unipc_step_cfg(_p(x), _p(eps2), _p(xc), _p(hist), _p(coef), float(cfg_scale), _p(out), _p(out2), n, _stream())
+    return out
+
+
 # ---- likelihood: gathered noising, the bound's per-row terms, the prior (include/afd.h gives the exact expressions) ---------
 def _rows_args(what, x0, img, t, rows_like, check_range, T=None):
     """Common checks of the row-wise entry points -> (n_img, rows, per).  img / t: int64 device vectors of one value per row;

@@ -157,8 +157,9 @@ def ddpm_run(params):
     else:
         print("skipped saving training dataset")
     # optional DDIM for the FID/KID image set only: params["sample_steps"] (S, or an explicit list of timesteps) and
-    # params["sample_eta"] (default 0, deterministic); params["sample_solver"]: None / "ddim" or "dpmpp_2m" (DPM-Solver++(2M)
-    # over the same steps, eta 0); without them the full DDPM chain runs as before
+    # params["sample_eta"] (default 0, deterministic); params["sample_solver"]: None / "ddim", "dpmpp_2m" (DPM-Solver++(2M)) or
+    # "unipc" / "unipc_1" / "unipc_2" / "unipc_3" (UniPC of that order; "unipc" = order 2), the last two kinds over the same
+    # steps with eta 0; without them the full DDPM chain runs as before
     gen_kw = {}
     if params.get("sample_steps") is not None:
         gen_kw = {"steps": params["sample_steps"], "eta": params.get("sample_eta", 0.0)}

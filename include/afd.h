@@ -466,6 +466,25 @@ int afd_dpmpp_step(const float* x, const float* eps, const float* x0_prev /* NUL
  * it either (nor any of eps2's 2n values). */
 int afd_dpmpp_step_cfg(const float* x, const float* eps2, const float* x0_prev, const float* coef, float cfg_scale, float* x_out,
                        float* x_out2, float* x0_out, long n, afd_stream_t stream);
+/* UniPC (Zhao et al. 2023; multistep, data prediction, B(h) = expm1(-h)), orders 1-3: at one evaluation of the network, the
+ * corrector of the move that led here and the predictor of the next move, for a model trained on the eps-objective.  coef: 12 fp32
+ * values in device memory, one row of Diffusion.unipc_coefficients, [alpha, sigma, Ac, c0, c1, c2, c3, Ap, p0, p1, p2, slot].
+ * fp32 with one IEEE rounding per operation (no FMA contraction, correctly rounded /), in exactly this order:
+ *   m  = (x - (sigma * eps)) / alpha
+ *   xc = ((((Ac * xc) + (c0 * m)) + (c1 * h1)) + (c2 * h2)) + (c3 * h3)      (in place)
+ *   xn = (((Ap * xc) + (p0 * m)) + (p1 * h1)) + (p2 * h2)                    (x_out; the xc of the line above)
+ * hist holds three planes of n values, a ring: h_j is plane (slot - j) mod 3, and m is written to plane slot (h3's: each element
+ * reads its h3 first).  slot is coef[11], read on the device and clamped into {0, 1, 2}.  Every term is evaluated on every call,
+ * so hist must hold finite values (zeros before the first call) wherever the row's weights are 0.  Because coef is read on the
+ * device, the same call serves graph replay.  x_out may alias x; xc and hist must not overlap each other, x, eps or x_out.
+ * Requires n > 0.  n: elements of x. */
+int afd_unipc_step(const float* x, const float* eps, float* xc, float* hist, const float* coef, float* x_out, long n,
+                   afd_stream_t stream);
+/* classifier-free guided form: eps2 as for afd_denoise_step_cfg, eps = torch.lerp(e_u, e_c, cfg_scale) with the same scalar
+ * formula, then exactly the afd_unipc_step expression.  x_out2 is NULL or a second destination of xn; xc and hist must not
+ * overlap it either (nor any of eps2's 2n values). */
+int afd_unipc_step_cfg(const float* x, const float* eps2, float* xc, float* hist, const float* coef, float cfg_scale, float* x_out,
+                       float* x_out2, long n, afd_stream_t stream);
 /* ---- likelihood: the variational bound in bits/dim (Ho et al. 2020, section 3.3; Diffusion.calc_bpd) ----
  * A row r pairs image img[r] of x0 (n_img images of `per` fp32 values each) with timestep t[r].  img and t are int64 device
  * arrays of `rows` values, read on the device: the caller keeps them in [0, n_img) and [1, T) (nothing checks them here).
