@@ -533,7 +533,6 @@ static void wgrad_bf3_tile(int Cin, int Cout, long nt, int* bn, int* bk) {
   *bk = (Cin % 64 == 0 && Cout % 64 && (force ? force >= 64 : true)) ? 64 : 32;
 }
 
-void wgrad_bf3_tile_for(int Cin, int Cout, long nt, int* bn, int* bk) { wgrad_bf3_tile(Cin, Cout, nt, bn, bk); }   // (h2_wgrad.hip shares the plan)
 static int g_wg_arith_bf3 = 0;     // afd_debug_conv_path 78 / 79: the 3x3 weight gradient's arithmetic is f16x2 (h2_wgrad.hip, default) / bf16x3 (this file)
 void wgrad_arith_set(int m) { g_wg_arith_bf3 = m; }
 bool wgrad_arith_is_bf3() { return g_wg_arith_bf3 != 0; }
@@ -542,27 +541,73 @@ bool wgrad_arith_is_bf3() { return g_wg_arith_bf3 != 0; }
 static long g_wgb_target = 256;
 void wgrad_plan_target_set(long wgs) { g_wgb_target = wgs; }
 
-int wgrad_bf3_plan(int B, int Cin, int Cout, int H, int W, int* tps, int* ntiles) {
+// waves per workgroup of the f16x2 kernels (h2_wgrad.hip; the bf16x3 kernels of this file have the eight-wave form only).
+// An eight-wave workgroup holds a CU's whole register file, so beside it no wave of the dependent chain's matrix-pipe
+// kernels fits on that CU; a four-wave workgroup (256 threads, two resident per CU) leaves half of it.  A 64 x 64 block
+// has eight wave roles: its four-wave form is the two 64 x 32 halves along the input channels as workgroups of their own
+// (the same loads, splits, MFMAs and slab writes; the x scale is then a maximum over 32 channels).
+// afd_debug_conv_path 50 / 51 / 52: by the rule / eight waves everywhere / four wherever covered; 53 / 54 / 55: four waves on
+// 64 x 32 / 32 x 64 / 32 x 32 blocks wherever the channel counts allow, else as 52 (tests).  AFD_WGB_WAVES=8 / 4 forces
+// one, AFD_WGB_W4=<mask> sets the rule (bit 0: the 64 x 64 blocks, 1: 64 x 32 and 32 x 64, 2: 32 x 32), AFD_WGB_TARGET4 the
+// workgroups per four-wave launch (never more splits than the eight-wave plan: no layer writes more slab bytes)
+static int g_wg_waves_mode = 0;
+void wgrad_waves_set(int m) { g_wg_waves_mode = m; }
+static constexpr int kWg4RuleMask = 7;                                 // measured in the step, not alone: alone the four-wave plan is 10 % slower
+static bool wgrad_four_waves(int BN, int BK) {
+  if (g_wg_arith_bf3) return false;
+  static const int force = [] { const char* e = getenv("AFD_WGB_WAVES"); return e ? atoi(e) : 0; }();   // tuning hooks
+  static const int mask = [] { const char* e = getenv("AFD_WGB_W4"); return e ? atoi(e) : kWg4RuleMask; }();
+  if (force == 4 || force == 8) return force == 4;
+  if (g_wg_waves_mode) return g_wg_waves_mode >= 2;
+  const int kind = BN == 64 && BK == 64 ? 1 : (BN == 64 || BK == 64 ? 2 : 4);
+  return (mask & kind) != 0;
+}
+
+int wgrad_plan_full(int B, int Cin, int Cout, int H, int W, int* tps, int* ntiles, int* bn, int* bk, int* nw) {
   if (g_wgbf3_mode == 1) return 0;
   if (H != W || (W != 4 && W != 8 && W != 16 && W != 32)) return 0;
   if (Cin % 32 || Cout % 32) return 0;
   if ((long)B * H * W * (Cin > Cout ? Cin : Cout) >= (1L << 31)) return 0;
   const long nt = W == 4 ? (B + 7) / 8 : (W == 8 ? (B + 1) / 2 : (long)B * (H * W / 128));
   int BN, BK;
-  wgrad_bf3_tile(Cin, Cout, W == 4 ? (B + 7) / 8 : (W == 8 ? (B + 1) / 2 : (long)B * (H * W / 128)), &BN, &BK);
-  const long blocks = (long)(Cout / BN) * (Cin / BK);
-  // workgroups per launch (512 threads each, a CU's whole register file).  Alone a launch is fastest with one per CU (256: the default); IN SITU,
+  wgrad_bf3_tile(Cin, Cout, nt, &BN, &BK);
+  if (g_wg_waves_mode >= 3 && !g_wg_arith_bf3) {                         // a four-wave block by name (tests)
+    if (g_wg_waves_mode == 3 && Cout % 64 == 0) { BN = 64; BK = 32; }
+    else if (g_wg_waves_mode == 4 && Cin % 64 == 0) { BN = 32; BK = 64; }
+    else if (g_wg_waves_mode == 5) { BN = 32; BK = 32; }
+  }
+  const long blocks = (long)(Cout / BN) * (Cin / BK);                   // of the eight-wave form
+  // workgroups per launch.  EIGHT waves (512 threads, a CU's whole register file): alone a launch is fastest with one per CU (256: the default); IN SITU,
   // beside the dependent chain on the other stream, fewer are better -- they leave CUs to the chain and write fewer slabs:
-  // step time with 64 / 96 / 128 / 160 / 192 / 256 / 384 / 512: 8.00 / 7.44 / 7.06 / 7.07 / 7.08 / 7.14 / 7.24 / 7.42 ms (tools/step_median.py --lanes)
-  static const long env_target = [] { const char* e = getenv("AFD_WGB_TARGET"); return e ? atol(e) : 0L; }();   // tuning hook
+  // step time with 64 / 96 / 128 / 160 / 192 / 256 / 384 / 512: 8.00 / 7.44 / 7.06 / 7.07 / 7.08 / 7.14 / 7.24 / 7.42 ms (tools/step_median.py --lanes).
+  // FOUR waves (the default rule: every block kind) leave half of every CU to the chain as they are: step time, bench.py alternating, eight waves 6.59-6.62,
+  // four at 256 / 192 / 160 / 128 per launch 6.48 / 6.63 / 6.81 / 7.02 ms; four on the 64 x 64 blocks only 6.45 against 6.51 and 6.40 everywhere
+  // (profiles/wgrad_w4_ab.txt)
+  const char* et = getenv("AFD_WGB_TARGET");                            // tuning hook, read per call (tools/ab_env.py; tests)
+  const long env_target = et ? atol(et) : 0L;
   const long target = env_target > 0 ? env_target : g_wgb_target;       // 256 standalone, 160 beside the chain (afd_debug_conv_path 48 / 49)
   long s = target / blocks;
   if (s < 1) s = 1;
   if (s > nt) s = nt;
-  const long c = (nt + s - 1) / s;
   if (g_wgbf3_mode != 2 && nt * blocks < 128) return 0;               // too little work to fill half the chip: the other forms
-  *tps = (int)c; *ntiles = (int)nt;
+  int NW = 8;
+  if (wgrad_four_waves(BN, BK)) {
+    // half a 64 x 64 block per workgroup doubles the blocks: at the same workgroup target the splits, the slabs and the fold
+    // traffic of that layer halve.  The other blocks keep their splits.
+    static const long target4 = [] { const char* e = getenv("AFD_WGB_TARGET4"); return e ? atol(e) : 0L; }();   // tuning hook
+    NW = 4;
+    if (BN == 64 && BK == 64) BK = 32;
+    const long s4 = (target4 > 0 ? target4 : target) / ((long)(Cout / BN) * (Cin / BK));
+    if (s4 < s) s = s4 < 1 ? 1 : s4;
+  }
+  const long c = (nt + s - 1) / s;
+  *tps = (int)c; *ntiles = (int)nt; *bn = BN; *bk = BK; *nw = NW;
   return (int)((nt + c - 1) / c);
+}
+
+int wgrad_bf3_plan(int B, int Cin, int Cout, int H, int W, int* tps, int* ntiles) {
+  int bn, bk, nw;
+  return wgrad_plan_full(B, Cin, Cout, H, W, tps, ntiles, &bn, &bk, &nw);
 }
 
 template <int S, int BN, int BK>

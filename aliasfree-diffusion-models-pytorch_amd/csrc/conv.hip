@@ -824,10 +824,12 @@ void wino_set_grid(int g);
 int wgrad_wino_plan(int B, int Cin, int Cout, int H, int W, int* bn, int* bk, int* cps, int* nchunks);
 // bf3_wgrad.hip: the 3x3 weight gradient on the bf16 matrix cores (three-piece splits)
 int wgrad_bf3_plan(int B, int Cin, int Cout, int H, int W, int* tps, int* ntiles);
+int wgrad_plan_full(int B, int Cin, int Cout, int H, int W, int* tps, int* ntiles, int* bn, int* bk, int* nw);
 int wgrad_bf3(const float* x, const float* dy, float* part, int B, int Cin, int Cout, int H, int W, hipStream_t s);
 void wgrad_bf3_set_mode(int m);
 void wgrad_arith_set(int m);
 void wgrad_plan_target_set(long wgs);
+void wgrad_waves_set(int m);
 bool wgrad_arith_is_bf3();
 // h2_wgrad.hip: the same on the fp16 matrix cores (two-piece splits, online scaling; the plan is shared)
 int wgrad_h2(const float* x, const float* dy, float* part, int B, int Cin, int Cout, int H, int W, hipStream_t s);
@@ -955,6 +957,7 @@ int afd_debug_conv_path(int mode) {
   if (mode >= 88 && mode <= 89) { pw_wgrad_bf3_set_mode(mode - 88); return AFD_OK; }   // bf16x3 1x1 wgrad: 88 = by rule (default), 89 = off
   if (mode >= 84 && mode <= 86) { wgrad_bf3_set_mode(mode - 84); return AFD_OK; }   // bf16x3 3x3 wgrad: 84 = by rule (default), 85 = off, 86 = wherever covered
   if (mode >= 48 && mode <= 49) { wgrad_plan_target_set(mode == 48 ? 256 : 160); return AFD_OK; }   // 3x3 matrix-core weight gradient, workgroups per launch: 48 = one per CU (fastest alone; default), 49 = 160 (fastest beside the dependent chain of a train step: TrainStep asks for it)
+  if (mode >= 50 && mode <= 55) { wgrad_waves_set(mode - 50); return AFD_OK; }   // f16x2 3x3 weight gradient, waves per workgroup: 50 = by rule (default), 51 = eight everywhere (one workgroup per CU), 52 = four wherever covered (two per CU), 53 / 54 / 55 = four on 64x32 / 32x64 / 32x32 blocks where the channels allow (tests)
   if (mode >= 59 && mode <= 63) { h2_lds_set(mode == 59 ? 4 : (mode == 60 ? 1 : (mode == 61 ? 0 : mode - 60))); return AFD_OK; }   // f16x2 tile kernel: 60 = both operands from LDS, weights by LDS-DMA (default), 61 = the register-fed kernel (before round 3's last third), 62 / 63 / 59 = LDS-fed wherever covered, the (128 px, 64 ch) / (256 px, 32 ch) / (128 px, 32 ch) workgroup first (tests)
   if (mode == 73) { h2_sk_set_mode(2); return AFD_OK; }                          // ... 73 = wherever the shape is covered (tests)
   if (mode >= 71 && mode <= 72) { h2_skw_set(mode - 70); return AFD_OK; }          // slice-walking form of the split-K kernel (conv_h2_skw, 4x4 maps): 71 = wherever the split-K kernel runs and two or more slices per wave are possible (tests), 72 = never (conv_h2_sk everywhere); 74 returns it to the rule
@@ -1103,6 +1106,12 @@ int afd_conv_wgrad_form(int B, int Cin, int Cout, int H, int W, int ksize) {
   if (wgrad_bf3_plan(B, Cin, Cout, H, W, &a, &b)) return wgrad_arith_is_bf3() ? 2 : 4;
   if (wgrad_cin3_plan(B, Cin, Cout, H, W)) return 3;
   return wgrad_wino_plan(B, Cin, Cout, H, W, &a, &b, &c, &d) ? 1 : 0;
+}
+
+int afd_conv_wgrad3_plan(int B, int Cin, int Cout, int H, int W, int* info) {
+  if (!info || B <= 0 || Cin <= 0 || Cout <= 0 || H <= 0 || W <= 0) return 0;
+  for (int i = 0; i < 5; ++i) info[i] = 0;
+  return wgrad_plan_full(B, Cin, Cout, H, W, &info[0], &info[1], &info[2], &info[3], &info[4]);
 }
 
 static int conv_wgrad_impl(const float* x, const float* dy, float* dw, float* dbias, int B, int Cin, int Cout, int H, int W,

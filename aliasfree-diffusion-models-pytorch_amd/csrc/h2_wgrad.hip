@@ -11,6 +11,9 @@
 //   NINE v_mfma_f32_16x16x32_f16 per (16-channel block, row shift) unit instead of eighteen.  Both scales follow the data
 //   (lowered when a tile / a 32-pixel step would overflow fp16, the accumulators multiplied by the ratio); before the wave
 //   groups are summed and the slab is written every wave multiplies its sums by 1 / (s_x s_d).  All factors are powers of two.
+//   A workgroup is EIGHT waves (one per CU: blocks of 64 x 64 ... 32 x 32 output x input channels) or FOUR (256 threads, two
+//   per CU or one beside a workgroup of the dependent chain: 64 x 32, 32 x 64, 32 x 32; a 64 x 64 block runs as its two 64 x 32
+//   halves, whose x scale is a maximum over 32 channels).  The plan (bf3_wgrad.hip) picks the form per layer.
 #include <algorithm>
 #include <cstdint>
 #include <cstdlib>
@@ -22,15 +25,16 @@ namespace afd {
 using f32x4 = __attribute__((ext_vector_type(4))) float;
 using u32x4 = __attribute__((ext_vector_type(4))) uint32_t;
 
-template <int S, int BN_, int BK_> struct HwGeo {
+template <int S, int BN_, int BK_, int NW_ = 8> struct HwGeo {
   static constexpr int TP = 128, G8 = S / 8;                          // pixels per tile, 8-pixel groups per row
   static constexpr int IPT = S * S >= TP ? 1 : TP / (S * S);          // images per tile
   static constexpr int R = S * S >= TP ? TP / S : S;                  // rows per image in the tile
   static constexpr int TPI = S * S >= TP ? S * S / TP : 1;            // tiles per image
   static constexpr int IG = (R + 2) * G8, NG = IPT * IG;              // groups per image incl. the two halo rows / per tile
-  static constexpr int BK = BK_, BN = BN_;
-  static constexpr int NR = (BN / 16) * (BK / 32), NSG = 8 / NR;      // wave roles, wave groups sharing a tile's steps
-  static constexpr int TASKS = (BK / 16) * NG * 16, NE = (TASKS + 511) / 512;
+  static constexpr int BK = BK_, BN = BN_, NW = NW_, NT = 64 * NW;    // waves / threads per workgroup (8 | 4)
+  static constexpr int NR = (BN / 16) * (BK / 32), NSG = NW / NR;     // wave roles, wave groups sharing a tile's steps
+  static_assert(NR <= NW && NSG * NR == NW && NSG <= 4, "block and waves per workgroup do not fit");
+  static constexpr int TASKS = (BK / 16) * NG * 16, NE = (TASKS + NT - 1) / NT;
   static constexpr int PIECE = (BK / 16) * NG * 16;                   // records per piece
 };
 
@@ -124,14 +128,14 @@ __device__ __forceinline__ void hw_rescale(f32x4 (&acc)[2][9], float& s, float m
   }
 }
 
-template <int S, int BN, int BK>
-__global__ __launch_bounds__(512, 1) void wgrad_h2(const float* __restrict__ x, const float* __restrict__ dy, float* __restrict__ part,
+template <int S, int BN, int BK, int NW>
+__global__ __launch_bounds__(64 * NW, 8 / NW) void wgrad_h2(const float* __restrict__ x, const float* __restrict__ dy, float* __restrict__ part,
                                                     int B, int K, int N, int tiles_per_split, int ntiles) {
-  using G = HwGeo<S, BN, BK>;
-  constexpr int HW = S * S, G8 = G::G8, NG = G::NG, NE = G::NE, PIECE = G::PIECE, NSG = G::NSG;
+  using G = HwGeo<S, BN, BK, NW>;
+  constexpr int HW = S * S, G8 = G::G8, NG = G::NG, NE = G::NE, PIECE = G::PIECE, NSG = G::NSG, NT = G::NT;
   extern __shared__ __attribute__((aligned(16))) uint8_t smem_raw[];
   h8* Xs = reinterpret_cast<h8*>(smem_raw);                           // [piece 2][ksub BK / 16][NG][16] records
-  float* wmax = reinterpret_cast<float*>(smem_raw + (size_t)2 * PIECE * 16);   // the eight waves' tile maxima
+  float* wmax = reinterpret_cast<float*>(smem_raw + (size_t)2 * PIECE * 16);   // the waves' tile maxima
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, l15 = lane & 15, kgl = lane >> 4;
   const int role = wv % G::NR, sg = wv / G::NR;                       // wave group sg takes steps sg, sg + NSG, ..
   const int ns = role % (BN / 16), kh = role / (BN / 16);             // this wave: output channels n0 + 16 ns .., input channels k0 + 32 kh ..
@@ -144,7 +148,7 @@ __global__ __launch_bounds__(512, 1) void wgrad_h2(const float* __restrict__ x, 
   int s_off[NE], s_rr[NE];                                            // element offset less the tile base; halo-inclusive row (-1: no task)
 #pragma unroll
   for (int e = 0; e < NE; ++e) {
-    const int t = tid + 512 * e;
+    const int t = tid + NT * e;
     s_rr[e] = -1; s_off[e] = 0;
     if (t < G::TASKS) {
       const int c16 = t & 15, g = (t >> 4) % NG, ksub = t / (16 * NG);
@@ -182,7 +186,7 @@ __global__ __launch_bounds__(512, 1) void wgrad_h2(const float* __restrict__ x, 
       if (s_rr[e] < 0) continue;
       h8 p0, p1;
       h2_split8(xr[e], s, p0, p1);
-      const int t = tid + 512 * e;
+      const int t = tid + NT * e;
       Xs[t] = p0; Xs[PIECE + t] = p1;
     }
   };
@@ -222,11 +226,11 @@ __global__ __launch_bounds__(512, 1) void wgrad_h2(const float* __restrict__ x, 
   if (tbeg < tend) { x_fetch(tbeg); d_fetch(tbeg, sg); }
   for (int tile = tbeg; tile < tend; ++tile) {
     x_amax();
-    __syncthreads();                                                   // the previous tile's fragment reads are done; the eight maxima are visible
+    __syncthreads();                                                   // the previous tile's fragment reads are done; the waves' maxima are visible
     {
       float m = wmax[0];
 #pragma unroll
-      for (int q = 1; q < 8; ++q) m = fmaxf(m, wmax[q]);
+      for (int q = 1; q < NW; ++q) m = fmaxf(m, wmax[q]);
       hw_rescale(acc, sx, m);
     }
     x_commit(sx);
@@ -272,10 +276,12 @@ __global__ __launch_bounds__(512, 1) void wgrad_h2(const float* __restrict__ x, 
 // records per piece -- the aligned pairs (rows 0-1, 2-3: row shift 0) and the odd pairs (rows -1-0, 1-2, 3-4 with the
 // outside rows zero: shifts -1 / +1).  A 128-pixel tile = 8 whole images, a 32-pixel step = 2 of them; the column shift
 // stays inside each row of four (no neighbour loads).  One staging task = one (image, channel): 16 contiguous floats.
-template <int BN, int BK>
-__global__ __launch_bounds__(512, 1) void wgrad_h2_s4(const float* __restrict__ x, const float* __restrict__ dy, float* __restrict__ part,
+template <int BN, int BK, int NW>
+__global__ __launch_bounds__(64 * NW, 8 / NW) void wgrad_h2_s4(const float* __restrict__ x, const float* __restrict__ dy, float* __restrict__ part,
                                                        int B, int K, int N, int tiles_per_split, int ntiles) {
-  constexpr int NR = (BN / 16) * (BK / 32), NSG = 8 / NR, NG = 40, PIECE = (BK / 16) * NG * 16, TASKS = 8 * BK;
+  constexpr int NR = (BN / 16) * (BK / 32), NSG = NW / NR, NG = 40, PIECE = (BK / 16) * NG * 16, TASKS = 8 * BK, NT = 64 * NW;
+  constexpr int NE = (TASKS + NT - 1) / NT;                            // staging tasks per thread
+  static_assert(NR <= NW && NSG * NR == NW && NSG <= 4, "block and waves per workgroup do not fit");
   extern __shared__ __attribute__((aligned(16))) uint8_t smem_raw[];
   h8* Xs = reinterpret_cast<h8*>(smem_raw);                           // [piece 2][ksub BK / 16][image 8][record 5][16] records
   float* wmax = reinterpret_cast<float*>(smem_raw + (size_t)2 * PIECE * 16);
@@ -287,44 +293,54 @@ __global__ __launch_bounds__(512, 1) void wgrad_h2_s4(const float* __restrict__ 
   const int split = blockIdx.x;
   const int tbeg = split * tiles_per_split, tend = min(ntiles, tbeg + tiles_per_split);
 
-  const bool has_task = tid < TASKS;
-  const int ti = tid / BK, tc = tid % BK;                              // staging task: image ti of the tile, channel tc
-  float xr[16];
+  // staging task e of this thread: image ti of the tile, channel tc (one task per thread, two in a four-wave 64-channel block)
+  auto has_task = [&](int e) { return tid + NT * e < TASKS; };
+  float xr[NE][16];
   auto x_fetch = [&](int tile) {
-    const int img = tile * 8 + ti;
-    const bool ok = has_task && img < B;
-    const float4* p = reinterpret_cast<const float4*>(x + ((long)(ok ? img : 0) * K + k0 + tc) * 16);
 #pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      const float4 v = ok ? p[q] : make_float4(0.f, 0.f, 0.f, 0.f);
-      xr[4 * q] = v.x; xr[4 * q + 1] = v.y; xr[4 * q + 2] = v.z; xr[4 * q + 3] = v.w;
+    for (int e = 0; e < NE; ++e) {
+      const int t = tid + NT * e, ti = t / BK, tc = t % BK;
+      const int img = tile * 8 + ti;
+      const bool ok = has_task(e) && img < B;
+      const float4* p = reinterpret_cast<const float4*>(x + ((long)(ok ? img : 0) * K + k0 + tc) * 16);
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        const float4 v = ok ? p[q] : make_float4(0.f, 0.f, 0.f, 0.f);
+        xr[e][4 * q] = v.x; xr[e][4 * q + 1] = v.y; xr[e][4 * q + 2] = v.z; xr[e][4 * q + 3] = v.w;
+      }
     }
   };
   auto x_amax = [&]() {
     float m = 0.f;
 #pragma unroll
-    for (int j = 0; j < 16; ++j) m = fmaxf(m, fabsf(xr[j]));             // (threads without a task hold zeros)
+    for (int e = 0; e < NE; ++e)
+#pragma unroll
+      for (int j = 0; j < 16; ++j) m = fmaxf(m, fabsf(xr[e][j]));        // (threads without a task hold zeros)
     m = wave_amax(m);
     if (lane == 0) wmax[wv] = m;
   };
   auto x_commit = [&](float s) {
-    if (!has_task) return;
-    _Float16 pc[2][16];
 #pragma unroll
-    for (int j = 0; j < 16; ++j) h2_split(xr[j], s, pc[0][j], pc[1][j]);
-    const _Float16 Z = (_Float16)0.f;
-    const int rec = (((tc >> 4) * 8 + ti) * 5) * 16 + (tc & 15);       // record 0 of this (image, channel)
+    for (int e = 0; e < NE; ++e) {
+      if (!has_task(e)) continue;
+      const int t = tid + NT * e, ti = t / BK, tc = t % BK;
+      _Float16 pc[2][16];
 #pragma unroll
-    for (int p = 0; p < 2; ++p) {
-      h8 a0, a1, o0, o1, o2;
+      for (int j = 0; j < 16; ++j) h2_split(xr[e][j], s, pc[0][j], pc[1][j]);
+      const _Float16 Z = (_Float16)0.f;
+      const int rec = (((tc >> 4) * 8 + ti) * 5) * 16 + (tc & 15);     // record 0 of this (image, channel)
 #pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        a0[j] = pc[p][j]; a1[j] = pc[p][8 + j]; o1[j] = pc[p][4 + j];
-        o0[j] = j < 4 ? Z : pc[p][j - 4];                              // rows (-1, 0)
-        o2[j] = j < 4 ? pc[p][12 + j] : Z;                             // rows (3, 4)
+      for (int p = 0; p < 2; ++p) {
+        h8 a0, a1, o0, o1, o2;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+          a0[j] = pc[p][j]; a1[j] = pc[p][8 + j]; o1[j] = pc[p][4 + j];
+          o0[j] = j < 4 ? Z : pc[p][j - 4];                            // rows (-1, 0)
+          o2[j] = j < 4 ? pc[p][12 + j] : Z;                           // rows (3, 4)
+        }
+        h8* d = Xs + p * PIECE + rec;
+        d[0] = a0; d[16] = a1; d[32] = o0; d[48] = o1; d[64] = o2;
       }
-      h8* d = Xs + p * PIECE + rec;
-      d[0] = a0; d[16] = a1; d[32] = o0; d[48] = o1; d[64] = o2;
     }
   };
 
@@ -346,10 +362,10 @@ __global__ __launch_bounds__(512, 1) void wgrad_h2_s4(const float* __restrict__ 
   const int brec0 = ((2 * kh) * NG) * 16 + l15;
 
   float sx = __uint_as_float(kH2ScaleCapBits), sd = sx;
-  if (!has_task) {
 #pragma unroll
-    for (int j = 0; j < 16; ++j) xr[j] = 0.f;
-  }
+  for (int e = 0; e < NE; ++e)
+#pragma unroll
+    for (int j = 0; j < 16; ++j) xr[e][j] = 0.f;
   if (tbeg < tend) { x_fetch(tbeg); d_fetch(tbeg, sg); }
   for (int tile = tbeg; tile < tend; ++tile) {
     x_amax();
@@ -357,7 +373,7 @@ __global__ __launch_bounds__(512, 1) void wgrad_h2_s4(const float* __restrict__ 
     {
       float m = wmax[0];
 #pragma unroll
-      for (int q = 1; q < 8; ++q) m = fmaxf(m, wmax[q]);
+      for (int q = 1; q < NW; ++q) m = fmaxf(m, wmax[q]);
       hw_rescale(acc, sx, m);
     }
     x_commit(sx);
@@ -535,49 +551,59 @@ __global__ __launch_bounds__(512, 1) void pw_wgrad_h2(const float* __restrict__ 
   }
 }
 
-// ---- host side (the plan -- tiles per split, block sizes -- is bf3_wgrad.hip's) ---------------------------------------------
-int wgrad_bf3_plan(int B, int Cin, int Cout, int H, int W, int* tps, int* ntiles);
-void wgrad_bf3_tile_for(int Cin, int Cout, long nt, int* bn, int* bk);
+// ---- host side (the plan -- tiles per split, block sizes, waves per workgroup -- is bf3_wgrad.hip's) -------------------------
+int wgrad_plan_full(int B, int Cin, int Cout, int H, int W, int* tps, int* ntiles, int* bn, int* bk, int* nw);
 
-template <int S, int BN, int BK>
+template <int S, int BN, int BK, int NW>
 static void wgrad_h2_launch_t(const float* x, const float* dy, float* part, int B, int Cin, int Cout, int tps, int nt, int splits,
                               hipStream_t s) {
-  using G = HwGeo<S, BN, BK>;
+  using G = HwGeo<S, BN, BK, NW>;
   const size_t lds = std::max((size_t)2 * G::PIECE * 16 + 32, G::NSG > 1 ? sizeof(float) * G::NR * 72 * 64 : (size_t)0);
-  (void)lds_opt_in(&wgrad_h2<S, BN, BK>, lds);                    // (> 64 KB of dynamic LDS: once per device and kernel)
-  hipLaunchKernelGGL((wgrad_h2<S, BN, BK>), dim3((unsigned)splits, (unsigned)((Cout / BN) * (Cin / BK))), dim3(512), lds, s, x, dy,
+  (void)lds_opt_in(&wgrad_h2<S, BN, BK, NW>, lds);                // (> 64 KB of dynamic LDS: once per device and kernel)
+  hipLaunchKernelGGL((wgrad_h2<S, BN, BK, NW>), dim3((unsigned)splits, (unsigned)((Cout / BN) * (Cin / BK))), dim3(G::NT), lds, s, x, dy,
                      part, B, Cin, Cout, tps, nt);
 }
 
-template <int BN, int BK>
+template <int BN, int BK, int NW>
 static void wgrad_h2_s4_launch_t(const float* x, const float* dy, float* part, int B, int Cin, int Cout, int tps, int nt, int splits,
                                  hipStream_t s) {
   constexpr int NR = (BN / 16) * (BK / 32);
-  const size_t lds = std::max((size_t)2 * (BK / 16) * 40 * 16 * 16 + 32, 8 / NR > 1 ? sizeof(float) * NR * 72 * 64 : (size_t)0);
-  (void)lds_opt_in(&wgrad_h2_s4<BN, BK>, lds);                    // (> 64 KB of dynamic LDS: once per device and kernel)
-  hipLaunchKernelGGL((wgrad_h2_s4<BN, BK>), dim3((unsigned)splits, (unsigned)((Cout / BN) * (Cin / BK))), dim3(512), lds, s, x, dy, part, B,
-                     Cin, Cout, tps, nt);
+  const size_t lds = std::max((size_t)2 * (BK / 16) * 40 * 16 * 16 + 32, NW / NR > 1 ? sizeof(float) * NR * 72 * 64 : (size_t)0);
+  (void)lds_opt_in(&wgrad_h2_s4<BN, BK, NW>, lds);                // (> 64 KB of dynamic LDS: once per device and kernel)
+  hipLaunchKernelGGL((wgrad_h2_s4<BN, BK, NW>), dim3((unsigned)splits, (unsigned)((Cout / BN) * (Cin / BK))), dim3(64 * NW), lds, s, x, dy,
+                     part, B, Cin, Cout, tps, nt);
+}
+
+// S = 0: the 4 x 4 maps' kernel
+template <int S, int BN, int BK, int NW>
+static void wgrad_h2_form_t(const float* x, const float* dy, float* part, int B, int Cin, int Cout, int tps, int nt, int splits, hipStream_t s) {
+  if constexpr (S == 0) wgrad_h2_s4_launch_t<BN, BK, NW>(x, dy, part, B, Cin, Cout, tps, nt, splits, s);
+  else wgrad_h2_launch_t<S, BN, BK, NW>(x, dy, part, B, Cin, Cout, tps, nt, splits, s);
+}
+
+template <int S>
+static void wgrad_h2_map_t(const float* x, const float* dy, float* part, int B, int Cin, int Cout, int tps, int nt, int splits, int bn, int bk,
+                           int nw, hipStream_t s) {
+  const bool n64 = bn == 64, k64 = bk == 64;
+  if (nw == 4) {                                                       // (the plan gives a four-wave workgroup no 64 x 64 block: eight roles)
+    if (n64) wgrad_h2_form_t<S, 64, 32, 4>(x, dy, part, B, Cin, Cout, tps, nt, splits, s);
+    else if (k64) wgrad_h2_form_t<S, 32, 64, 4>(x, dy, part, B, Cin, Cout, tps, nt, splits, s);
+    else wgrad_h2_form_t<S, 32, 32, 4>(x, dy, part, B, Cin, Cout, tps, nt, splits, s);
+  } else if (n64 && k64) wgrad_h2_form_t<S, 64, 64, 8>(x, dy, part, B, Cin, Cout, tps, nt, splits, s);
+  else if (n64) wgrad_h2_form_t<S, 64, 32, 8>(x, dy, part, B, Cin, Cout, tps, nt, splits, s);
+  else if (k64) wgrad_h2_form_t<S, 32, 64, 8>(x, dy, part, B, Cin, Cout, tps, nt, splits, s);
+  else wgrad_h2_form_t<S, 32, 32, 8>(x, dy, part, B, Cin, Cout, tps, nt, splits, s);
 }
 
 // writes `slabs` partial [9][Cout][Cin] slabs into part; the caller folds them
 int wgrad_h2(const float* x, const float* dy, float* part, int B, int Cin, int Cout, int H, int W, hipStream_t s) {
-  int tps, nt;
-  const int splits = wgrad_bf3_plan(B, Cin, Cout, H, W, &tps, &nt);
+  int tps, nt, bn, bk, nw;
+  const int splits = wgrad_plan_full(B, Cin, Cout, H, W, &tps, &nt, &bn, &bk, &nw);
   if (!splits) return 0;
-  int bn_, bk_;
-  wgrad_bf3_tile_for(Cin, Cout, nt, &bn_, &bk_);
-  const bool n64 = bn_ == 64, k64 = bk_ == 64;
-#define AFD_WGH(S_)                                                                                      \
-  if (n64 && k64) wgrad_h2_launch_t<S_, 64, 64>(x, dy, part, B, Cin, Cout, tps, nt, splits, s);          \
-  else if (n64) wgrad_h2_launch_t<S_, 64, 32>(x, dy, part, B, Cin, Cout, tps, nt, splits, s);            \
-  else if (k64) wgrad_h2_launch_t<S_, 32, 64>(x, dy, part, B, Cin, Cout, tps, nt, splits, s);            \
-  else wgrad_h2_launch_t<S_, 32, 32>(x, dy, part, B, Cin, Cout, tps, nt, splits, s)
-  if (W == 32) { AFD_WGH(32); } else if (W == 16) { AFD_WGH(16); } else if (W == 8) { AFD_WGH(8); }
-  else if (n64 && k64) wgrad_h2_s4_launch_t<64, 64>(x, dy, part, B, Cin, Cout, tps, nt, splits, s);
-  else if (n64) wgrad_h2_s4_launch_t<64, 32>(x, dy, part, B, Cin, Cout, tps, nt, splits, s);
-  else if (k64) wgrad_h2_s4_launch_t<32, 64>(x, dy, part, B, Cin, Cout, tps, nt, splits, s);
-  else wgrad_h2_s4_launch_t<32, 32>(x, dy, part, B, Cin, Cout, tps, nt, splits, s);
-#undef AFD_WGH
+  if (W == 32) wgrad_h2_map_t<32>(x, dy, part, B, Cin, Cout, tps, nt, splits, bn, bk, nw, s);
+  else if (W == 16) wgrad_h2_map_t<16>(x, dy, part, B, Cin, Cout, tps, nt, splits, bn, bk, nw, s);
+  else if (W == 8) wgrad_h2_map_t<8>(x, dy, part, B, Cin, Cout, tps, nt, splits, bn, bk, nw, s);
+  else wgrad_h2_map_t<0>(x, dy, part, B, Cin, Cout, tps, nt, splits, bn, bk, nw, s);
   return splits;
 }
 

@@ -830,6 +830,8 @@ class TrainStep:
             # opt-in: the 3x3 weight gradients on 160 workgroups per launch instead of one per CU -- 26 % slower alone, but beside the
             # dependent chain they leave CUs to it and write fewer slabs (step 7.14 -> 7.07 ms: csrc/bf3_wgrad.hip).  Off by default so
             # that the step and the per-kernel roofline table of bench.py run ONE plan; process-wide, like every plan switch.
+            # (Measured with the eight-wave workgroups.  The four-wave workgroups that are the default now share their CUs with
+            # the chain instead, and 160 of THEM cost the step 0.33 ms: profiles/wgrad_w4_ab.txt.)
             lib().afd_debug_conv_path(49)
         # layers per fork (AFD_WGRAD_BATCH overrides, read per step: tuning hook).  Round 3, after the convolutions moved to the
         # fp16 matrix pipe (tools/ab_env.py AFD_WGRAD_BATCH, same box): 2 / 4 / 8 / 12 / 16 -> 7.49 / 7.46 / 7.32 / 7.34 / 7.34 ms

@@ -138,6 +138,11 @@ int afd_colsum2(const float* in, float* out_a, float* out_b, int rows, int C, in
  *           73 = wherever the shape is covered, ahead of the tile kernel (tests);
  * 48 / 49 = workgroups per launch of the matrix-core 3x3 weight gradient: one per CU (256: fastest alone, default) / 160 (fastest
  *           beside the dependent chain on another stream: -1 % on the train step; training.TrainStep asks for it);
+ * 50 / 51 / 52 = waves per workgroup of the f16x2 3x3 weight gradient (csrc/h2_wgrad.hip): by the measured rule (default) /
+ *           eight everywhere (one workgroup holds a CU) / four wherever covered (two workgroups per CU, or one beside a
+ *           workgroup of the dependent chain; a 64 x 64 block becomes two 64 x 32 workgroups and half the splits) (tests);
+ *           53 / 54 / 55 = four waves on blocks of 64 x 32 / 32 x 64 / 32 x 32 (output x input channels) wherever the channel
+ *           counts allow (tests);
  * 60 / 61 = the f16x2 tile kernel's operand feed: by rule (default: both operands from LDS, the weights by LDS-DMA, where a
  *           workgroup holds one block of 32 output channels on the 32 x 32 maps; the weights straight from L2 into registers
  *           elsewhere) / always the register-fed kernel;  62 / 63 / 59 = the LDS-fed kernel wherever the shape is covered,
@@ -170,6 +175,12 @@ size_t afd_conv_wgrad_workspace_bytes(int B, int Cin, int Cout, int H, int W, in
  * backward) must be ordered on one stream, and two fold descriptors with one dst must not share an afd_fold_batched call
  * (ops.deal_lane / ops.fold_batches see to both). */
 int afd_conv_wgrad_form(int B, int Cin, int Cout, int H, int W, int ksize);
+/* the plan of the matrix-core 3x3 weight gradient (forms 2 and 4) for the shape under the current afd_debug_conv_path
+ * settings, as afd_conv_wgrad_workspace_bytes sizes it and afd_conv_wgrad launches it: returns the number of slabs (= splits
+ * over the pixel tiles; 0 = the shape does not take these forms) and fills info[0..4] = tiles per split, tiles, output
+ * channels per workgroup, input channels per workgroup, waves per workgroup (8: one workgroup per CU; 4: two).  Nothing is
+ * launched. */
+int afd_conv_wgrad3_plan(int B, int Cin, int Cout, int H, int W, int* info);
 int afd_conv_wgrad(const float* x, const float* dy, float* dw, float* dbias /* or NULL */,
                    int B, int Cin, int Cout, int H, int W, int ksize, int accumulate,
                    void* workspace, afd_stream_t stream);
