@@ -149,7 +149,7 @@ __global__ void gelu_grad_mul_gen(const float* __restrict__ u, float* __restrict
 // form of erf costs ~19 of them.  GELU(u) = u Phi(u) and GELU'(u) = Phi(u) + u phi(u): Phi and GELU' are tabulated over
 // SIGNED u on [-6, 6) as 192 cubic Hermite pieces of width 1/16 each (coefficients from fp64 erf / exp: interpolation
 // error <= 2.2e-8 and 1.2e-7, below the 6e-7 of the A&S form it replaces; beyond +-6 both are 0 / 1 to 1e-9), copied to
-// LDS by every workgroup: a lookup is fma + clamp + cvt + shift + fract, one ds_read_b128 (neighbouring pixels mostly
+// LDS by every workgroup: a lookup is mul + clamp + cvt + shift + fract, one ds_read_b128 (neighbouring pixels mostly
 // hit the same piece: broadcast) and 3 fma -- 9 vector instructions per GELU, 8 per GELU' (the unsigned |u| tables of
 // the first version needed a copysign and a recombination with u/2 on top: 11 / 10).
 // The table is produced ON THE DEVICE by a one-thread-per-piece kernel at first use -- a launch, so it is legal under
@@ -185,10 +185,23 @@ static void ensure_gelu_table(hipStream_t s) {
   // a captured launch only runs at replay: keep launching (12 us once per call) until one eager launch has happened
   if (hipStreamIsCapturing(s, &st) == hipSuccess && st == hipStreamCaptureStatusNone) done = true;
 }
-// T[piece](t), piece = floor(16 u + 96) clamped to the table, t = frac
+// T[piece](t), piece = floor(16 u) + 96 clamped to the table, t = frac(16 u).  The product 16 u is EXACT, so piece and t carry
+// no rounding of their own.  (The first form took both from one fma, 16 u + 96: for |u| < 2 that value lies in [64, 128) and
+// its half ulp of 2^-18 moves u by 2.4e-7, which GELU'' = 0.8 turns into 1.9e-7 of GELU' -- with the pieces' 1.2e-7 the
+// backward was at 2.6e-7 ... 2.8e-7 per element, above twice plain fp32 torch's error; now 2.0e-7, tests/gelu_cases.py.)
+// Same count: mul, clamp, floor-and-convert, shift (the + 96 pieces fold into the LDS read's offset), fract.  The compiler
+// only selects v_cvt_flr_i32_f32 for (int)floorf() under no-NaNs; spelled out, it is floor + convert, one instruction more.
+__device__ __forceinline__ int floor_to_int(float s) {
+  int i;
+  asm("v_cvt_flr_i32_f32 %0, %1" : "=v"(i) : "v"(s));
+  return i;
+}
+__device__ __forceinline__ float gelu_scaled(float u) {
+  return __builtin_amdgcn_fmed3f(u * kGeluScale, -kGeluOffset, kGeluOffset - 0.001f);
+}
 __device__ __forceinline__ float gelu_piece(float u, const float4* __restrict__ T) {
-  const float sx = __builtin_amdgcn_fmed3f(fmaf(u, kGeluScale, kGeluOffset), 0.f, (float)kGeluPieces - 0.001f);
-  const float4 c = T[(int)sx];
+  const float sx = gelu_scaled(u);
+  const float4 c = T[floor_to_int(sx) + kGeluPieces / 2];
   const float t = __builtin_amdgcn_fractf(sx);
   return fmaf(fmaf(fmaf(c.w, t, c.z), t, c.y), t, c.x);
 }
@@ -292,8 +305,8 @@ struct ActRow { float U[4], t[4]; float4 c[4]; };            // stage 1: filter 
 struct ActG { float g00, g01, g10, g11, g01l, g11l; };       // stage 2: GELU values + the left neighbours' odd columns
 
 __device__ __forceinline__ void act_lookup(float U, const float4* __restrict__ T, float& t, float4& c) {
-  const float sx = __builtin_amdgcn_fmed3f(fmaf(U, kGeluScale, kGeluOffset), 0.f, (float)kGeluPieces - 0.001f);
-  c = T[(int)sx];
+  const float sx = gelu_scaled(U);
+  c = T[floor_to_int(sx) + kGeluPieces / 2];
   t = __builtin_amdgcn_fractf(sx);
 }
 __device__ __forceinline__ float act_cubic(const float4& c, float t) { return fmaf(fmaf(fmaf(c.w, t, c.z), t, c.y), t, c.x); }
