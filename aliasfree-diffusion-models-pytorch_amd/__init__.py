@@ -3,7 +3,7 @@
 Public surface = the reference's Python API for the hot path:
 UNet, Diffusion, train, custom_upsample, custom_downsample, circularLowpassKernel, argument,
 set_seed, EMA, plus the engine-side helpers TrainStep / FusedAdamW / GradAllReduce / LRSchedule / DistillStep / progressive_distill /
-LossSecondMomentSampler / DeviceDataset / DeviceLoader.
+ConsistencyStep / consistency_distill / LossSecondMomentSampler / DeviceDataset / DeviceLoader.
 Device work runs in libafd_hip.so (hand-written gfx950 kernels, C ABI in include/afd.h).
 """
 from ._lib import AfdError, lib  # noqa: F401
@@ -23,7 +23,7 @@ from .unet import UNet  # noqa: F401
 from .diffusion import Diffusion  # noqa: F401
 from .training import (argument, set_seed, setup_logging, train, TrainStep, FusedAdamW, FlatParams,  # noqa: F401
                        GradAllReduce, EMA, LRSchedule, clip_coefficient, DistillStep, progressive_distill,
-                       LossSecondMomentSampler)
+                       ConsistencyStep, consistency_distill, LossSecondMomentSampler)
 
 from .tasks import (bpd_results, ddpm_run, edit_results, equivariance_results, fidelity_results, ilvr_results,  # noqa: F401
                     inpaint_results, likelihood_results, manifold_results, posterior_results, reconstruct_results, restoration_results,

@@ -491,6 +491,92 @@ __global__ __launch_bounds__(256) void distill_target_k(const float* out2, const
   });
 }
 
+// ---- consistency distillation (Song et al. 2023; Luo et al. 2023): the consistency function, its target and the sampler's step ----
+// coef: the (T, 2) fp64 table [c_skip, c_out] of Diffusion.consistency_coefficients, row 0 exactly (1, 0).  With x_hat the split
+// above (distill_split) of a raw output p at z on level t:
+//   f(z, t)   = c_skip[t] z + c_out[t] x_hat(p, z; t)                   (consistency_fn_k, consistency_step_k)
+//   f_tgt     = f(z_prev, t_prev) of the target network's output         (consistency_target_k)
+//   x_tilde   = (f_tgt - c_skip[t] z_t) / c_out[t]
+//   eps_tilde = (z_t - al x_tilde) / sg
+// so that a student predicting x_tilde at (z_t, t) has f(z_t, t) = f_tgt.  Where c_out == 0 (t = 0, the boundary) f IS z: p is
+// not used there, whatever it holds (a product 0 * NaN would poison the row).  fp64 per element as above, one rounding on the store.
+struct Consist64 {
+  double cs, co;
+};
+__device__ __forceinline__ Consist64 consist64(const double* __restrict__ coef, long t) { return Consist64{coef[2 * t], coef[2 * t + 1]}; }
+// f in fp64 (c.co != 0)
+__device__ __forceinline__ double consistency_f64(int kind, float p, float z, const Level64& k, const Consist64& c) {
+  double x, e;
+  distill_split(kind, (double)p, (double)z, k, x, e);
+  return c.cs * (double)z + c.co * x;
+}
+// f rounded once; z's own bits at the boundary
+__device__ __forceinline__ float consistency_f(int kind, float p, float z, const Level64& k, const Consist64& c) {
+  return c.co == 0.0 ? z : (float)consistency_f64(kind, p, z, k, c);
+}
+template <bool VEC>
+__global__ __launch_bounds__(256) void consistency_fn_k(const float* out, const float* z_in, const int64_t* __restrict__ t,
+                                                        const float* __restrict__ alpha_hat, const double* __restrict__ coef, int kind,
+                                                        float* f_out, long items, long segs, long chw) {
+  for_row_quads(items, segs, chw, [&](const RowQuad& rq) {
+    const long tb = t[rq.b];
+    const Level64 k = level64(alpha_hat, tb);
+    const Consist64 c = consist64(coef, tb);
+    if (rq.left <= 0) return;
+    const float4 p = load_quad<VEC>(out, rq.o, rq.left), z = load_quad<VEC>(z_in, rq.o, rq.left);
+    store_quad<VEC>(f_out, rq.o, rq.left, quad_map([&](float pi, float zi) { return consistency_f(kind, pi, zi, k, c); }, p, z));
+  });
+}
+template <bool VEC>
+__global__ __launch_bounds__(256) void consistency_target_k(const float* out_tgt, const float* z_prev, const float* z_t,
+                                                            const int64_t* __restrict__ t, const int64_t* __restrict__ t_prev,
+                                                            const float* __restrict__ alpha_hat, const double* __restrict__ coef,
+                                                            int kind, float* x_tilde, float* eps_tilde, long items, long segs,
+                                                            long chw) {
+  for_row_quads(items, segs, chw, [&](const RowQuad& rq) {
+    const long tb = t[rq.b], tp = t_prev[rq.b];
+    const Level64 k = level64(alpha_hat, tb), n = level64(alpha_hat, tp);
+    const Consist64 c = consist64(coef, tb), cn = consist64(coef, tp);
+    if (rq.left <= 0) return;
+    const float4 p = load_quad<VEC>(out_tgt, rq.o, rq.left), zp = load_quad<VEC>(z_prev, rq.o, rq.left);
+    const float4 z = load_quad<VEC>(z_t, rq.o, rq.left);
+    float xs[4], es[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const double zi = (double)lane(z, i);
+      const double f = cn.co == 0.0 ? (double)lane(zp, i) : consistency_f64(kind, lane(p, i), lane(zp, i), n, cn);
+      const double x = (f - c.cs * zi) / c.co;
+      xs[i] = (float)x;
+      es[i] = (float)((zi - k.al * x) / k.sg);
+    }
+    store_quad<VEC>(x_tilde, rq.o, rq.left, make_float4(xs[0], xs[1], xs[2], xs[3]));
+    store_quad<VEC>(eps_tilde, rq.o, rq.left, make_float4(es[0], es[1], es[2], es[3]));
+  });
+}
+// the sampler's move at one level for every row: f rounded to fp32, then afd_noise_images' fp32 expression towards t_next
+// (`noised`), or f itself at t_next == 0.  t / t_next come from the host or, DEV, from element 0 of t_dev / t_next_dev.
+template <bool VEC>
+__global__ __launch_bounds__(256) void consistency_step_k(const float* out, const float* z_in, const float* noise,
+                                                          const float* __restrict__ alpha_hat, const double* __restrict__ coef, int kind,
+                                                          int t_host, int t_next_host, const int64_t* __restrict__ t_dev,
+                                                          const int64_t* __restrict__ t_next_dev, float* x_out, long items, long segs,
+                                                          long chw) {
+  const long t = t_dev ? (long)t_dev[0] : t_host, tn = t_next_dev ? (long)t_next_dev[0] : t_next_host;
+  const Level64 k = level64(alpha_hat, t);
+  const Consist64 c = consist64(coef, t);
+  const Roots r = roots(alpha_hat[tn]);
+  const bool renoise = tn > 0, has_noise = noise != nullptr;
+  for_row_quads(items, segs, chw, [&](const RowQuad& rq) {
+    if (rq.left <= 0) return;
+    const float4 p = load_quad<VEC>(out, rq.o, rq.left), z = load_quad<VEC>(z_in, rq.o, rq.left);
+    const float4 nz = renoise && has_noise ? load_quad<VEC>(noise, rq.o, rq.left) : make_float4(0.f, 0.f, 0.f, 0.f);
+    store_quad<VEC>(x_out, rq.o, rq.left, quad_map([&](float pi, float zi, float ni) {
+                      const float f = consistency_f(kind, pi, zi, k, c);
+                      return renoise ? noised(r.sa, r.sb, f, ni) : f;
+                    }, p, z, nz));
+  });
+}
+
 }  // namespace afd
 using namespace afd;
 
@@ -621,6 +707,69 @@ int afd_distill_target(const float* out2, const float* z_mid, const float* z_t, 
   launch_vec(vec_ok(chw, {out2, z_mid, z_t, x_tilde, eps_tilde}), distill_target_k<true>, distill_target_k<false>, g.grid, as_stream(st),
              out2, z_mid, z_t, t, t_mid, t_prev, alpha_hat, kind, x_tilde, eps_tilde, g.items, g.segs, chw);
   return check_launch("afd_distill_target");
+}
+
+// ---- consistency distillation --------------------------------------------------------------------------------------------------
+int afd_consistency_fn(const float* out, const float* z, const int64_t* t, const float* alpha_hat, const double* coef, int kind,
+                       float* f_out, long B, long chw, afd_stream_t st) {
+  AFD_REQUIRE(out && z && t && alpha_hat && coef && f_out,
+              "afd_consistency_fn: out, z, t, alpha_hat, coef and f_out must not be NULL");
+  AFD_REQUIRE_KIND("afd_consistency_fn", kind);
+  AFD_REQUIRE_B_CHW("afd_consistency_fn", B, chw);
+  const long fb = B * chw * kF;
+  AFD_REQUIRE(same_or_apart(f_out, fb, {out, z}) && all_apart({{f_out, fb}}, {{t, B * kI}}),
+              "afd_consistency_fn: f_out must be out or z itself or apart from them, and must not overlap t");
+  const RowQuadGrid g(B, chw, kObjBlocks);
+  launch_vec(vec_ok(chw, {out, z, f_out}), consistency_fn_k<true>, consistency_fn_k<false>, g.grid, as_stream(st), out, z, t, alpha_hat,
+             coef, kind, f_out, g.items, g.segs, chw);
+  return check_launch("afd_consistency_fn");
+}
+int afd_consistency_target(const float* out_tgt, const float* z_prev, const float* z_t, const int64_t* t, const int64_t* t_prev,
+                           const float* alpha_hat, const double* coef, int kind, float* x_tilde, float* eps_tilde, long B, long chw,
+                           afd_stream_t st) {
+  AFD_REQUIRE(out_tgt && z_prev && z_t && t && t_prev && alpha_hat && coef && x_tilde && eps_tilde,
+              "afd_consistency_target: out_tgt, z_prev, z_t, t, t_prev, alpha_hat, coef, x_tilde and eps_tilde must not be NULL");
+  AFD_REQUIRE_KIND("afd_consistency_target", kind);
+  AFD_REQUIRE_B_CHW("afd_consistency_target", B, chw);
+  const long fb = B * chw * kF, ib = B * kI;
+  AFD_REQUIRE(same_or_apart(x_tilde, fb, {out_tgt, z_prev, z_t}) && same_or_apart(eps_tilde, fb, {out_tgt, z_prev, z_t}) &&
+                  all_apart({{x_tilde, fb}, {eps_tilde, fb}}, {{t, ib}, {t_prev, ib}}),
+              "afd_consistency_target: x_tilde and eps_tilde must each be an input itself or apart from it, and must not overlap "
+              "each other, t or t_prev");
+  const RowQuadGrid g(B, chw, kObjBlocks);
+  launch_vec(vec_ok(chw, {out_tgt, z_prev, z_t, x_tilde, eps_tilde}), consistency_target_k<true>, consistency_target_k<false>, g.grid,
+             as_stream(st), out_tgt, z_prev, z_t, t, t_prev, alpha_hat, coef, kind, x_tilde, eps_tilde, g.items, g.segs, chw);
+  return check_launch("afd_consistency_target");
+}
+// the two step entry points: t / t_next from the host, or read on the device (dev)
+static int consistency_step(const char* name, bool dev, const float* out, const float* z, const float* noise, const float* alpha_hat,
+                            const double* coef, int kind, int t, int t_next, const int64_t* t_dev, const int64_t* t_next_dev,
+                            float* x_out, long n_rows, long chw, afd_stream_t st) {
+  AFD_REQUIRE(out && z && alpha_hat && coef && x_out && (!dev || (t_dev && t_next_dev)),
+              "%s: out, z, alpha_hat, coef%s and x_out must not be NULL", name, dev ? ", t_dev, t_next_dev" : "");
+  AFD_REQUIRE_KIND(name, kind);
+  AFD_REQUIRE_B_CHW(name, n_rows, chw);
+  AFD_REQUIRE(dev || (t_next >= 0 && t_next < t), "%s: need 0 <= t_next < t (got t = %d, t_next = %d)", name, t, t_next);
+  AFD_REQUIRE(dev || noise || t_next == 0, "%s: noise must not be NULL unless t_next == 0", name);
+  const long fb = n_rows * chw * kF;
+  AFD_REQUIRE(same_or_apart(x_out, fb, {out, z}) && all_apart({{x_out, fb}}, {{noise, fb}, {t_dev, kI}, {t_next_dev, kI}}),
+              "%s: x_out must be out or z itself or apart from them, and must not overlap noise%s", name,
+              dev ? ", t_dev or t_next_dev" : "");
+  const RowQuadGrid g(n_rows, chw, kObjBlocks);
+  launch_vec(vec_ok(chw, {out, z, noise, x_out}), consistency_step_k<true>, consistency_step_k<false>, g.grid, as_stream(st), out, z,
+             noise, alpha_hat, coef, kind, t, t_next, t_dev, t_next_dev, x_out, g.items, g.segs, chw);
+  return check_launch(name);
+}
+int afd_consistency_step(const float* out, const float* z, const float* noise, const float* alpha_hat, const double* coef, int kind,
+                         int t, int t_next, float* x_out, long n_rows, long chw, afd_stream_t st) {
+  return consistency_step("afd_consistency_step", false, out, z, noise, alpha_hat, coef, kind, t, t_next, nullptr, nullptr, x_out,
+                          n_rows, chw, st);
+}
+int afd_consistency_step_dev(const float* out, const float* z, const float* noise, const float* alpha_hat, const double* coef,
+                             int kind, const int64_t* t_dev, const int64_t* t_next_dev, float* x_out, long n_rows, long chw,
+                             afd_stream_t st) {
+  return consistency_step("afd_consistency_step_dev", true, out, z, noise, alpha_hat, coef, kind, 0, 0, t_dev, t_next_dev, x_out,
+                          n_rows, chw, st);
 }
 
 // ---- likelihood (bits/dim) ------------------------------------------------------------------------------------------------

@@ -261,6 +261,129 @@ class Diffusion:
             x_tilde, eps_tilde = ops.distill_target(out2, z_mid, z_t, t, t_mid, t_prev, self.alpha_hat, self.prediction)
         return x_tilde, eps_tilde, t
 
+    # Consistency distillation (Song et al. 2023; Luo et al. 2023) --------------------------------------------------------------------
+    def consistency_coefficients(self, sigma_data=0.5, timestep_scaling=10.0):
+        """(T, 2) fp64 host table [c_skip, c_out] of the consistency parametrisation (LCM's form), with sd = sigma_data and
+        s = timestep_scaling:  c_skip[t] = sd^2 / ((s t)^2 + sd^2),  c_out[t] = s t / sqrt((s t)^2 + sd^2).  Row 0 is exactly
+        (1, 0), the boundary condition: the consistency function f(z, t) = c_skip[t] z + c_out[t] x_hat(z, t) is the identity at
+        t = 0, whatever the model.  c_skip strictly decreases and c_out strictly increases with t."""
+        for name, v in (("sigma_data", sigma_data), ("timestep_scaling", timestep_scaling)):
+            if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not math.isfinite(v) or not v > 0:
+                raise ValueError(f"Diffusion.consistency_coefficients: {name} must be a finite number > 0 (got {v!r})")
+        sd2 = float(sigma_data) ** 2
+        st = float(timestep_scaling) * torch.arange(self.noise_steps, dtype=torch.float64)
+        d = st * st + sd2
+        return torch.stack([sd2 / d, st / torch.sqrt(d)], dim=1).contiguous()
+
+    def _cm(self, sigma_data=0.5, timestep_scaling=10.0):
+        """`consistency_coefficients` on the device, built once per (sigma_data, timestep_scaling)."""
+        cache = self.__dict__.setdefault("_cm_dev", {})
+        key = (float(sigma_data), float(timestep_scaling))
+        if key not in cache:
+            cache[key] = self.consistency_coefficients(sigma_data, timestep_scaling).to(self.device).contiguous()
+        return cache[key]
+
+    def consistency_levels(self, chain):
+        """The per-position timestep tables of a consistency distillation over the teacher's DDIM `chain` (an explicit strictly
+        decreasing sequence of ints in [1, T - 1], any length N >= 1, validated as `sample(steps=chain)` validates it).  With the
+        levels L = chain + [0], position k is the teacher's step L[k] -> L[k + 1]: -> (t, t_prev), two (N,) int64 host tensors.
+        ValueError also when alpha_hat does not strictly decrease along the levels."""
+        if isinstance(chain, (int, np.integer)):
+            raise ValueError("Diffusion.consistency_levels: chain must be an explicit sequence of timesteps (e.g. ddim_timesteps(S))")
+        levels = [t for t, _ in self._ddim_pairs(chain, 0.0)] + [0]
+        a = self.alpha_hat.detach().cpu().double()[levels].tolist()      # (level 0 is alpha_hat[0], as the DDIM step reads it)
+        if any(lo >= hi for lo, hi in zip(a, a[1:])):
+            raise ValueError("Diffusion.consistency_levels: alpha_hat must strictly decrease with t along the chain's levels")
+        as_t = lambda v: torch.tensor(v, dtype=torch.long)
+        return as_t(levels[:-1]), as_t(levels[1:])
+
+    def consistency_targets(self, teacher, target_model, x0, k, chain, coef, eps=None, y=None):
+        """-> (x_tilde, eps_tilde, t): the consistency-distillation target of each row of x0 (B, C, H, W on the device) at position
+        k[b] of the teacher's `chain` (`consistency_levels`).  z_t = noise_images(x0, t, eps); one deterministic DDIM step of the
+        frozen teacher, t -> t_prev (ops.distill_mid); one forward of the target network at (z_prev, t_prev); then
+        ops.consistency_target: the x0 (and the eps re-forming z_t with it) that a student must predict at (z_t, t) for its
+        consistency function to equal the target network's at (z_prev, t_prev) (afd.h has the expressions).  Two forwards and three
+        elementwise launches, under no_grad, both models hinted and in eval mode; their modes are put back also after an exception.
+        TrainStep(x_tilde, t, eps_tilde) re-forms z_t and trains towards training_target(x_tilde, eps_tilde, t).
+        k: (B,) integer tensor (host or device) or a (t, t_prev) tuple of (B,) int64 device tensors already gathered
+        (ConsistencyStep).  coef: the (T, 2) fp64 device table (`consistency_coefficients` on the device).  eps: injected noise,
+        default the device generator's; y: class labels handed to both forwards."""
+        if self.variance == "learned":
+            raise ValueError("Diffusion.consistency_targets: variance='learned' is not supported (the consistency function is "
+                             "deterministic; distilling a learned variance is out of scope)")
+        if isinstance(k, tuple):
+            t, t_prev = k
+        else:
+            tabs = self.consistency_levels(chain)
+            k = torch.as_tensor(k)
+            if k.dtype.is_floating_point or k.dtype == torch.bool or tuple(k.shape) != (x0.shape[0],):
+                raise ValueError(f"Diffusion.consistency_targets: k must hold {x0.shape[0]} integer positions, one per row")
+            kh = k.cpu().long()
+            if int(kh.min()) < 0 or int(kh.max()) >= tabs[0].numel():
+                raise ValueError(f"Diffusion.consistency_targets: every position must lie in [0, {tabs[0].numel()}) (got {kh.tolist()})")
+            t, t_prev = (tab[kh].to(x0.device).contiguous() for tab in tabs)
+        with self._model_scope(teacher, leave_training=False), self._model_scope(target_model, leave_training=False):
+            x0 = x0.contiguous()
+            z_t, _ = self.noise_images(x0, t, eps)
+            out = self._raw_output(teacher, z_t, t, y)
+            z_prev = ops.distill_mid(out, z_t, t, t_prev, self.alpha_hat, self.prediction)
+            out_tgt = self._raw_output(target_model, z_prev, t_prev, y)
+            x_tilde, eps_tilde = ops.consistency_target(out_tgt, z_prev, z_t, t, t_prev, self.alpha_hat, coef, self.prediction)
+        return x_tilde, eps_tilde, t
+
+    def consistency_sample(self, model, n, image_channels, steps, noise_source="reference", graph=None, labels=None,
+                           return_float=False, sigma_data=0.5, timestep_scaling=10.0):
+        """Few-step sampling of a consistency model (`ConsistencyStep`, `consistency_distill`): multistep consistency sampling.
+        steps: an int S (the timesteps `ddim_timesteps(S)`) or an explicit strictly decreasing sequence of timesteps in
+        [1, T - 1]; [T - 1] alone is one-step generation.  x starts as the initial noise at steps[0]; every step runs ONE forward
+        at (x, t) and one fused launch (ops.consistency_step): x <- f(x, t) noised again to the next timestep with fresh noise
+        (`_step_noise`), and x <- f(x, t) itself at the last step.  More steps trade time for quality with no retraining.
+        sigma_data / timestep_scaling: those the model was distilled with (`consistency_coefficients`).  noise_source, labels,
+        return_float and the snapshots are `sample`'s for DDIM; graph=True captures one step (forward, device noise, the update
+        with t and the next timestep read on the device) and replays it for every step but the last, as the DDIM loop does.
+        Guidance is not offered."""
+        logging.info(f"Sampling {n} new images....")
+        if self.variance == "learned":
+            raise ValueError("Diffusion.consistency_sample: variance='learned' is not supported")
+        pairs = self._ddim_pairs(steps, 0.0)
+        self.consistency_coefficients(sigma_data, timestep_scaling)                      # (argument errors before device work)
+        if labels is not None:
+            labels = self._check_labels(model, n, None, labels, "consistency_sample")
+        coef = self._cm(sigma_data, timestep_scaling)
+        self.check_model(model, image_channels, "Diffusion.consistency_sample")
+        kind, ah = self.prediction, self.alpha_hat
+        snaps = []
+        with self._model_scope(model):
+            x = self._initial_noise(n, image_channels, noise_source)
+
+            def step(t_rows, t, tn, draw):
+                out = self._raw_output(model, x, t_rows, labels)
+                if isinstance(t, torch.Tensor):
+                    ops.consistency_step_dev(out, x, draw(), ah, coef, kind, t, tn, x)
+                else:
+                    ops.consistency_step(out, x, draw() if draw else None, ah, coef, kind, t, tn, x_out=x)
+
+            replay = None
+            if graph and noise_source != "cpu" and len(pairs) > 1:
+                t_dev = torch.full((n,), pairs[0][0], device=x.device, dtype=torch.long)
+                tn_dev = torch.full((1,), pairs[0][1], device=x.device, dtype=torch.long)
+                g = self._capture(lambda: step(t_dev, t_dev, tn_dev, lambda: torch.randn_like(x)), x)
+
+                def replay(t, tn):
+                    t_dev.fill_(t)
+                    tn_dev.fill_(tn)
+                    g.replay()
+            for t, tn in pairs:
+                if replay is not None and tn > 0:
+                    replay(t, tn)
+                else:
+                    step(self._t_full(n, t, x.device), t, tn, (lambda: self._step_noise(x, noise_source)) if tn > 0 else None)
+                if self.ddim_snapshot(t, tn):
+                    snaps.append(x.clone())
+            x = x.clone()
+        snaps.append(x)
+        return self._finish(x, snaps, return_float)
+
     # F14 ---------------------------------------------------------------------------------
     def noise_images(self, x, t, eps=None):
         """-> (x_t, eps).  `eps` may be injected (parity mode); default = device RNG like the reference."""

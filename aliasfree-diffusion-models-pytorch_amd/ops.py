@@ -1852,6 +1852,76 @@ def distill_target(out2, z_mid, z_t, t, t_mid, t_prev, alpha_hat, kind, x_out=No
     return x_out, eps_out
 
 
+# ---- consistency distillation: the consistency function, its target and the sampler's step (include/afd.h has the expressions) ----
+def _consistency_coef(what, coef, alpha_hat):
+    """coef: the (T, 2) fp64 device table [c_skip, c_out] of `Diffusion.consistency_coefficients`"""
+    T = alpha_hat.numel()
+    if (not isinstance(coef, torch.Tensor) or not coef.is_cuda or coef.dtype != torch.float64 or tuple(coef.shape) != (T, 2)
+            or not coef.is_contiguous()):
+        raise AfdError(f"afdm: {what}: coef must be the contiguous ({T}, 2) float64 device table of Diffusion.consistency_coefficients")
+
+
+def consistency_fn(out, z, t, alpha_hat, coef, kind, f_out=None):
+    """The raw output `out` at (z, t) with per-row timesteps t (int64, on the device) -> f = c_skip[t] z + c_out[t] x_hat, fp64 per
+    element and rounded once; z's bits where c_out[t] == 0 (t = 0), whatever `out` holds there; one launch (afd.h:
+    afd_consistency_fn).  f_out may be out or z (in place)."""
+    f_out = torch.empty_like(out) if f_out is None else f_out
+    code, B, chw = _objective_args("consistency_fn", kind, t, alpha_hat, out, z, f_out)
+    _consistency_coef("consistency_fn", coef, alpha_hat)
+    lib().afd_consistency_fn(_p(out), _p(z), _p(t), _p(alpha_hat), _p(coef), code, _p(f_out), B, chw, _stream())
+    return f_out
+
+
+def consistency_target(out_tgt, z_prev, z_t, t, t_prev, alpha_hat, coef, kind, x_out=None, eps_out=None):
+    """The target network's raw output `out_tgt` at (z_prev, t_prev) -> (x_tilde, eps_tilde): the x0 a student must predict at
+    (z_t, t) for its consistency function to equal the target's f(z_prev, t_prev), and the eps that re-forms z_t with it; fp64 per
+    element, rounded once; one launch (afd.h: afd_consistency_target).  Needs t >= 1 and t_prev < t per row (read on the device,
+    unchecked); at t_prev == 0 the target is z_prev itself and out_tgt is not used.  x_out / eps_out may each be one of out_tgt,
+    z_prev, z_t."""
+    x_out = torch.empty_like(out_tgt) if x_out is None else x_out
+    eps_out = torch.empty_like(out_tgt) if eps_out is None else eps_out
+    code, B, chw = _objective_args("consistency_target", kind, t, alpha_hat, out_tgt, z_prev, z_t, x_out, eps_out)
+    _row_t_and_table("consistency_target", t_prev, alpha_hat, B)
+    _consistency_coef("consistency_target", coef, alpha_hat)
+    lib().afd_consistency_target(_p(out_tgt), _p(z_prev), _p(z_t), _p(t), _p(t_prev), _p(alpha_hat), _p(coef), code, _p(x_out),
+                                 _p(eps_out), B, chw, _stream())
+    return x_out, eps_out
+
+
+def _consistency_step_args(what, out, z, noise, alpha_hat, coef, kind, x_out):
+    tensors = tuple(o for o in (out, z, noise, x_out) if o is not None)
+    first = _pred_tensors(what, kind, (alpha_hat,), tensors, 1, "(n, ...)")
+    if alpha_hat.dim() != 1 or not alpha_hat.is_contiguous():
+        raise AfdError(f"afdm: {what}: alpha_hat must be a contiguous (T,) table")
+    _consistency_coef(what, coef, alpha_hat)
+    n = first.shape[0]
+    return PRED_KINDS[kind], n, first.numel() // n
+
+
+def consistency_step(out, z, noise, alpha_hat, coef, kind, t, t_next, x_out=None):
+    """The consistency sampler's move at level t for every row: f = consistency_fn(out, z, t), then x_out = f at t_next == 0 (noise
+    may be None) and noise_images(f, noise, t_next) otherwise, with the bits of those two calls, in one launch (afd.h:
+    afd_consistency_step).  x_out may be z or out (in place)."""
+    x_out = torch.empty_like(z) if x_out is None else x_out
+    code, n, chw = _consistency_step_args("consistency_step", out, z, noise, alpha_hat, coef, kind, x_out)
+    t, t_next = int(t), int(t_next)
+    if not 0 <= t_next < t < alpha_hat.numel():
+        raise AfdError(f"afdm: consistency_step needs 0 <= t_next < t < {alpha_hat.numel()} (got t = {t}, t_next = {t_next})")
+    if noise is None and t_next > 0:
+        raise AfdError("afdm: consistency_step needs noise unless t_next == 0")
+    lib().afd_consistency_step(_p(out), _p(z), _p(noise), _p(alpha_hat), _p(coef), code, t, t_next, _p(x_out), n, chw, _stream())
+    return x_out
+
+
+def consistency_step_dev(out, z, noise, alpha_hat, coef, kind, t_dev, t_next_dev, x_out):
+    """consistency_step with t = t_dev[0] and t_next = t_next_dev[0] read on the device (graph-replayable)."""
+    code, n, chw = _consistency_step_args("consistency_step", out, z, noise, alpha_hat, coef, kind, x_out)
+    _ddim_dev_t("consistency_step", t_dev, t_next_dev)
+    lib().afd_consistency_step_dev(_p(out), _p(z), _p(noise), _p(alpha_hat), _p(coef), code, _p(t_dev), _p(t_next_dev), _p(x_out), n,
+                                   chw, _stream())
+    return x_out
+
+
 # ---- learned reverse-process variances and the hybrid loss (include/afd.h gives the exact expressions) ----------------------
 def _lvar_args(what, kind, out2, t, alpha_hat, lv_coef, *tensors, rows2=1):
     """-> (AFD_PRED_* code, B, chw): out2 is the contiguous (rows2 * B, 2C, ...) output of a learned-variance network, `tensors`

@@ -15,7 +15,8 @@ import torch
 from .data import (DeviceDataset, get_data, get_data_MNIST, get_data_device, get_data_MNIST_device, make_collage,
                    normalisation_table, save_dataset_MNIST, save_gen_images)
 from .diffusion import Diffusion
-from .training import argument, diffusion_kwargs, ema_path, model_out_channels, progressive_distill, set_seed, train
+from .training import (argument, consistency_distill, diffusion_kwargs, ema_path, model_out_channels, progressive_distill, set_seed,
+                       train)
 from .unet import UNet
 
 
@@ -83,6 +84,8 @@ def ddpm_run(params):
     data_keys = [k for k in DATA_KEYS if params.get(k) is not None]
     if params.get("distill") is not None:
         _distill_cfg(params)                                   # a malformed key fails here, not after the training
+    if params.get("consistency") is not None:
+        _consistency_cfg(params)                               # (same rule)
     evals = _eval_cfgs(params)                                 # (and so does a malformed evaluation key: EVALS)
     cwd = os.getcwd()
     modelpath = os.path.join(cwd, f"models/DDPM_Uncondtional_{name}_{v}/ckpt_{name}_{v}.pt")
@@ -176,11 +179,19 @@ def ddpm_run(params):
     distill = None
     if params.get("distill") is not None:
         distill, gen_model, gen_kw = _distill(params, args, diffusion, gen_model, modelpath, name, seed, dataloader)
+    # optional consistency distillation: params["consistency"] = {"steps", "iters", "sample_steps", "lr", "target_beta"} distils the
+    # model the image set is drawn from over its DDIM chain of "steps" steps in one run of "iters" iterations
+    # (training.consistency_distill; "lr" defaults to the run's, "target_beta" to 0.95), saves the target network beside the
+    # checkpoint and draws the image set from it with diffusion.consistency_sample(steps=sample_steps)
+    consistency, draw = None, diffusion.sample
+    if params.get("consistency") is not None:
+        consistency, gen_model, gen_kw = _consistency(params, args, diffusion, gen_model, modelpath, name, seed, dataloader)
+        draw = diffusion.consistency_sample
     keep_n = max([cfg["n"] for e, cfg in evals.items() if e.samples], default=0)
     generated = []                                             # the first images of the set that an evaluation asks for, uint8 as sampled
     for start in np.arange(0, params["gen_total"], params["gen_per_batch"]):
         fileno = np.arange(start, start + params["gen_per_batch"], 1)
-        xg, _ = diffusion.sample(gen_model, n=params["gen_per_batch"], image_channels=args.image_channels, **gen_kw)
+        xg, _ = draw(gen_model, n=params["gen_per_batch"], image_channels=args.image_channels, **gen_kw)
         save_gen_images(gen_dir, xg, fileno)
         if start < keep_n:
             generated.append(xg[:keep_n - start])
@@ -192,6 +203,8 @@ def ddpm_run(params):
         out["ema_modelpath"] = ema_path(modelpath)
     if distill is not None:
         out["distill"] = distill
+    if consistency is not None:
+        out["consistency"] = consistency
     dev_set = dataset if isinstance(dataset, DeviceDataset) else None      # (the host path loads its data set again, as before)
     ctx = EvalContext(params, args, diffusion, gen_model, run_dir, name, v, seed, dev_set, torch.cat(generated) if generated else None)
     for e, cfg in evals.items():
@@ -211,6 +224,38 @@ def _distill_cfg(params):
     if unknown or not {"start_steps", "end_steps", "iters"} <= set(cfg):
         raise ValueError(f"ddpm_run: distill needs start_steps, end_steps and iters (and optionally lr); got {sorted(cfg)}")
     return cfg
+
+
+def consistency_path(model_path, steps):
+    """Where `ddpm_run` writes a consistency model beside a checkpoint: ckpt_X.pt -> ckpt_X_consistency{steps}.pt."""
+    root, ext = os.path.splitext(model_path)
+    return f"{root}_consistency{int(steps)}{ext}"
+
+
+def _consistency_cfg(params):
+    cfg = params["consistency"]
+    if not isinstance(cfg, dict):
+        raise ValueError(f"ddpm_run: consistency must be a dict with steps, iters and sample_steps (got {type(cfg).__name__})")
+    cfg = dict(cfg)
+    unknown = sorted(set(cfg) - {"steps", "iters", "sample_steps", "lr", "target_beta"})
+    if unknown or not {"steps", "iters", "sample_steps"} <= set(cfg):
+        raise ValueError(f"ddpm_run: consistency needs steps, iters and sample_steps (and optionally lr, target_beta); got {sorted(cfg)}")
+    if params.get("distill") is not None:
+        raise ValueError("ddpm_run: distill and consistency both replace the model the image set is drawn from: pass one of them")
+    return cfg
+
+
+def _consistency(params, args, diffusion, model, modelpath, name, seed, device_loader=None):
+    """-> (out["consistency"], the target network, the sampler arguments of the image set).  device_loader: as for `_distill`."""
+    cfg = _consistency_cfg(params)
+    set_seed(seed)
+    loader = device_loader if params.get("device_loader") else _loader(name, args)[0]
+    kw = {} if cfg.get("target_beta") is None else {"target_beta": cfg["target_beta"]}
+    net, info = consistency_distill(model, diffusion, loader, cfg["steps"], cfg["iters"], args.lr if cfg.get("lr") is None else cfg["lr"],
+                                    args.device, **kw)
+    path = consistency_path(modelpath, cfg["steps"])
+    torch.save(net.state_dict(), path)
+    return dict(info, modelpath=path, sample_steps=cfg["sample_steps"]), net, {"steps": cfg["sample_steps"]}
 
 
 def _distill(params, args, diffusion, model, modelpath, name, seed, device_loader=None):

@@ -1142,6 +1142,111 @@ def progressive_distill(model, diffusion, dataloader, start_steps, end_steps, it
     return teacher, rounds
 
 
+class ConsistencyStep:
+    """One training step of consistency distillation (Song et al. 2023; Luo et al. 2023 for this discrete-time form over a DDIM
+    chain with skipped steps): the student's consistency function f(z_t, t) = c_skip[t] z_t + c_out[t] x_hat(z_t, t) learns to
+    equal the TARGET network's f at the point one teacher DDIM step further down the chain, f(z_prev, t_prev), so that in the end
+    every point of a trajectory maps to its origin and the student samples in 1 to 4 forwards (`Diffusion.consistency_sample`).
+    Per call: draw a position k of `chain` per row, gather (t, t_prev) on the device, `diffusion.consistency_targets` (one eager
+    teacher forward and one of the target network, under no_grad, and three elementwise launches), then the inner TrainStep on
+    (x_tilde, t, eps_tilde): it re-forms z_t and trains towards diffusion.training_target(x_tilde, eps_tilde, t), so every
+    TrainStep launch mode (graph=False | True | "lanes"), clipping, schedules, conditional= and data parallelism work as they
+    are.  The target network `.target` is a deep copy of the student, kept as the exponential moving average of its weights with
+    rate target_beta by the EMA fused into the inner step's AdamW launch (ema_start = 0): no extra launch.  It is the network to
+    sample from.  The loss weight is a choice of the paper's lambda(t_n): the "truncated_snr" table on the x0 error, on which the
+    squared distance between the two f is c_out[t]^2 times the x0 error.  The teacher's parameters are never touched.  `.step` is
+    the inner TrainStep."""
+
+    def __init__(self, student, teacher, diffusion, chain, lr, target_beta=0.95, sigma_data=0.5, timestep_scaling=10.0,
+                 loss_weighting="truncated_snr", **train_step_kw):
+        import copy
+        if student is teacher:
+            raise ValueError("ConsistencyStep: student is teacher: the teacher must stay frozen (student = copy.deepcopy(teacher))")
+        if getattr(diffusion, "variance", "fixed") == "learned":
+            raise ValueError("ConsistencyStep: variance='learned' is not supported (the consistency function is deterministic)")
+        for bad in ("ema", "ema_model", "ema_start", "t_sampler"):
+            if bad in train_step_kw:
+                raise ValueError(f"ConsistencyStep: {bad} is not supported (the step keeps its target network with the inner "
+                                 f"step's EMA, see target_beta, and draws positions of the chain, not timesteps)")
+        if isinstance(target_beta, bool) or not isinstance(target_beta, (int, float)) or not 0.0 <= target_beta < 1.0:
+            raise ValueError(f"ConsistencyStep: target_beta must lie in [0, 1) (got {target_beta!r})")
+        levels = diffusion.consistency_levels(chain)          # ValueError for an unordered or out-of-range chain
+        coef = diffusion.consistency_coefficients(sigma_data, timestep_scaling)       # and for bad sigma_data / timestep_scaling
+        if diffusion.prediction == "eps":
+            logging.warning("DistillStep: prediction='eps' is unstable at few sampling steps (Salimans & Ho 2022, section 4); "
+                            "'v' or 'x0' is the parametrisation to distil with")
+        self.student, self.teacher, self.diffusion = student, teacher, diffusion
+        self.chain = [int(v) for v in chain]
+        self.n_steps = levels[0].numel()
+        self.sigma_data, self.timestep_scaling = float(sigma_data), float(timestep_scaling)
+        dev = diffusion.alpha_hat.device
+        self.levels = tuple(tab.to(dev).contiguous() for tab in levels)          # (t, t_prev), (N,) int64 each
+        self.coef = coef.to(dev).contiguous()                                      # (T, 2) fp64
+        self.target = copy.deepcopy(student)
+        self.step = TrainStep(student, diffusion, lr, loss_weighting=loss_weighting, ema=EMA(float(target_beta)),
+                              ema_model=self.target, ema_start=0, **train_step_kw)
+
+    def __call__(self, images, k=None, eps=None, y=None):
+        """images (B, C, S, S) on the device; k (B,) positions of the chain in [0, N) [default: diffusion.sample_distill_steps];
+        eps: injected noise or None (device RNG); y: class labels, handed to both forwards and the inner step.
+        Returns the inner step's loss, a 0-d device tensor."""
+        B = images.shape[0]
+        if k is None:
+            k = self.diffusion.sample_distill_steps(B, self.n_steps)
+        k = torch.as_tensor(k)
+        if k.dtype.is_floating_point or k.dtype == torch.bool or tuple(k.shape) != (B,):
+            raise ValueError(f"ConsistencyStep: k must hold {B} integer positions, one per image")
+        if not k.is_cuda and (int(k.min()) < 0 or int(k.max()) >= self.n_steps):
+            raise ValueError(f"ConsistencyStep: every position must lie in [0, {self.n_steps})")
+        k = k.to(images.device, non_blocking=True).long()
+        rows = tuple(tab[k] for tab in self.levels)
+        x_tilde, eps_tilde, t = self.diffusion.consistency_targets(self.teacher, self.target, images, rows, self.chain, self.coef,
+                                                                   eps, y)
+        return self.step(x_tilde, t, eps_tilde, y)
+
+
+def consistency_distill(model, diffusion, dataloader, steps, iters, lr, device, target_beta=0.95, on_done=None, **train_step_kw):
+    """Consistency distillation of `model` in ONE training run: the teacher is `model` on chain = diffusion.ddim_timesteps(steps),
+    the student a deep copy of it, trained by a ConsistencyStep for `iters` steps over the loader (cycled; batches are (images, ...)
+    tuples or tensors) with LRSchedule("linear", total=iters) unless the caller passes lr_schedule=.  steps in [1, T - 1] and
+    iters >= 1 are integers (ValueError otherwise, before any device work).  on_done(info, student, target) is called at the end.
+    **train_step_kw go to the ConsistencyStep (sigma_data=, timestep_scaling=, loss_weighting=) and its inner TrainStep (graph=,
+    max_grad_norm=, ...).  Single-process.  -> (the target network, the one to sample with `diffusion.consistency_sample`,
+    {"chain", "mean_loss"}); `model` is left as it was."""
+    import copy
+    T = diffusion.noise_steps
+    ok = all(isinstance(v, int) and not isinstance(v, bool) for v in (steps, iters))
+    if not ok or iters < 1:
+        raise ValueError(f"consistency_distill: steps and iters must be integers >= 1 (got {steps!r}, {iters!r})")
+    if not 1 <= steps <= T - 1:
+        raise ValueError(f"consistency_distill: steps must lie in [1, {T - 1}] (got {steps})")
+    for bad in ("ema", "ema_model", "ema_start", "t_sampler"):
+        if bad in train_step_kw:
+            raise ValueError(f"consistency_distill: {bad} is not supported (the target network is the step's average: target_beta)")
+    if isinstance(target_beta, bool) or not isinstance(target_beta, (int, float)) or not 0.0 <= target_beta < 1.0:
+        raise ValueError(f"consistency_distill: target_beta must lie in [0, 1) (got {target_beta!r})")
+    if getattr(diffusion, "variance", "fixed") == "learned":
+        raise ValueError("consistency_distill: variance='learned' is not supported (the consistency function is deterministic)")
+    chain = diffusion.ddim_timesteps(steps)
+    kw = dict(train_step_kw)
+    kw.setdefault("lr_schedule", LRSchedule("linear", total=iters))
+    student = copy.deepcopy(model)
+    step = ConsistencyStep(student, model, diffusion, chain, lr, target_beta=target_beta, **kw)
+    total, batches = torch.zeros((), device=device), None
+    for _ in range(iters):
+        batch = None if batches is None else next(batches, None)
+        if batch is None:                                      # cycle the loader
+            batches = iter(dataloader)
+            batch = next(batches)
+        images = batch[0] if isinstance(batch, (tuple, list)) else batch
+        total += step(images.to(device))
+    info = {"chain": list(chain), "mean_loss": total.item() / iters}
+    logging.info(f"consistency_distill: {len(chain)} teacher steps, {iters} iterations, mean loss {info['mean_loss']:.6f}")
+    if on_done is not None:
+        on_done(info, student, step.target)
+    return step.target, info
+
+
 def train(args, model_path=None, dataloader=None, model=None, diffusion=None):
     """Drop-in for modules/ddpm_utils.py:483-518: returns the list of per-epoch mean losses; saves a
     preview grid and the state_dict every epoch."""

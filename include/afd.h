@@ -668,6 +668,43 @@ int afd_distill_target(const float* out2, const float* z_mid, const float* z_t, 
                        const int64_t* t_prev, const float* alpha_hat, int kind, float* x_tilde, float* eps_tilde, long B, long chw,
                        afd_stream_t stream);
 
+/* ---- consistency distillation (Song et al. 2023; Luo et al. 2023, the discrete-time DDIM-solver form) ------
+ * Diffusion.consistency_targets / consistency_sample, training.ConsistencyStep.  coef: the (T, 2) fp64 device table
+ * [c_skip, c_out] of Diffusion.consistency_coefficients, c_skip[t] = sd^2 / ((s t)^2 + sd^2), c_out[t] = s t / sqrt((s t)^2 + sd^2),
+ * row 0 exactly (1, 0).  With (al, sg) and x_hat(p, z; t) as for afd_distill_* above (level 0 is alpha_hat[0]), the consistency
+ * function of a raw output p of `kind` at z on level t is
+ *     f(z, t) = c_skip[t] z + c_out[t] x_hat(p, z; t),
+ * and where c_out[t] == 0 (the boundary t = 0) p is NOT used: f has z's bits even if p holds NaN or Inf there.
+ * afd_consistency_fn:     f_out = f(z, t[b]) per row b, from out = the output at (z, t).
+ * afd_consistency_target: out_tgt = the target network's output at (z_prev, t_prev); per row
+ *     f_tgt = f(z_prev, t_prev)   (z_prev itself at t_prev == 0),
+ *     x_tilde = (f_tgt - c_skip[t] z_t) / c_out[t],   eps_tilde = (z_t - al x_tilde) / sg:
+ *     the x0 a student must predict at (z_t, t) for its f to equal f_tgt, and the eps that re-forms z_t with it, so a TrainStep on
+ *     (x_tilde, t, eps_tilde) trains the student's f(z_t, t) towards the target's f(z_prev, t_prev).  Needs t[b] >= 1 (c_out[t] > 0)
+ *     and t_prev[b] < t[b]; both are read on the device, unchecked, in [0, T).
+ * afd_consistency_step[_dev]: the sampler's move at one level for all n_rows rows (t, t_next host ints, 0 <= t_next < t, or
+ *     element 0 of two int64 device tensors: graph-replayable).  f = f(z, t) rounded to fp32 once, then
+ *         t_next == 0:  x_out = f                                                  (noise is not read and may be NULL)
+ *         otherwise:    x_out = (sqrt(a_next) * f) + (sqrt(1 - a_next) * noise)    (afd_noise_images' fp32 expression and order)
+ *     so the step has the bits of afd_noise_images(afd_consistency_fn(out, z, t), noise, t_next).
+ * One launch each, no reduction, no atomics.  f, x_tilde and eps_tilde are evaluated in fp64 from the widened fp32 elements with
+ * the roots taken in fp64 from the fp32 table, and rounded once on the store.  Aliasing: every output may be a float input of the
+ * same call ITSELF (f_out: out or z; x_tilde / eps_tilde: out_tgt, z_prev or z_t; x_out: out or z) and must otherwise share no
+ * memory with it; outputs must not overlap each other, noise or the timestep tensors.  128-bit accesses when chw % 4 == 0 and the
+ * float pointers are 16-byte aligned, element by element otherwise, with the same values either way.  AFD_EINVAL (nothing
+ * launched) on NULL pointers, sizes <= 0, a bad kind, such an overlap, host t / t_next out of order, or noise NULL with host
+ * t_next > 0. */
+int afd_consistency_fn(const float* out, const float* z, const int64_t* t, const float* alpha_hat, const double* coef, int kind,
+                       float* f_out, long B, long chw, afd_stream_t stream);
+int afd_consistency_target(const float* out_tgt, const float* z_prev, const float* z_t, const int64_t* t, const int64_t* t_prev,
+                           const float* alpha_hat, const double* coef, int kind, float* x_tilde, float* eps_tilde, long B, long chw,
+                           afd_stream_t stream);
+int afd_consistency_step(const float* out, const float* z, const float* noise_or_null, const float* alpha_hat, const double* coef,
+                         int kind, int t, int t_next, float* x_out, long n_rows, long chw, afd_stream_t stream);
+int afd_consistency_step_dev(const float* out, const float* z, const float* noise_or_null, const float* alpha_hat, const double* coef,
+                             int kind, const int64_t* t_dev, const int64_t* t_next_dev, float* x_out, long n_rows, long chw,
+                             afd_stream_t stream);
+
 /* ---- learned reverse-process variances and the hybrid loss (Nichol & Dhariwal 2021) ------ Diffusion(variance="learned") /
  * TrainStep(vlb_lambda=).  The network's output out2 holds, per row b, 2 chw floats: the prediction p (eps, v or x0 by `kind`)
  * and, chw floats later, the interpolation coefficient v.  lv_coef: the (T, 3) fp64 device table [lb_t, lbt_t, k_t] of
