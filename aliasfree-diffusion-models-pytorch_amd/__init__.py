@@ -21,11 +21,12 @@ from .likelihood import ode_likelihood_reference  # noqa: F401
 from .unipc import unipc_reference  # noqa: F401
 from .unet import UNet  # noqa: F401
 from .diffusion import Diffusion  # noqa: F401
+from .analytic import AnalyticVariance  # noqa: F401
 from .training import (argument, set_seed, setup_logging, train, TrainStep, FusedAdamW, FlatParams,  # noqa: F401
                        GradAllReduce, EMA, LRSchedule, clip_coefficient, DistillStep, progressive_distill,
                        ConsistencyStep, consistency_distill, LossSecondMomentSampler)
 
-from .tasks import (bpd_results, ddpm_run, edit_results, equivariance_results, fidelity_results, ilvr_results,  # noqa: F401
+from .tasks import (analytic_results, bpd_results, ddpm_run, edit_results, equivariance_results, fidelity_results, ilvr_results,  # noqa: F401
                     inpaint_results, likelihood_results, manifold_results, posterior_results, reconstruct_results, restoration_results,
                     rotation_results, shift_results, spectrum_results)
 from .data import (get_data, get_data_MNIST, save_gen_images, make_collage, DeviceDataset, DeviceLoader,  # noqa: F401

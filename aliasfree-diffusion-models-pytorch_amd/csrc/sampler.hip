@@ -73,6 +73,26 @@ struct Ddim {
   __device__ __forceinline__ bool gen_takes_noise() const { return eta != 0.0f && tp > 0; }
 };
 
+// DDIM with the noise scale read from a table (Analytic-DPM, Bao et al. 2022): sig (T floats) holds the optimal sigma of the step
+// that leaves t, built on the host (analytic.py).  Everything but sigma is Ddim's, from the same fp32 expressions, so the mean is
+// DDIM's at that eta and the output is Ddim's bit for bit whenever sig[t] holds Ddim's own sigma.  No masked form: t_prev() and
+// gen_takes_noise() are here because step_k names them.
+struct DdimVar {
+  struct Args : Ddim::Args {
+    const float* sig;
+  };
+  Ddim k;
+  __device__ __forceinline__ static DdimVar make(const Args& a) {
+    DdimVar v;
+    v.k = Ddim::make(a);
+    v.k.sigma = a.sig[a.t_dev ? (int)a.t_dev[0] : a.t];
+    return v;
+  }
+  __device__ __forceinline__ float update(float x, float e, float z, bool has_noise) const { return k.update(x, e, z, has_noise); }
+  __device__ __forceinline__ int t_prev() const { return k.tp; }
+  __device__ __forceinline__ bool gen_takes_noise() const { return k.tp > 0; }
+};
+
 // The ascending DDIM step (inversion), one move s -> u of a chain walked upwards, 0 <= s < u.  a_s = alpha_hat[s],
 // a_u = alpha_hat[u]; fp32, one rounding per operation, in this order:
 //   x0  = (x - sqrt(1 - a_s) * e) / sqrt(a_s)
@@ -503,6 +523,42 @@ int afd_ddim_step_masked_cfg_dev(const float* x, const float* eps2, const float*
                                  float* x_out, float* x_out2, long n, afd_stream_t st) {
   return ddim_step({"afd_ddim_step_masked_cfg_dev", true, true, true}, x, eps2, noise, x0, mask, alpha_hat, 0, 0, t_dev, t_prev_dev, eta,
                    cfg_scale, x_out, x_out2, n, st);
+}
+
+// DDIM with sigma from a table (Analytic-DPM): ddim_step's checks, sig among the tables.  sig[t] is read on the device, unchecked.
+static int ddim_step_var(const StepForm& f, const float* x, const float* eps, const float* noise, const float* alpha_hat,
+                         const float* sig, int t, int t_prev, const int64_t* t_dev, const int64_t* t_prev_dev, float eta, float s,
+                         float* x_out, float* x_out2, long n, afd_stream_t st) {
+  if (int rc = check_step_buffers(f, alpha_hat && sig && (!f.dev || (t_dev && t_prev_dev)),
+                                  f.dev ? "alpha_hat, sig, t_dev, t_prev_dev" : "alpha_hat, sig", x, eps, nullptr, nullptr, x_out, x_out2, n))
+    return rc;
+  AFD_REQUIRE(f.dev || (t_prev >= 0 && t_prev < t), "%s: need 0 <= t_prev < t (got t = %d, t_prev = %d)", f.name, t, t_prev);
+  AFD_REQUIRE(eta >= 0.0f, "%s: eta must be >= 0", f.name);
+  auto launch = f.cfg ? launch_step<DdimVar, true, false> : launch_step<DdimVar, false, false>;      // (no masked kernels)
+  launch(x, eps, noise, DdimVar::Args{{alpha_hat, t, t_prev, t_dev, t_prev_dev, eta}, sig}, s, nullptr, nullptr, x_out, x_out2, n,
+         as_stream(st));
+  return check_launch(f.name);
+}
+int afd_ddim_step_var(const float* x, const float* eps, const float* noise, const float* alpha_hat, const float* sig, int t, int t_prev,
+                      float eta, float* x_out, long n, afd_stream_t st) {
+  return ddim_step_var({"afd_ddim_step_var", false, false, false}, x, eps, noise, alpha_hat, sig, t, t_prev, nullptr, nullptr, eta, 0.0f,
+                       x_out, nullptr, n, st);
+}
+int afd_ddim_step_var_dev(const float* x, const float* eps, const float* noise, const float* alpha_hat, const float* sig,
+                          const int64_t* t_dev, const int64_t* t_prev_dev, float eta, float* x_out, long n, afd_stream_t st) {
+  return ddim_step_var({"afd_ddim_step_var_dev", true, false, false}, x, eps, noise, alpha_hat, sig, 0, 0, t_dev, t_prev_dev, eta, 0.0f,
+                       x_out, nullptr, n, st);
+}
+int afd_ddim_step_var_cfg(const float* x, const float* eps2, const float* noise, const float* alpha_hat, const float* sig, int t,
+                          int t_prev, float eta, float cfg_scale, float* x_out, float* x_out2, long n, afd_stream_t st) {
+  return ddim_step_var({"afd_ddim_step_var_cfg", false, true, false}, x, eps2, noise, alpha_hat, sig, t, t_prev, nullptr, nullptr, eta,
+                       cfg_scale, x_out, x_out2, n, st);
+}
+int afd_ddim_step_var_cfg_dev(const float* x, const float* eps2, const float* noise, const float* alpha_hat, const float* sig,
+                              const int64_t* t_dev, const int64_t* t_prev_dev, float eta, float cfg_scale, float* x_out, float* x_out2,
+                              long n, afd_stream_t st) {
+  return ddim_step_var({"afd_ddim_step_var_cfg_dev", true, true, false}, x, eps2, noise, alpha_hat, sig, 0, 0, t_dev, t_prev_dev, eta,
+                       cfg_scale, x_out, x_out2, n, st);
 }
 
 // The ascending DDIM step: 0 <= s < u where the host knows them.  x_out is normally apart from x (the refinement re-reads the

@@ -15,6 +15,7 @@ import torch
 import torch.distributed as dist
 
 from . import ops, unipc
+from .analytic import AnalyticVariance
 from .filters import circularLowpassKernel
 
 
@@ -538,12 +539,16 @@ class Diffusion:
         return t_prev // 100 < t // 100
 
     def _ddim_loop(self, model, n, image_channels, pairs, eta, noise_source="reference", graph=None, labels=None, cfg_scale=0.0,
-                   start=None):
+                   analytic=None, start=None):
         """`_loop` over the DDIM steps `pairs` (see `sample`).  x_T is drawn as in `_loop`; with eta > 0 every step but the
         last draws the noise of n images (`_step_noise`), with eta == 0 none is drawn.  graph: capture one step (forward,
         noise, the update with t and t_prev read on the device) and replay it for every step but the last, which runs eagerly.
-        start: the (n, C, S, S) state at level pairs[0][0] to start from instead of drawn noise (`decode`); it is not written."""
+        start: the (n, C, S, S) state at level pairs[0][0] to start from instead of drawn noise (`decode`); it is not written.
+        analytic: an `AnalyticVariance`; the steps then draw with its sigmas (ops.ddim_step_var), whose table is built here, once,
+        and stays on the device, and the noise is drawn as for eta > 0 whatever eta is."""
         snaps = []
+        sig = None if analytic is None else analytic.sigma_table(self, pairs, eta).to(self.device).contiguous()
+        noisy = eta > 0 or sig is not None
         with self._model_scope(model):
             x = self._initial_noise(n, image_channels, noise_source) if start is None else start.to(self.device).contiguous().clone()
             y, s = self._guided(labels, cfg_scale)
@@ -552,13 +557,13 @@ class Diffusion:
 
             def step(t_rows, t, tp, draw):
                 eps = self.predict_eps(model, xs, t_rows, y)
-                self._update(xs, n, eps, draw() if draw else None, t, tp, eta=eta, cfg_scale=s)
+                self._update(xs, n, eps, draw() if draw else None, t, tp, eta=eta, cfg_scale=s, sig=sig)
 
             replay = None
             if graph and noise_source != "cpu" and len(pairs) > 1:
                 t_dev = torch.full((rows,), pairs[0][0], device=x.device, dtype=torch.long)
                 tp_dev = torch.full((1,), pairs[0][1], device=x.device, dtype=torch.long)
-                g = self._capture(lambda: step(t_dev, t_dev, tp_dev, (lambda: torch.randn_like(xs[:n])) if eta > 0 else None), xs)
+                g = self._capture(lambda: step(t_dev, t_dev, tp_dev, (lambda: torch.randn_like(xs[:n])) if noisy else None), xs)
 
                 def replay(t, tp):
                     t_dev.fill_(t)
@@ -569,7 +574,7 @@ class Diffusion:
                     replay(t, tp)
                 else:
                     step(self._t_full(rows, t, x.device), t, tp,
-                         (lambda: self._step_noise(xs[:n], noise_source)) if eta > 0 and tp > 0 else None)
+                         (lambda: self._step_noise(xs[:n], noise_source)) if noisy and tp > 0 else None)
                 if self.ddim_snapshot(t, tp):
                     snaps.append(xs[:n].clone())
             x = xs[:n].clone()
@@ -877,7 +882,8 @@ class Diffusion:
         noise is drawn after x_T).  Guidance, graph= and the snapshots work as for DDIM.  "unipc_1" / "unipc_2" / "unipc_3"
         ("unipc" = "unipc_2") run UniPC of that order under the same rules: a predictor-corrector that still costs one forward
         per step.  Order 3 pays from about S = 16 on; below that its extrapolation over log-SNR steps near 1 is worse than
-        "unipc_2" or "dpmpp_2m" (DESIGN.md section 6z)."""
+        "unipc_2" or "dpmpp_2m" (DESIGN.md section 6z).
+        `sample_analytic` is this sampler's DDIM chain drawing with the optimal variances of Analytic-DPM."""
         logging.info(f"Sampling {n} new images....")
         if theta is not None:
             logging.info(f"Theta {theta} provided. Rotation will be applied.")
@@ -896,6 +902,44 @@ class Diffusion:
         else:
             x, snaps = self._ddim_loop(model, n, image_channels, pairs, float(eta), noise_source, graph, labels, float(cfg_scale))
         return self._finish(x, snaps, return_float)
+
+    def sample_analytic(self, model, n, image_channels, analytic, theta=None, noise_source="reference", return_float=False, graph=None,
+                        labels=None, cfg_scale=0.0, steps=None, eta=0.0, sampler=None):
+        """`sample` over the DDIM chain `steps` with the optimal reverse variances of Analytic-DPM (Bao et al. 2022): `sample`'s
+        arguments with `analytic`, an `AnalyticVariance` (`estimate_analytic_variance`) that holds an estimate at every
+        timestep of the chain.  The chain keeps DDIM's mean at that eta (eta = 1: Analytic-DDPM, eta = 0: Analytic-DDIM) and
+        draws with sigma* in place of eta^2 beta~, which is far too small on a short chain: every step but the last draws the
+        noise of n images, also at eta = 0.  x_T, the generator path, labels, guidance (the table should then be the guided
+        eps's: estimate it with the same cfg_scale), graph=, return_float and the snapshots are `sample`'s.  Refused with
+        ValueError before any device work: steps=None (pass steps=T-1 for the full chain), a sampler other than None / "ddim",
+        theta, a process with variance="learned", a table of another process or one that misses a timestep of the chain.
+        (A method of its own because `sample`'s parameter list is pinned.)  Returns what `sample` returns."""
+        logging.info(f"Sampling {n} new images....")
+        self._check_analytic("sample_analytic", analytic, steps, sampler, theta)
+        pairs = self._check_ddim("sample_analytic", steps, eta)
+        analytic.sigma2(self, pairs, eta)                      # refuses a foreign table or a missing timestep before any device work
+        if labels is not None:
+            labels = self._check_labels(model, n, None, labels, "sample_analytic")
+        elif cfg_scale:
+            raise ValueError("Diffusion.sample_analytic: cfg_scale needs class labels")
+        x, snaps = self._ddim_loop(model, n, image_channels, pairs, float(eta), noise_source, graph, labels, float(cfg_scale),
+                                   analytic=analytic)
+        return self._finish(x, snaps, return_float)
+
+    def _check_analytic(self, where, analytic, steps, sampler=None, theta=None):
+        """ValueError for a request the analytic variance cannot serve; nothing touches a device."""
+        if not isinstance(analytic, AnalyticVariance):
+            raise ValueError(f"Diffusion.{where}: analytic must be an AnalyticVariance (got {type(analytic).__name__})")
+        if steps is None:
+            raise ValueError(f"Diffusion.{where}: analytic needs steps (the analytic variance belongs to the DDIM chain: pass "
+                             f"steps={self.noise_steps - 1}, T - 1, for the full chain)")
+        if not (sampler is None or (isinstance(sampler, str) and sampler == "ddim")):
+            raise ValueError(f"Diffusion.{where}: analytic goes with sampler None or 'ddim' (got {sampler!r}: that solver draws no noise)")
+        if theta is not None:
+            raise ValueError(f"Diffusion.{where}: analytic together with a rotation (theta) is not supported")
+        if self.variance == "learned":
+            raise ValueError(f"Diffusion.{where}: analytic is for a process with variance='fixed' (this one draws with the variance "
+                             "its network emits)")
 
     def _finish(self, x, snaps, return_float):
         """What `sample` and `inpaint` return: the final x and the snapshots, quantised; with return_float also x itself."""
@@ -977,21 +1021,25 @@ class Diffusion:
                                       float(cfg_scale))
         return self._finish(x, snaps, return_float)
 
-    def _update(self, xs, n, out, z, t, tp=None, eta=None, learned=False, cfg_scale=0.0, x0=None, mask=None):
+    def _update(self, xs, n, out, z, t, tp=None, eta=None, learned=False, cfg_scale=0.0, x0=None, mask=None, sig=None):
         """One update of the state xs, in place: its n rows, or both halves of the 2n rows [x ; x] of a guided forward
         (cfg_scale > 0).  out: that forward's output (eps; with `learned` the raw 2C output); z: the step's noise of n images, or
         None.  eta None: the DDPM step t -> t - 1, with the fixed or (`learned`) the network's variance; otherwise the DDIM step
         t -> tp.  x0 and mask: the masked form of `inpaint`.  t and tp: host ints, or int64 device tensors (the graph-replayable
-        _dev form).  One launch: the wrapper these facts name, ops.{denoise,ddim}_step[_lvar][_masked][_cfg][_dev]."""
+        _dev form).  sig: the (T,) fp32 device table of the analytic sigmas; the DDIM step then scales z by sig[t].  One launch:
+        the wrapper these facts name, ops.{denoise,ddim}_step[_var][_lvar][_masked][_cfg][_dev]."""
         ddim, masked, guided, dev = eta is not None, mask is not None, cfg_scale > 0, isinstance(t, torch.Tensor)
+        var = sig is not None
         if learned and (ddim or masked):
             raise NotImplementedError("Diffusion: the learned variance is drawn by the unmasked DDPM step alone")
-        step = getattr(ops, ("ddim_step" if ddim else "denoise_step") + "_lvar" * learned + "_masked" * masked + "_cfg" * guided
-                       + "_dev" * dev)
+        if var and (masked or not ddim):
+            raise NotImplementedError("Diffusion: the analytic variance is drawn by the unmasked DDIM step alone")
+        step = getattr(ops, ("ddim_step" if ddim else "denoise_step") + "_var" * var + "_lvar" * learned + "_masked" * masked
+                       + "_cfg" * guided + "_dev" * dev)
         x = xs[:n] if guided else xs
         args = [x, out, z] + ([x0, mask] if masked else [])
         if ddim:
-            args += [self.alpha_hat, t, tp, eta]
+            args += [self.alpha_hat] + ([sig] if var else []) + [t, tp, eta]
         else:
             args += [self.alpha, self.alpha_hat, self.beta] + ([self._lv(), self.prediction] if learned else []) + [t]
         step(*args, *([cfg_scale, x, xs[n:]] if guided else [x]))
@@ -1598,12 +1646,16 @@ class Diffusion:
           c_t = (-1 + log(s2 / beta~_t) + beta~_t / s2) / 2   (per element; exactly 0 for "posterior", computed without
                                                                 cancellation for "beta": (u - log1p(u)) / 2, u = beta~_t / s2 - 1)
           log_scale_t = log(s2) / 2                            (the decoder's at t = 1)
-          prior = (-1 - log(1 - ah[T-1]) + (1 - ah[T-1])) / 2  (per element, the same in every row)."""
-        if not isinstance(sigma, str) or sigma not in self.VLB_SIGMAS:
+          prior = (-1 - log(1 - ah[T-1]) + (1 - ah[T-1])) / 2  (per element, the same in every row).
+        sigma may also be an `AnalyticVariance` with an estimate at every t in 1 .. T - 1: s2 = its sigma*2(t, t - 1) at eta = 1
+        (Analytic-DDPM, whose mean is the posterior's), and w_t, c_t, log_scale_t by the same formulas, c_t as (u - log1p(u)) / 2."""
+        analytic = isinstance(sigma, AnalyticVariance)
+        if not analytic and (not isinstance(sigma, str) or sigma not in self.VLB_SIGMAS):
             raise ValueError(f"Diffusion.vlb_coefficients: unknown sigma {sigma!r} ('beta' or 'posterior')")
         T = self.noise_steps
         if T < 2:
             raise ValueError(f"Diffusion.vlb_coefficients: needs noise_steps >= 2 (got {T})")
+        s2_av = sigma.sigma2(self, [(t, t - 1) for t in range(1, T)], 1.0) if analytic else None
         b = self.beta.detach().cpu().double().numpy()
         a = self.alpha.detach().cpu().double().numpy()
         ah = self.alpha_hat.detach().cpu().double().numpy()
@@ -1611,10 +1663,10 @@ class Diffusion:
         tab = np.zeros((T, 4), dtype=np.float64)
         for t in range(1, T):
             bt = om[t - 1] / om[t] * b[t]
-            s2 = b[t] if sigma == "beta" else bt
+            s2 = s2_av[t - 1] if analytic else (b[t] if sigma == "beta" else bt)
             tab[t, 0] = b[t] * b[t] / (2.0 * s2 * a[t] * om[t])
-            if sigma == "beta":                                 # beta~ / beta - 1 = (ah[t] - ah[t-1]) / (1 - ah[t])
-                u = (ah[t] - ah[t - 1]) / om[t]
+            if analytic or sigma == "beta":                     # beta~ / beta - 1 = (ah[t] - ah[t-1]) / (1 - ah[t])
+                u = (bt - s2) / s2 if analytic else (ah[t] - ah[t - 1]) / om[t]
                 if abs(u) < 0.1:
                     tab[t, 1] = 0.5 * sum((-u) ** k / k for k in range(2, 40))     # u - log1p(u), summed from its series
                 else:
@@ -1703,7 +1755,8 @@ class Diffusion:
         images: (n, C, img_size, img_size), float in [-1, 1] or uint8.  Float values are snapped once to the nearest of the
         256 levels (`snap_8bit`): the result is the likelihood of that 8-bit image, not of the float one.
         prior = KL(q(x_{T-1} | x0) || N(0, I)); L_t = KL(q(x_{t-1} | x_t, x0) || p(x_{t-1} | x_t)) with variance s2 from
-        sigma ("beta": beta_t, what the sampler draws; "posterior": beta~_t); L_1 = -log p(x0 | x_1), the discretised
+        sigma ("beta": beta_t, what the sampler draws; "posterior": beta~_t; an `AnalyticVariance` with an estimate at every t:
+        the optimal sigma*2(t, t - 1) of Analytic-DPM, which tightens the bound); L_1 = -log p(x0 | x_1), the discretised
         Gaussian around the image the sampler returns.  Coefficients: `vlb_coefficients`.
         Rows (image, t) are image-major, t descending within an image (`bpd_rows`), and go to the model in chunks of `batch`
         (`bpd_chunks`), one forward per chunk with per-row t.  Each chunk draws its noise, (rows, C, H, W), from the device
@@ -1724,7 +1777,8 @@ class Diffusion:
         if learned and self.variance != "learned":
             raise ValueError(f"Diffusion.calc_bpd: unknown sigma 'learned' for a process with variance={self.variance!r} ('beta' or "
                              "'posterior'; 'learned' needs Diffusion(variance='learned'))")
-        coef = self.vlb_coefficients("beta" if learned else sigma)           # (the prior column does not depend on sigma)
+        coef = self.vlb_coefficients("beta" if learned else sigma)           # (the prior column does not depend on sigma; an
+        #                                                                      AnalyticVariance is checked there, before any launch)
         if t_samples is not None and (isinstance(t_samples, bool) or not isinstance(t_samples, (int, np.integer))
                                       or not 1 <= t_samples <= T - 1):
             raise ValueError(f"Diffusion.calc_bpd: t_samples must be an int in [1, {T - 1}] or None (got {t_samples!r})")
@@ -1765,6 +1819,91 @@ class Diffusion:
                               term[lo:hi], sq[lo:hi], check_range=False)
         prior_nats = prior.cpu().numpy() + per * float(coef[0, 3])
         return self.bpd_combine(n, per, img, t, term.cpu().numpy(), sq.cpu().numpy(), prior_nats, K, return_terms)
+
+    # Analytic-DPM (Bao et al. 2022): the statistic of the optimal reverse variance ------------------------------------------------
+    def estimate_analytic_variance(self, model, images, timesteps=None, rows_per_step=64, batch=256, labels=None, cfg_scale=0.0,
+                                   noise_source="device", noise_fn=None):
+        """Monte-Carlo estimate of G_t = E|eps_theta(x_t, t)|^2 / d over `images` -> an `AnalyticVariance` (analytic.py) with an
+        estimate at every timestep of `timesteps`: None = 1 .. T - 1, an int S = `ddim_timesteps(S)`, or a sequence of ints in
+        [1, T - 1] taken as given.  images: (N, C, img_size, img_size), uint8 pixels (k -> k / 127.5 - 1) or float values, used
+        as they are (nothing is snapped or clipped), or a `DeviceDataset`.
+        Rows are timestep-major: timestep k takes the rows [k rows_per_step, (k + 1) rows_per_step), and row r reads image
+        r mod N, so the images are cycled through.  The rows go to the model in chunks of `batch` with per-row t, as in `calc_bpd`:
+        each chunk draws its noise (`_chunk_noise`: the device generator, the CPU generator, or noise_fn(shape)), is noised by one
+        gather launch and goes through `predict_eps` (a v- or x0-model's output is converted; of a learned-variance model the
+        prediction half is read); one ops.eps_sqnorm_rows launch per chunk leaves the rows' fp64 sums on the device, read back
+        once at the end and folded into per-timestep means with np.bincount in fp64.
+        labels: (N,) int64 class labels, one per image, for a UNet(num_classes=K): the table of the conditional eps; with
+        cfg_scale > 0 each chunk is one forward over 2B rows [x_t ; x_t] with labels [y ; NULL_LABEL] and the table is that of
+        the guided eps = lerp(eps_uncond, eps_cond, cfg_scale), what `sample(labels=, cfg_scale=)` steps with.
+        The model's mode and timestep hint come back as they were found."""
+        T = self.noise_steps
+        where = "Diffusion.estimate_analytic_variance"
+        if timesteps is None:
+            ts = list(range(1, T))
+        elif isinstance(timesteps, (int, np.integer)) and not isinstance(timesteps, bool):
+            ts = self.ddim_timesteps(timesteps)
+        else:
+            try:
+                ts = list(timesteps)
+            except TypeError:
+                raise ValueError(f"{where}: timesteps must be None, an int or a sequence of ints") from None
+            if not ts or any(isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not 1 <= v <= T - 1 for v in ts):
+                raise ValueError(f"{where}: timesteps must be a non-empty sequence of ints in [1, {T - 1}]")
+            ts = [int(v) for v in ts]
+        for name, v in (("rows_per_step", rows_per_step), ("batch", batch)):
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v < 1:
+                raise ValueError(f"{where}: {name} must be a positive int (got {v!r})")
+        if noise_source not in ("device", "cpu"):
+            raise ValueError(f"{where}: noise_source must be 'device' or 'cpu' (got {noise_source!r})")
+        rows = len(ts) * int(rows_per_step)
+        from .data import DeviceDataset
+        if isinstance(images, DeviceDataset):
+            N = len(images)
+            x0 = images.batch(torch.arange(min(N, rows), device=images.device))[0]
+        else:
+            if not isinstance(images, torch.Tensor) or images.dim() != 4 or images.shape[0] < 1 or \
+                    not (images.dtype == torch.uint8 or images.dtype.is_floating_point):
+                raise ValueError(f"{where}: images must be an (N, C, H, W) uint8 or float tensor with N >= 1, or a DeviceDataset")
+            N = images.shape[0]
+            x0 = images[:min(N, rows)].detach()
+            x0 = x0.float() / 127.5 - 1.0 if x0.dtype == torch.uint8 else x0.float()
+        if tuple(x0.shape[2:]) != (self.img_size, self.img_size):
+            raise ValueError(f"{where}: images of shape {tuple(x0.shape)} do not match img_size {self.img_size}")
+        y = None if labels is None else self._check_labels(model, N, None, labels, "estimate_analytic_variance")
+        if y is None and cfg_scale:
+            raise ValueError(f"{where}: cfg_scale needs class labels")
+        self.check_model(model, x0.shape[1], where)
+        shape = tuple(x0.shape[1:])
+        per = int(np.prod(shape))
+        t = np.repeat(np.asarray(ts, dtype=np.int64), int(rows_per_step))
+        img = np.arange(rows, dtype=np.int64) % N
+        dev = self.device
+        x0 = x0.to(dev).contiguous()
+        img_d, t_d = torch.from_numpy(img).to(dev), torch.from_numpy(t).to(dev)
+        y_rows = None if y is None else y[img_d]
+        guided = y is not None and cfg_scale > 0
+        sums = torch.empty(rows, device=dev, dtype=torch.float64)
+        with self._model_scope(model, leave_training=False):
+            for lo, hi in self.bpd_chunks(rows, int(batch)):
+                eps = self._chunk_noise((hi - lo,) + shape, noise_source, noise_fn)
+                rows_t = t_d[lo:hi]
+                xt = ops.noise_images_gather(x0, img_d[lo:hi], eps, rows_t, self.alpha_hat, check_range=False)
+                if guided:
+                    yc = y_rows[lo:hi]
+                    eh = self.predict_eps(model, torch.cat([xt, xt]), torch.cat([rows_t, rows_t]),
+                                          torch.cat([yc, torch.full_like(yc, ops.NULL_LABEL)]))
+                    ops.eps_sqnorm_rows(eh, float(cfg_scale), out=sums[lo:hi])
+                else:
+                    eh = self.predict_eps(model, xt, rows_t, None if y_rows is None else y_rows[lo:hi])
+                    ops.eps_sqnorm_rows(eh, out=sums[lo:hi])
+        sums = sums.cpu().numpy()
+        count = np.bincount(t, minlength=T).astype(np.int64)
+        total = np.bincount(t, weights=sums, minlength=T)
+        gamma = np.full(T, np.nan, dtype=np.float64)
+        hit = count > 0
+        gamma[hit] = total[hit] / (count[hit].astype(np.float64) * per)
+        return AnalyticVariance(gamma, count, T, self.schedule, self.prediction, self.alpha_hat)
 
     # Equivariance scores: EQ-T / EQ-R of Karras et al. 2021 (StyleGAN3, section 2 and appendix E) for eps_theta -------------
     EQ_KINDS = ("translate", "rotate")

@@ -1226,20 +1226,27 @@ def _ddim_dev_t(what, t_dev, t_prev_dev):
             raise AfdError(f"afdm: {what}: t_dev / t_prev_dev must be int64 device tensors (element 0 is read)")
 
 
-def _step(what, x, eps, noise, tables, index, out, eta=None, cfg_scale=None, out2=None, x0=None, mask=None, masked=False, dev=False):
+def _step(what, x, eps, noise, tables, index, out, eta=None, cfg_scale=None, out2=None, x0=None, mask=None, masked=False, dev=False,
+          var=False):
     """One DDPM step (eta None; tables = (alpha, alpha_hat, beta), index = (i,)) or DDIM step (tables = (alpha_hat,), index =
-    (t, t_prev)): checks the arguments and calls afd_{denoise,ddim}_step[_masked][_cfg][_dev], whose arguments run
+    (t, t_prev); var: tables = (alpha_hat, sig), the step whose sigma is sig[t]): checks the arguments and calls
+    afd_{denoise,ddim}_step[_var][_masked][_cfg][_dev], whose arguments run
     x, eps, noise, [x0, mask], tables, index, [eta], [cfg_scale], x_out, [x_out2], n, stream.  dev: index holds device tensors."""
     ddim, guided = eta is not None, cfg_scale is not None
     out = torch.empty_like(x) if out is None else out
     n = _step_args(what, x, eps, noise, tables[0] if ddim else None, out, out2, guided, x0, mask, masked)
+    if var:
+        sig = tables[1]
+        _chk(sig)
+        if tuple(sig.shape) != tuple(tables[0].shape) or not sig.is_contiguous():
+            raise AfdError(f"afdm: {what}: sig must be a contiguous table of alpha_hat's shape {tuple(tables[0].shape)}")
     if ddim and dev:
         _ddim_dev_t(what, *index)
         eta = float(eta)
     elif ddim:
         *index, eta = _ddim_host_t(what, tables[0], *index, eta)
     index = [_p(v) if dev else int(v) for v in index]
-    name = ("afd_ddim_step" if ddim else "afd_denoise_step") + "_masked" * masked + "_cfg" * guided + "_dev" * dev
+    name = ("afd_ddim_step" if ddim else "afd_denoise_step") + "_var" * var + "_masked" * masked + "_cfg" * guided + "_dev" * dev
     args = [_p(x), _p(eps), _p(noise)] + ([_p(x0), _p(mask)] if masked else []) + [_p(t) for t in tables] + index
     args += ([eta] if ddim else []) + ([float(cfg_scale)] if guided else []) + [_p(out)] + ([_p(out2)] if guided else [])
     getattr(lib(), name)(*args, n, _stream())
@@ -1288,6 +1295,30 @@ def ddim_step_cfg_dev(x, eps2, noise, alpha_hat, t_dev, t_prev_dev, eta, cfg_sca
     """ddim_step_cfg with the step indices read on the device (graph-replayable)."""
     return _step("guided DDIM step", x, eps2, noise, (alpha_hat,), (t_dev, t_prev_dev), out, eta=eta, cfg_scale=cfg_scale, out2=out2,
                  dev=True)
+
+
+def ddim_step_var(x, eps, noise, alpha_hat, sig, t, t_prev, eta, out=None):
+    """The DDIM update t -> t_prev with the noise scaled by sig[t], a (T,) fp32 device table, in place of DDIM's own sigma
+    (Analytic-DPM; include/afd.h: afd_ddim_step_var).  The mean is `ddim_step`'s at that eta.  `out` may be x (in place)."""
+    return _step("analytic DDIM step", x, eps, noise, (alpha_hat, sig), (t, t_prev), out, eta=eta, var=True)
+
+
+def ddim_step_var_dev(x, eps, noise, alpha_hat, sig, t_dev, t_prev_dev, eta, out):
+    """ddim_step_var with t = t_dev[0] and t_prev = t_prev_dev[0] read on the device (graph-replayable)."""
+    return _step("analytic DDIM step", x, eps, noise, (alpha_hat, sig), (t_dev, t_prev_dev), out, eta=eta, dev=True, var=True)
+
+
+def ddim_step_var_cfg(x, eps2, noise, alpha_hat, sig, t, t_prev, eta, cfg_scale, out=None, out2=None):
+    """Classifier-free guided form: e = torch.lerp(eps2[n:], eps2[:n], cfg_scale), then exactly `ddim_step_var(x, e, ...)`, in
+    one launch.  `out` may be x (in place); `out2` (optional) receives the same values."""
+    return _step("guided analytic DDIM step", x, eps2, noise, (alpha_hat, sig), (t, t_prev), out, eta=eta, cfg_scale=cfg_scale,
+                 out2=out2, var=True)
+
+
+def ddim_step_var_cfg_dev(x, eps2, noise, alpha_hat, sig, t_dev, t_prev_dev, eta, cfg_scale, out, out2=None):
+    """ddim_step_var_cfg with the step indices read on the device (graph-replayable)."""
+    return _step("guided analytic DDIM step", x, eps2, noise, (alpha_hat, sig), (t_dev, t_prev_dev), out, eta=eta, cfg_scale=cfg_scale,
+                 out2=out2, dev=True, var=True)
 
 
 def _ddim_invert(what, x, eps, alpha_hat, s, u, out, cfg_scale=None, out2=None, dev=False):
@@ -2049,6 +2080,26 @@ def lvar_loss_rows(out2, x0, eps, t, alpha, alpha_hat, beta, lv_coef, w=None, ki
     out = _rows_out("lvar_loss_rows", out, B, out2.device)
     lib().afd_lvar_loss_rows(_p(out2), _p(x0), _p(eps), _p(t), _p(alpha), _p(alpha_hat), _p(beta), _p(lv_coef), _p(w), code, scale,
                              _p(out), B, chw, _stream())
+    return out
+
+
+def eps_sqnorm_rows(eps, cfg_scale=None, out=None):
+    """rows[b] = sum_i (double)e_i^2 over row b of the contiguous fp32 (B, ...) batch eps -> (B,) fp64 device tensor; one launch,
+    a fixed summation tree (afd.h: afd_eps_sqnorm_rows).  cfg_scale given: eps holds the 2B-row guided forward and e =
+    torch.lerp(eps[B:], eps[:B], cfg_scale), formed as the sampler steps form it.  No gradient."""
+    _chk(eps)
+    eps = _c(eps.detach())
+    guided = cfg_scale is not None
+    if eps.dim() < 2 or eps.shape[0] < 1 or eps.numel() == 0 or (guided and eps.shape[0] % 2):
+        raise AfdError(f"afdm: eps_sqnorm_rows: eps must be a non-empty (B, ...) batch{', of 2B rows when guided' if guided else ''} "
+                       f"(got {tuple(eps.shape)})")
+    B = eps.shape[0] // 2 if guided else eps.shape[0]
+    chw = eps.numel() // eps.shape[0]
+    out = _rows_out("eps_sqnorm_rows", out, B, eps.device)
+    if guided:
+        lib().afd_eps_sqnorm_rows_cfg(_p(eps), float(cfg_scale), _p(out), B, chw, _stream())
+    else:
+        lib().afd_eps_sqnorm_rows(_p(eps), _p(out), B, chw, _stream())
     return out
 
 

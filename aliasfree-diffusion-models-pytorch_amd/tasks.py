@@ -677,6 +677,24 @@ def ilvr_results(model_data, reference, **kw):
     return diffusion.ilvr(model, reference, **kw)
 
 
+def analytic_results(model_data, images, out_dir=None, **kw):
+    """Load the checkpoint as rotation_results does, seed, and estimate the Analytic-DPM table of the model over `images` (a
+    DeviceDataset, or (N, C, H, W) uint8 pixels or float values: Diffusion.estimate_analytic_variance; **kw: timesteps,
+    rows_per_step, batch, labels, cfg_scale, noise_source, noise_fn).  Writes analytic_<name>_<v>.npz (name =
+    model_data["dataset"] when given, else the checkpoint's file stem; v = model_data["unet_v"]) into out_dir, by default the
+    checkpoint's directory, and returns the AnalyticVariance with the file's path as `.path`: what
+    `Diffusion.sample_analytic(steps=, eta=)` and `calc_bpd(sigma=)` take, and AnalyticVariance.load reads back."""
+    model, diffusion, _ = _load(model_data)
+    set_seed(model_data["seed"])
+    av = diffusion.estimate_analytic_variance(model, images, **kw)
+    name = model_data.get("dataset") or os.path.splitext(os.path.basename(model_data["modelpath"]))[0]
+    out_dir = os.path.dirname(os.path.abspath(model_data["modelpath"])) if out_dir is None else out_dir
+    os.makedirs(out_dir, exist_ok=True)
+    av.path = os.path.join(out_dir, f"analytic_{name}_{model_data['unet_v']}.npz")
+    av.save(av.path)
+    return av
+
+
 def bpd_results(model_data, images, **kw):
     """Load the checkpoint as rotation_results does, seed, and score `images` in bits/dim (Diffusion.calc_bpd; **kw: labels,
     sigma, t_samples, batch, noise_source, noise_fn, return_terms).  Returns calc_bpd's dict."""

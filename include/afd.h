@@ -440,6 +440,23 @@ int afd_ddim_step_cfg(const float* x, const float* eps2, const float* noise, con
 int afd_ddim_step_cfg_dev(const float* x, const float* eps2, const float* noise, const float* alpha_hat, const int64_t* t_dev,
                           const int64_t* t_prev_dev, float eta, float cfg_scale, float* x_out, float* x_out2, long n,
                           afd_stream_t stream);
+/* The DDIM step with the noise scale read from a table (Analytic-DPM, Bao et al. 2022: Diffusion.sample_analytic): sig is a
+ * (T,) fp32 device table indexed by t, and the step is afd_ddim_step's with sigma = sig[t] in place of sqrt(var):
+ *   x0  = (x - sqrt(1 - a_t) * eps) / sqrt(a_t)
+ *   r   = (1 - a_p) / (1 - a_t)          q = 1 - a_t / a_p
+ *   var = (eta * eta) * (r * q)          sigma = sig[t]             dir = sqrt(max((1 - a_p) - var, 0))
+ *   out = ((sqrt(a_p) * x0) + (dir * eps)) + (noise ? sigma * noise : +0)
+ * so the mean is DDIM's at that eta, and the output is afd_ddim_step's bit for bit whenever sig[t] holds its fp32 sigma.
+ * The same requirements and aliasing rules as afd_ddim_step[_cfg][_dev]; sig must not be NULL.  No masked form. */
+int afd_ddim_step_var(const float* x, const float* eps, const float* noise /* NULL => none */, const float* alpha_hat,
+                      const float* sig, int t, int t_prev, float eta, float* x_out, long n, afd_stream_t stream);
+int afd_ddim_step_var_dev(const float* x, const float* eps, const float* noise, const float* alpha_hat, const float* sig,
+                          const int64_t* t_dev, const int64_t* t_prev_dev, float eta, float* x_out, long n, afd_stream_t stream);
+int afd_ddim_step_var_cfg(const float* x, const float* eps2, const float* noise, const float* alpha_hat, const float* sig, int t,
+                          int t_prev, float eta, float cfg_scale, float* x_out, float* x_out2, long n, afd_stream_t stream);
+int afd_ddim_step_var_cfg_dev(const float* x, const float* eps2, const float* noise, const float* alpha_hat, const float* sig,
+                              const int64_t* t_dev, const int64_t* t_prev_dev, float eta, float cfg_scale, float* x_out,
+                              float* x_out2, long n, afd_stream_t stream);
 /* The ascending DDIM step (DDIM inversion): one move s -> u of a chain walked upwards, 0 <= s < u; level 0 is the image, read
  * as alpha_hat[0] exactly as afd_ddim_step's last step t_prev = 0 reads it.  a_s = alpha_hat[s], a_u = alpha_hat[u].  fp32 with
  * one IEEE rounding per operation (no FMA contraction, correctly rounded / and sqrt), evaluated in exactly this order:
@@ -1150,6 +1167,20 @@ int afd_ode_trace_rows(const float* v, const float* w_or_null, double cvv, doubl
                        afd_stream_t stream);
 int afd_ode_heun_step(const float* x, const float* eps_s, const float* eps_u, const float* alpha_hat, int s, int u, float* x_out, long n,
                       afd_stream_t stream);
+
+/* ---- Analytic-DPM (Bao et al. 2022): the statistic of the optimal reverse variance ------------- analytic.py, Diffusion.
+ * estimate_analytic_variance.  eps: contiguous fp32 (B, chw); rows: B doubles on the device,
+ *     rows[b] = sum_i (double)e_i * (double)e_i          over row b (each product is exact in fp64)
+ *   The _cfg form reads eps2, the 2B-row forward [conditional rows ; unconditional rows], and e_i is the guided eps of the two
+ *   halves: e = torch.lerp(e_u, e_c, s) formed in fp32 with ATen's scalar formula, one rounding per operation (|s| < 0.5:
+ *   u + s (c - u); otherwise c - (c - u)(1 - s)), exactly as the sampler steps form it.
+ *   One launch, one 256-thread workgroup per row: thread i takes the quads i, i + 256, ... of the row and their elements in
+ *   index order, a shuffle tree adds the 64 lanes and the four waves are added in order.  No atomics, no workspace: identical
+ *   bytes run to run; 16-byte loads when chw % 4 == 0 and the pointer is 16-byte aligned, scalar loads of the same elements in
+ *   the same order otherwise.  AFD_EINVAL (nothing launched) on NULL pointers, B <= 0, chw <= 0, B >= 2^31 or rows overlapping
+ *   the input. */
+int afd_eps_sqnorm_rows(const float* eps, double* rows, long B, long chw, afd_stream_t stream);
+int afd_eps_sqnorm_rows_cfg(const float* eps2, float cfg_scale, double* rows, long B, long chw, afd_stream_t stream);
 
 #ifdef __cplusplus
 }
