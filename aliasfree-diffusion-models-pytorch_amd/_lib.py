@@ -43,7 +43,7 @@ def parse_header(path=HEADER):
 
 
 _VALUE_RETURNING = {"afd_device_count", "afd_tok_supported", "afd_conv3x3_weight_kinds", "afd_conv_wgrad_form", "afd_conv_wgrad3_plan",
-                    "afd_grad_sqnorm_n_partials"}      # int results, not status codes
+                    "afd_grad_sqnorm_n_partials", "afd_debug_conv_state"}      # int results, not status codes
 
 
 class AfdError(RuntimeError):

@@ -16,7 +16,7 @@
 // loads -> SGPR-bound backward (5.8 ms).  R rows per lane cut the LDS traffic per (q,k) pair by 4R.
 // Forward: lane = query rows.  Backward: pass 1 lane = query rows (dQ, stores delta = rowsum(dO*O)),
 // pass 2 lane = key rows (dK, dV) -- no atomics, bitwise reproducible.
-#include "common.h"
+#include "attn_forms.h"
 
 namespace afd {
 
@@ -333,24 +333,6 @@ template <int D, int R> static void launch_dkv(const float* qkv, const float* d_
   else hipLaunchKernelGGL((attn_bwd_dkv_k<D, R, 256>), grid, block, 0, s, qkv, d_o, lse, delta, dqkv, heads, L, sc);
 }
 
-namespace afd {   // attn_mfma.hip: d = 8 / 16 passes with the d-contractions on the matrix cores
-bool attn_mfma8_ok(int d, int L);
-void attn_pv_set(int m);
-void attn_pv16_set(int m);
-bool attn_fused_bwd(const float* qkv, const float* o, const float* d_o, const float* lse, float* dqkv, float* delta, int B, int heads,
-                    int d, int L, float sc, hipStream_t s);
-void attn_mfma8_fwd(const float* qkv, float* o, float* lse, int B, int heads, int d, int L, float sc, hipStream_t s);
-void attn_mfma8_bwd_dq(const float* qkv, const float* o, const float* d_o, const float* lse, float* dqkv, float* delta,
-                       int B, int heads, int d, int L, float sc, hipStream_t s);
-void attn_mfma8_bwd_dkv(const float* qkv, const float* d_o, const float* lse, const float* delta, float* dqkv, int B, int heads, int L,
-                        float sc, hipStream_t s);
-}
-namespace afd {   // attn_small.hip: d in {16,32}, L in {16,32,48,64}, one wave per (batch, head) on the fp32 matrix pipe
-bool attn_small_ok(int d, int L);
-void attn_small_fwd_launch(const float* qkv, float* o, float* lse, int B, int heads, int d, int L, float sc, hipStream_t s);
-void attn_small_bwd_launch(const float* qkv, const float* d_o, float* dqkv, int B, int heads, int d, int L, float sc,
-                           hipStream_t s);
-}
 static int g_attn_mfma_bwd_all = 1;   // (afd_debug_attn_rows(10) off / (11) on): the MFMA d = 8 backward also at L = 1024 -- with the K / V tiles
                                       // prefetched through registers it beats the all-VALU pair there too (1.31 vs 1.49 ms at B = 256)
 static int g_attn_rows = 0;      // tuning hook: 0 = default (MFMA path for d = 8 when L % 256 == 0); 1,2,4 force the
@@ -364,8 +346,8 @@ static inline bool attn_small_use(int B, int heads, int d, int L) {      // (the
 extern "C" {
 
 int afd_debug_attn_rows(int r) {
-  if (r == 20 || r == 21) { attn_pv_set(r - 20); return AFD_OK; }                   // rank-8 products of the d = 8 MFMA kernels: vector pipe / fp16 matrix pipe (default)
-  if (r == 40 || r == 41) { attn_pv16_set(r - 40); return AFD_OK; }                  // d = 16, L % 256 == 0: the round-2 kernels (40) / P V and the one-pass backward on the fp16 matrix pipe (41, default)
+  if (r == 20 || r == 21) { g_attn_pv = r - 20; return AFD_OK; }                   // rank-8 products of the d = 8 MFMA kernels: vector pipe / fp16 matrix pipe (default)
+  if (r == 40 || r == 41) { g_attn_pv16 = r - 40; return AFD_OK; }                  // d = 16, L % 256 == 0: the round-2 kernels (40) / P V and the one-pass backward on the fp16 matrix pipe (41, default)
   if (r == 30 || r == 31) { g_attn_small = r - 30; return AFD_OK; }                // L <= 64 kernels of attn_small.hip off (the vector kernels) / on (default)
   if (r == 10 || r == 11) { g_attn_mfma_bwd_all = r - 10; return AFD_OK; }         // MFMA d = 8 backward at L = 1024 off / on (default on)
   AFD_REQUIRE(r == 0 || r == 1 || r == 2 || r == 4, "afd_debug_attn_rows: r must be 0, 1, 2, 4 (rows per lane of the VALU kernels), 10, 11, 20, 21, 30, 31, 40 or 41");

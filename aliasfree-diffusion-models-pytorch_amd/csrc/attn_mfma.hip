@@ -13,7 +13,7 @@
 // 16 of 30 (dQ) and 16 of 38 (dK/dV) vector instructions per (query, key) pair.
 // Scores live in the log2 domain: log2(e)/sqrt(d) is folded into the Q (K) fragments, exp is v_exp_f32.
 // Requirements: d in {8, 16}, L % 256 == 0 (others use attn.hip).  Deterministic, no atomics.
-#include "common.h"
+#include "attn_forms.h"
 #include "h2_common.h"
 
 namespace afd {
@@ -1005,10 +1005,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_fused(const float* __restrict
 
 // host-side launchers used by attn.hip
 bool attn_mfma8_ok(int d, int L) { return (d == 8 || d == 16) && L % 256 == 0; }
-static int g_attn_pv = 1;           // afd_debug_attn_rows 20 / 21: rank-8 products of the d = 8 kernels on the vector pipe (round 2) / on the fp16 matrix pipe
-static int g_attn_pv16 = 1;         // afd_debug_attn_rows 40 / 41: d = 16 on the round-2 kernels / on attn_fwd_pv<16> and attn_bwd_fused<16, 1>
-void attn_pv_set(int m) { g_attn_pv = m; }
-void attn_pv16_set(int m) { g_attn_pv16 = m; }
+int g_attn_pv = 1, g_attn_pv16 = 1;   // (attn_forms.h; both default to the fp16 matrix pipe)
 void attn_mfma8_fwd(const float* qkv, float* o, float* lse, int B, int heads, int d, int L, float sc, hipStream_t s) {
   if (d == 8 && g_attn_pv) hipLaunchKernelGGL(attn_fwd_pv<8>, dim3(L / 256, heads, B), dim3(256), 0, s, qkv, o, lse, heads, L, sc);
   else if (d == 16 && g_attn_pv16) hipLaunchKernelGGL(attn_fwd_pv<16>, dim3(L / 256, heads, B), dim3(256), 0, s, qkv, o, lse, heads, L, sc);

@@ -21,7 +21,7 @@
 // o, lse or the delta workspace.  (The step's replay list keeps its length -- tests/test_gpu_clip.py pins it -- and the two
 // halves could overlap.)  Both redo the two-pass softmax (max, exp2, sum) instead of P = exp2(S - lse): lse is stored in
 // natural log, and at |lse| ~ 300 (a peaked row) its fp32 rounding alone is a 3e-5 relative error on every probability.
-#include "common.h"
+#include "attn_forms.h"
 
 namespace afd {
 

@@ -24,7 +24,7 @@
 //                  16-byte records), one or two (tap, chunk) groups ahead.  6 MFMAs per (tap, chunk, 16 x 16 block).
 #include <algorithm>
 #include <cstdint>
-#include "common.h"
+#include "conv_forms.h"
 #include "bf3_weights.h"
 
 namespace afd {
@@ -216,11 +216,6 @@ __global__ __launch_bounds__(256, 2) void conv_bf3(const float* __restrict__ x, 
 }
 
 // ---- host side -------------------------------------------------------------------------------------------------------------
-static int g_bf3_mode = 0;          // afd_debug_conv_path 80 / 81 / 82: by the rule / off / wherever the shape is covered
-void bf3_set_mode(int m) { g_bf3_mode = m; }
-static int g_direct_bf3 = 0;        // afd_debug_conv_path 76 / 77: the direct form is f16x2 (h2.hip, default) / bf16x3 (this file)
-void direct_form_set(int m) { g_direct_bf3 = m; }
-bool direct_form_is_bf3() { return g_direct_bf3 != 0; }
 static int g_bf3_nblk = 0;          // tools/micro/bf3_abl.hip: force the channel blocks per workgroup (0 = by the rule)
 void bf3_set_nblk(int n) { g_bf3_nblk = n; }
 // channel blocks per workgroup: as many as divide N while the launch still has two workgroups per CU (four only on 16 x 16
@@ -235,19 +230,16 @@ static int bf3_nblk(long tiles, int N, int S) {
 // does a direct matrix-core kernel take the layer (reduction width K, N output channels)?  0 = no, 1 = the 128-pixel tile
 // kernel (conv_h2 / conv_bf3), 2 = the split-K small-map kernel (conv_h2_sk: f16x2 arithmetic only; afd_debug_conv_path 74 / 75
 // = by this rule (default) / never)
-bool h2_sk_ok(int B, int K, int N, int H, int W, bool force);          // h2.hip
-static int g_sk_mode = 0;           // afd_debug_conv_path 74 / 75 / 73: by the rule / never / wherever the shape is covered (ahead of the tile kernel)
-void h2_sk_set_mode(int m) { g_sk_mode = m; }
 int direct_plan(int B, int K, int N, int H, int W) {
-  if (g_bf3_mode == 1) return 0;
-  if (!g_direct_bf3 && g_sk_mode == 2 && h2_sk_ok(B, K, N, H, W, true)) return 2;
-  const bool sk = !g_direct_bf3 && g_sk_mode != 1 && h2_sk_ok(B, K, N, H, W, g_bf3_mode == 2);
+  if (g_conv.bf3_mode == 1) return 0;
+  if (!g_conv.direct_bf3 && g_conv.sk_mode == 2 && h2_sk_ok(B, K, N, H, W, true)) return 2;
+  const bool sk = !g_conv.direct_bf3 && g_conv.sk_mode != 1 && h2_sk_ok(B, K, N, H, W, g_conv.bf3_mode == 2);
   // (4 x 4 maps on the tile kernel: 8 images per tile, 32 tiles x N / 32 = 128-256 workgroups of one wave per SIMD: measured
   // 20 / 41 us for 128->128 / 256->256 in round 2 -- not instantiated; the split-K kernel takes them)
   if (H != W || (W != 8 && W != 16 && W != 32)) return sk ? 2 : 0;
   if (K % 32 || N % 32 || K < 32) return 0;
   if ((long)B * K * H * W >= (1L << 31) || (long)B * N * H * W >= (1L << 31)) return 0;
-  if (g_bf3_mode == 2) return 1;
+  if (g_conv.bf3_mode == 2) return 1;
   const long tiles = ((long)B * H * W + 127) / 128;
   const int nblk = bf3_nblk(tiles, N, W);
   if (tiles * (N / (32 * nblk)) >= 512) return 1;                     // two workgroups per CU (measured: below that the small-map forms win)

@@ -25,7 +25,7 @@
 #include <algorithm>
 #include <cstdint>
 #include <cstdlib>
-#include "common.h"
+#include "conv_forms.h"
 #include "bf3_weights.h"
 
 namespace afd {
@@ -517,9 +517,6 @@ __global__ __launch_bounds__(512, 1) void wgrad_cin3(const float* __restrict__ x
 }
 
 // ---- host side -------------------------------------------------------------------------------------------------------------
-static int g_wgbf3_mode = 0;       // afd_debug_conv_path 84 / 85 / 86: by the rule / off / wherever the shape is covered
-void wgrad_bf3_set_mode(int m) { g_wgbf3_mode = m; }
-
 // the (output, input) channel block of a workgroup: 64 x 64 where the layer has >= 1024 (tile, block) work items -- twice
 // the operand reuse per MFMA, 18 % faster on the large layers -- else 32 x 32: four times the blocks per split, so a quarter
 // of the splits and of the slab bytes, 15-30 % faster on the 4x4 maps and the thin 8x8 layers (tools/wgrad_bench.py,
@@ -533,14 +530,6 @@ static void wgrad_bf3_tile(int Cin, int Cout, long nt, int* bn, int* bk) {
   *bk = (Cin % 64 == 0 && Cout % 64 && (force ? force >= 64 : true)) ? 64 : 32;
 }
 
-static int g_wg_arith_bf3 = 0;     // afd_debug_conv_path 78 / 79: the 3x3 weight gradient's arithmetic is f16x2 (h2_wgrad.hip, default) / bf16x3 (this file)
-void wgrad_arith_set(int m) { g_wg_arith_bf3 = m; }
-bool wgrad_arith_is_bf3() { return g_wg_arith_bf3 != 0; }
-
-// plan: the number of slabs (0 = not covered / not chosen) and the tiles per split
-static long g_wgb_target = 256;
-void wgrad_plan_target_set(long wgs) { g_wgb_target = wgs; }
-
 // waves per workgroup of the f16x2 kernels (h2_wgrad.hip; the bf16x3 kernels of this file have the eight-wave form only).
 // An eight-wave workgroup holds a CU's whole register file, so beside it no wave of the dependent chain's matrix-pipe
 // kernels fits on that CU; a four-wave workgroup (256 threads, two resident per CU) leaves half of it.  A 64 x 64 block
@@ -550,31 +539,30 @@ void wgrad_plan_target_set(long wgs) { g_wgb_target = wgs; }
 // 64 x 32 / 32 x 64 / 32 x 32 blocks wherever the channel counts allow, else as 52 (tests).  AFD_WGB_WAVES=8 / 4 forces
 // one, AFD_WGB_W4=<mask> sets the rule (bit 0: the 64 x 64 blocks, 1: 64 x 32 and 32 x 64, 2: 32 x 32), AFD_WGB_TARGET4 the
 // workgroups per four-wave launch (never more splits than the eight-wave plan: no layer writes more slab bytes)
-static int g_wg_waves_mode = 0;
-void wgrad_waves_set(int m) { g_wg_waves_mode = m; }
 static constexpr int kWg4RuleMask = 7;                                 // measured in the step, not alone: alone the four-wave plan is 10 % slower
 static bool wgrad_four_waves(int BN, int BK) {
-  if (g_wg_arith_bf3) return false;
+  if (g_conv.wg_arith_bf3) return false;
   static const int force = [] { const char* e = getenv("AFD_WGB_WAVES"); return e ? atoi(e) : 0; }();   // tuning hooks
   static const int mask = [] { const char* e = getenv("AFD_WGB_W4"); return e ? atoi(e) : kWg4RuleMask; }();
   if (force == 4 || force == 8) return force == 4;
-  if (g_wg_waves_mode) return g_wg_waves_mode >= 2;
+  if (g_conv.wg_waves_mode) return g_conv.wg_waves_mode >= 2;
   const int kind = BN == 64 && BK == 64 ? 1 : (BN == 64 || BK == 64 ? 2 : 4);
   return (mask & kind) != 0;
 }
 
+// plan: the number of slabs (0 = not covered / not chosen) and the tiles per split
 int wgrad_plan_full(int B, int Cin, int Cout, int H, int W, int* tps, int* ntiles, int* bn, int* bk, int* nw) {
-  if (g_wgbf3_mode == 1) return 0;
+  if (g_conv.wgbf3_mode == 1) return 0;
   if (H != W || (W != 4 && W != 8 && W != 16 && W != 32)) return 0;
   if (Cin % 32 || Cout % 32) return 0;
   if ((long)B * H * W * (Cin > Cout ? Cin : Cout) >= (1L << 31)) return 0;
   const long nt = W == 4 ? (B + 7) / 8 : (W == 8 ? (B + 1) / 2 : (long)B * (H * W / 128));
   int BN, BK;
   wgrad_bf3_tile(Cin, Cout, nt, &BN, &BK);
-  if (g_wg_waves_mode >= 3 && !g_wg_arith_bf3) {                         // a four-wave block by name (tests)
-    if (g_wg_waves_mode == 3 && Cout % 64 == 0) { BN = 64; BK = 32; }
-    else if (g_wg_waves_mode == 4 && Cin % 64 == 0) { BN = 32; BK = 64; }
-    else if (g_wg_waves_mode == 5) { BN = 32; BK = 32; }
+  if (g_conv.wg_waves_mode >= 3 && !g_conv.wg_arith_bf3) {                         // a four-wave block by name (tests)
+    if (g_conv.wg_waves_mode == 3 && Cout % 64 == 0) { BN = 64; BK = 32; }
+    else if (g_conv.wg_waves_mode == 4 && Cin % 64 == 0) { BN = 32; BK = 64; }
+    else if (g_conv.wg_waves_mode == 5) { BN = 32; BK = 32; }
   }
   const long blocks = (long)(Cout / BN) * (Cin / BK);                   // of the eight-wave form
   // workgroups per launch.  EIGHT waves (512 threads, a CU's whole register file): alone a launch is fastest with one per CU (256: the default); IN SITU,
@@ -585,11 +573,11 @@ int wgrad_plan_full(int B, int Cin, int Cout, int H, int W, int* tps, int* ntile
   // (profiles/wgrad_w4_ab.txt)
   const char* et = getenv("AFD_WGB_TARGET");                            // tuning hook, read per call (tools/ab_env.py; tests)
   const long env_target = et ? atol(et) : 0L;
-  const long target = env_target > 0 ? env_target : g_wgb_target;       // 256 standalone, 160 beside the chain (afd_debug_conv_path 48 / 49)
+  const long target = env_target > 0 ? env_target : g_conv.wgb_target;       // 256 standalone, 160 beside the chain (afd_debug_conv_path 48 / 49)
   long s = target / blocks;
   if (s < 1) s = 1;
   if (s > nt) s = nt;
-  if (g_wgbf3_mode != 2 && nt * blocks < 128) return 0;               // too little work to fill half the chip: the other forms
+  if (g_conv.wgbf3_mode != 2 && nt * blocks < 128) return 0;               // too little work to fill half the chip: the other forms
   int NW = 8;
   if (wgrad_four_waves(BN, BK)) {
     // half a 64 x 64 block per workgroup doubles the blocks: at the same workgroup target the splits, the slabs and the fold
@@ -611,23 +599,25 @@ int wgrad_bf3_plan(int B, int Cin, int Cout, int H, int W, int* tps, int* ntiles
 }
 
 template <int S, int BN, int BK>
-static void wgrad_bf3_launch_t(const float* x, const float* dy, float* part, int B, int Cin, int Cout, int tps, int nt, int splits,
+static int wgrad_bf3_launch_t(const float* x, const float* dy, float* part, int B, int Cin, int Cout, int tps, int nt, int splits,
                                hipStream_t s) {
   using G = BwGeo<S, BN, BK>;
   const size_t lds = std::max((size_t)3 * G::PIECE * 16, G::NSG > 1 ? sizeof(float) * G::NR * 72 * 64 : (size_t)0);
-  (void)lds_opt_in(&wgrad_bf3<S, BN, BK>, lds);                    // (> 64 KB of dynamic LDS: once per device and kernel)
+  if (int rc = lds_opt_in(&wgrad_bf3<S, BN, BK>, lds)) return -rc;  // (> 64 KB of dynamic LDS: once per device and kernel)
   hipLaunchKernelGGL((wgrad_bf3<S, BN, BK>), dim3((unsigned)splits, (unsigned)((Cout / BN) * (Cin / BK))), dim3(512), lds, s, x, dy,
                      part, B, Cin, Cout, tps, nt);
+  return splits;
 }
 
 template <int BN, int BK>
-static void wgrad_bf3_s4_launch_t(const float* x, const float* dy, float* part, int B, int Cin, int Cout, int tps, int nt, int splits,
+static int wgrad_bf3_s4_launch_t(const float* x, const float* dy, float* part, int B, int Cin, int Cout, int tps, int nt, int splits,
                                   hipStream_t s) {
   constexpr int NR = (BN / 16) * (BK / 32);
   const size_t lds = std::max((size_t)3 * (BK / 16) * 40 * 16 * 16, 8 / NR > 1 ? sizeof(float) * NR * 72 * 64 : (size_t)0);
-  (void)lds_opt_in(&wgrad_bf3_s4<BN, BK>, lds);                    // (> 64 KB of dynamic LDS: once per device and kernel)
+  if (int rc = lds_opt_in(&wgrad_bf3_s4<BN, BK>, lds)) return -rc;  // (> 64 KB of dynamic LDS: once per device and kernel)
   hipLaunchKernelGGL((wgrad_bf3_s4<BN, BK>), dim3((unsigned)splits, (unsigned)((Cout / BN) * (Cin / BK))), dim3(512), lds, s, x, dy, part, B,
                      Cin, Cout, tps, nt);
+  return splits;
 }
 
 // writes `slabs` partial [9][Cout][Cin] slabs into part; the caller reduces them (wgrad_reduce)
@@ -639,25 +629,22 @@ int wgrad_bf3(const float* x, const float* dy, float* part, int B, int Cin, int 
   wgrad_bf3_tile(Cin, Cout, nt, &bn_, &bk_);
   const bool n64 = bn_ == 64, k64 = bk_ == 64;
 #define AFD_WGB(S_)                                                                                       \
-  if (n64 && k64) wgrad_bf3_launch_t<S_, 64, 64>(x, dy, part, B, Cin, Cout, tps, nt, splits, s);          \
-  else if (n64) wgrad_bf3_launch_t<S_, 64, 32>(x, dy, part, B, Cin, Cout, tps, nt, splits, s);            \
-  else if (k64) wgrad_bf3_launch_t<S_, 32, 64>(x, dy, part, B, Cin, Cout, tps, nt, splits, s);            \
-  else wgrad_bf3_launch_t<S_, 32, 32>(x, dy, part, B, Cin, Cout, tps, nt, splits, s)
+  if (n64 && k64) return wgrad_bf3_launch_t<S_, 64, 64>(x, dy, part, B, Cin, Cout, tps, nt, splits, s);          \
+  else if (n64) return wgrad_bf3_launch_t<S_, 64, 32>(x, dy, part, B, Cin, Cout, tps, nt, splits, s);            \
+  else if (k64) return wgrad_bf3_launch_t<S_, 32, 64>(x, dy, part, B, Cin, Cout, tps, nt, splits, s);            \
+  else return wgrad_bf3_launch_t<S_, 32, 32>(x, dy, part, B, Cin, Cout, tps, nt, splits, s)
   if (W == 32) { AFD_WGB(32); } else if (W == 16) { AFD_WGB(16); } else if (W == 8) { AFD_WGB(8); }
-  else if (n64 && k64) wgrad_bf3_s4_launch_t<64, 64>(x, dy, part, B, Cin, Cout, tps, nt, splits, s);
-  else if (n64) wgrad_bf3_s4_launch_t<64, 32>(x, dy, part, B, Cin, Cout, tps, nt, splits, s);
-  else if (k64) wgrad_bf3_s4_launch_t<32, 64>(x, dy, part, B, Cin, Cout, tps, nt, splits, s);
-  else wgrad_bf3_s4_launch_t<32, 32>(x, dy, part, B, Cin, Cout, tps, nt, splits, s);
+  else if (n64 && k64) return wgrad_bf3_s4_launch_t<64, 64>(x, dy, part, B, Cin, Cout, tps, nt, splits, s);
+  else if (n64) return wgrad_bf3_s4_launch_t<64, 32>(x, dy, part, B, Cin, Cout, tps, nt, splits, s);
+  else if (k64) return wgrad_bf3_s4_launch_t<32, 64>(x, dy, part, B, Cin, Cout, tps, nt, splits, s);
+  else return wgrad_bf3_s4_launch_t<32, 32>(x, dy, part, B, Cin, Cout, tps, nt, splits, s);
 #undef AFD_WGB
-  return splits;
 }
 
 
 // 1x1 plan: slabs (0 = not covered / not chosen); fills the steps per split, the roles per workgroup and NT
-static int g_pwbf3_mode = 0;       // afd_debug_conv_path 88 / 89: the 1x1 form by the rule / off
-void pw_wgrad_bf3_set_mode(int m) { g_pwbf3_mode = m; }
 int pw_wgrad_bf3_plan(int B, int Cin, int Cout, int L, int* sps, int* nsteps, int* nr, int* nt) {
-  if (g_wgbf3_mode == 1 || g_pwbf3_mode == 1) return 0;
+  if (g_conv.wgbf3_mode == 1 || g_conv.pwbf3_mode == 1) return 0;
   if (Cin % 32 || Cout % 32 || L % 8 || ((long)B * L) % 32) return 0;    // (L = 16: a 32-pixel step takes two 4x4 images)
   if ((long)B * L * (Cin > Cout ? Cin : Cout) >= (1L << 31)) return 0;
   const int NT = Cout % 48 == 0 ? 3 : 2;
@@ -694,7 +681,7 @@ int pw_wgrad_bf3(const float* x, const float* dy, float* part, float* bias_part,
 
 // first-layer form: slabs (0 = not covered)
 int wgrad_cin3_plan(int B, int Cin, int Cout, int H, int W) {
-  if (g_wgbf3_mode == 1) return 0;
+  if (g_conv.wgbf3_mode == 1) return 0;
   if (Cin != 3 || Cout % 32 || H != W || (W != 16 && W != 32 && W != 64)) return 0;
   return B < 256 ? B : 256;
 }

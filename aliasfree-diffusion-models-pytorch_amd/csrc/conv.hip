@@ -11,8 +11,9 @@
 // from OIHW (no transform pass) into rows of odd stride, which makes every fragment read
 // conflict-free.  fp32 in / fp32 accumulate: bitwise an fma chain, no reduced precision anywhere.
 #include <cstdlib>
+#include <cstring>
 #include <algorithm>
-#include "common.h"
+#include "conv_forms.h"
 
 namespace afd {
 
@@ -780,8 +781,6 @@ __global__ __launch_bounds__(256) void wgrad_reduce4(const float* __restrict__ p
   }
 }
 
-int fold_launch(const afd_fold_desc* descs, int n, hipStream_t s);          // fold.hip
-
 // The deterministic fold of weight-gradient slabs (and bias slabs) = one or two fold descriptors (fold.hip).  With `out`
 // the descriptors are handed to the caller (who batches them with other layers' folds into one launch, later, on the
 // same stream); without, they are folded now -- through the same kernel, so both ways give the same bits.
@@ -802,54 +801,9 @@ static int launch_wgrad_reduce(const float* part, float* dw, long n, int slabs, 
 // ------------------------------------------------------------------------------------------
 // host dispatch
 // ------------------------------------------------------------------------------------------
-// pw.hip: streaming kernel for the 1x1 projections
-bool pw_launch(const float* in, const float* w, const float* bias, const float* res, float* out, int B, int K, int N, int P,
-               int act, bool dgrad, hipStream_t s);
-void pw_set_mode(int m);
-// wino.hip: Winograd F(2x2,3x3) forward / dgrad
-int wino_plan(int B, int K, int N, int H, int W);
-int wino_conv(const float* x, const float* w, const float* bias, const float* res, float* y, float* U, int B, int K, int N, int H,
-               int W, int act, bool dgrad, bool weights_ready, hipStream_t s);
-void wino_set_mode(int m);
-void wino_weights_launch(const float* w, float* Uf, float* Ud, int Cin, int Cout, int kinds, hipStream_t s);
-bool bf3_ok(int B, int K, int N, int H, int W);       // bf3.hip: the direct bf16x3 form of a 3x3 layer
-void bf3_set_mode(int m);
-void direct_form_set(int m);
-bool direct_form_is_bf3();
-void h2_sk_set_mode(int m);
-void h2_lds_set(int m);
-void h2_skw_set(int m);
-void wino_weights_batched_launch(const afd_wino_desc* descs, const int* wg_desc, int n_wg, hipStream_t s);
-void wino_set_grid(int g);
-int wgrad_wino_plan(int B, int Cin, int Cout, int H, int W, int* bn, int* bk, int* cps, int* nchunks);
-// bf3_wgrad.hip: the 3x3 weight gradient on the bf16 matrix cores (three-piece splits)
-int wgrad_bf3_plan(int B, int Cin, int Cout, int H, int W, int* tps, int* ntiles);
-int wgrad_plan_full(int B, int Cin, int Cout, int H, int W, int* tps, int* ntiles, int* bn, int* bk, int* nw);
-int wgrad_bf3(const float* x, const float* dy, float* part, int B, int Cin, int Cout, int H, int W, hipStream_t s);
-void wgrad_bf3_set_mode(int m);
-void wgrad_arith_set(int m);
-void wgrad_plan_target_set(long wgs);
-void wgrad_waves_set(int m);
-bool wgrad_arith_is_bf3();
-// h2_wgrad.hip: the same on the fp16 matrix cores (two-piece splits, online scaling; the plan is shared)
-int wgrad_h2(const float* x, const float* dy, float* part, int B, int Cin, int Cout, int H, int W, hipStream_t s);
-int pw_wgrad_h2(const float* x, const float* dy, float* part, float* bias_part, int B, int Cin, int Cout, int L, hipStream_t s);
-// ends.hip: the 1x1 output layer and its dgrad as streaming vector kernels
-bool ends_fwd(const float* x, const float* w, const float* bias, const float* res, float* y, int B, int Cin, int Cout, int H, int W,
-              int ksize, int act, hipStream_t s);
-bool ends_dgrad(const float* dy, const float* w, float* dx, int B, int Cin, int Cout, int H, int W, int ksize, hipStream_t s);
-void ends_set_mode(int m);
-int wgrad_cin3_plan(int B, int Cin, int Cout, int H, int W);
-int wgrad_cin3(const float* x, const float* dy, float* part, int B, int Cin, int Cout, int H, int W, hipStream_t s);
-void pw_wgrad_bf3_set_mode(int m);
-int pw_wgrad_bf3_plan(int B, int Cin, int Cout, int L, int* sps, int* nsteps, int* nr, int* nt);
-int pw_wgrad_bf3(const float* x, const float* dy, float* part, float* bias_part, int B, int Cin, int Cout, int L, hipStream_t s);
-int wgrad_wino(const float* x, const float* dy, float* part, int B, int Cin, int Cout, int H, int W, hipStream_t s);
-void wgrad_wino_set_mode(int m);
+ConvSwitches g_conv;             // every switch of afd_debug_conv_path (conv_forms.h)
 
 static inline bool use_mfma(int K, int N, int H, int W, int PT) { return N >= 8 && tile_ok(H, W, PT); }   // K < 8 (inc.conv1) rides the ragged-chunk path
-
-static int g_conv_path = 0;       // 0 auto, 1 force the 64x128 tile, 2 force the split-K small tile (tests)
 
 template <int T, bool DGRAD>
 static int launch_mfma(const float* x, const float* w, const float* bias, const float* res, float* y,
@@ -863,8 +817,8 @@ static int launch_mfma(const float* x, const float* w, const float* bias, const 
   // layers the 32x64 tile with in-workgroup split-K
   const long wgs64 = (long)ptiles * ((N + 63) / 64), wgs32 = (long)ptiles * ((N + 31) / 32);
   bool use32 = N <= 32 || (wgs64 < 256 && wgs32 >= 256);
-  const bool want_sk = g_conv_path == 2 || (g_conv_path == 0 && wgs64 < 256 && wgs32 < 256);
-  if (g_conv_path == 1) use32 = N <= 32;
+  const bool want_sk = g_conv.tile_path == 2 || (g_conv.tile_path == 0 && wgs64 < 256 && wgs32 < 256);
+  if (g_conv.tile_path == 1) use32 = N <= 32;
   if (want_sk && K >= 32 && tile_ok(H, W, 64)) {         // (1x1 too: 128->128 @ 4x4 16.3 -> 12.4 us)
     const TileGeom g = make_geom(H, W, 64, T == 9 ? 1 : 0);
     if (g.XS <= 256) {
@@ -900,7 +854,6 @@ static int launch_mfma(const float* x, const float* w, const float* bias, const 
   return 0;
 }
 
-static int g_wgrad_nw = 0;        // tuning hook: waves per wgrad workgroup (0 = default 8)
 struct WgradPlan { int wnn, wcn, wk, splits, slabs, nchunks, cps, npb; };
 static inline WgradPlan wgrad_plan(int B, int Cin, int Cout, int H, int W, int ksize) {
   WgradPlan p;
@@ -927,7 +880,7 @@ static void launch_wgrad(const float* x, const float* dy, float* part, float* bi
                          const WgradPlan& p, const TileGeom& g, hipStream_t s) {
   // 8 waves (two per SIMD: one wave's staging and epilogue overlap the other's MFMAs, same slab count) pay off once a
   // workgroup has several chunks to stream; measured per layer in tools/wgrad_nw.py
-  const int nw = g_wgrad_nw ? g_wgrad_nw : ((p.cps >= 8 || (p.cps >= 4 && H * W >= 256)) ? 8 : 4);
+  const int nw = g_conv.wgrad_nw ? (int)g_conv.wgrad_nw : ((p.cps >= 8 || (p.cps >= 4 && H * W >= 256)) ? 8 : 4);
   size_t lds = sizeof(float) * ((size_t)32 * WNn * 65 + (size_t)32 * WCn * (g.XS | 1)) + sizeof(int) * 64;
   const size_t red = sizeof(float) * nw * 16 * 64;                                                // cross-wave reduce buffer
   if (WNn * WCn < nw && lds < red) lds = red;
@@ -947,33 +900,48 @@ static void launch_wgrad_roles(const float* x, const float* dy, float* part, flo
   else launch_wgrad<T, 1, 1, NPB>(x, dy, part, bp, B, Cin, Cout, H, W, p, g, s);
 }
 
+// afd_debug_conv_path: mode -> the switch it sets and the value (a mode may own several rows: 74 returns both split-K switches to
+// the rule; 100000 + g, the Winograd grid, is handled apart).  Every other integer is refused.
+using CS = ConvSwitches;
+struct ConvModeRow { int mode; long CS::* member; long value; };
+static const ConvModeRow kConvModes[] = {
+    {0, &CS::tile_path, 0}, {1, &CS::tile_path, 1}, {2, &CS::tile_path, 2}, {8, &CS::pw_mode, 0}, {9, &CS::pw_mode, 1}, {10, &CS::pw_mode, 2},
+    {32, &CS::wgrad_nw, 4}, {33, &CS::wgrad_nw, 8}, {34, &CS::wgrad_nw, 0}, {48, &CS::wgb_target, 256}, {49, &CS::wgb_target, 160},
+    {50, &CS::wg_waves_mode, 0}, {51, &CS::wg_waves_mode, 1}, {52, &CS::wg_waves_mode, 2}, {53, &CS::wg_waves_mode, 3},
+    {54, &CS::wg_waves_mode, 4}, {55, &CS::wg_waves_mode, 5},
+    {59, &CS::h2_lds, 4}, {60, &CS::h2_lds, 1}, {61, &CS::h2_lds, 0}, {62, &CS::h2_lds, 2}, {63, &CS::h2_lds, 3},
+    {64, &CS::wino_mode, 0}, {65, &CS::wino_mode, 1}, {66, &CS::wino_mode, 2}, {67, &CS::wino_mode, 3}, {68, &CS::wino_mode, 4},
+    {69, &CS::wino_mode, 5}, {70, &CS::wino_mode, 6},
+    {71, &CS::h2_skw, 1}, {72, &CS::h2_skw, 2}, {73, &CS::sk_mode, 2}, {74, &CS::h2_skw, 0}, {74, &CS::sk_mode, 0}, {75, &CS::sk_mode, 1},
+    {76, &CS::direct_bf3, 0}, {77, &CS::direct_bf3, 1}, {78, &CS::wg_arith_bf3, 0}, {79, &CS::wg_arith_bf3, 1},
+    {80, &CS::bf3_mode, 0}, {81, &CS::bf3_mode, 1}, {82, &CS::bf3_mode, 2}, {84, &CS::wgbf3_mode, 0}, {85, &CS::wgbf3_mode, 1}, {86, &CS::wgbf3_mode, 2},
+    {88, &CS::pwbf3_mode, 0}, {89, &CS::pwbf3_mode, 1}, {92, &CS::ends_mode, 0}, {93, &CS::ends_mode, 1},
+    {96, &CS::wgwino_mode, 0}, {97, &CS::wgwino_mode, 1}, {98, &CS::wgwino_mode, 2},
+};
+static const char kConvModesMsg[] =
+    "afd_debug_conv_path: mode must be 0..2 (fp32 tile path), 8..10 (1x1 streaming), 32..34 (fp32 wgrad waves), 48..49 (wgrad workgroups per launch), "
+    "50..55 (f16x2 wgrad waves), 59..63 (f16x2 operand feed), 64..70 (Winograd), 71..72 (slice-walking split-K), 73..75 (f16x2 split-K), 76..77 (direct-form "
+    "arithmetic), 78..79 (wgrad arithmetic), 80..82 (direct form), 84..86 (matrix-core 3x3 wgrad), 88..89 (matrix-core 1x1 wgrad), 92..93 (output-layer "
+    "kernels), 96..98 (Winograd wgrad) or 100000 + g (Winograd grid), not %d";
+
 }  // namespace afd
 using namespace afd;
 
 extern "C" {
 
 int afd_debug_conv_path(int mode) {
-  if (mode >= 92 && mode <= 93) { ends_set_mode(mode - 92); return AFD_OK; }   // output-layer streaming kernels: 92 = by rule (default), 93 = off
-  if (mode >= 88 && mode <= 89) { pw_wgrad_bf3_set_mode(mode - 88); return AFD_OK; }   // bf16x3 1x1 wgrad: 88 = by rule (default), 89 = off
-  if (mode >= 84 && mode <= 86) { wgrad_bf3_set_mode(mode - 84); return AFD_OK; }   // bf16x3 3x3 wgrad: 84 = by rule (default), 85 = off, 86 = wherever covered
-  if (mode >= 48 && mode <= 49) { wgrad_plan_target_set(mode == 48 ? 256 : 160); return AFD_OK; }   // 3x3 matrix-core weight gradient, workgroups per launch: 48 = one per CU (fastest alone; default), 49 = 160 (fastest beside the dependent chain of a train step: TrainStep asks for it)
-  if (mode >= 50 && mode <= 55) { wgrad_waves_set(mode - 50); return AFD_OK; }   // f16x2 3x3 weight gradient, waves per workgroup: 50 = by rule (default), 51 = eight everywhere (one workgroup per CU), 52 = four wherever covered (two per CU), 53 / 54 / 55 = four on 64x32 / 32x64 / 32x32 blocks where the channels allow (tests)
-  if (mode >= 59 && mode <= 63) { h2_lds_set(mode == 59 ? 4 : (mode == 60 ? 1 : (mode == 61 ? 0 : mode - 60))); return AFD_OK; }   // f16x2 tile kernel: 60 = both operands from LDS, weights by LDS-DMA (default), 61 = the register-fed kernel (before round 3's last third), 62 / 63 / 59 = LDS-fed wherever covered, the (128 px, 64 ch) / (256 px, 32 ch) / (128 px, 32 ch) workgroup first (tests)
-  if (mode == 73) { h2_sk_set_mode(2); return AFD_OK; }                          // ... 73 = wherever the shape is covered (tests)
-  if (mode >= 71 && mode <= 72) { h2_skw_set(mode - 70); return AFD_OK; }          // slice-walking form of the split-K kernel (conv_h2_skw, 4x4 maps): 71 = wherever the split-K kernel runs and two or more slices per wave are possible (tests), 72 = never (conv_h2_sk everywhere); 74 returns it to the rule
-  if (mode == 74) h2_skw_set(0);
-  if (mode >= 74 && mode <= 75) { h2_sk_set_mode(mode - 74); return AFD_OK; }    // f16x2 split-K kernel for the 4x4 / thin 8x8 maps: 74 = by rule (default), 75 = off (round 1's fp32 Winograd split-K kernel)
-  if (mode >= 78 && mode <= 79) { wgrad_arith_set(mode - 78); return AFD_OK; }   // arithmetic of the matrix-core 3x3 weight gradient: 78 = f16x2 (default), 79 = bf16x3 (round 2)
-  if (mode >= 76 && mode <= 77) { direct_form_set(mode - 76); return AFD_OK; }   // arithmetic of the direct 3x3 forward / dgrad: 76 = f16x2 (default), 77 = bf16x3 (round 2)
-  if (mode >= 80 && mode <= 82) { bf3_set_mode(mode - 80); return AFD_OK; }   // direct bf16x3 3x3 kernel: 80 = by rule (default), 81 = off, 82 = wherever covered
-  if (mode >= 8 && mode <= 10) { pw_set_mode(mode - 8); return AFD_OK; }     // 1x1 streaming kernel: 8 = by rule (default), 9 = off, 10 = forced
-  if (mode >= 100000 && mode < 200000) { wino_set_grid(mode - 100000); return AFD_OK; }   // Winograd persistent grid size (0 = default)
-  if (mode >= 96 && mode <= 98) { wgrad_wino_set_mode(mode - 96); return AFD_OK; }   // Winograd wgrad: 96 = by rule (default), 97 = off, 98 = whenever covered
-  if (mode >= 64 && mode <= 70) { wino_set_mode(mode - 64); return AFD_OK; }   // Winograd 3x3: 64 = by rule (default), 65 = off, 66..69 = forced, workgroups of 64x64 / 32x64 / 64x32 / 32x32 (channels x tiles)
-  if (mode >= 32 && mode <= 34) { g_wgrad_nw = mode == 32 ? 4 : (mode == 33 ? 8 : 0); return AFD_OK; }   // wgrad waves: 4 / 8 / auto
-  AFD_REQUIRE(mode >= 0 && mode <= 2, "afd_debug_conv_path: mode must be 0 (auto), 1 (big tile), 2 (split-K tile), 8..10 (1x1 streaming auto/off/forced), 32..34 (wgrad waves 4/8/auto), 64..69 (Winograd fwd/dgrad auto/off/forced shapes) or 96..98 (Winograd wgrad auto/off/forced)");
-  g_conv_path = mode;
+  if (mode >= 100000 && mode < 200000) { g_conv.wino_grid = mode - 100000; return AFD_OK; }
+  bool known = false;
+  for (const ConvModeRow& r : kConvModes)
+    if (r.mode == mode) { g_conv.*r.member = r.value; known = true; }
+  AFD_REQUIRE(known, kConvModesMsg, mode);
   return AFD_OK;
+}
+
+int afd_debug_conv_state(long* values, int n) {
+  static_assert(sizeof(ConvSwitches) == kConvSwitchCount * sizeof(long), "ConvSwitches: every member is a long");
+  if (values && n > 0) memcpy(values, &g_conv, sizeof(long) * std::min(n, kConvSwitchCount));
+  return kConvSwitchCount;
 }
 
 int afd_conv_fwd(const float* x, const float* w, const float* bias, const float* res, float* y,
@@ -1024,7 +992,7 @@ size_t afd_conv3x3_wino_workspace_bytes(int B, int Cin, int Cout, int H, int W, 
 int afd_conv3x3_weight_kinds(int B, int Cin, int Cout, int H, int W) {
   if (B <= 0 || Cin <= 0 || Cout <= 0 || H <= 0 || W <= 0) return 0;
   const int k = (bf3_ok(B, Cin, Cout, H, W) ? 1 : 0) | (bf3_ok(B, Cout, Cin, H, W) ? 2 : 0);
-  return k && direct_form_is_bf3() ? k | 4 : k;
+  return k && g_conv.direct_bf3 ? k | 4 : k;
 }
 
 int afd_conv3x3_wino_weights(const float* w, float* u_fwd, float* u_dgrad, int Cin, int Cout, int kinds, afd_stream_t st) {
@@ -1101,9 +1069,9 @@ size_t afd_conv_wgrad_workspace_bytes(int B, int Cin, int Cout, int H, int W, in
 int afd_conv_wgrad_form(int B, int Cin, int Cout, int H, int W, int ksize) {
   if (B <= 0 || Cin <= 0 || Cout <= 0 || H <= 0 || W <= 0) return 0;
   int a, b, c, d;
-  if (ksize == 1) return pw_wgrad_bf3_plan(B, Cin, Cout, H * W, &a, &b, &c, &d) ? (wgrad_arith_is_bf3() ? 2 : 4) : 0;
+  if (ksize == 1) return pw_wgrad_bf3_plan(B, Cin, Cout, H * W, &a, &b, &c, &d) ? (g_conv.wg_arith_bf3 ? 2 : 4) : 0;
   if (ksize != 3) return 0;
-  if (wgrad_bf3_plan(B, Cin, Cout, H, W, &a, &b)) return wgrad_arith_is_bf3() ? 2 : 4;
+  if (wgrad_bf3_plan(B, Cin, Cout, H, W, &a, &b)) return g_conv.wg_arith_bf3 ? 2 : 4;
   if (wgrad_cin3_plan(B, Cin, Cout, H, W)) return 3;
   return wgrad_wino_plan(B, Cin, Cout, H, W, &a, &b, &c, &d) ? 1 : 0;
 }
@@ -1127,9 +1095,10 @@ static int conv_wgrad_impl(const float* x, const float* dy, float* dw, float* db
   const bool vec = aligned16(x) && aligned16(dy);
   if (ksize == 3 && !dbias && workspace) {                               // bf16x3 form on the matrix pipe, else Winograd F(3x3, 2x2): 16 multiplies per tile instead of 36
     float* part = static_cast<float*>(workspace);
-    int slabs = !vec ? 0 : (wgrad_arith_is_bf3() ? wgrad_bf3(x, dy, part, B, Cin, Cout, H, W, s) : wgrad_h2(x, dy, part, B, Cin, Cout, H, W, s));
+    int slabs = !vec ? 0 : (g_conv.wg_arith_bf3 ? wgrad_bf3(x, dy, part, B, Cin, Cout, H, W, s) : wgrad_h2(x, dy, part, B, Cin, Cout, H, W, s));
     if (!slabs) slabs = wgrad_cin3(x, dy, part, B, Cin, Cout, H, W, s);
     if (!slabs && vec) slabs = wgrad_wino(x, dy, part, B, Cin, Cout, H, W, s);
+    if (slabs < 0) return -slabs;                                          // (a failed LDS opt-in: nothing launched, nothing queued)
     if (slabs) {
       const long n = (long)Cout * Cin * 9;
       rc = launch_wgrad_reduce(part, dw, n, slabs, nullptr, nullptr, 0, accumulate, 9, s, sink);
@@ -1143,7 +1112,7 @@ static int conv_wgrad_impl(const float* x, const float* dy, float* dw, float* db
       float* part = static_cast<float*>(workspace);
       const long n = (long)Cout * Cin;
       float* bp = dbias ? part + (size_t)slabs * n : nullptr;
-      if (wgrad_arith_is_bf3()) pw_wgrad_bf3(x, dy, part, bp, B, Cin, Cout, H * W, s);
+      if (g_conv.wg_arith_bf3) pw_wgrad_bf3(x, dy, part, bp, B, Cin, Cout, H * W, s);
       else pw_wgrad_h2(x, dy, part, bp, B, Cin, Cout, H * W, s);
       rc = launch_wgrad_reduce(part, dw, n, slabs, bp, dbias, dbias ? Cout : 0, accumulate, 1, s, sink);
       return rc != AFD_OK ? rc : check_launch(who);

@@ -7,7 +7,7 @@
 // Any shape or epilogue outside the conditions below stays on the general kernels.
 #include <algorithm>
 #include <cstdint>
-#include "common.h"
+#include "conv_forms.h"
 
 namespace afd {
 
@@ -68,12 +68,9 @@ __global__ __launch_bounds__(256) void outc_dgrad_k(const float* __restrict__ dy
 }
 
 // ---- host side -------------------------------------------------------------------------------------------------------------
-static int g_ends_mode = 0;          // afd_debug_conv_path 92 / 93: these kernels by the rule / never
-void ends_set_mode(int m) { g_ends_mode = m; }
-
 bool ends_fwd(const float* x, const float* w, const float* bias, const float* res, float* y, int B, int Cin, int Cout, int H, int W,
               int ksize, int act, hipStream_t s) {
-  if (g_ends_mode == 1 || res || act) return false;
+  if (g_conv.ends_mode == 1 || res || act) return false;
   const long HW = (long)H * W;
   if (ksize == 1 && Cout <= 4 && Cin <= 1024 && HW % 4 == 0 && (reinterpret_cast<uintptr_t>(x) & 15) == 0 &&
       (reinterpret_cast<uintptr_t>(y) & 15) == 0) {
@@ -89,7 +86,7 @@ bool ends_fwd(const float* x, const float* w, const float* bias, const float* re
 }
 
 bool ends_dgrad(const float* dy, const float* w, float* dx, int B, int Cin, int Cout, int H, int W, int ksize, hipStream_t s) {
-  if (g_ends_mode == 1) return false;
+  if (g_conv.ends_mode == 1) return false;
   const long HW = (long)H * W;
   if (ksize == 1 && Cout <= 4 && Cin <= 1024 && HW % 4 == 0 && (reinterpret_cast<uintptr_t>(dy) & 15) == 0 &&
       (reinterpret_cast<uintptr_t>(dx) & 15) == 0) {

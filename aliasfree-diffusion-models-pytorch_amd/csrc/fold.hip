@@ -11,7 +11,7 @@
 // Element j of a slab lands at dst[(j % inner) * rstride + j / inner]:
 //   identity            inner = n,            rstride = 1
 //   [tap][plane] slabs  inner = plane = n/T,  rstride = T   (the weight gradient is OIHW: (cout*Cin+cin)*T + tap)
-#include "common.h"
+#include "conv_forms.h"
 
 namespace afd {
 

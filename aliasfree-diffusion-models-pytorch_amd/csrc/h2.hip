@@ -13,7 +13,7 @@
 // multiplies the accumulators by the ratio.  The epilogue multiplies by 1 / (s_x s_w[n]).  All factors are powers of two.
 #include <algorithm>
 #include <cstdint>
-#include "common.h"
+#include "conv_forms.h"
 #include "h2_common.h"
 
 namespace afd {
@@ -975,12 +975,10 @@ static int h2_skw_launch_t(const float* x, const void* Wp, const float* bias, co
 // measured, the second workgroup's multiplies behind this one's staging and epilogue are worth more than half the weight
 // fetches again (256 -> 256: SW = 1 / 2 / 4 = 18.6 / 15.1 / 18.5 us against conv_h2_sk's 23.0; 128 -> 128: 7.0 / 7.8 / 11.9
 // against 9.3)
-static int g_h2_skw = 0;                                              // afd_debug_conv_path 71 / 72: wherever SW >= 2 is possible (tests) / never; 74 = by rule (default)
-void h2_skw_set(int m) { g_h2_skw = m; }
 static int h2_skw_width(const float* x, int B, int K, int N, int S) {
-  if (S != 4 || g_h2_skw == 2 || !aligned16(x)) return 0;             // (the staging loads are dwordx4)
+  if (S != 4 || g_conv.h2_skw == 2 || !aligned16(x)) return 0;             // (the staging loads are dwordx4)
   const long nslices = ((long)B * 16 + 31) / 32, psp = K >= 128 ? 1 : 2;
-  if (g_h2_skw == 1) return nslices > 2 * psp ? 4 : 2;
+  if (g_conv.h2_skw == 1) return nslices > 2 * psp ? 4 : 2;
   if (K < 128) return 0;
   for (int sw = 4; sw >= 1; sw >>= 1)
     if (((nslices + sw - 1) / sw) * (N / 32) >= 512) return sw;
@@ -998,8 +996,6 @@ bool h2_sk_ok(int B, int K, int N, int H, int W, bool force) {
 }
 // ---- the LDS-fed tile kernel's launch: (tile pixels, 32-channel blocks per workgroup) = (128, 2) where N % 64 == 0 and the launch
 // keeps two workgroups per CU, (256, 1) for the 32-output-channel layers of the big maps, (128, 1) otherwise
-static int g_h2_lds = 1;                                              // afd_debug_conv_path 60 (by rule, default) / 61 (the register-fed kernel above) / 62, 63, 59 (tests: LDS-fed wherever covered, (128, 2) / (256, 1) / (128, 1) first)
-void h2_lds_set(int m) { g_h2_lds = m; }
 template <int S, int TP, int NB>
 static int h2l_launch_t(const float* x, const void* Wp, const float* bias, const float* res, float* y, int B, int K, int N, int act,
                         hipStream_t s) {
@@ -1015,10 +1011,10 @@ template <int S>
 static int h2l_launch(const float* x, const void* Wp, const float* bias, const float* res, float* y, int B, int K, int N, int act,
                       hipStream_t s) {
   const long px = (long)B * S * S;
-  if (g_h2_lds != 4 && N % 64 == 0 && (g_h2_lds == 2 || (g_h2_lds == 1 && ((px + 127) / 128) * (N / 64) >= 512)))
+  if (g_conv.h2_lds != 4 && N % 64 == 0 && (g_conv.h2_lds == 2 || (g_conv.h2_lds == 1 && ((px + 127) / 128) * (N / 64) >= 512)))
     return h2l_launch_t<S, 128, 2>(x, Wp, bias, res, y, B, K, N, act, s);
   if constexpr (S >= 16) {
-    if (g_h2_lds == 3 || (g_h2_lds == 1 && ((px + 255) / 256) * (N / 32) >= 512)) return h2l_launch_t<S, 256, 1>(x, Wp, bias, res, y, B, K, N, act, s);
+    if (g_conv.h2_lds == 3 || (g_conv.h2_lds == 1 && ((px + 255) / 256) * (N / 32) >= 512)) return h2l_launch_t<S, 256, 1>(x, Wp, bias, res, y, B, K, N, act, s);
   }
   return h2l_launch_t<S, 128, 1>(x, Wp, bias, res, y, B, K, N, act, s);
 }
@@ -1039,7 +1035,7 @@ int h2_conv(const float* x, const void* Wp, const float* bias, const float* res,
   // by rule (measured per layer shape at B = 256, tools/abl_conv_bench.py 61 62): the LDS-fed kernel wins where a workgroup has ONE block
   // of 32 output channels on the 32 x 32 maps (every wave of the register-fed kernel then re-reads the same weight fragments:
   // 27.6 -> 25.3 and 47.3 -> 41.7 us), the register-fed one elsewhere (64 -> 64 @ 32 x 32: 63.5 against 67.9; 128 -> 128 @ 16 x 16: 48 against 63)
-  if (g_h2_lds > 1 || (g_h2_lds == 1 && S == 32 && N % 64 != 0)) {
+  if (g_conv.h2_lds > 1 || (g_conv.h2_lds == 1 && S == 32 && N % 64 != 0)) {
     if (S == 32) return h2l_launch<32>(x, Wp, bias, res, y, B, K, N, act, s);
     if (S == 16) return h2l_launch<16>(x, Wp, bias, res, y, B, K, N, act, s);
     return h2l_launch<8>(x, Wp, bias, res, y, B, K, N, act, s);

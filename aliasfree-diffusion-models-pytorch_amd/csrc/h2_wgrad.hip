@@ -17,7 +17,7 @@
 #include <algorithm>
 #include <cstdint>
 #include <cstdlib>
-#include "common.h"
+#include "conv_forms.h"
 #include "h2_common.h"
 
 namespace afd {
@@ -551,48 +551,48 @@ __global__ __launch_bounds__(512, 1) void pw_wgrad_h2(const float* __restrict__ 
   }
 }
 
-// ---- host side (the plan -- tiles per split, block sizes, waves per workgroup -- is bf3_wgrad.hip's) -------------------------
-int wgrad_plan_full(int B, int Cin, int Cout, int H, int W, int* tps, int* ntiles, int* bn, int* bk, int* nw);
-
+// ---- host side (the plan is bf3_wgrad.hip's; the launch templates return the slabs, or -code where the LDS opt-in failed) ----------
 template <int S, int BN, int BK, int NW>
-static void wgrad_h2_launch_t(const float* x, const float* dy, float* part, int B, int Cin, int Cout, int tps, int nt, int splits,
+static int wgrad_h2_launch_t(const float* x, const float* dy, float* part, int B, int Cin, int Cout, int tps, int nt, int splits,
                               hipStream_t s) {
   using G = HwGeo<S, BN, BK, NW>;
   const size_t lds = std::max((size_t)2 * G::PIECE * 16 + 32, G::NSG > 1 ? sizeof(float) * G::NR * 72 * 64 : (size_t)0);
-  (void)lds_opt_in(&wgrad_h2<S, BN, BK, NW>, lds);                // (> 64 KB of dynamic LDS: once per device and kernel)
+  if (int rc = lds_opt_in(&wgrad_h2<S, BN, BK, NW>, lds)) return -rc;   // (> 64 KB of dynamic LDS: once per device and kernel)
   hipLaunchKernelGGL((wgrad_h2<S, BN, BK, NW>), dim3((unsigned)splits, (unsigned)((Cout / BN) * (Cin / BK))), dim3(G::NT), lds, s, x, dy,
                      part, B, Cin, Cout, tps, nt);
+  return splits;
 }
 
 template <int BN, int BK, int NW>
-static void wgrad_h2_s4_launch_t(const float* x, const float* dy, float* part, int B, int Cin, int Cout, int tps, int nt, int splits,
+static int wgrad_h2_s4_launch_t(const float* x, const float* dy, float* part, int B, int Cin, int Cout, int tps, int nt, int splits,
                                  hipStream_t s) {
   constexpr int NR = (BN / 16) * (BK / 32);
   const size_t lds = std::max((size_t)2 * (BK / 16) * 40 * 16 * 16 + 32, NW / NR > 1 ? sizeof(float) * NR * 72 * 64 : (size_t)0);
-  (void)lds_opt_in(&wgrad_h2_s4<BN, BK, NW>, lds);                // (> 64 KB of dynamic LDS: once per device and kernel)
+  if (int rc = lds_opt_in(&wgrad_h2_s4<BN, BK, NW>, lds)) return -rc;   // (> 64 KB of dynamic LDS: once per device and kernel)
   hipLaunchKernelGGL((wgrad_h2_s4<BN, BK, NW>), dim3((unsigned)splits, (unsigned)((Cout / BN) * (Cin / BK))), dim3(64 * NW), lds, s, x, dy,
                      part, B, Cin, Cout, tps, nt);
+  return splits;
 }
 
 // S = 0: the 4 x 4 maps' kernel
 template <int S, int BN, int BK, int NW>
-static void wgrad_h2_form_t(const float* x, const float* dy, float* part, int B, int Cin, int Cout, int tps, int nt, int splits, hipStream_t s) {
-  if constexpr (S == 0) wgrad_h2_s4_launch_t<BN, BK, NW>(x, dy, part, B, Cin, Cout, tps, nt, splits, s);
-  else wgrad_h2_launch_t<S, BN, BK, NW>(x, dy, part, B, Cin, Cout, tps, nt, splits, s);
+static int wgrad_h2_form_t(const float* x, const float* dy, float* part, int B, int Cin, int Cout, int tps, int nt, int splits, hipStream_t s) {
+  if constexpr (S == 0) return wgrad_h2_s4_launch_t<BN, BK, NW>(x, dy, part, B, Cin, Cout, tps, nt, splits, s);
+  else return wgrad_h2_launch_t<S, BN, BK, NW>(x, dy, part, B, Cin, Cout, tps, nt, splits, s);
 }
 
 template <int S>
-static void wgrad_h2_map_t(const float* x, const float* dy, float* part, int B, int Cin, int Cout, int tps, int nt, int splits, int bn, int bk,
+static int wgrad_h2_map_t(const float* x, const float* dy, float* part, int B, int Cin, int Cout, int tps, int nt, int splits, int bn, int bk,
                            int nw, hipStream_t s) {
   const bool n64 = bn == 64, k64 = bk == 64;
   if (nw == 4) {                                                       // (the plan gives a four-wave workgroup no 64 x 64 block: eight roles)
-    if (n64) wgrad_h2_form_t<S, 64, 32, 4>(x, dy, part, B, Cin, Cout, tps, nt, splits, s);
-    else if (k64) wgrad_h2_form_t<S, 32, 64, 4>(x, dy, part, B, Cin, Cout, tps, nt, splits, s);
-    else wgrad_h2_form_t<S, 32, 32, 4>(x, dy, part, B, Cin, Cout, tps, nt, splits, s);
-  } else if (n64 && k64) wgrad_h2_form_t<S, 64, 64, 8>(x, dy, part, B, Cin, Cout, tps, nt, splits, s);
-  else if (n64) wgrad_h2_form_t<S, 64, 32, 8>(x, dy, part, B, Cin, Cout, tps, nt, splits, s);
-  else if (k64) wgrad_h2_form_t<S, 32, 64, 8>(x, dy, part, B, Cin, Cout, tps, nt, splits, s);
-  else wgrad_h2_form_t<S, 32, 32, 8>(x, dy, part, B, Cin, Cout, tps, nt, splits, s);
+    if (n64) return wgrad_h2_form_t<S, 64, 32, 4>(x, dy, part, B, Cin, Cout, tps, nt, splits, s);
+    else if (k64) return wgrad_h2_form_t<S, 32, 64, 4>(x, dy, part, B, Cin, Cout, tps, nt, splits, s);
+    else return wgrad_h2_form_t<S, 32, 32, 4>(x, dy, part, B, Cin, Cout, tps, nt, splits, s);
+  } else if (n64 && k64) return wgrad_h2_form_t<S, 64, 64, 8>(x, dy, part, B, Cin, Cout, tps, nt, splits, s);
+  else if (n64) return wgrad_h2_form_t<S, 64, 32, 8>(x, dy, part, B, Cin, Cout, tps, nt, splits, s);
+  else if (k64) return wgrad_h2_form_t<S, 32, 64, 8>(x, dy, part, B, Cin, Cout, tps, nt, splits, s);
+  else return wgrad_h2_form_t<S, 32, 32, 8>(x, dy, part, B, Cin, Cout, tps, nt, splits, s);
 }
 
 // writes `slabs` partial [9][Cout][Cin] slabs into part; the caller folds them
@@ -600,15 +600,13 @@ int wgrad_h2(const float* x, const float* dy, float* part, int B, int Cin, int C
   int tps, nt, bn, bk, nw;
   const int splits = wgrad_plan_full(B, Cin, Cout, H, W, &tps, &nt, &bn, &bk, &nw);
   if (!splits) return 0;
-  if (W == 32) wgrad_h2_map_t<32>(x, dy, part, B, Cin, Cout, tps, nt, splits, bn, bk, nw, s);
-  else if (W == 16) wgrad_h2_map_t<16>(x, dy, part, B, Cin, Cout, tps, nt, splits, bn, bk, nw, s);
-  else if (W == 8) wgrad_h2_map_t<8>(x, dy, part, B, Cin, Cout, tps, nt, splits, bn, bk, nw, s);
-  else wgrad_h2_map_t<0>(x, dy, part, B, Cin, Cout, tps, nt, splits, bn, bk, nw, s);
-  return splits;
+  if (W == 32) return wgrad_h2_map_t<32>(x, dy, part, B, Cin, Cout, tps, nt, splits, bn, bk, nw, s);
+  if (W == 16) return wgrad_h2_map_t<16>(x, dy, part, B, Cin, Cout, tps, nt, splits, bn, bk, nw, s);
+  if (W == 8) return wgrad_h2_map_t<8>(x, dy, part, B, Cin, Cout, tps, nt, splits, bn, bk, nw, s);
+  return wgrad_h2_map_t<0>(x, dy, part, B, Cin, Cout, tps, nt, splits, bn, bk, nw, s);
 }
 
 
-int pw_wgrad_bf3_plan(int B, int Cin, int Cout, int L, int* sps, int* nsteps, int* nr, int* nt);
 int pw_wgrad_h2(const float* x, const float* dy, float* part, float* bias_part, int B, int Cin, int Cout, int L, hipStream_t s) {
   int sps, st, NR, NT;
   const int splits = pw_wgrad_bf3_plan(B, Cin, Cout, L, &sps, &st, &NR, &NT);

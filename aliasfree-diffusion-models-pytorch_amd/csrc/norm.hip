@@ -518,7 +518,6 @@ static int g_gn_bwd_mode = 0;      // afd_debug_norm_path 0 / 1: the sample-resi
 
 extern "C" {
 
-int afd_colsum2(const float* in, float* out_a, float* out_b, int rows, int C, int accumulate, afd_stream_t st);
 int afd_debug_norm_path(int mode) { g_gn_bwd_mode = mode == 1 ? 1 : 0; return AFD_OK; }
 
 int afd_groupnorm1_fwd(const float* x, float* y, float* stats_out, int B, int C, int HW, float eps,
@@ -631,8 +630,6 @@ int afd_layernorm_c_bwd(const float* x, const float* dy, const float* stats, int
 #undef AFD_LN_SPLIT
   return check_launch("afd_layernorm_c_bwd");
 }
-
-int afd_colsum2(const float* in, float* out_a, float* out_b, int rows, int C, int accumulate, afd_stream_t st);
 
 int afd_layernorm_c_bwd_partials(const float* x, const float* dy, const float* stats, int B, int C, int HW, float* part, afd_stream_t st) {
   AFD_REQUIRE(x && dy && stats && part && B > 0 && C > 0 && HW > 0, "afd_layernorm_c_bwd_partials: bad argument");

@@ -16,7 +16,7 @@
 // 32-channel output blocks.  Measured against the tiled kernel (tools/pw_bench.py, B=256): 32->96 @32x32 forward
 // 96 -> 41 us (3.3 TB/s), 32->32 @32x32 30 -> 19 us (3.6 TB/s); it loses below ~32k pixels (too few 32-pixel tiles
 // to fill the chip) and for K > 64 (register pressure), where the tiled kernel keeps the layer.
-#include "common.h"
+#include "conv_forms.h"
 
 namespace afd {
 
@@ -104,15 +104,12 @@ __global__ __launch_bounds__(256) void pw_mfma(const float* __restrict__ in, con
 }
 
 // Host side.  Returns false when the layer stays with the tiled kernel (conv_mfma<1,...>).
-static int g_pw_mode = 0;        // test / tuning hook: 0 = by the measured rule, 1 = never, 2 = whenever the shape is covered
-void pw_set_mode(int m) { g_pw_mode = m; }
-
 bool pw_launch(const float* in, const float* w, const float* bias, const float* res, float* out, int B, int K, int N, int P,
                int act, bool dgrad, hipStream_t s) {
-  if (g_pw_mode == 1) return false;
+  if (g_conv.pw_mode == 1) return false;
   if (K % 2 != 0 || K < 8 || K > 64 || N < 8) return false;
   if ((long)B * P * (K > N ? K : N) >= (1L << 31)) return false;              // 32-bit element offsets
-  if (g_pw_mode == 0 && ((long)B * P < 32768 || (dgrad && K > 32))) return false;
+  if (g_conv.pw_mode == 0 && ((long)B * P < 32768 || (dgrad && K > 32))) return false;
   const long ntile = ((long)B * P + 31) / 32;
   const unsigned gx = (unsigned)std::min<long>((ntile + 3) / 4, 512);
   const int n_per_wg = (N + 31) / 32 * 32;

@@ -15,7 +15,7 @@
 //                  The 16 xi of one (channel, tile) sit in ONE lane, so the output transform A^T M A is
 //                  register arithmetic and the 2x2 results leave as float2 stores.
 #include <cstdlib>
-#include "common.h"
+#include "conv_forms.h"
 #include "bf3_weights.h"
 #include "h2_common.h"
 
@@ -518,27 +518,22 @@ static void wino_sk_launch(const float* x, const float* U, const float* bias, co
   hipLaunchKernelGGL((conv_wino_sk<S>), dim3(N / 32, tg), dim3(256), lds, s, x, U, bias, res, y, B, K, N, act);
 }
 
-static int g_wino_grid = 0;      // test / tuning hook: persistent grid size (0 = fill the chip once)
-void wino_set_grid(int g) { g_wino_grid = g; }
-static int g_wino_mode = 0;        // 0 = by rule, 1 = off, 2..5 = whenever the shape is supported: workgroups of 64x64, 32x64, 64x32, 32x32 (channels x tiles); 6 = the small-map split-K kernel wherever covered
-void wino_set_mode(int m) { g_wino_mode = m; }
-
 // workgroup shape for a Winograd launch: BN * 256 + NT, or 0 when the layer stays on the direct kernel
 int wino_plan(int B, int K, int N, int H, int W) {
-  if (g_wino_mode == 1) return 0;
+  if (g_conv.wino_mode == 1) return 0;
   if (H != W || (W != 64 && W != 32 && W != 16 && W != 8 && W != 4)) return 0;
   if (K % 8 || N % 32 || K < 8) return 0;
   if ((long)B * K * H * W >= (1L << 31) || (long)B * N * H * W >= (1L << 31) || (long)16 * N * K >= (1L << 28)) return 0;
   const bool n64 = N % 64 == 0;
-  if (g_wino_mode == 2) return (n64 ? 64 : 32) * 256 + 64;
-  if (g_wino_mode == 3) return 32 * 256 + 64;
-  if (g_wino_mode == 4) return (n64 ? 64 : 32) * 256 + 32;
-  if (g_wino_mode == 5) return 32 * 256 + 32;
+  if (g_conv.wino_mode == 2) return (n64 ? 64 : 32) * 256 + 64;
+  if (g_conv.wino_mode == 3) return 32 * 256 + 64;
+  if (g_conv.wino_mode == 4) return (n64 ? 64 : 32) * 256 + 32;
+  if (g_conv.wino_mode == 5) return 32 * 256 + 32;
   // measured per layer at B = 256 (tools/wino_bench.py): 64 channels x 64 tiles (8 waves, one workgroup per CU, the input
   // transform shared by two channel blocks) is best once it gives every CU a workgroup; below that 32 x 64 (two
   // workgroups per CU); Winograd wins from 4 chunks up; the 4x4 maps (4 tiles per image) and thin launches stay direct
   const long tiles = (long)B * (H / 2) * (W / 2);
-  if (g_wino_mode == 6) return (W <= 8 && K % 32 == 0 && K >= 64) ? 1 : 0;       // (tests) the small-map kernel wherever covered
+  if (g_conv.wino_mode == 6) return (W <= 8 && K % 32 == 0 && K >= 64) ? 1 : 0;       // (tests) the small-map kernel wherever covered
   // 4x4 and 8x8 maps whose launch cannot give every CU a 64-tile workgroup: the in-workgroup split-K kernel
   if (W <= 8 && K % 32 == 0 && K >= 64 && !(n64 && (tiles / 64) * (N / 64) >= 256) && (tiles / 16) * (N / 32) >= 128) return 1;
   if (K < 32 || W < 8) return 0;
@@ -548,42 +543,33 @@ int wino_plan(int B, int K, int N, int H, int W) {
 }
 
 template <int GEO, int BN, int NT>
-static void wino_launch_t(const float* x, const float* U, const float* bias, const float* res, float* y, int B, int K, int N, int act,
+static int wino_launch_t(const float* x, const float* U, const float* bias, const float* res, float* y, int B, int K, int N, int act,
                           hipStream_t s) {
   using G = WGeo<GEO, NT>;
   const size_t lds = 2 * sizeof(float) * (16 * BN * 10 + 8 * G::RSP);   // two stages
-  (void)lds_opt_in(&conv_wino<GEO, BN, NT>, lds);                    // (> 64 KB of dynamic LDS: once per device and kernel)
+  if (int rc = lds_opt_in(&conv_wino<GEO, BN, NT>, lds)) return rc;  // (> 64 KB of dynamic LDS: once per device and kernel)
   const int tg = G::TI == 1 ? B * G::GPI : (B + G::TI - 1) / G::TI;
   const int items = tg * (N / BN);
   // persistent grid: as many workgroups as fit the chip at once (8-wave groups: one per CU, smaller ones: two), each
-  // walking items g, g + grid, ...  (g_wino_grid overrides, tools/wino_bench.py)
+  // walking items g, g + grid, ...  (g_conv.wino_grid overrides, tools/wino_bench.py)
   // one item per workgroup by default: with two workgroups per CU the hardware's own dispatch already overlaps one
   // group's prologue / store tail with the other's multiplies, and balances better than a fixed walk (measured);
-  // g_wino_grid > 0 makes the groups persistent (tools)
-  int grid = g_wino_grid > 0 ? g_wino_grid : items;
+  // g_conv.wino_grid > 0 makes the groups persistent (tools)
+  int grid = g_conv.wino_grid > 0 ? (int)g_conv.wino_grid : items;
   if (grid > items) grid = items;
   hipLaunchKernelGGL((conv_wino<GEO, BN, NT>), dim3(grid), dim3(BN * NT / 8), lds, s, x, U, bias, res, y, B, K, N, act, items);
+  return AFD_OK;
 }
 
 // the direct forms (take the layers they cover ahead of the Winograd kernels): f16x2 (h2.hip, round 3) or bf16x3 (bf3.hip)
-bool bf3_ok(int B, int K, int N, int H, int W);
-bool direct_form_is_bf3();
-void bf3_weights_launch(const float* w, void* Wf, void* Wd, int Cin, int Cout, hipStream_t s);
-void bf3_conv(const float* x, const void* Wp, const float* bias, const float* res, float* y, int B, int K, int N, int S, int act,
-              hipStream_t s);
-void h2_weights_launch(const float* w, void* Wf, void* Wd, int Cin, int Cout, hipStream_t s);
-int h2_conv(const float* x, const void* Wp, const float* bias, const float* res, float* y, int B, int K, int N, int S, int act,
-            hipStream_t s, bool small);
-int direct_plan(int B, int K, int N, int H, int W);
-
 // conv (dgrad = false: x (B,K,H,W), w (N,K,3,3)) or its input gradient (dgrad = true: x = dY (B,K=Cout,H,W), w (K,N,3,3)).
-// Returns -1 where the shape is not covered, else AFD_OK or the code of a launcher that could not launch (the f16x2 direct form's
-// LDS opt-in)
+// Returns -1 where the shape is not covered, else AFD_OK or the code of a launcher that could not launch (a failed LDS opt-in of
+// the f16x2 direct form or of conv_wino)
 int wino_conv(const float* x, const float* w, const float* bias, const float* res, float* y, float* U, int B, int K, int N, int H,
                int W, int act, bool dgrad, bool weights_ready, hipStream_t s) {
   const int Cin = dgrad ? N : K, Cout = dgrad ? K : N;
   if (U && bf3_ok(B, K, N, H, W)) {                 // the workspace then holds the direct form's weight image of this pass
-    if (direct_form_is_bf3()) {
+    if (g_conv.direct_bf3) {
       if (!weights_ready) bf3_weights_launch(w, dgrad ? nullptr : U, dgrad ? U : nullptr, Cin, Cout, s);
       bf3_conv(x, U, bias, res, y, B, K, N, W, act, s);
     } else {
@@ -604,13 +590,12 @@ int wino_conv(const float* x, const float* w, const float* bias, const float* re
   if (!weights_ready)
     hipLaunchKernelGGL(wino_weights, dim3((unsigned)((K * N / 64 + 3) / 4)), dim3(256), 0, s, w, dgrad ? nullptr : U, dgrad ? U : nullptr, Cin, Cout);
 #define AFD_WINO(GEO_)                                                                            \
-  if (bn == 64 && nt == 64) wino_launch_t<GEO_, 64, 64>(x, U, bias, res, y, B, K, N, act, s);     \
-  else if (bn == 32 && nt == 64) wino_launch_t<GEO_, 32, 64>(x, U, bias, res, y, B, K, N, act, s); \
-  else if (bn == 64) wino_launch_t<GEO_, 64, 32>(x, U, bias, res, y, B, K, N, act, s);            \
-  else wino_launch_t<GEO_, 32, 32>(x, U, bias, res, y, B, K, N, act, s)
+  if (bn == 64 && nt == 64) return wino_launch_t<GEO_, 64, 64>(x, U, bias, res, y, B, K, N, act, s);     \
+  else if (bn == 32 && nt == 64) return wino_launch_t<GEO_, 32, 64>(x, U, bias, res, y, B, K, N, act, s); \
+  else if (bn == 64) return wino_launch_t<GEO_, 64, 32>(x, U, bias, res, y, B, K, N, act, s);            \
+  else return wino_launch_t<GEO_, 32, 32>(x, U, bias, res, y, B, K, N, act, s)
   if (W == 64) { AFD_WINO(64); } else if (W == 32) { AFD_WINO(32); } else if (W == 16) { AFD_WINO(16); } else if (W == 8) { AFD_WINO(8); } else { AFD_WINO(4); }
 #undef AFD_WINO
-  return AFD_OK;
 }
 
 
@@ -817,12 +802,9 @@ void wgrad_wino(const float* __restrict__ x, const float* __restrict__ dy, float
     }
 }
 
-static int g_wgwino_mode = 0;      // 0 = by rule, 1 = off, 2 = whenever covered
-void wgrad_wino_set_mode(int m) { g_wgwino_mode = m; }
-
 // Winograd wgrad plan: returns the number of slabs (0 = not covered / not chosen); fills the block shape and split
 int wgrad_wino_plan(int B, int Cin, int Cout, int H, int W, int* bn, int* bk, int* cps, int* nchunks) {
-  if (g_wgwino_mode == 1) return 0;
+  if (g_conv.wgwino_mode == 1) return 0;
   if (H != W || (W != 32 && W != 16 && W != 8 && W != 4)) return 0;
   if (Cin % 32 || Cout % 32) return 0;
   if ((long)B * H * W * (Cin > Cout ? Cin : Cout) >= (1L << 31)) return 0;
@@ -841,13 +823,14 @@ int wgrad_wino_plan(int B, int Cin, int Cout, int H, int W, int* bn, int* bk, in
 }
 
 template <int S, int BN, int BK>
-static void wgrad_wino_launch_t(const float* x, const float* dy, float* part, int B, int Cin, int Cout, int cps, int nch, int splits,
+static int wgrad_wino_launch_t(const float* x, const float* dy, float* part, int B, int Cin, int Cout, int cps, int nch, int splits,
                                 hipStream_t s) {
   using Q = WgGeo<S>;
   const size_t lds = sizeof(float) * ((size_t)BK * Q::RSX + (size_t)BN * Q::DS);
-  (void)lds_opt_in(&wgrad_wino<S, BN, BK>, lds);                    // (> 64 KB of dynamic LDS: once per device and kernel)
+  if (int rc = lds_opt_in(&wgrad_wino<S, BN, BK>, lds)) return -rc;  // (> 64 KB of dynamic LDS: once per device and kernel)
   hipLaunchKernelGGL((wgrad_wino<S, BN, BK>), dim3(Cout / BN, Cin / BK, splits), dim3((BN / 32) * (BK / 16) * 64), lds, s,
                      x, dy, part, B, Cin, Cout, cps, nch);
+  return splits;
 }
 
 // writes `slabs` partial [9][Cout][Cin] slabs into part; the caller reduces them (wgrad_reduce)
@@ -856,13 +839,12 @@ int wgrad_wino(const float* x, const float* dy, float* part, int B, int Cin, int
   const int splits = wgrad_wino_plan(B, Cin, Cout, H, W, &bn, &bk, &cps, &nch);
   if (!splits) return 0;
 #define AFD_WGW(S_)                                                                                              \
-  if (bn == 64 && bk == 64) wgrad_wino_launch_t<S_, 64, 64>(x, dy, part, B, Cin, Cout, cps, nch, splits, s);     \
-  else if (bn == 32 && bk == 64) wgrad_wino_launch_t<S_, 32, 64>(x, dy, part, B, Cin, Cout, cps, nch, splits, s); \
-  else if (bn == 64) wgrad_wino_launch_t<S_, 64, 32>(x, dy, part, B, Cin, Cout, cps, nch, splits, s);            \
-  else wgrad_wino_launch_t<S_, 32, 32>(x, dy, part, B, Cin, Cout, cps, nch, splits, s)
+  if (bn == 64 && bk == 64) return wgrad_wino_launch_t<S_, 64, 64>(x, dy, part, B, Cin, Cout, cps, nch, splits, s);     \
+  else if (bn == 32 && bk == 64) return wgrad_wino_launch_t<S_, 32, 64>(x, dy, part, B, Cin, Cout, cps, nch, splits, s); \
+  else if (bn == 64) return wgrad_wino_launch_t<S_, 64, 32>(x, dy, part, B, Cin, Cout, cps, nch, splits, s);            \
+  else return wgrad_wino_launch_t<S_, 32, 32>(x, dy, part, B, Cin, Cout, cps, nch, splits, s)
   if (W == 32) { AFD_WGW(32); } else if (W == 16) { AFD_WGW(16); } else if (W == 8) { AFD_WGW(8); } else { AFD_WGW(4); }
 #undef AFD_WGW
-  return splits;
 }
 
 // both (or either) transformed-weight images of a layer; kinds bit 0 / 1: the forward / dgrad image is the direct form's

@@ -151,8 +151,16 @@ int afd_colsum2(const float* in, float* out_a, float* out_b, int rows, int C, in
  *           three bf16 pieces (round 2, csrc/bf3.hip);  78 / 79 = the same choice for the matrix-core 3x3 weight gradient
  *           (csrc/h2_wgrad.hip / csrc/bf3_wgrad.hip);
  * 92 / 93 = streaming vector kernels for the 1x1 output layer (<= 4 output channels) and its dgrad (csrc/ends.hip) by rule
- *           (default) / never */
+ *           (default) / never;
+ * 64 ... 70 = the Winograd form of the 3x3 forward / dgrad, 71 / 72 = the slice-walking form of the f16x2 split-K kernel (both
+ *           described at afd_conv3x3_wino_workspace_bytes below); 100000 + g (g < 100000) = persistent Winograd grid of g
+ *           workgroups (0 = one item per workgroup, default).
+ * Every other integer is refused with AFD_EINVAL and changes nothing.  The defaults are 0, 8, 34, 48, 50, 60, 64, 74, 76, 78, 80,
+ * 84, 88, 92, 96 and 100000. */
 int afd_debug_conv_path(int mode);
+/* the switches afd_debug_conv_path sets, read back (nothing is launched): copies them, in the member order of ConvSwitches
+ * (csrc/conv_forms.h), into values[0..min(n, count)) and returns count. */
+int afd_debug_conv_state(long* values, int n);
 int afd_conv_fwd(const float* x, const float* w, const float* bias, const float* res, float* y,
                  int B, int Cin, int Cout, int H, int W, int ksize, int act, afd_stream_t stream);
 int afd_conv_dgrad(const float* dy, const float* w, float* dx,
